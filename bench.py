@@ -2,6 +2,8 @@
 """bench.py -- CSPN propagation throughput on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,12 +12,16 @@ over this rank's batch of synthetic affinity + depth tensors, already resident i
 Workload (config.workload): BASELINE.json configs[2] -- 2D CSPN 3x3, 24 iterations, KITTI
 304x1216 -- at 64 images PER GPU (the full config-3 batch fits one MI355X: 1.0 GB of 288 GB);
 the batch shards embarrassingly, so N>1 is weak scaling with no data-path collective (--scaling strong --global-batch 64 shards
-ONE batch over the ranks instead: BASELINE config 3 as written, 64 / N images per GPU).  The only
-collective is the one-time RCCL broadcast of a backbone-sized weight buffer (outside the timed
-region, reported as broadcast_ms).  Data: image i of the global batch is seeded by 1000 + i on the
-CPU.  Before the counted warm-up the launch runs untimed for --prewarm-s seconds
-(shader clocks settle; reported as prewarm_s); after the timed region the oracle checks a sample
-of `out` (parity_checked).
+ONE batch over the ranks instead: BASELINE config 3 as written, 64 / N images per GPU).  Data: image i of the global batch is
+seeded by 1000 + i on the CPU.  Before the counted warm-up the launch runs untimed for --prewarm-s seconds
+(shader clocks settle; reported as prewarm_s).
+
+A plain run does only what the headline needs: set-up, prewarm, warm-up, the K timed steps, the outputs of the last step
+(--dump-outputs DIR: DIR/out.npy, float32, whole images, a fixed seeded sample of them when the batch is over 60 MB) and the
+line.  --full adds everything else, as before: the oracle's check of a sample of `out` after the timed region
+(parity_checked), the other BASELINE configs and the backward / head legs (N = 1, "configs"), the CPU baselines (N = 1,
+"cpu_baseline"), the strong-scaling leg (N > 1, weak scaling, "strong") and the one collective of the path, the one-time RCCL
+broadcast of a backbone-sized weight buffer (N > 1, outside the timed region, reported as broadcast_ms).
 """
 import argparse
 import json
@@ -98,6 +104,31 @@ WORKLOADS = {
     "kitti_w1218": (304, 1218, 24, False, 80.0, "304x1218 (W % 4 != 0), 24 iterations: rows padded to 1220 columns in the workspace, fused path on those (round 5; before: fold + one launch per iteration)"),
 }
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: .npy payload in all (the headline's `out` is 94.6 MB: 40 of its 64 images go)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor, batch first) as path/<name>.npy in float32.  Whole images (volumes) while they fit
+    DUMP_BYTES, the same seeded sample of batch indices for every array and in every run; an image alone over the budget: a seeded
+    sample of each array's elements instead.  -> the line's `dumped` entry"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    per_item = sum(t[0].numel() * 4 for t in arrays.values())
+    k = min(B, DUMP_BYTES // per_item)
+    gen = torch.Generator().manual_seed(0)
+    idx = list(range(B)) if k == B else sorted(torch.randperm(B, generator=gen)[:k].tolist()) if k > 0 else None
+    for name, t in arrays.items():
+        if idx is not None:
+            a = t[idx].float().cpu().numpy()
+        else:
+            flat = t.reshape(-1)
+            sel = torch.randperm(flat.numel(), generator=gen)[:DUMP_BYTES // (4 * len(arrays))].sort().values
+            a = flat[sel.to(flat.device)].float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    sample = "all" if k == B else idx if idx is not None else "%d elements per array" % (DUMP_BYTES // (4 * len(arrays)))
+    return {"files": sorted(n + ".npy" for n in arrays), "batch_items": sample, "of": B}
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -113,10 +144,17 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=64)
     ap.add_argument("--algo", default="auto", choices=["auto", "stepwise", "fused", "fused_cxx", "fused_padded"])
     ap.add_argument("--norm-type", default="8sum", choices=["8sum", "8sum_abs"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: parity against the oracle, the other BASELINE configs and "
+                         "legs (N = 1), the CPU baselines (N = 1), the strong-scaling leg and the weight broadcast (N > 1).  Off: the "
+                         "headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32; at most %d bytes in all: "
+                         "a fixed, seeded sample of whole images / volumes when the batch is larger)" % DUMP_BYTES)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--write-legend", action="store_true", help="write profiles/bench_legend.json (the prose behind the line's @codes) and exit; no GPU needed")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="N = 1, default workload: do not also time BASELINE configs 4, 2, 3-as-written's per-GPU share, 5 and the 2D "
+                    help="--full, N = 1, default workload: do not also time BASELINE configs 4, 2, 3-as-written's per-GPU share, 5 and the 2D "
                          "backward after the headline's timed region (reported under \"configs\")")
     ap.add_argument("--prewarm-s", type=float, default=1.0,
                     help="seconds of untimed launches before the counted warm-up (lets the shader clock settle: the first "
@@ -130,7 +168,7 @@ def parse():
                     help="bracket every N-th timed launch with a HIP event pair (1: every launch).  Event records between kernels cost "
                          "inter-kernel gap (wall time per step), not kernel time; the reported device time is the mean over the bracketed launches")
     ap.add_argument("--no-strong-leg", action="store_true",
-                    help="N > 1, weak scaling: do not also time BASELINE config 3 as written (--global-batch images sharded over the ranks)")
+                    help="--full, N > 1, weak scaling: do not also time BASELINE config 3 as written (--global-batch images sharded over the ranks)")
     ap.add_argument("--plan-mode", type=int, default=0, choices=[0, 1, 2, 3, 8, 9, 10, 16, 17, 18],
                     help="A/B measurements only (through the hook library, not the ABI): 1 = the linear plan without XCD-aware placement, "
                          "2 = the band-group plan of rounds 1-3, 3 = the round-3 loop (experiment builds); 0 = the product (the ABI call)")
@@ -316,7 +354,8 @@ def cpu_baseline(H, W, n_iter, sparse, scale, norm):
     return res
 
 
-def measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, steps, warmup, prewarm_s, cpu_base=False):
+def measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, steps, warmup, prewarm_s, cpu_base=False, parity_check=True,
+                  dump_dir=None):
     """BASELINE config 5: 3x3x3 propagation, 12 iterations, 32x160x608 volume, batch B per GPU, gates normalised by the
     caller and used as given (the fluid.layers.affinity_propagate contract, reference cspn_paddle/demo.py:41-52).
     algo3 0 / 2: the persistent kernel (gates resident in registers across all steps: one pass over the 104 B/voxel
@@ -348,10 +387,11 @@ def measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, st
     if dist is not None:
         dist.barrier()
     dev_ms_avg = sum(dev_ms) / len(dev_ms)
+    dumped = dump_outputs(dump_dir, {"out": out}) if dump_dir else None
     # parity of what the timed launches left in `out`: the other 3D path on every voxel + the CPU oracle on ONE FULL volume
     # (volume 1: the chunks of the persistent kernel are cut across the row of volumes, so it has a neighbour on both sides)
     parity = None
-    if not a.no_parity_check:
+    if parity_check and not a.no_parity_check:
         other = torch.empty_like(out)
         _lib.check(lib.cspn3d_forward_f32_algo(g.data_ptr(), h.data_ptr(), None, other.data_ptr(), B, D, H, W, n_iter, norm,
                                                1 if algo3 != 1 else 0, ws.data_ptr(), ws_bytes, stream.cuda_stream), "other 3D path")
@@ -405,6 +445,8 @@ def measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, st
                    "parallelism": "batch-sharded x%d, no data-path collective" % world},
         "roofline": roof,
     }
+    if dumped is not None:
+        res["dumped"] = dumped
     if cpu_base:
         from oracle import cspn3d_oracle, oracle_threads, set_oracle_threads
         set_oracle_threads(os.cpu_count() or 1)
@@ -425,8 +467,9 @@ def run_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu):
     algo3 = {"auto": 0, "stepwise": 1, "fused": 2, "fused_cxx": 2}.get(a.algo)
     if algo3 is None:
         raise SystemExit("--workload vol3d takes --algo auto | stepwise | fused (not %s: that is a 2D path)" % a.algo)
-    res = measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, min(a.steps, 60), min(a.warmup, 20), a.prewarm_s,
-                        cpu_base=(world == 1 and not a.no_cpu_baseline))
+    res = measure_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu, B, algo3, a.steps, a.warmup, a.prewarm_s,
+                        cpu_base=(a.full and world == 1 and not a.no_cpu_baseline), parity_check=a.full,
+                        dump_dir=a.dump_outputs if rank == 0 else None)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
@@ -776,7 +819,7 @@ def _barrier(dist, notes):
 
 
 def measure2d(a, lib, _lib, dev, dist, world, rank, shared_gpu, scaling, steps, warmup, prewarm_s, notes, parity=True,
-              workload=None, batch=None, keep_tensors=False, layout=None):
+              workload=None, batch=None, keep_tensors=False, layout=None, dump_dir=None):
     """One timed leg of the 2D hot path: `steps` forwards over this rank's batch, bracketed by barrier + synchronize on both sides
     (max over ranks), per-launch device time from HIP events on the launch stream.  scaling 'weak': --batch-per-gpu images on
     every rank; 'strong': --global-batch images sharded (BASELINE config 3 as written)."""
@@ -868,6 +911,7 @@ def measure2d(a, lib, _lib, dev, dist, world, rank, shared_gpu, scaling, steps, 
     elapsed = time.perf_counter() - t0
     dev_ms = sorted(ev[0].elapsed_time(ev[1]) for ev in evs if ev is not None)
     dev_ms_avg = sum(dev_ms) / len(dev_ms)
+    dumped = dump_outputs(dump_dir, {"out": out}) if dump_dir else None
     par = None
     if parity:
         par = parity_check(out, g, h, s, n_iter, a.norm_type)
@@ -885,7 +929,7 @@ def measure2d(a, lib, _lib, dev, dist, world, rank, shared_gpu, scaling, steps, 
             "B": B, "H": H, "W": W, "n_iter": n_iter, "sparse": sparse, "scale": scale, "desc": desc, "algo_name": algo_name,
             "elapsed": elapsed, "dev_ms_avg": dev_ms_avg, "dev_ms_min": dev_ms[0], "parity": par, "total_images": total_images,
             "value": total_images * H * W * n_iter * steps / 1e6 / elapsed, "alg_bytes": alg_bytes,
-            "achieved": alg_bytes / (dev_ms_avg * 1e-3) / 1e9, "prewarm_s": prewarm_done, "prewarm_launches": prewarm_launches}
+            "achieved": alg_bytes / (dev_ms_avg * 1e-3) / 1e9, "prewarm_s": prewarm_done, "prewarm_launches": prewarm_launches, "dumped": dumped}
 
 
 def main():
@@ -915,6 +959,7 @@ def main():
     dist = None
     notes = []
     broadcast_ms, broadcast_error, backend = None, None, None
+    do_broadcast = a.full and not a.no_broadcast
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -922,13 +967,13 @@ def main():
         # every rank says where it is BEFORE the first collective: if the rendezvous or RCCL hangs or dies, this is in the log
         sys.stderr.write("[bench.py rank %d/%d] device %d of %d: %s, backend %s (%s), broadcast %s bytes, HSA_ENABLE_IPC_MODE_LEGACY=%s\n" % (
             rank, world, dev_index, ndev, torch.cuda.get_device_name(dev_index), backend, "RCCL over xGMI" if backend == "nccl" else "CPU",
-            "none" if (a.no_broadcast or shared_gpu) else str(BACKBONE_PARAMS * 4), os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")))
+            "none" if (not do_broadcast or shared_gpu) else str(BACKBONE_PARAMS * 4), os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")))
         sys.stderr.flush()
         if shared_gpu:
             dist.init_process_group("gloo", rank=rank, world_size=world)
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-        if not a.no_broadcast and not shared_gpu:
+        if do_broadcast and not shared_gpu:
             # the one collective of the path (weights of the affinity backbone, once).  It is not part of the timed region: if it
             # fails, the throughput line is still printed, with "broadcast_ms": null and the error
             try:
@@ -947,16 +992,16 @@ def main():
 
     if a.workload == "vol3d":
         return run_vol3d(a, lib, _lib, dev, dist, world, rank, shared_gpu)
-    extras_wanted = (world == 1 and not a.no_extra_configs and a.workload == "kitti" and a.scaling == "weak" and a.layout == "planar"
+    extras_wanted = (a.full and world == 1 and not a.no_extra_configs and a.workload == "kitti" and a.scaling == "weak" and a.layout == "planar"
                      and not a.plan_mode and a.algo == "auto")
     m = measure2d(a, lib, _lib, dev, dist, world, rank, shared_gpu, a.scaling, a.steps, a.warmup, a.prewarm_s, notes,
-                  parity=not a.no_parity_check, keep_tensors=extras_wanted)
-    # N = 1, the driver's command: after the headline's timed region the other BASELINE configs and the backward, each timed the same way
+                  parity=a.full and not a.no_parity_check, keep_tensors=extras_wanted, dump_dir=a.dump_outputs if rank == 0 else None)
+    # --full, N = 1: after the headline's timed region the other BASELINE configs and the backward, each timed the same way
     configs = extra_configs(a, lib, _lib, dev, m, notes) if extras_wanted else None
-    # N > 1, weak scaling (the driver's command): BASELINE config 3 as written is the STRONG shape (batch 64 sharded over the GPUs),
+    # --full, N > 1, weak scaling: BASELINE config 3 as written is the STRONG shape (batch 64 sharded over the GPUs),
     # so the same run also times that and reports it under "strong" (same K / W, same barriers, outside the first timed region)
     strong = None
-    if world > 1 and a.scaling == "weak" and not a.no_strong_leg:
+    if a.full and world > 1 and a.scaling == "weak" and not a.no_strong_leg:
         try:
             if _COLLECTIVES_BROKEN[0]:
                 raise SystemExit("a collective failed in the first leg")
@@ -1007,13 +1052,15 @@ def main():
                 "B_per_gpu": strong["B"], "global_batch": strong["total_images"],
                 "roofline_frac_per_gpu": round(strong["achieved"] / HBM_PEAK_GBS, 4), "device_ms_per_launch": round(strong["dev_ms_avg"], 4),
                 "parity_checked": strong["parity"]}
+        if m["dumped"] is not None:
+            res["dumped"] = m["dumped"]
         if configs is not None:
             res["configs"] = configs
         if _COLLECTIVES_BROKEN[0]:
             res["reduced"] = False   # a collective failed: value / ms_per_step are rank 0's, not the max over ranks
         if notes:
             res["notes"] = notes
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(H, W, n_iter, sparse, scale, a.norm_type)
         print(emit_line(res), flush=True)
     if dist is not None:

@@ -1,5 +1,10 @@
+import hashlib
+import os
+
 import numpy as np
 import torch
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def make_inputs(B, H, W, seed=0, sparse=True, p_sparse=0.05, depth_scale=10.0, neg=False, dtype=torch.float32):
@@ -73,3 +78,25 @@ def assert_close_tight(a, b, what="", rtol=RTOL, atol_frac=1e-6):
     1e-6 * max|ref| (instead of 1e-4 * max|ref|), so small-magnitude pixels next to 80 m depths are really checked
     to 1e-4 relative.  Holds because the engine's error is ~3e-7 of max|ref| (float reordering noise)."""
     return assert_close(a, b, what, rtol=rtol, atol_frac=atol_frac)
+
+
+def digest(a):
+    """sha256 of dtype, shape and bytes, NaNs canonicalised: how tests/golden/reference_digests.json records the reference's arrays"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        a = np.where(np.isnan(a), np.array(np.nan, a.dtype), a)
+    h = hashlib.sha256()
+    h.update(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def live_reference(key):
+    """an output of the unmodified reference for the seeded inputs of a test (tests/golden/make_live_golden.py)"""
+    return np.load(os.path.join(GOLDEN, "live_reference_golden.npz"))[key]
+
+
+def reference_digests(fixture):
+    """-> {array name: digest} of what the unmodified reference produces for the committed fixture `fixture` (tests/golden/make_live_golden.py)"""
+    import json
+    return json.load(open(os.path.join(GOLDEN, "reference_digests.json")))[fixture]

@@ -65,3 +65,26 @@ def test_committed_driver_line_of_this_round_fits_and_carries_every_leg():
     assert d["roofline"]["frac"] > 0.4 and d["cpu_baseline"]["kind"] == "port" and "reference_op_sequence" in d["cpu_baseline"]
     codes = set(re.findall(r'"@([a-z0-9_]+)"', raw))
     assert codes <= set(bench.LEGEND)
+
+
+def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 .npy files within 64 MB; a batch over the budget becomes the same seeded sample of whole images in
+    every run, a batch under it goes whole, an image alone over it becomes a seeded sample of its elements"""
+    import numpy as np
+    import torch
+    out = torch.arange(64 * 304 * 1216, dtype=torch.float32).reshape(64, 1, 304, 1216)   # the headline's `out`: 94.6 MB
+    d1 = bench.dump_outputs(str(tmp_path / "a"), {"out": out})
+    d2 = bench.dump_outputs(str(tmp_path / "b"), {"out": out})
+    a, b = np.load(str(tmp_path / "a" / "out.npy")), np.load(str(tmp_path / "b" / "out.npy"))
+    idx = d1["batch_items"]
+    assert d1 == d2 and d1["files"] == ["out.npy"] and d1["of"] == 64 and idx == sorted(set(idx)) and len(idx) == 40
+    assert a.dtype == np.float32 and os.path.getsize(str(tmp_path / "a" / "out.npy")) <= 64e6 and np.array_equal(a, b)
+    assert np.array_equal(a, out[idx].numpy())
+    small = torch.rand(4, 1, 32, 16, 60, dtype=torch.float64)
+    d = bench.dump_outputs(str(tmp_path / "c"), {"out": small})
+    got = np.load(str(tmp_path / "c" / "out.npy"))
+    assert d["batch_items"] == "all" and got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    big = torch.rand(1, 16_000_001)
+    bench.dump_outputs(str(tmp_path / "d"), {"out": big})
+    got = np.load(str(tmp_path / "d" / "out.npy"))
+    assert got.dtype == np.float32 and got.nbytes == bench.DUMP_BYTES and np.isin(got, big.numpy()).all()

@@ -94,7 +94,7 @@ def test_bench_two_ranks_launch_path():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--batch-per-gpu", "4", "--global-batch", "6", "--prewarm-s", "0.1", "--no-cpu-baseline"]
+           "--batch-per-gpu", "4", "--global-batch", "6", "--prewarm-s", "0.1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -121,7 +121,7 @@ def test_bench_two_ranks_strong_scaling_shards_the_global_batch():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--scaling", "strong", "--global-batch", "7", "--prewarm-s", "0.1", "--no-cpu-baseline"]
+           "--scaling", "strong", "--global-batch", "7", "--prewarm-s", "0.1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
