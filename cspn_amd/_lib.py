@@ -123,6 +123,24 @@ def load():
     return lib
 
 
+# exports added to ABI 5 after its release (purely additive, the version stayed): looked up on first use, so that a library built before
+# them still loads and serves everything else, and a call of a missing one says to rebuild instead of raising AttributeError
+_LATE_SYMBOLS = {
+    "cspn2d_normalize_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+}
+
+
+def late_symbol(name):
+    lib = load()
+    try:
+        f = getattr(lib, name)
+    except AttributeError:
+        raise CspnError("cspn_amd: %s does not export %s (a library built before it was added) -- rebuild with `make -C cspn_amd/csrc`"
+                        % (LIB_PATH, name)) from None
+    f.restype, f.argtypes = _LATE_SYMBOLS[name]
+    return f
+
+
 def load_hooks():
     """libcspn_amd_hooks.so: what tests and measuring tools need beyond the ABI (plan dumps, plan A/B, the muted-workgroup launch
     of the persistent 3D kernel ...).  It links against libcspn_amd.so and calls the same code with the test's choice as an

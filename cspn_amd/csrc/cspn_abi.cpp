@@ -130,6 +130,16 @@ int cspn2d_normalize_f32(const float* guidance, float* wb, int B, int H, int W, 
     return normalize2d(guidance, wb, B, H, W, norm_type, (hipStream_t)stream);
 }
 
+int cspn2d_normalize_backward_f32(const float* guidance, const float* grad_wb, float* grad_guidance, int B, int H, int W, int norm_type,
+                                  cspn_stream_t stream) {
+    if (!guidance || !grad_wb || !grad_guidance) { set_error("cspn2d_normalize_backward_f32: null pointer"); return CSPN_E_BADARG; }
+    if (B <= 0 || H <= 0 || W <= 0) { set_error("cspn2d_normalize_backward_f32: bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
+    if (norm_type != CSPN_NORM_8SUM && norm_type != CSPN_NORM_8SUM_ABS) { set_error("cspn2d_normalize_backward_f32: norm_type must be 8SUM or 8SUM_ABS (got %d)", norm_type); return CSPN_E_BADARG; }
+    if (grad_guidance == guidance || grad_guidance == grad_wb) { set_error("cspn2d_normalize_backward_f32: grad_guidance must not alias an input"); return CSPN_E_BADARG; }
+    if ((long long)B * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    return normalize2d_backward(guidance, grad_wb, grad_guidance, B, H, W, norm_type, (hipStream_t)stream);
+}
+
 int cspn2d_forward_prenorm_f32(const float* wb, const float* blur, const float* sparse, float* out, int B, int H, int W, int n_iter,
                                void* ws, size_t ws_bytes, cspn_stream_t stream) {
     return cspn2d_forward_f32_algo(wb, blur, sparse, out, B, H, W, n_iter, CSPN_NORM_PRENORM, CSPN_ALGO_AUTO, ws, ws_bytes, stream);

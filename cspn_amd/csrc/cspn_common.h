@@ -33,6 +33,8 @@ int stepwise2d_forward(const float* g, const float* blur, const float* sparse, f
                        int n_iter, int norm, void* ws, hipStream_t st);
 // reference affinity_normalization (cspn.py:85-144) as a stand-alone kernel: g [B,8,H,W] -> gate_wb [B,8,H,W] (norm 8SUM / 8SUM_ABS)
 int normalize2d(const float* g, float* wb, int B, int H, int W, int norm, hipStream_t st);
+// its adjoint (cspn2d_normalize_backward.hip): g [B,8,H,W] raw, gwb = dL/dgate_wb [B,8,H,W] -> gg = dL/dg [B,8,H,W]
+int normalize2d_backward(const float* g, const float* gwb, float* gg, int B, int H, int W, int norm, hipStream_t st);
 // W % 4 != 0: the fused path on rows padded to a multiple of 4 columns (cspn2d_stepwise.hip)
 bool padded2d_supported(int B, int H, int W, int n_iter);
 size_t padded2d_workspace(int B, int H, int W, int n_iter);

@@ -52,10 +52,7 @@ def cspn2d_forward(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type
     return out
 
 
-def cspn2d_normalize(guidance, norm_type="8sum"):
-    """reference affinity_normalization (cspn_pytorch/models/cspn.py:85-144) as a stand-alone HIP kernel: guidance [B,8,H,W] ->
-    gate_wb [B,8,H,W] (normalised, consumer-sited): what a producer head with a fused epilogue would emit, and what
-    cspn2d_forward(..., norm_type="prenorm") takes in place of the raw guidance."""
+def _normalize(guidance, norm_type):
     lib = _lib.load()
     if guidance.dim() != 4 or guidance.shape[1] != 8:
         raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
@@ -69,6 +66,56 @@ def cspn2d_normalize(guidance, norm_type="8sum"):
                                       torch.cuda.current_stream(g.device).cuda_stream)
     _lib.check(rc, "cspn2d_normalize_f32")
     return out
+
+
+def cspn2d_normalize_backward(guidance, grad_wb, norm_type="8sum"):
+    """The adjoint of cspn2d_normalize (cspn2d_normalize_backward_f32): guidance [B,8,H,W] (raw, as cspn2d_normalize takes it) and
+    grad_wb = dL/dgate_wb [B,8,H,W] (consumer-sited: what cspn2d_backward(..., 'prenorm') returns for its guidance) -> dL/dguidance
+    [B,8,H,W], the gradient torch autograd computes through the reference's affinity_normalization (cspn.py:85-144).  Elements no pixel
+    reads get 0; NaN where a pixel's neighbourhood sums to 0 (as the forward)."""
+    fn = _lib.late_symbol("cspn2d_normalize_backward_f32")
+    if norm_type not in ("8sum", "8sum_abs"):
+        raise ValueError("norm_type must be '8sum' or '8sum_abs' (got %r)" % (norm_type,))
+    if guidance.dim() != 4 or guidance.shape[1] != 8:
+        raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
+    B, _, H, W = guidance.shape
+    g = _prep(guidance, "guidance")
+    r = _prep(grad_wb, "grad_wb", (B, 8, H, W))
+    if r.device != g.device:
+        raise ValueError("all tensors must live on the same device")
+    out = torch.empty_like(g)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(g.device):
+        rc = fn(g.data_ptr(), r.data_ptr(), out.data_ptr(), B, H, W, _lib.NORM_TYPES[norm_type],
+                torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_normalize_backward_f32")
+    return out
+
+
+class _NormalizeFunction(torch.autograd.Function):
+    """cspn2d_normalize under autograd: keeps the raw guidance, the backward is one cspn2d_normalize_backward_f32 launch"""
+
+    @staticmethod
+    def forward(ctx, guidance, norm_type):
+        ctx.norm_type = norm_type
+        ctx.save_for_backward(guidance)
+        return _normalize(guidance, norm_type)
+
+    @staticmethod
+    def backward(ctx, grad_wb):
+        guidance, = ctx.saved_tensors
+        return cspn2d_normalize_backward(guidance, grad_wb, ctx.norm_type), None
+
+
+def cspn2d_normalize(guidance, norm_type="8sum"):
+    """reference affinity_normalization (cspn_pytorch/models/cspn.py:85-144) as a stand-alone HIP kernel: guidance [B,8,H,W] ->
+    gate_wb [B,8,H,W] (normalised, consumer-sited): what a producer head with a fused epilogue would emit, and what
+    cspn2d_forward(..., norm_type="prenorm") takes in place of the raw guidance.  Differentiable w.r.t. guidance
+    (cspn2d_normalize_backward) when grad mode is on and guidance requires grad; otherwise the plain forward kernel, no graph."""
+    if torch.is_grad_enabled() and isinstance(guidance, torch.Tensor) and guidance.requires_grad:
+        return _NormalizeFunction.apply(guidance, norm_type)
+    return _normalize(guidance, norm_type)
 
 
 def guidance_to_sited8(guidance, norm_type="8sum"):

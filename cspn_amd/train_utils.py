@@ -11,14 +11,14 @@
       nyu_dataset_loader.py:135-144, kitti_dataset_loader.py:138-148   seed): the Bernoulli mask drawn on the GPU, batched
     gud_up_proj_layer6(x), gud_up_proj_layer5(x)                  guidance_heads(x, layer6.conv1.weight, layer5.conv1.weight, oheight, owidth
       torch_resnet_cspn_nyu.py:187-206, :318-319, :372-373          [, norm_type]): both Simple_Gudi_UpConv_Block_Last_Layer heads (Unpool + 3x3 conv) as
-                                                                  ONE kernel; with norm_type the guidance comes back as gate_wb (forward only)
+                                                                  ONE kernel; with norm_type the guidance comes back as gate_wb; differentiable
 
 The reference moves every prediction to the host before reducing it (train.py:204-206, eval.py:146-150)."""
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .functional import _prep, _workspace
+from .functional import _prep, _workspace, cspn2d_normalize
 
 _KEYS = ['MSE', 'RMSE', 'ABS_REL', 'LG10', 'MAE', 'DELTA1.02', 'DELTA1.05', 'DELTA1.10', 'DELTA1.25', 'DELTA1.25^2',
          'DELTA1.25^3']
@@ -208,7 +208,11 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     norm_type None: -> (guidance [B,8,H,W], blur [B,1,H,W] | None), bit-compatible inputs of Affinity_Propagate(..., norm_type)(guidance, blur, sparse);
     differentiable w.r.t. x and both weights (cspn_guidance_head_backward_f32: the gradients torch autograd computes through the reference layers).
     norm_type '8sum' | '8sum_abs': the guidance comes back normalised -- gate_wb of affinity_normalization (cspn.py:85-144) -- for
-    cspn2d_forward(gate_wb, blur, sparse, n_iter, 'prenorm') / cspn_amd.propagate_prenorm; these two modes are forward only (inference / frozen heads)."""
+    cspn2d_forward(gate_wb, blur, sparse, n_iter, 'prenorm') / cspn_amd.propagate_prenorm.  With grad off the normalisation runs fused behind the conv
+    (one kernel); with grad on and any input requiring grad, the raw heads (_GuidanceHeadsFunction) then the differentiable cspn2d_normalize: autograd chains
+    cspn2d_normalize_backward_f32 into cspn_guidance_head_backward_f32, so dL/dgate_wb from propagate_prenorm reaches x and both weights."""
+    if norm_type is not None and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, weight_guidance, weight_blur)):
+        return _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth, norm_type)
     xx = _prep(x, "x")
     B, C, h, w = xx.shape
     wg = _prep(weight_guidance, "weight_guidance", (8, C, 3, 3))
@@ -219,3 +223,22 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     if norm_type is None and torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
         return _GuidanceHeadsFunction.apply(xx, wg, wb, H, W)
     return _heads_forward(xx, wg, wb, H, W, _lib.NORM_TYPES["none" if norm_type is None else norm_type])
+
+
+def _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth, norm_type):
+    """guidance_heads with norm_type under autograd: the raw heads, then cspn2d_normalize (both differentiable).  Forward traffic: the raw guidance
+    written (32 B/pixel) and normalised (36 B read + 32 B written) -- the fused mode writes 32 B and normalises in place in the same 32 + 32 B."""
+    if norm_type not in ("8sum", "8sum_abs"):
+        raise ValueError("norm_type must be None (raw guidance), '8sum' or '8sum_abs' (gate_wb)")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("x must be [B,C,h,w], got %s" % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__,))
+    for t in (weight_guidance, weight_blur):
+        if isinstance(t, torch.Tensor) and t.device != x.device:
+            raise ValueError("all tensors must live on the same device")
+    xx = _prep(x, "x")
+    B, C, h, w = xx.shape
+    wg = _prep(weight_guidance, "weight_guidance", (8, C, 3, 3))
+    wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
+    H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
+    g, b = _GuidanceHeadsFunction.apply(xx, wg, wb, H, W)
+    return cspn2d_normalize(g, norm_type), b

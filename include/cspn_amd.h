@@ -44,7 +44,8 @@ extern "C" {
                               * 4: CSPN_NORM_PRENORM, cspn2d_normalize_f32, cspn2d_forward_prenorm_f32, cspn3d_backward_multi_f32; the
                               *    sited8 experiment's three entry points left the ABI (hook library, experiment builds); CSPN_ALGO_FUSED_PADDED
                               *    (what AUTO returns for W % 4 != 0; cspn2d_workspace_bytes grows accordingly for such widths);
-                              * 5: cspn_guidance_head_f32 (the producer of the path's inputs) and cspn_guidance_head_backward_f32; CSPN_NORM_PRENORM on the 2D backward entry points */
+                              * 5: cspn_guidance_head_f32 (the producer of the path's inputs) and cspn_guidance_head_backward_f32; CSPN_NORM_PRENORM on the 2D backward entry points;
+                              *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32 */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -104,10 +105,21 @@ int cspn2d_auto_algo(int B, int H, int W, int n_iter);
  * and the mask (cspn.py:81) -- no abs-sum, no reciprocal, no edge patching, aligned loads.  Results: those of CSPN_NORM_8SUM /
  * _8SUM_ABS on the raw guidance up to the rounding of the division (<= 1e-6 relative; NaN where sum |G| = 0, as the reference).
  * Every shape and n_iter the forward takes.  Backward (ABI 5): cspn2d_backward_f32 / _history_f32 with CSPN_NORM_PRENORM return dL/d(wb) in grad_guidance --
- * dL/dwb_k(p) = (1 - m)(dW'_k - dC H_0)(p), no normalisation chain, no scatter -- and dL/d(blur_depth); chaining dL/d(wb) into the head is the producer's.
+ * dL/dwb_k(p) = (1 - m)(dW'_k - dC H_0)(p), no normalisation chain, no scatter -- and dL/d(blur_depth); cspn2d_normalize_backward_f32 (below) chains dL/d(wb) into the raw guidance.
  * cspn2d_normalize_f32 is that producer epilogue as a stand-alone kernel (norm_type 8SUM or 8SUM_ABS; tests, A/B timing):
  * 36 B read + 32 B written per pixel.  cspn2d_forward_prenorm_f32 = cspn2d_forward_f32 with norm_type CSPN_NORM_PRENORM. */
 int cspn2d_normalize_f32(const float* guidance, float* wb, int B, int H, int W, int norm_type, cspn_stream_t stream);
+/* The adjoint of cspn2d_normalize_f32 (what torch autograd computes through affinity_normalization, cspn.py:85-144, for the cropped gate_wb):
+ *   guidance      [B,8,H,W]  the raw guidance, as cspn2d_normalize_f32 takes it
+ *   grad_wb       [B,8,H,W]  dL/d(gate_wb), consumer-sited: what cspn2d_backward_f32 / _history_f32 return in grad_guidance under CSPN_NORM_PRENORM
+ *   grad_guidance [B,8,H,W]  dL/d(guidance) (must not alias either input)
+ * With g~ = g (8SUM) or |g| (8SUM_ABS), G_k(p) = g~_k(p + off_k) (0 outside the image), S(p) = sum_j |G_j(p)|, T(p) = sum_j grad_wb_j(p) G_j(p):
+ *   dL/dg_k(p + off_k) = ( grad_wb_k(p) / S(p) - sign(G_k(p)) T(p) / S(p)^2 )  [ * sign(g_k(p + off_k)) for 8SUM_ABS ],
+ * the chain cspn2d_backward_f32 evaluates inside the raw route; elements no pixel reads get 0, S(p) = 0 gives NaN (IEEE, as torch).
+ * norm_type 8SUM or 8SUM_ABS; every B, H, W >= 1; 4-byte-aligned pointers.  No workspace, no atomics: every output element is written
+ * once, deterministic.  96 B/pixel (raw guidance + grad_wb read, grad_guidance written). */
+int cspn2d_normalize_backward_f32(const float* guidance, const float* grad_wb, float* grad_guidance, int B, int H, int W, int norm_type,
+                                  cspn_stream_t stream);
 int cspn2d_forward_prenorm_f32(const float* wb, const float* blur, const float* sparse, float* out,
                                int B, int H, int W, int n_iter, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
