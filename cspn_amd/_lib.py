@@ -127,10 +127,28 @@ def load():
 # them still loads and serves everything else, and a call of a missing one says to rebuild instead of raising AttributeError
 _LATE_SYMBOLS = {
     "cspn2d_normalize_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    # C channels on shared 2D guidance
+    "cspn2d_workspace_bytes_multi": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn2d_multi_supported": (ctypes.c_int, [ctypes.c_int] * 5),
+    "cspn2d_forward_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_history_bytes_multi": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn2d_forward_history_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_int] * 7
+                                         + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn2d_backward_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_history_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn2d_backward_history_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+                                          + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 
+_late = {}
+
+
 def late_symbol(name):
+    f = _late.get(name)
+    if f is not None:
+        return f
     lib = load()
     try:
         f = getattr(lib, name)
@@ -138,6 +156,7 @@ def late_symbol(name):
         raise CspnError("cspn_amd: %s does not export %s (a library built before it was added) -- rebuild with `make -C cspn_amd/csrc`"
                         % (LIB_PATH, name)) from None
     f.restype, f.argtypes = _LATE_SYMBOLS[name]
+    _late[name] = f
     return f
 
 

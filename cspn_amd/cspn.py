@@ -15,11 +15,50 @@ Differences a caller can observe, all deliberate:
   * inputs must already be on the GPU (the reference calls .cuda() itself, cspn.py:50);
   * differentiable w.r.t. guidance and blur_depth (HIP backward kernels, cspn_amd/csrc/cspn2d_backward.hip: the gradient
     torch autograd computes through the reference forward, which reference train.py:196-198 back-propagates through);
-    sparse_depth gets no gradient (only its sign is used, cspn.py:64)."""
+    sparse_depth gets no gradient (only its sign is used, cspn.py:64);
+  * blur_depth [B,C,H,W] with C > 1 is propagated on the shared affinities like the reference's broadcast (cspn.py:58-81), with
+    sparse_depth None, [B,1,H,W] or [B,C,H,W]: one engine call each way (cspn2d_forward_multi_f32 / cspn2d_backward_multi_f32),
+    dL/dguidance summed over the channels."""
 import torch
 import torch.nn as nn
 
 from . import functional as F
+
+
+class _CSPN2dMultiFunction(torch.autograd.Function):
+    """blur_depth [B,C,H,W], C > 1, on the shared guidance (reference cspn.py:58-81 broadcasts the affinities): one engine call each way,
+    dL/dguidance summed over the channels inside the engine"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo, keep_history):
+        ctx.n_iter, ctx.norm_type = n_iter, norm_type
+        needs_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        B, C, H, W = blur_depth.shape
+        if (keep_history and needs_grad and algo in ("auto", "fused") and guidance.is_cuda
+                and F.cspn2d_history_bytes_multi(B, C, H, W, n_iter) > 0):
+            out, hist = F.cspn2d_forward_with_history_multi(guidance, blur_depth, sparse_depth, n_iter, norm_type)
+            ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
+            return out
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, None)
+        return F.cspn2d_forward_multi(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
+        if hist is not None:
+            gg, gh = F.cspn2d_backward_from_history_multi(guidance, blur_depth, sparse_depth, grad_out, hist, ctx.n_iter, ctx.norm_type,
+                                                          need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
+        else:
+            gg, gh = F.cspn2d_backward_multi(guidance, blur_depth, sparse_depth, grad_out, ctx.n_iter, ctx.norm_type,
+                                             need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
+        return gg, gh, None, None, None, None, None
+
+
+def _apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history):
+    # blur_depth [B,C,H,W] with C > 1: the multi-channel call; C = 1 runs exactly the single-channel path
+    if isinstance(blur_depth, torch.Tensor) and blur_depth.dim() == 4 and blur_depth.shape[1] > 1:
+        return _CSPN2dMultiFunction.apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history)
+    return _CSPN2dFunction.apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history)
 
 
 class _CSPN2dFunction(torch.autograd.Function):
@@ -60,7 +99,7 @@ def propagate_prenorm(gate_wb, blur_depth, sparse_depth=None, n_iter=24, algo="a
     train_utils.guidance_heads(..., norm_type='8sum' | '8sum_abs') (that, then cspn_guidance_head_backward_f32)."""
     if n_iter == 0:
         return blur_depth
-    return _CSPN2dFunction.apply(gate_wb, blur_depth, sparse_depth, int(n_iter), "prenorm", algo, keep_history)
+    return _apply(gate_wb, blur_depth, sparse_depth, int(n_iter), "prenorm", algo, keep_history)
 
 
 class Affinity_Propagate(nn.Module):
@@ -83,7 +122,7 @@ class Affinity_Propagate(nn.Module):
             raise ValueError('unknown norm %s' % self.norm_type)
         if n == 0:
             return blur_depth  # cspn.py:61,66,83: the very same tensor object
-        return _CSPN2dFunction.apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
+        return _apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
 
     def extra_repr(self):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)

@@ -181,6 +181,15 @@ __device__ __forceinline__ float4 ld4u(const float* p) {   // 16 bytes, 4-byte a
     return v;
 }
 __device__ __forceinline__ void st4u(float* p, float4 v) { __builtin_memcpy(p, &v, 16); }
+// dL/dguidance of channels on shared guidance (cspn2d_backward_multi_f32): channel 0 stores, every later channel adds its part
+__device__ __forceinline__ void st4u_acc(float* p, float4 v, bool acc) {
+    if (acc) { const float4 o = ld4u(p); v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w); }
+    st4u(p, v);
+}
+__device__ __forceinline__ void st4a_acc(float* p, float4 v, bool acc) {   // 16-byte aligned
+    if (acc) { const float4 o = *reinterpret_cast<const float4*>(p); v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w); }
+    *reinterpret_cast<float4*>(p) = v;
+}
 
 // ---- the end of the final pass for one group of 4 columns (b, y, x .. x + 3): from dW'_k and dC through the fold,
 // the normalisation and the neighbour-sited gather to dL/dguidance and dL/dblur_depth (see the file header)
@@ -189,7 +198,7 @@ template <bool INTERIOR>
 __device__ __forceinline__ void bwd_epilogue4(const float* __restrict__ g, const float* __restrict__ blur, const float* __restrict__ sparse,
                                               const float* __restrict__ a0p, float* __restrict__ gg, float* __restrict__ gb, int b, int y,
                                               int x, size_t idx, size_t HW, int H, int W, int norm, const float (&dW)[8][4],
-                                              const float (&dC)[4]) {
+                                              const float (&dC)[4], bool acc = false) {
     // ---- epilogue: the chain through the fold, the normalisation and the neighbour-sited gather (see the file header)
     const float4 h0q = *reinterpret_cast<const float4*>(blur + idx);
     const float h0[4] = {h0q.x, h0q.y, h0q.z, h0q.w};
@@ -208,8 +217,8 @@ __device__ __forceinline__ void bwd_epilogue4(const float* __restrict__ g, const
         if (ggp) {
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                *reinterpret_cast<float4*>(ggp + k * HW + (size_t)y * W + x) =
-                    make_float4((1.f - m[0]) * dW[k][0], (1.f - m[1]) * dW[k][1], (1.f - m[2]) * dW[k][2], (1.f - m[3]) * dW[k][3]);
+                st4a_acc(ggp + k * HW + (size_t)y * W + x,
+                         make_float4((1.f - m[0]) * dW[k][0], (1.f - m[1]) * dW[k][1], (1.f - m[2]) * dW[k][2], (1.f - m[3]) * dW[k][3]), acc);
         }
         return;
     }
@@ -228,8 +237,8 @@ __device__ __forceinline__ void bwd_epilogue4(const float* __restrict__ g, const
         if (ggp) {
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                *reinterpret_cast<float4*>(ggp + k * HW + (size_t)y * W + x) =
-                    make_float4(om[0] * (dW[k][0] - ch[0]), om[1] * (dW[k][1] - ch[1]), om[2] * (dW[k][2] - ch[2]), om[3] * (dW[k][3] - ch[3]));
+                st4a_acc(ggp + k * HW + (size_t)y * W + x,
+                         make_float4(om[0] * (dW[k][0] - ch[0]), om[1] * (dW[k][1] - ch[1]), om[2] * (dW[k][2] - ch[2]), om[3] * (dW[k][3] - ch[3])), acc);
         }
         return;
     }
@@ -308,11 +317,11 @@ __device__ __forceinline__ void bwd_epilogue4(const float* __restrict__ g, const
                 d[i] = r;
             }
             float* dst = ggp + k * HW + (size_t)yy * W;   // g_k(p + off_k) is read by pixel p only
-            if (INTERIOR || (xs >= 0 && xs + 3 < W)) st4u(dst + xs, make_float4(d[0], d[1], d[2], d[3]));
+            if (INTERIOR || (xs >= 0 && xs + 3 < W)) st4u_acc(dst + xs, make_float4(d[0], d[1], d[2], d[3]), acc);
             else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (xs + i >= 0 && xs + i < W) dst[xs + i] = d[i];
+                    if (xs + i >= 0 && xs + i < W) dst[xs + i] = acc ? dst[xs + i] + d[i] : d[i];
             }
         }
     }
@@ -325,7 +334,7 @@ template <bool INTERIOR, class GetDW>
 __device__ __attribute__((noinline)) void bwd_epilogue4_2pass(const float* __restrict__ g, const float* __restrict__ blur, const float* __restrict__ sparse,
                                                     const float* __restrict__ a0p, float* __restrict__ gg, float* __restrict__ gb, int b, int y,
                                                     int x, size_t idx, size_t HW, int H, int W, int norm, GetDW get_dw /* k -> dW'_k of the 4 pixels */,
-                                                    const float (&dC)[4]) {
+                                                    const float (&dC)[4], bool acc = false) {
     const float4 h0q = *reinterpret_cast<const float4*>(blur + idx);
     const float h0[4] = {h0q.x, h0q.y, h0q.z, h0q.w};
     float m[4] = {0.f, 0.f, 0.f, 0.f};
@@ -344,8 +353,7 @@ __device__ __attribute__((noinline)) void bwd_epilogue4_2pass(const float* __res
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float4 w = get_dw(k);
-                *reinterpret_cast<float4*>(ggp + k * HW + (size_t)y * W + x) =
-                    make_float4((1.f - m[0]) * w.x, (1.f - m[1]) * w.y, (1.f - m[2]) * w.z, (1.f - m[3]) * w.w);
+                st4a_acc(ggp + k * HW + (size_t)y * W + x, make_float4((1.f - m[0]) * w.x, (1.f - m[1]) * w.y, (1.f - m[2]) * w.z, (1.f - m[3]) * w.w), acc);
             }
         }
         return;
@@ -369,8 +377,7 @@ __device__ __attribute__((noinline)) void bwd_epilogue4_2pass(const float* __res
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float4 w = get_dw(k);
-                *reinterpret_cast<float4*>(ggp + k * HW + (size_t)y * W + x) =
-                    make_float4(om[0] * (w.x - ch[0]), om[1] * (w.y - ch[1]), om[2] * (w.z - ch[2]), om[3] * (w.w - ch[3]));
+                st4a_acc(ggp + k * HW + (size_t)y * W + x, make_float4(om[0] * (w.x - ch[0]), om[1] * (w.y - ch[1]), om[2] * (w.z - ch[2]), om[3] * (w.w - ch[3])), acc);
             }
         }
         return;
@@ -447,11 +454,11 @@ __device__ __attribute__((noinline)) void bwd_epilogue4_2pass(const float* __res
                 d[i] = r;
             }
             float* dst = ggp + k * HW + (size_t)yy * W;   // g_k(p + off_k) is read by pixel p only
-            if (INTERIOR || (xs >= 0 && xs + 3 < W)) st4u(dst + xs, make_float4(d[0], d[1], d[2], d[3]));
+            if (INTERIOR || (xs >= 0 && xs + 3 < W)) st4u_acc(dst + xs, make_float4(d[0], d[1], d[2], d[3]), acc);
             else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (xs + i >= 0 && xs + i < W) dst[xs + i] = d[i];
+                    if (xs + i >= 0 && xs + i < W) dst[xs + i] = acc ? dst[xs + i] + d[i] : d[i];
             }
         }
     }
@@ -688,11 +695,14 @@ __global__ __launch_bounds__(CK_ROWS * CK_GR) __attribute__((amdgpu_waves_per_eu
 __device__ __forceinline__ float4 img_to_reg(float4 q) { return make_float4(q.x, q.w, q.y, q.z); }   // (c0..c3) -> (c0,c3,c1,c2)
 __device__ __forceinline__ v2f swp2(v2f v) { return __builtin_shufflevector(v, v, 1, 0); }
 
-template <int CK_ROWS>
+template <int CK_ROWS, bool MULTI>
 __global__ __launch_bounds__(CK_ROWS * CK_GR) __attribute__((amdgpu_waves_per_eu(CK_ROWS / 16, CK_ROWS / 16))) void bwd_final_mx_kernel(
     const float* __restrict__ g, const float* __restrict__ blur, const float* __restrict__ sparse, const float* __restrict__ hh,
     const float* __restrict__ ah, const float* __restrict__ wf, const float* __restrict__ a0p, const float* __restrict__ gout,
-    float* __restrict__ gg, float* __restrict__ gb, int B, int H, int W, int norm, int nseg) {
+    float* __restrict__ gg, float* __restrict__ gb, int B, int H, int W, int norm, int nseg, int C, int c) {
+    // C > 1: B guidance images of C channels each (cspn2d_backward_multi_f32); this launch takes channel c of every image: the
+    // level / coefficient planes and the 1-channel tensors are [B*C][H][W] (image-channel b * C + c), gg [B][8][H][W] gets the channel's part
+    // added to what the launches of channels 0 .. c - 1 left there
     constexpr int CK_NT = CK_ROWS * CK_GR, CK_TR = CK_ROWS - 2 * CK;
     const int NSEG = nseg;   // n_iter / 4 segments of four levels (round 5: n_iter = 4, 8 .. 24; 6 for the reference's 24)
     __shared__ __attribute__((aligned(16))) float4 sH[2][CK_NT];       // H_{s+l} of the region, two planes alternating (REGISTER order inside a quad)
@@ -708,8 +718,11 @@ __global__ __launch_bounds__(CK_ROWS * CK_GR) __attribute__((amdgpu_waves_per_eu
     const bool inimg = y >= 0 && y < H && xg >= 0 && xg < W4;
     const bool intile = inimg && ry >= CK && ry < CK_ROWS - CK && gx >= 1 && gx < CK_GR - 1;
     const int x = 4 * (inimg ? xg : 0);
-    const size_t HW = (size_t)H * W, total = (size_t)B * HW;
-    const size_t idx = (size_t)b * HW + (size_t)(inimg ? y : 0) * W + x;
+    // (MULTI false: the single-channel kernel exactly -- C = 1, c = 0 as constants, no accumulation)
+    const int Cm = MULTI ? C : 1, cm = MULTI ? c : 0;
+    const size_t HW = (size_t)H * W, total = (size_t)B * Cm * HW;
+    const size_t idx = ((size_t)b * Cm + cm) * HW + (size_t)(inimg ? y : 0) * W + x;
+    const bool acc = MULTI && c > 0;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     auto ld = [&](const float* p) {
         typedef float v4g __attribute__((ext_vector_type(4)));
@@ -1009,11 +1022,11 @@ __global__ __launch_bounds__(CK_ROWS * CK_GR) __attribute__((amdgpu_waves_per_eu
             const float4* a; const float4* t; int nt;
             __device__ float4 operator()(int k) const { return k < 4 ? a[k * nt] : t[(k - 4) * nt]; }
         } get_dw{&sA[0][tid], &sT[0][0][tid], CK_NT};
-        if (blk_in) bwd_epilogue4_2pass<true>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, get_dw, dCs);
-        else bwd_epilogue4_2pass<false>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, get_dw, dCs);
+        if (blk_in) bwd_epilogue4_2pass<true>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, get_dw, dCs, acc);
+        else bwd_epilogue4_2pass<false>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, get_dw, dCs, acc);
     } else {
-        if (blk_in) bwd_epilogue4<true>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, dWs, dCs);
-        else bwd_epilogue4<false>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, dWs, dCs);
+        if (blk_in) bwd_epilogue4<true>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, dWs, dCs, acc);
+        else bwd_epilogue4<false>(g, blur, sparse, a0p, gg, gb, b, y, x, idx, HW, H, W, norm, dWs, dCs, acc);
     }
 #endif
 }
@@ -1046,28 +1059,35 @@ static void reg_to_img_plane(const float* src, float* dst, size_t total, hipStre
     hipLaunchKernelGGL(reg_to_img_plane_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, (const float4*)src, (float4*)dst, total / 4);
 }
 
-// final pass of the assembly-sweep backward: from the checkpoints of both sweeps
+// final pass of the assembly-sweep backward: from the checkpoints of both sweeps.  C > 1: B guidance images, the sweeps ran over B * C
+// image-channels; one launch per channel, in channel order, each adding its part of dL/dguidance to what the one before left
 static void launch_final_ck(const float* g, const float* blur, const float* sparse, const float* hh, const float* ah, const float* wf,
-                            const float* a0, const float* gout, float* gg, float* gb, int B, int H, int W, int norm, int nseg, hipStream_t st) {
+                            const float* a0, const float* gout, float* gg, float* gb, int B, int H, int W, int norm, int nseg, hipStream_t st,
+                            int C = 1) {
 #ifdef BWD_FINAL_ROWS   // (A/B build: 64 = 1 024 threads, four waves per SIMD at 128 registers, all 160 KB of LDS)
     constexpr int ROWS = BWD_FINAL_ROWS, TROWS = ROWS - 2 * CK;
 #else
     constexpr int ROWS = 48, TROWS = ROWS - 2 * CK;
 #endif
     const int ntile = ((W / 4 + CK_TG - 1) / CK_TG) * ((H + TROWS - 1) / TROWS) * B, per = (ntile + 7) / 8;
-#ifdef BWD_FINAL_CK   // (A/B build: the round-3 kernel, image-order pixel pairs)
+#ifdef BWD_FINAL_CK   // (A/B build: the round-3 kernel, image-order pixel pairs; one channel only)
+    (void)C;
     hipLaunchKernelGGL(bwd_final_ck_kernel<ROWS>, dim3((unsigned)(per * 8)), dim3(ROWS * CK_GR), 0, st, g, blur, sparse, hh, ah, wf, a0, gout,
                        gg, gb, B, H, W, norm, nseg);
 #else
-    hipLaunchKernelGGL(bwd_final_mx_kernel<ROWS>, dim3((unsigned)(per * 8)), dim3(ROWS * CK_GR), 0, st, g, blur, sparse, hh, ah, wf, a0, gout,
-                       gg, gb, B, H, W, norm, nseg);
+    for (int c = 0; c < C; ++c)
+        hipLaunchKernelGGL((C > 1 ? bwd_final_mx_kernel<ROWS, true> : bwd_final_mx_kernel<ROWS, false>), dim3((unsigned)(per * 8)), dim3(ROWS * CK_GR), 0,
+                           st, g, blur, sparse, hh, ah, wf, a0, gout, gg, gb, B, H, W, norm, nseg, C, c);
 #endif
 }
 
+bool backward2d_multi_supported(int BC, int H, int W, int n_iter) { return asm_path(BC, H, W, n_iter); }
+
 int backward2d(const float* g, const float* blur, const float* sparse, const float* gout, float* gg, float* gb, int B, int H,
-               int W, int n_iter, int norm, void* ws, hipStream_t st) {
+               int W, int n_iter, int norm, void* ws, hipStream_t st, int C) {
     const size_t total = (size_t)B * H * W;
     float* wf = (float*)ws;
+    if (C > 1 && !asm_path(B, H, W, n_iter)) { set_error("channels on shared guidance: the assembly sweeps only"); return CSPN_E_UNSUPPORTED; }
     if (asm_path(B, H, W, n_iter)) {
         // both sweeps run in the fused ring kernel (cspn2d_tsw.hip), each keeping every fourth of its levels: the forward
         // as it is (it also leaves the 8 folded coefficient planes right behind its level planes), the adjoint as a
@@ -1079,10 +1099,10 @@ int backward2d(const float* g, const float* blur, const float* sparse, const flo
         float* a0 = ah + NCKP * total;
         float* scratch = a0 + total;
         const int nseg = n_iter / CK;
-        if (int e = tsw2d_pass(g, blur, blur, sparse, scratch, B, H, W, norm, st, hh)) return e;
+        if (int e = tsw2d_pass(g, blur, blur, sparse, scratch, B, H, W, norm, st, hh, 0, 0, C)) return e;
         if (int e = tsw2d_adjoint_pass(wf, gout, a0, B, H, W, st, ah)) return e;
         if (nseg <= NCKP) reg_to_img_plane(ah + (size_t)(nseg - 1) * total, a0, total, st);   // A_0 of a sweep shorter than the ring
-        launch_final_ck(g, blur, sparse, hh, ah, wf, a0, gout, gg, gb, B, H, W, norm, nseg, st);
+        launch_final_ck(g, blur, sparse, hh, ah, wf, a0, gout, gg, gb, B / C, H, W, norm, nseg, st, C);
         return check_launch("bwd_final_ck_kernel");
     }
     float* wt = wf + 9 * total;                       // transposed coefficients of the adjoint stencil
@@ -1111,10 +1131,10 @@ size_t history2d_bytes(int B, int H, int W, int n_iter) {
 }
 
 int forward2d_history(const float* g, const float* blur, const float* sparse, float* out, void* history, int B, int H, int W,
-                      int n_iter, int norm, void* ws, hipStream_t st) {
+                      int n_iter, int norm, void* ws, hipStream_t st, int C) {
     float* hh = (float*)((char*)history + FRONT_PAD);
     (void)ws;
-    if (int e = tsw2d_pass(g, blur, blur, sparse, out, B, H, W, norm, st, hh)) return e;   // (n_iter < 24: `out` = level 24 for a moment)
+    if (int e = tsw2d_pass(g, blur, blur, sparse, out, B, H, W, norm, st, hh, 0, 0, C)) return e;   // (n_iter < 24: `out` = level 24 for a moment)
     const int nseg = n_iter / CK;
     if (nseg <= NCKP) {   // the result is the checkpoint H_n
         reg_to_img_plane(hh + (size_t)(nseg - 1) * B * H * W, out, (size_t)B * H * W, st);
@@ -1128,7 +1148,7 @@ size_t backward2d_history_workspace(int B, int H, int W) {
 }
 
 int backward2d_history(const float* g, const float* blur, const float* sparse, const float* gout, const void* history, float* gg,
-                       float* gb, int B, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+                       float* gb, int B, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, int C) {
     const size_t total = (size_t)B * H * W;
     const float* hh = (const float*)((const char*)history + FRONT_PAD);
     const float* wf = hh + NCKP * total;
@@ -1137,7 +1157,7 @@ int backward2d_history(const float* g, const float* blur, const float* sparse, c
     const int nseg = n_iter / CK;
     if (int e = tsw2d_adjoint_pass(wf, gout, a0, B, H, W, st, ah)) return e;
     if (nseg <= NCKP) reg_to_img_plane(ah + (size_t)(nseg - 1) * total, a0, total, st);
-    launch_final_ck(g, blur, sparse, hh, ah, wf, a0, gout, gg, gb, B, H, W, norm, nseg, st);
+    launch_final_ck(g, blur, sparse, hh, ah, wf, a0, gout, gg, gb, B / C, H, W, norm, nseg, st, C);
     return check_launch("bwd_final_ck_kernel");
 }
 

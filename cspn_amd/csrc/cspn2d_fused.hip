@@ -567,8 +567,9 @@ size_t fused2d_workspace(int B, int H, int W, int n_iter) {
 }
 
 int fused2d_forward(const float* g, const float* blur, const float* sparse, float* out, int B, int H, int W,
-                    int n_iter, int norm, void* ws, hipStream_t st, bool use_asm, int plan_mode) {
+                    int n_iter, int norm, void* ws, hipStream_t st, bool use_asm, int plan_mode, int C) {
     if (((uintptr_t)out & 15u) != 0) { set_error("fused kernel needs a 16-byte aligned output"); return CSPN_E_UNSUPPORTED; }
+    if (C > 1 && !(use_asm && tsw2d_supported(B, H, W) && (plan_mode & 7) < 3)) { set_error("channels on shared guidance: the assembly ring only"); return CSPN_E_UNSUPPORTED; }
     const int passes = (n_iter + LV - 1) / LV;
     float* pingpong = (float*)ws;
     const bool asm_ok = use_asm && tsw2d_supported(B, H, W);
@@ -582,7 +583,7 @@ int fused2d_forward(const float* g, const float* blur, const float* sparse, floa
         // the last pass writes `out`; earlier passes alternate so that no pass reads what it writes
         float* dst = ((passes - 1 - p) % 2 == 0) ? out : pingpong;
         if (asm_ok && n < LV) {
-            if (int e = tsw2d_pass(g, blur, blur, sparse, dst, B, H, W, norm, st, nullptr, plan_mode & 7, n)) return e;
+            if (int e = tsw2d_pass(g, blur, blur, sparse, dst, B, H, W, norm, st, nullptr, plan_mode & 7, n, C)) return e;
             hin = dst;
             done += n;
             continue;
@@ -595,9 +596,9 @@ int fused2d_forward(const float* g, const float* blur, const float* sparse, floa
             } else
 #endif
             if (hin == blur && !(plan_mode & 8) && ((plan_mode & 16) ? tsw4_supported(B, H, W) : tsw4_preferred(B, H, W, sparse != nullptr))) {   // round 6: 12 waves x 3 rows, three waves per SIMD
-                if (int e = tsw4_pass(g, blur, sparse, dst, B, H, W, norm, st, plan_mode)) return e;
+                if (int e = tsw4_pass(g, blur, sparse, dst, B, H, W, norm, st, plan_mode, C)) return e;
             } else
-            if (int e = tsw2d_pass(g, blur, hin, sparse, dst, B, H, W, norm, st, nullptr, plan_mode & 7)) return e;
+            if (int e = tsw2d_pass(g, blur, hin, sparse, dst, B, H, W, norm, st, nullptr, plan_mode & 7, 0, C)) return e;
             hin = dst;
             done += n;
             continue;

@@ -166,10 +166,11 @@ bool tsw4_preferred(int B, int H, int W, bool sparse) {
     return longest >= (sparse ? 420 : 190);
 }
 
-int tsw4_pass(const float* gd, const float* blur, const float* sparse, float* out, int B, int H, int W, int norm, hipStream_t st, int plan_mode) {
+int tsw4_pass(const float* gd, const float* blur, const float* sparse, float* out, int B, int H, int W, int norm, hipStream_t st, int plan_mode,
+              int C) {
     // the linear plan of the forward passes (cspn2d_tsw_plan.h: one piece per CU, cuts where the longest stream is shortest); band
     // groups with more workgroups than CUs when a piece's table would not fit this loop's LDS
-    const PlanGeo& g = tswplan::make_geo_linear(B, H, W, TSW4_PADF, TSW4_PADB, TSW4_TAB_MAX_ROWS, plan_mode & 3);
+    const PlanGeo& g = tswplan::make_geo_linear(B, H, W, TSW4_PADF, TSW4_PADB, TSW4_TAB_MAX_ROWS, plan_mode & 3, C);
     switch (norm) {
         case 0: tsw4_launch_norm0(sparse != nullptr, g, st, gd, blur, sparse, out); break;
         case 1: tsw4_launch_norm1(sparse != nullptr, g, st, gd, blur, sparse, out); break;

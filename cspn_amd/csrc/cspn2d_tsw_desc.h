@@ -11,7 +11,8 @@ namespace tswplan {
 enum { F_ACTIVE = 0, F_UP = 1, F_DN = 2, F_FIRST = 3, F_LAST = 4, F_OWNED = 5, F_PLAIN = 6 };
 
 // descriptor of stream row q of workgroup wg (zeros: separator / padding row); *Q = number of stream rows of the share
-// dword 0:1 byte offset of (image, channel 0, y, p0) in the guidance tensor, 2 the same in a 1-channel tensor,
+// dword 0:1 byte offset of (image, channel 0, y, p0) in the guidance tensor, 2 the same in a 1-channel tensor (image-channel i of
+// a multi-channel plan: guidance image i / C),
 // 3 flags | (lo - p0) << 8 | (hi - p0) << 20: the band's owned columns travel with every row (a linear plan's piece may
 // continue in the next band)
 __device__ __forceinline__ uint4 tsw_desc(const PlanGeo& g, int wg, int q, int* Q) {
@@ -20,7 +21,8 @@ __device__ __forceinline__ uint4 tsw_desc(const PlanGeo& g, int wg, int q, int* 
     if (wg_stream_row(g, wg, q, s, Q)) {
         int p0, lo, hi;
         band_of(g, s.bi, p0, lo, hi);
-        const unsigned long long goff = 4ull * ((unsigned long long)s.b * 8ull * g.H * g.W + (unsigned long long)s.y * g.W + p0);
+        const int gb = g.C > 1 ? s.b / g.C : s.b;   // (channels on shared guidance: PlanGeo::C)
+        const unsigned long long goff = 4ull * ((unsigned long long)gb * 8ull * g.H * g.W + (unsigned long long)s.y * g.W + p0);
         d[0] = (unsigned)goff;
         d[1] = (unsigned)(goff >> 32);
         d[2] = 4u * (unsigned)(s.b * g.H * g.W + s.y * g.W + p0);

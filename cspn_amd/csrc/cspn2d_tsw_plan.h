@@ -40,6 +40,9 @@ struct PlanGeo {
     // kind 1: xcd != 0 -> piece p runs as workgroup (p % per_xcd) * 8 + p / per_xcd (runs of per_xcd pieces share an XCD).
     int xcd, ng, per_xcd, gpx, extra;
     int kind, kimg;         // kind 1: images per chunk
+    // C > 1: the B images are B / C images of C channels each that share one guidance tensor (image i = b * C + c; 0 and 1 both mean
+    // one channel): the 1-channel offsets follow i, the guidance offsets b = i / C.  The plan itself does not depend on C.
+    int C;
     int cut[MAX_CUT + 1];   // kind 1: piece p = positions [cut[p], cut[p + 1]) of the linear order
 };
 
@@ -188,9 +191,10 @@ __device__ __forceinline__ bool tsw_stream_row(const PlanGeo& g, int r0, int r1,
 
 // ---- kind 0 --------------------------------------------------------------------------------------------------------------------
 // padf / padb: inactive descriptors in front of / behind a stream; tab_max: descriptors that fit in the kernel's LDS table
-inline PlanGeo make_geo(int B, int H, int W, int padf, int padb, int tab_max, int ncu = 0, bool allow_xcd = true) {
+inline PlanGeo make_geo(int B, int H, int W, int padf, int padb, int tab_max, int ncu = 0, bool allow_xcd = true, int C = 1) {
     PlanGeo g;
     memset(&g, 0, sizeof(g));
+    g.C = C;
     if (ncu <= 0) ncu = num_cus();
     g.B = B; g.H = H; g.W = W; g.n_iter = LV;
     g.halo = 4 * ((LV + 3) / 4);
@@ -310,13 +314,15 @@ inline bool make_geo_linear_uncached(PlanGeo& g, int B, int H, int W, int padf, 
 
 // The forward passes' plan.  Falls back to band groups when the linear plan does not apply (n_wg would exceed MAX_CUT).
 // The optimiser costs ~1 ms of host time: the last plans are kept per thread (no shared mutable state).
-inline const PlanGeo& make_geo_linear(int B, int H, int W, int padf, int padb, int tab_max, int mode /*0: default, 1: no XCD placement, 2: band groups*/) {
+// C > 1: B = (images) x C image-channels on shared guidance (PlanGeo::C)
+inline const PlanGeo& make_geo_linear(int B, int H, int W, int padf, int padb, int tab_max, int mode /*0: default, 1: no XCD placement, 2: band groups*/,
+                                      int C = 1) {
     struct Entry { int key[8]; PlanGeo g; };
     constexpr int N = 4;
     thread_local Entry cache[N];
     thread_local int next = 0;
     const int ncu = num_cus();
-    const int key[8] = {1, B, H, W, padf, padb, tab_max, ncu * 4 + mode};
+    const int key[8] = {C, B, H, W, padf, padb, tab_max, ncu * 4 + mode};
     for (int i = 0; i < N; ++i)
         if (!memcmp(cache[i].key, key, sizeof(key))) return cache[i].g;
     Entry& e = cache[next];
@@ -324,6 +330,7 @@ inline const PlanGeo& make_geo_linear(int B, int H, int W, int padf, int padb, i
     memcpy(e.key, key, sizeof(key));
     if (mode == 2 || !make_geo_linear_uncached(e.g, B, H, W, padf, padb, tab_max, ncu, mode != 1))
         e.g = make_geo(B, H, W, padf, padb, tab_max, ncu, mode != 1);
+    e.g.C = C;
     return e.g;
 }
 

@@ -199,6 +199,197 @@ int cspn2d_backward_history_f32(const float* guidance, const float* blur, const 
                               (hipStream_t)stream);
 }
 
+// ---- C channels on shared 2D guidance (include/cspn_amd.h: the cspn2d_*_multi entry points) ----
+static size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+static int check_multi(int B, int C, int sparse_channels, const float* sparse, int H, int W) {
+    if (B < 0 || C <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d C=%d H=%d W=%d", B, C, H, W); return CSPN_E_BADARG; }
+    if (sparse && sparse_channels != 1 && sparse_channels != C) {
+        set_error("sparse has %d channels: 1 (one mask for every channel) or C = %d expected", sparse_channels, C);
+        return CSPN_E_BADARG;
+    }
+    if ((long long)B * C * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing (B*C*H*W)"); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
+// the shared-gate forward: one ring launch per pass over the B*C image-channels (the fused assembly path of the single-channel call)
+static bool multi_fast(int B, int C, int H, int W, int n_iter) { return B > 0 && n_iter > 0 && fused2d_supported(B * C, H, W, n_iter) && tsw2d_supported(B * C, H, W); }
+
+// the per-channel loop of the fallbacks: channel c of a [B][C][HW] tensor <-> a [B][HW] plane
+static hipError_t gather_channel(float* dst, const float* src, int B, int C, int c, size_t HW, hipStream_t st) {
+    return hipMemcpy2DAsync(dst, HW * sizeof(float), src + (size_t)c * HW, (size_t)C * HW * sizeof(float), HW * sizeof(float), B,
+                            hipMemcpyDeviceToDevice, st);
+}
+static hipError_t scatter_channel(float* dst, const float* src, int B, int C, int c, size_t HW, hipStream_t st) {
+    return hipMemcpy2DAsync(dst + (size_t)c * HW, (size_t)C * HW * sizeof(float), src, HW * sizeof(float), HW * sizeof(float), B,
+                            hipMemcpyDeviceToDevice, st);
+}
+#define MULTI_COPY(call)                                                                                  \
+    do {                                                                                                  \
+        hipError_t e_ = (call);                                                                           \
+        if (e_ != hipSuccess) { set_error("hipMemcpy2DAsync: %s", hipGetErrorString(e_)); return (int)e_; } \
+    } while (0)
+
+// a shared mask widened to [B][C][HW] at the front of the workspace (the fast paths)
+static size_t widened_bytes(int B, int C, int H, int W) { return al256(sizeof(float) * (size_t)B * C * H * W); }
+
+static int widen_if_shared(const float*& sparse, int sparse_channels, int B, int C, int H, int W, void* ws, hipStream_t st) {
+    if (!sparse || sparse_channels == C) return 0;
+    if (int e = widen_channels(sparse, (float*)ws, B, C, (size_t)H * W, st)) return e;
+    sparse = (const float*)ws;
+    return 0;
+}
+
+int cspn2d_multi_supported(int B, int C, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (long long)B * C * H * W > 0x7fffffffLL / 9) return 0;
+    return multi_fast(B, C, H, W, n_iter) ? 1 : 0;
+}
+
+size_t cspn2d_workspace_bytes_multi(int B, int C, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
+    if (C == 1) return cspn2d_workspace_bytes(B, H, W, n_iter);
+    const size_t plane = al256(sizeof(float) * (size_t)B * H * W);
+    const size_t loop = 3 * plane + al256(cspn2d_workspace_bytes(B, H, W, n_iter));   // blur, mask and out of one channel + its call's workspace
+    const size_t fast = multi_fast(B, C, H, W, n_iter) ? widened_bytes(B, C, H, W) + fused2d_workspace(B * C, H, W, n_iter) : 0;
+    return loop > fast ? loop : fast;
+}
+
+int cspn2d_forward_multi_f32(const float* guidance, const float* blur, const float* sparse, float* out, int B, int C, int sparse_channels,
+                             int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = check_multi(B, C, sparse_channels, sparse, H, W)) return e;
+    if (C == 1) return cspn2d_forward_f32_algo(guidance, blur, sparse, out, B, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
+    if (B == 0) return 0;
+    if (algo < CSPN_ALGO_AUTO || algo > CSPN_ALGO_FUSED_PADDED) { set_error("unknown algo %d", algo); return CSPN_E_BADARG; }
+    if (int e = check_common(guidance, blur, out, n_iter, norm_type, ws, ws_bytes, n_iter == 0 ? 0 : cspn2d_workspace_bytes_multi(B, C, H, W, n_iter),
+                             CSPN_NORM_PRENORM)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    if (n_iter == 0) {  // reference cspn.py:61,66,83: the loop body never runs
+        hipError_t e = hipMemcpyAsync(out, blur, sizeof(float) * (size_t)B * C * HW, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    // the fast path where the single-channel call would take the assembly ring too (AUTO / FUSED, 16-byte aligned output)
+    if ((algo == CSPN_ALGO_AUTO || algo == CSPN_ALGO_FUSED) && multi_fast(B, C, H, W, n_iter) && ((uintptr_t)out & 15u) == 0) {
+        if (int e = widen_if_shared(sparse, sparse_channels, B, C, H, W, ws, st)) return e;
+        return fused2d_forward(guidance, blur, sparse, out, B * C, H, W, n_iter, norm_type, (char*)ws + widened_bytes(B, C, H, W), st, true, 0, C);
+    }
+    // everything else: channel by channel through the single-channel entry point
+    const size_t plane = al256(sizeof(float) * (size_t)B * HW);
+    float* blur_c = (float*)ws;
+    float* sp_c = (float*)((char*)ws + plane);
+    float* out_c = (float*)((char*)ws + 2 * plane);
+    void* ws_c = (char*)ws + 3 * plane;
+    const size_t ws_c_bytes = cspn2d_workspace_bytes(B, H, W, n_iter);
+    for (int c = 0; c < C; ++c) {
+        MULTI_COPY(gather_channel(blur_c, blur, B, C, c, HW, st));
+        const float* sp = sparse;
+        if (sparse && sparse_channels == C) { MULTI_COPY(gather_channel(sp_c, sparse, B, C, c, HW, st)); sp = sp_c; }
+        if (int e = cspn2d_forward_f32_algo(guidance, blur_c, sp, out_c, B, H, W, n_iter, norm_type, algo, ws_c, ws_c_bytes, stream)) return e;
+        MULTI_COPY(scatter_channel(out, out_c, B, C, c, HW, st));
+    }
+    return 0;
+}
+
+size_t cspn2d_history_bytes_multi(int B, int C, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (long long)B * C * H * W > 0x7fffffffLL / 9) return 0;
+    if (C == 1) return cspn2d_history_bytes(B, H, W, n_iter);
+    return multi_fast(B, C, H, W, n_iter) ? history2d_bytes(B * C, H, W, n_iter) : 0;
+}
+
+int cspn2d_forward_history_multi_f32(const float* guidance, const float* blur, const float* sparse, float* out, void* history,
+                                     size_t history_bytes, int B, int C, int sparse_channels, int H, int W, int n_iter, int norm_type,
+                                     void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = check_multi(B, C, sparse_channels, sparse, H, W)) return e;
+    if (C == 1) return cspn2d_forward_history_f32(guidance, blur, sparse, out, history, history_bytes, B, H, W, n_iter, norm_type, ws, ws_bytes, stream);
+    if (B == 0) { set_error("bad shape B=0"); return CSPN_E_BADARG; }
+    const size_t hb = cspn2d_history_bytes_multi(B, C, H, W, n_iter);
+    if (hb == 0) { set_error("no history mode for B=%d C=%d H=%d W=%d n_iter=%d", B, C, H, W, n_iter); return CSPN_E_UNSUPPORTED; }
+    if (!history || history_bytes < hb || ((uintptr_t)history & 255u)) { set_error("history buffer too small or misaligned: need %zu bytes", hb); return CSPN_E_WORKSPACE; }
+    if (int e = check_common(guidance, blur, out, n_iter, norm_type, ws, ws_bytes, cspn2d_workspace_bytes_multi(B, C, H, W, n_iter), CSPN_NORM_PRENORM)) return e;
+    if (((uintptr_t)out & 15u) != 0) { set_error("output must be 16-byte aligned"); return CSPN_E_UNSUPPORTED; }
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = widen_if_shared(sparse, sparse_channels, B, C, H, W, ws, st)) return e;
+    return forward2d_history(guidance, blur, sparse, out, history, B * C, H, W, n_iter, norm_type, nullptr, st, C);
+}
+
+size_t cspn2d_backward_multi_workspace_bytes(int B, int C, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
+    if (C == 1) return cspn2d_backward_workspace_bytes(B, H, W, n_iter);
+    if (backward2d_multi_supported(B * C, H, W, n_iter)) return widened_bytes(B, C, H, W) + backward2d_workspace(B * C, H, W, n_iter);
+    const size_t plane = al256(sizeof(float) * (size_t)B * H * W);
+    return 4 * plane + 8 * plane + al256(backward2d_workspace(B, H, W, n_iter));   // blur, mask, grad_out, grad_blur of one channel; its grad_guidance
+}
+
+int cspn2d_backward_multi_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out, float* grad_guidance,
+                              float* grad_blur, int B, int C, int sparse_channels, int H, int W, int n_iter, int norm_type,
+                              void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = check_multi(B, C, sparse_channels, sparse, H, W)) return e;
+    if (C == 1) return cspn2d_backward_f32(guidance, blur, sparse, grad_out, grad_guidance, grad_blur, B, H, W, n_iter, norm_type, ws, ws_bytes, stream);
+    if (B == 0) return 0;
+    if (n_iter < 1) { set_error("backward needs n_iter >= 1 (got %d)", n_iter); return CSPN_E_BADARG; }
+    if (!grad_out) { set_error("null grad_out"); return CSPN_E_BADARG; }
+    if (int e = check_common(guidance, blur, grad_out, n_iter, norm_type, ws, ws_bytes, cspn2d_backward_multi_workspace_bytes(B, C, H, W, n_iter),
+                             CSPN_NORM_PRENORM)) return e;
+    if (!grad_guidance && !grad_blur) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t HW = (size_t)H * W;
+    if (backward2d_multi_supported(B * C, H, W, n_iter)) {
+        if (int e = widen_if_shared(sparse, sparse_channels, B, C, H, W, ws, st)) return e;
+        return backward2d(guidance, blur, sparse, grad_out, grad_guidance, grad_blur, B * C, H, W, n_iter, norm_type,
+                          (char*)ws + widened_bytes(B, C, H, W), st, C);
+    }
+    const size_t plane = al256(sizeof(float) * (size_t)B * HW);
+    float* blur_c = (float*)ws;
+    float* sp_c = (float*)((char*)ws + plane);
+    float* go_c = (float*)((char*)ws + 2 * plane);
+    float* gb_c = (float*)((char*)ws + 3 * plane);
+    float* gg_c = (float*)((char*)ws + 4 * plane);
+    void* ws_c = (char*)ws + 12 * plane;
+    const size_t ws_c_bytes = backward2d_workspace(B, H, W, n_iter);
+    for (int c = 0; c < C; ++c) {
+        MULTI_COPY(gather_channel(blur_c, blur, B, C, c, HW, st));
+        MULTI_COPY(gather_channel(go_c, grad_out, B, C, c, HW, st));
+        const float* sp = sparse;
+        if (sparse && sparse_channels == C) { MULTI_COPY(gather_channel(sp_c, sparse, B, C, c, HW, st)); sp = sp_c; }
+        float* gg = grad_guidance ? (c == 0 ? grad_guidance : gg_c) : nullptr;
+        if (int e = cspn2d_backward_f32(guidance, blur_c, sp, go_c, gg, grad_blur ? gb_c : nullptr, B, H, W, n_iter, norm_type, ws_c, ws_c_bytes,
+                                        stream)) return e;
+        if (grad_guidance && c > 0)
+            if (int e = add_inplace(grad_guidance, gg_c, 8 * (size_t)B * HW, st)) return e;
+        if (grad_blur) MULTI_COPY(scatter_channel(grad_blur, gb_c, B, C, c, HW, st));
+    }
+    return 0;
+}
+
+size_t cspn2d_backward_history_multi_workspace_bytes(int B, int C, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    if (C == 1) return cspn2d_backward_history_workspace_bytes(B, H, W, n_iter);
+    if (cspn2d_history_bytes_multi(B, C, H, W, n_iter) == 0) return 0;
+    return widened_bytes(B, C, H, W) + backward2d_history_workspace(B * C, H, W);
+}
+
+int cspn2d_backward_history_multi_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out,
+                                      const void* history, size_t history_bytes, float* grad_guidance, float* grad_blur, int B, int C,
+                                      int sparse_channels, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes,
+                                      cspn_stream_t stream) {
+    if (int e = check_multi(B, C, sparse_channels, sparse, H, W)) return e;
+    if (C == 1) return cspn2d_backward_history_f32(guidance, blur, sparse, grad_out, history, history_bytes, grad_guidance, grad_blur, B, H, W,
+                                                   n_iter, norm_type, ws, ws_bytes, stream);
+    if (B == 0) { set_error("bad shape B=0"); return CSPN_E_BADARG; }
+    const size_t hb = cspn2d_history_bytes_multi(B, C, H, W, n_iter);
+    if (hb == 0) { set_error("no history mode for B=%d C=%d H=%d W=%d n_iter=%d", B, C, H, W, n_iter); return CSPN_E_UNSUPPORTED; }
+    if (!grad_out) { set_error("null grad_out"); return CSPN_E_BADARG; }
+    if (!history || history_bytes < hb) { set_error("history buffer too small: need %zu bytes", hb); return CSPN_E_WORKSPACE; }
+    if (int e = check_common(guidance, blur, grad_out, n_iter, norm_type, ws, ws_bytes, cspn2d_backward_history_multi_workspace_bytes(B, C, H, W, n_iter),
+                             CSPN_NORM_PRENORM)) return e;
+    if (!grad_guidance && !grad_blur) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = widen_if_shared(sparse, sparse_channels, B, C, H, W, ws, st)) return e;
+    return backward2d_history(guidance, blur, sparse, grad_out, history, grad_guidance, grad_blur, B * C, H, W, n_iter, norm_type,
+                              (char*)ws + widened_bytes(B, C, H, W), st, C);
+}
+
 // a persistent 3D launch of an EARLIER call gave up (cspn3d_persistent.hip): report it once, through whichever 3D call comes next
 static int async_failure_of_earlier_call() {
     if (persistent3d_take_status() == 0) return 0;

@@ -93,20 +93,22 @@ size_t fused2d_workspace(int B, int H, int W, int n_iter);
 // plan_mode (test-hook library only; the ABI passes 0): 0 the linear plan, 1 the same without XCD-aware placement, 2 band groups;
 // + 8: the 8-wave x 4-row loop of rounds 1-5 (cspn2d_tsw.hip) also for the passes the round-6 loop (cspn2d_tsw4.hip) would take;
 // + 16: the round-6 loop for every full first pass it supports (also the short streams on which the dispatcher prefers the other)
+// C > 1 (the assembly ring only): B image-channels [B][H][W] on B / C guidance images (cspn2d_forward_multi_f32)
 int fused2d_forward(const float* g, const float* blur, const float* sparse, float* out, int B, int H, int W,
-                    int n_iter, int norm, void* ws, hipStream_t st, bool use_asm = true, int plan_mode = 0);
+                    int n_iter, int norm, void* ws, hipStream_t st, bool use_asm = true, int plan_mode = 0, int C = 1);
 
 // ---- the same ring with the main loop in gfx950 assembly (cspn2d_tsw.hip); one pass = 24 iterations, or -- a FIRST pass only
 // (hin == blur, no history) -- n_early = 1 .. 23 of them ----
 bool tsw2d_supported(int B, int H, int W);
+// C > 1: B image-channels, C of them on each guidance image (cspn2d_tsw_plan.h PlanGeo::C)
 int tsw2d_pass(const float* gd, const float* blur, const float* hin, const float* sparse, float* out, int B, int H,
-               int W, int norm, hipStream_t st, float* hist = nullptr, int plan_mode = 0, int n_early = 0);
+               int W, int norm, hipStream_t st, float* hist = nullptr, int plan_mode = 0, int n_early = 0, int C = 1);
 // ---- round 6: the same ring as 12 waves x 3 rows at 168 VGPRs -- three waves per SIMD (cspn2d_tsw4.hip, tools/tswgen/kernel4.py): FIRST
 // passes of exactly 24 iterations ----
 bool tsw4_supported(int B, int H, int W);
 bool tsw4_preferred(int B, int H, int W, bool sparse);   // long streams on the linear plan: where it is the faster of the two rings
 int tsw4_pass(const float* gd, const float* blur, const float* sparse, float* out, int B, int H, int W, int norm, hipStream_t st,
-              int plan_mode = 0);
+              int plan_mode = 0, int C = 1);
 #ifdef CSPN_EXPERIMENTS
 // ---- experiments kept out of the default build (make EXPERIMENTS=1): the round-3 loop (cspn2d_tsw3.hip: LDS-DMA row slots;
 // ties with the loop above on long streams, slower on short ones: profiles/r03_perf_notes.md) and the sited8 guidance layout ----
@@ -119,17 +121,24 @@ int tsw2d_pass_sited8(const float* g8, const float* blur, const float* sparse, f
                       hipStream_t st);
 int tsw2d_adjoint_pass(const float* wf, const float* a_in, float* a0, int B, int H, int W, hipStream_t st, float* hist);
 
+// ---- multi-channel 2D entry points (cspn2d_multi.hip) ----
+int widen_channels(const float* src, float* dst, int B, int C, size_t HW, hipStream_t st);   // [B][HW] -> [B][C][HW]
+int add_inplace(float* dst, const float* src, size_t n, hipStream_t st);                      // dst += src
+
 // ---- backward of the 2D op (cspn2d_backward.hip) ----
 size_t backward2d_workspace(int B, int H, int W, int n_iter);
+// C > 1 (cspn2d_backward_multi_f32; the assembly sweeps only, backward2d_multi_supported): B counts image-channels [B][H][W], C of them share
+// each of the B / C guidance images; gg [B / C][8][H][W] is the sum over the channels
 int backward2d(const float* g, const float* blur, const float* sparse, const float* gout, float* gg, float* gb, int B, int H,
-               int W, int n_iter, int norm, void* ws, hipStream_t st);
+               int W, int n_iter, int norm, void* ws, hipStream_t st, int C = 1);
+bool backward2d_multi_supported(int BC, int H, int W, int n_iter);
 // training mode: the forward keeps its checkpoints (every fourth level + the folded coefficients; 24-iteration passes the assembly
 // kernel takes), the backward starts there
 size_t history2d_bytes(int B, int H, int W, int n_iter);  // 0: not available for this shape
 int forward2d_history(const float* g, const float* blur, const float* sparse, float* out, void* history, int B, int H, int W,
-                      int n_iter, int norm, void* ws, hipStream_t st);
+                      int n_iter, int norm, void* ws, hipStream_t st, int C = 1);
 size_t backward2d_history_workspace(int B, int H, int W);
 int backward2d_history(const float* g, const float* blur, const float* sparse, const float* gout, const void* history, float* gg,
-                       float* gb, int B, int H, int W, int n_iter, int norm, void* ws, hipStream_t st);
+                       float* gb, int B, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, int C = 1);
 
 }  // namespace cspn

@@ -234,6 +234,112 @@ def cspn2d_backward_from_history(guidance, blur_depth, sparse_depth, grad_out, h
     return gg, gh
 
 
+# ---- C channels on shared 2D guidance (reference cspn.py:58-81 broadcasts the affinities over blur_depth's channels) ----
+def _multi_args(guidance, blur_depth, sparse_depth, extra=()):
+    if guidance.dim() != 4 or guidance.shape[1] != 8:
+        raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
+    B, _, H, W = guidance.shape
+    if blur_depth.dim() != 4 or tuple(blur_depth.shape[:1]) + tuple(blur_depth.shape[2:]) != (B, H, W) or blur_depth.shape[1] < 1:
+        raise ValueError("blur_depth has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(blur_depth.shape), B, H, W))
+    C = blur_depth.shape[1]
+    g = _prep(guidance, "guidance")
+    h = _prep(blur_depth, "blur_depth", (B, C, H, W))
+    s, sc = None, 1
+    if sparse_depth is not None:
+        if sparse_depth.dim() != 4 or sparse_depth.shape[1] not in (1, C):
+            raise ValueError("sparse_depth has shape %s, expected (B,1,H,W) or (B,C,H,W) = (%d,%d,%d,%d)"
+                             % (tuple(sparse_depth.shape), B, C, H, W))
+        sc = sparse_depth.shape[1]
+        s = _prep(sparse_depth, "sparse_depth", (B, sc, H, W))
+    rest = [_prep(t, name, (B, C, H, W)) for t, name in extra]
+    if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
+        raise ValueError("all tensors must live on the same device")
+    return (g, h, s, sc, B, C, H, W) + tuple(rest)
+
+
+def cspn2d_multi_supported(B, C, H, W, n_iter):
+    """True where C channels on shared guidance take the fast path (one ring launch per pass over the B*C image-channels)"""
+    return bool(_lib.late_symbol("cspn2d_multi_supported")(int(B), int(C), int(H), int(W), int(n_iter)))
+
+
+def cspn2d_forward_multi(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum", algo="auto"):
+    """guidance [B,8,H,W], blur_depth [B,C,H,W], sparse_depth None, [B,1,H,W] (one mask for every channel) or [B,C,H,W] -> [B,C,H,W]:
+    the C channels propagated on the same affinities (reference cspn.py:58-81), one engine call (cspn2d_forward_multi_f32)."""
+    g, h, s, sc, B, C, H, W = _multi_args(guidance, blur_depth, sparse_depth)
+    out = torch.empty_like(h)
+    if B == 0:
+        return out
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn2d_workspace_bytes_multi")(B, C, H, W, int(n_iter))
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_forward_multi_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), B, C, sc, H, W, int(n_iter),
+            _lib.NORM_TYPES[norm_type], _lib.ALGOS[algo], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_forward_multi_f32")
+    return out
+
+
+def cspn2d_backward_multi(guidance, blur_depth, sparse_depth, grad_out, n_iter=24, norm_type="8sum", need_guidance=True, need_blur=True):
+    """Gradient of cspn2d_forward_multi: -> (grad_guidance [B,8,H,W] summed over the C channels or None, grad_blur [B,C,H,W] or None);
+    one engine call (cspn2d_backward_multi_f32)."""
+    g, h, s, sc, B, C, H, W, go = _multi_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    if B == 0 or not (need_guidance or need_blur):
+        return gg, gh
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn2d_backward_multi_workspace_bytes")(B, C, H, W, int(n_iter))
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_backward_multi_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(), gg.data_ptr() if gg is not None else None,
+            gh.data_ptr() if gh is not None else None, B, C, sc, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes,
+            torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_backward_multi_f32")
+    return gg, gh
+
+
+def cspn2d_history_bytes_multi(B, C, H, W, n_iter):
+    """bytes of the training-mode history of C channels on shared guidance (0: not available for this shape)"""
+    return int(_lib.late_symbol("cspn2d_history_bytes_multi")(int(B), int(C), int(H), int(W), int(n_iter)))
+
+
+def cspn2d_forward_with_history_multi(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum"):
+    """Training-mode cspn2d_forward_multi: (out [B,C,H,W], history) -- checkpoints and folded planes per image-channel."""
+    g, h, s, sc, B, C, H, W = _multi_args(guidance, blur_depth, sparse_depth)
+    out = torch.empty_like(h)
+    with torch.cuda.device(g.device):
+        hb = cspn2d_history_bytes_multi(B, C, H, W, n_iter)
+        if hb == 0:
+            raise _lib.CspnError("cspn_amd: no history mode for B=%d C=%d H=%d W=%d, n_iter %d" % (B, C, H, W, n_iter))
+        hist = torch.empty(hb, dtype=torch.uint8, device=g.device)
+        ws_bytes = _lib.late_symbol("cspn2d_workspace_bytes_multi")(B, C, H, W, int(n_iter))
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_forward_history_multi_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), hist.data_ptr(), hb, B, C, sc, H, W,
+            int(n_iter), _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_forward_history_multi_f32")
+    return out, hist
+
+
+def cspn2d_backward_from_history_multi(guidance, blur_depth, sparse_depth, grad_out, history, n_iter=24, norm_type="8sum",
+                                       need_guidance=True, need_blur=True):
+    """Gradients as cspn2d_backward_multi, starting from the history cspn2d_forward_with_history_multi kept."""
+    g, h, s, sc, B, C, H, W, go = _multi_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    if not (need_guidance or need_blur):
+        return gg, gh
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn2d_backward_history_multi_workspace_bytes")(B, C, H, W, int(n_iter))
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_backward_history_multi_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(), history.data_ptr(), history.numel(),
+            gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None, B, C, sc, H, W, int(n_iter),
+            _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_backward_history_multi_f32")
+    return gg, gh
+
+
 def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", algo="auto", _return_ws=False):
     """gate [B,26,D,H,W], feat [B,1,D,H,W] -> [B,1,D,H,W]; n_iter 3x3x3 propagation steps.  algo: 'auto' | 'stepwise'
     (one launch per step) | 'persistent' (gates resident in registers across the steps; norm_type 'none' without a mask)."""
@@ -370,6 +476,22 @@ class _AffinityPropagateMultiFunction(torch.autograd.Function):
         return gx, gg, None
 
 
+class _AffinityPropagate2dMultiFunction(torch.autograd.Function):
+    """2D, C > 1 input channels on shared gates: cspn2d_forward_multi / cspn2d_backward_multi (the gate gradient summed in the engine)"""
+
+    @staticmethod
+    def forward(ctx, x, gate_weight, n_iter):
+        ctx.n_iter = int(n_iter)
+        ctx.save_for_backward(x, gate_weight)
+        return cspn2d_forward_multi(gate_weight, x, None, n_iter, "none")
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gate_weight = ctx.saved_tensors
+        gg, gx = cspn2d_backward_multi(gate_weight, x, None, grad_out, ctx.n_iter, "none", ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gx, gg, None
+
+
 class _AffinityPropagateFunction(torch.autograd.Function):
     """n_iter chained propagation steps with the same gates, one input channel; differentiable w.r.t. both arguments."""
 
@@ -415,6 +537,11 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     if d == 3 and C > 1 and needs_grad and input.is_cuda:
         # training through C channels on shared gates (demo.py:65-75): one forward and one backward call for all of them
         return _AffinityPropagateMultiFunction.apply(input.contiguous(), gate_weight.contiguous(), n_iter)
+    if d == 2 and C > 1:
+        # C channels on shared gates (README.md:56): one forward and one backward engine call for all of them
+        if needs_grad:
+            return _AffinityPropagate2dMultiFunction.apply(input, gate_weight, n_iter)
+        return cspn2d_forward_multi(gate_weight, input, None, n_iter, "none")
     outs = []
     for c in range(C):  # gates shared across channels (README.md:56)
         x = input[:, c:c + 1].contiguous()

@@ -45,7 +45,8 @@ extern "C" {
                               *    sited8 experiment's three entry points left the ABI (hook library, experiment builds); CSPN_ALGO_FUSED_PADDED
                               *    (what AUTO returns for W % 4 != 0; cspn2d_workspace_bytes grows accordingly for such widths);
                               * 5: cspn_guidance_head_f32 (the producer of the path's inputs) and cspn_guidance_head_backward_f32; CSPN_NORM_PRENORM on the 2D backward entry points;
-                              *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32 */
+                              *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32,
+                              *    the cspn2d_*_multi entry points (C channels on shared 2D guidance) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -257,6 +258,38 @@ size_t cspn_guidance_head_workspace_bytes(int C);
 int cspn_guidance_head_f32(const float* x, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out,
                            int B, int C, int h, int w, int H, int W, int norm_type,
                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- 2D, C channels on SHARED guidance (reference cspn.py:58-81 only multiplies and broadcasts: a blur_depth [B,C,H,W] is propagated
+ * channel by channel on the same normalised affinities; the Paddle contract says the same, cspn_paddle/README.md:56).
+ *   guidance [B,8,H,W] (or gate_wb for PRENORM), blur / out / grad_out / grad_blur [B,C,H,W],
+ *   sparse NULL, [B,1,H,W] (sparse_channels 1: one mask for every channel) or [B,C,H,W] (sparse_channels C)
+ *   grad_guidance [B,8,H,W] = the gradient SUMMED over the channels (what autograd accumulates into the shared tensor).
+ * cspn2d_multi_supported() != 0 where the shared-gate fast path takes the call: ONE ring launch per pass over the B*C image-channels (image-channel
+ * b*C + c reads guidance image b), so a short batch of several channels fills the device the way a longer batch does; a shared mask is widened
+ * to [B,C,H,W] in the workspace first.  The backward's two sweeps run over the B*C image-channels as well; its final pass runs once per channel and
+ * adds that channel's part of grad_guidance to the previous ones (channel order: deterministic).  Everywhere else (W < 256, W % 4 != 0,
+ * other n_iter, the STEPWISE / FUSED_CXX / FUSED_PADDED algos, misaligned tensors) the library loops over the channels itself (each channel
+ * gathered into the workspace, propagated by the single-channel entry point, scattered back; the guidance gradients summed by a HIP kernel):
+ * the same results as a per-channel loop of the single-channel calls.  The history pair (training mode) only where the fast path holds
+ * (cspn2d_history_bytes_multi() > 0).  `B*C*H*W` is bounded like `B*H*W` of the single-channel calls.  With C = 1 (and sparse_channels 1)
+ * every entry point runs the single-channel one it mirrors. */
+size_t cspn2d_workspace_bytes_multi(int B, int C, int H, int W, int n_iter);
+int cspn2d_multi_supported(int B, int C, int H, int W, int n_iter);
+int cspn2d_forward_multi_f32(const float* guidance, const float* blur, const float* sparse, float* out, int B, int C, int sparse_channels,
+                             int H, int W, int n_iter, int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_history_bytes_multi(int B, int C, int H, int W, int n_iter);
+int cspn2d_forward_history_multi_f32(const float* guidance, const float* blur, const float* sparse, float* out, void* history,
+                                     size_t history_bytes, int B, int C, int sparse_channels, int H, int W, int n_iter, int norm_type,
+                                     void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_multi_workspace_bytes(int B, int C, int H, int W, int n_iter);
+int cspn2d_backward_multi_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out, float* grad_guidance,
+                              float* grad_blur, int B, int C, int sparse_channels, int H, int W, int n_iter, int norm_type,
+                              void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_history_multi_workspace_bytes(int B, int C, int H, int W, int n_iter);
+int cspn2d_backward_history_multi_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out,
+                                      const void* history, size_t history_bytes, float* grad_guidance, float* grad_blur, int B, int C,
+                                      int sparse_channels, int H, int W, int n_iter, int norm_type, void* workspace, size_t workspace_bytes,
+                                      cspn_stream_t stream);
 
 /* The gradient of the raw heads (norm_type NONE above): what torch autograd computes through the two reference layers when the training loop back-propagates
  * through torch_resnet_cspn_nyu.py:372-373.  grad_guidance [B,8,H,W] and grad_blur [B,1,H,W] (with w_blur; both or neither) are dL/d(outputs);
