@@ -139,6 +139,11 @@ _LATE_SYMBOLS = {
     "cspn2d_backward_history_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cspn2d_backward_history_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
                                           + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the demo's gate normalisation (reference cspn_paddle/demo.py:24,34-36,47-49) and the 3D module on raw gates
+    "cspn_gate_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn_gate_absnorm_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn3d_forward_absnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn3d_forward_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

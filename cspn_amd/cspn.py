@@ -126,3 +126,30 @@ class Affinity_Propagate(nn.Module):
 
     def extra_repr(self):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
+
+
+class CSPN(nn.Module):
+    """reference cspn_paddle/demo.py:10-54 (the demo's module): same constructor, same cspn(guide, feat) -- also the forward.  guide
+    [N, feat_chan*K, *S] raw (K = 3^dim_num - 1), feat [N, feat_chan, *S]: abs, each channel's slice of K gates divided by its abs-sum,
+    prop_step chained propagations (F.absnorm_propagate: one engine call for all channels, the 3D normalisation inside the persistent
+    kernel).  A port of demo.py changes its imports and tensor types, nothing else."""
+
+    def __init__(self, dim_num, feat_chan, prop_kernel, prop_step):
+        super(CSPN, self).__init__()
+        assert prop_kernel == 3, 'only the 3 x 3 (x 3) neighbourhood is supported'   # (demo.py:90)
+        assert dim_num in (2, 3), 'dim_num must be 2 or 3'   # (demo.py:87)
+        self.dim_num = dim_num
+        self.feat_chan = feat_chan
+        self.prop_kernel = prop_kernel
+        self.prop_step = prop_step
+
+    def cspn(self, guide, feat):
+        if feat.dim() != self.dim_num + 2:
+            raise ValueError("feat must have %d dimensions for dim_num %d, got %s" % (self.dim_num + 2, self.dim_num, tuple(feat.shape)))
+        return F.absnorm_propagate(guide, feat, self.prop_step)
+
+    def forward(self, guide, feat):
+        return self.cspn(guide, feat)
+
+    def extra_repr(self):
+        return "dim_num=%d, feat_chan=%d, prop_kernel=%d, prop_step=%d" % (self.dim_num, self.feat_chan, self.prop_kernel, self.prop_step)

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "cspn_common.h"
+#include "cspn_gate_norm.h"
 
 // P3_ROWS_PLAIN / P3_ROWS_CF / P3_NO_PRIO / P3_LYP: A/B builds of the round-5 row assignment (correct results, tools/r05/build_p3var.sh)
 #if (defined(P3_EXP_NOPOLL) || defined(P3_EXP_NOWAIT) || defined(P3_EXP_LANE_REMAP) || defined(P3_EXP_NT) || defined(P3_PRESLEEP)) && \
@@ -165,11 +166,14 @@ __device__ __forceinline__ void lds_dma16(unsigned byte_off, const float* base, 
 // MULTI (round 4): feat / out hold C value channels per volume that share the gates (reference cspn_paddle/README.md:56: "gate_weight
 // would be shared in the channel dimension for input when C>1"): the gates of a chunk are loaded ONCE and stay in the registers
 // while the n_iter steps are run for one channel after the other (only level 0 is re-read per channel, 4 B/voxel against 104)
-template <bool ADJ, bool HASC, bool MUTE = false, bool MULTI = false>
+// NRM: `gate` holds the demo's RAW guide (reference cspn_paddle/demo.py:24,34-36,47-49): the resident gates of every voxel inside the
+// volume are divided by their abs-sum in the registers (cspn_gate_norm.h, the stand-alone normaliser's arithmetic), no HBM bytes for it
+template <bool ADJ, bool HASC, bool MUTE = false, bool MULTI = false, bool NRM = false>
 __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) void cspn3d_persistent_kernel(const float* __restrict__ gate, const float* __restrict__ feat,
                                                                  const float* __restrict__ cprime, float* __restrict__ out,
                                                                  float* __restrict__ levels, float* __restrict__ scratch,
                                                                  unsigned* __restrict__ sync, Geo3 g) {
+    static_assert(!NRM || (!ADJ && !HASC && !MULTI), "the normalising instance is a forward on raw gates of one value channel");
     __shared__ __attribute__((aligned(16))) float lds[2 * LTILE];
     __shared__ __attribute__((aligned(16))) float4 s_c[HASC ? 2 * NTP : 1];   // c' of the thread's two quads, [quad][thread]
     constexpr int NPRE = Pre3<ADJ, HASC>::N;
@@ -487,6 +491,21 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     } else {
                         w[k][0] = in0 ? w[k][0] : zero;
                         w[k][1] = in1 ? w[k][1] : zero;
+                    }
+                }
+                if (NRM) {
+                    // w_k = |g_k| / sum_j |g_j| per voxel, inside the volume only: the gates outside stay 0 (0 / 0 = NaN there would
+                    // reach the valid voxels through 0 * NaN).  After the wait and the opaque statements above: the loads are in.
+                    // Outside, r = 0 instead of a select: |0| * 0 keeps the 0 without a second copy of the gates.  One voxel at a time
+                    // (the opaque statement): eight interleaved reductions and divisions do not fit beside the 208 gate registers.
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int q = e >> 2, c = e & 3;
+                        const float r = (q ? in1 : in0) ? absnorm_rcp<26>([&](int k) { return w[k][q][c]; }) : 0.f;
+#pragma unroll
+                        for (int k = 0; k < 26; ++k) w[k][q][c] = absnorm_gate(w[k][q][c], r);
+#pragma unroll
+                        for (int k = 0; k < 26; ++k) asm volatile("" : "+v"(w[k][q]));
                     }
                 }
                 P3_CHUNK(1);
@@ -808,7 +827,8 @@ int resident_wgs() {
         int occ = WG_PER_CU;
         const void* fns[] = {(const void*)cspn3d_persistent_kernel<false, false>, (const void*)cspn3d_persistent_kernel<false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false>, (const void*)cspn3d_persistent_kernel<false, false, false, true>,
-                             (const void*)cspn3d_persistent_kernel<true, false, false, true>};
+                             (const void*)cspn3d_persistent_kernel<true, false, false, true>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, true>};
         for (const void* fn : fns) {
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, NTP, 0) == hipSuccess && nb < occ) occ = nb < 0 ? 0 : nb;
@@ -892,7 +912,8 @@ size_t persistent3d_workspace(int B, int D, int H, int W) {
 // adjoint: the transposed operator (backward); levels: volume lv0 + it * lvs receives the result of step it < n_iter;
 // cprime != nullptr: gate holds the 26 folded planes [26][B][V] and cprime the constant term (normalising / masked modes)
 static int persistent3d_launch(const float* gate, const float* feat, const float* cprime, float* out, float* levels, int lv0, int lvs,
-                               bool adjoint, int B, int D, int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C = 1) {
+                               bool adjoint, int B, int D, int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C = 1,
+                               bool nrm = false) {
     Geo3 g = make_geo3(B, D, H, W, n_iter, opt.placement);
     g.C = C;
     g.wt = opt.write_through ? 1 : 0;
@@ -946,7 +967,8 @@ static int persistent3d_launch(const float* gate, const float* feat, const float
     }
     g.status = d.status_dev;
     void* args[] = {(void*)&gate, (void*)&feat, (void*)&cprime, (void*)&out, (void*)&levels, (void*)&scratch, (void*)&sync, (void*)&g};
-    const void* fn = cprime ? (const void*)cspn3d_persistent_kernel<false, true>
+    const void* fn = nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true>
+                   : cprime ? (const void*)cspn3d_persistent_kernel<false, true>
                    : adjoint ? (C > 1 ? (const void*)cspn3d_persistent_kernel<true, false, false, true> : (const void*)cspn3d_persistent_kernel<true, false>)
                    : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true>
                    : mute >= 0 ? (const void*)cspn3d_persistent_kernel<false, false, true> : (const void*)cspn3d_persistent_kernel<false, false>;
@@ -1020,6 +1042,13 @@ int persistent3d_forward_multi(const float* gate, const float* feat, float* out,
 int persistent3d_forward(const float* gate, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
                          hipStream_t st) {
     return persistent3d_run(gate, feat, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st);
+}
+
+// the demo's module (reference cspn_paddle/demo.py:24,34-36,47-49 then :41-43): `guide` holds the RAW gates [B][26][V], normalised per voxel
+// in the registers after the chunk's gate loads (NRM).  Takes exactly the calls persistent3d_supported takes.
+int persistent3d_forward_absnorm(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                                 hipStream_t st) {
+    return persistent3d_launch(guide, feat, nullptr, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), 1, true);
 }
 
 // (test-hook library) the plan of a persistent launch: info[9] = tz, ty, cx, tiles, workgroups launched, bz, by, bx (0: plain order), chunks

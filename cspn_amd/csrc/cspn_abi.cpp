@@ -55,6 +55,26 @@ static int check_common(const void* a, const void* b, const void* out, int n_ite
     return 0;
 }
 
+// argument checks of the gate normaliser entry points (cspn_gate_absnorm_f32 / _backward_f32)
+static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bn && y < x + an;
+}
+
+static int absnorm_check(const char* what, const float* guide, const float* a, const float* out, int N, int K, size_t V) {
+    if (!guide || !a || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (N <= 0 || V == 0) { set_error("%s: bad shape N=%d V=%zu", what, N, V); return CSPN_E_BADARG; }
+    if (K != 8 && K != 26) { set_error("%s: K must be 8 (2D) or 26 (3D), got %d", what, K); return CSPN_E_BADARG; }
+    if ((size_t)N * V > ((size_t)1 << 39)) { set_error("%s: N * V = %zu voxels is beyond the launch grid", what, (size_t)N * V); return CSPN_E_UNSUPPORTED; }
+    const size_t bytes = sizeof(float) * (size_t)N * K * V;
+    if (overlaps(out, bytes, guide, bytes) || overlaps(out, bytes, a, bytes)) { set_error("%s: the output must not alias an input", what); return CSPN_E_BADARG; }
+    return 0;
+}
+
+static size_t absnorm_planes_bytes(int B, int D, int H, int W) {   // the normalised gates of the unfused path, 256-byte multiple
+    return (26 * sizeof(float) * (size_t)B * D * H * W + 255) & ~(size_t)255;
+}
+
 }  // namespace cspn
 
 using namespace cspn;
@@ -517,6 +537,59 @@ int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float*
         return 0;
     }
     return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, st, false, C);
+}
+
+
+// ---- the demo's module (reference cspn_paddle/demo.py:20-54): w = |g| / sum_k |g_k| per voxel over one slice's K gates, then the NONE op ----
+int cspn_gate_absnorm_f32(const float* guide, float* gate, int N, int K, size_t V, cspn_stream_t stream) {
+    if (int e = absnorm_check("cspn_gate_absnorm_f32", guide, guide, gate, N, K, V)) return e;
+    return gate_absnorm(guide, gate, N, K, V, (hipStream_t)stream);
+}
+
+int cspn_gate_absnorm_backward_f32(const float* guide, const float* grad_gate, float* grad_guide, int N, int K, size_t V,
+                                   cspn_stream_t stream) {
+    if (int e = absnorm_check("cspn_gate_absnorm_backward_f32", guide, grad_gate, grad_guide, N, K, V)) return e;
+    return gate_absnorm_backward(guide, grad_gate, grad_guide, N, K, V, (hipStream_t)stream);
+}
+
+size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_iter) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
+    return absnorm_planes_bytes(B, D, H, W) + forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false);
+}
+
+int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
+                               void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (B < 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d D=%d H=%d W=%d", B, D, H, W); return CSPN_E_BADARG; }
+    if (B == 0) return 0;
+    if ((long long)B * D * H * W > 0x7fffffffLL / 27) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
+    const size_t total = (size_t)B * D * H * W;
+    if (guide && feat && out && (overlaps(out, total * sizeof(float), guide, 26 * total * sizeof(float)) || overlaps(out, total * sizeof(float), feat, total * sizeof(float)))) {
+        set_error("cspn3d_forward_absnorm_f32: out must not alias an input");
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = async_failure_of_earlier_call()) return e;
+    // misaligned feat / out take the folding path after the normaliser: its 27 planes more (as cspn3d_forward_f32 with such tensors)
+    const bool vals_aligned = ((((uintptr_t)feat | (uintptr_t)out) & 15u) == 0);
+    const size_t need = n_iter == 0 ? 0 : absnorm_planes_bytes(B, D, H, W) + (vals_aligned ? forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false)
+                                                                                            : stepwise3d_workspace(B, D, H, W, n_iter));
+    if (int e = check_common(guide, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes, need)) return e;
+    if (n_iter == 0) {
+        hipError_t e = hipMemcpyAsync(out, feat, sizeof(float) * total, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    const bool fused = vals_aligned && ((((uintptr_t)guide | (uintptr_t)ws) & 15u) == 0) && persistent3d_supported(B, D, H, W, n_iter);
+    if (algo == CSPN_ALGO3D_PERSISTENT && !fused) {
+        set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
+        return CSPN_E_UNSUPPORTED;
+    }
+    if (fused && algo != CSPN_ALGO3D_STEPWISE) return persistent3d_forward_absnorm(guide, feat, out, B, D, H, W, n_iter, ws, st);
+    // unfused: the normaliser into the workspace, then the NONE op on it
+    float* gate = (float*)ws;
+    if (int e = gate_absnorm(guide, gate, B, 26, (size_t)D * H * W, st)) return e;
+    return stepwise3d_forward(gate, feat, nullptr, out, B, D, H, W, n_iter, CSPN_NORM_NONE, (char*)ws + absnorm_planes_bytes(B, D, H, W), st, algo);
 }
 
 }  // extern "C"

@@ -68,9 +68,18 @@ bool persistent3d_multi_supported(int B, int C, int D, int H, int W, int n_iter)
 int persistent3d_forward_multi(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter, void* ws,
                                hipStream_t st);
 
+// the demo's module on RAW gates (NRM instantiation): each voxel's 26 gates divided by their abs-sum in the registers, then the n_iter
+// steps of persistent3d_forward; same calls as persistent3d_supported
+int persistent3d_forward_absnorm(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                                 hipStream_t st);
+
 // sticky per-device status of the persistent launches: != 0 once after a launch gave up (a workgroup waited in vain for a
 // neighbour: not all workgroups resident); read without synchronisation from a pinned host word, cleared by the read
 int persistent3d_take_status();
+
+// ---- the demo's gate normalisation (cspn_gate_norm.hip): guide [N][K][V] -> w_k = |g_k| / sum_j |g_j|, and its adjoint; K = 8 or 26 ----
+int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t st);
+int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

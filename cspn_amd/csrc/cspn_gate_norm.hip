@@ -1,0 +1,157 @@
+// cspn_gate_norm.hip -- the demo's gate normalisation as a stand-alone streaming pass and its adjoint (reference cspn_paddle/demo.py:24,
+// 34-36,47-49): guide [N][K][V] raw -> gate [N][K][V], w_k(p) = |g_k(p)| / sum_j |g_j(p)| per voxel p over the K = 3^d - 1 gate channels of
+// one slice (K = 26 in 3D, 8 in 2D).  The arithmetic form is cspn_gate_norm.h's, which the fused persistent 3D instance uses as well.
+//   forward   K * 4 B read + K * 4 B written per voxel
+//   backward  dL/dg_k = sign(g_k) (dL/dw_k - sum_j w_j dL/dw_j) / S, S = sum_j |g_j|, sign(0) = 0 (torch's abs backward): S and w are
+//             recomputed from g (no saved w, no workspace), every output element is written once (no atomics); 2 K * 4 B read +
+//             K * 4 B written per voxel.  An all-zero voxel gives NaN in all K gradients, as torch does (0 * NaN).
+// 16-byte loads (four voxels per thread) where V % 4 == 0 and every pointer is 16-byte aligned, one voxel per thread everywhere else.
+// Index arithmetic in size_t: N K V reaches 1.3 G elements at config 5.
+#include <initializer_list>
+
+#include "cspn_common.h"
+#include "cspn_gate_norm.h"
+
+namespace cspn {
+
+namespace {
+
+constexpr int NT = 256;
+
+__device__ __forceinline__ float sign0(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+
+template <int K>
+__global__ __launch_bounds__(NT) void gate_absnorm_kernel(const float* __restrict__ g, float* __restrict__ w, size_t V, size_t total) {
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;   // voxel of the N V
+    if (i >= total) return;
+    const size_t n = i / V, p = i - n * V;
+    const float* gb = g + n * K * V + p;
+    float* wb = w + n * K * V + p;
+    float x[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) x[k] = gb[(size_t)k * V];
+    const float r = absnorm_rcp<K>([&](int k) { return x[k]; });
+#pragma unroll
+    for (int k = 0; k < K; ++k) wb[(size_t)k * V] = absnorm_gate(x[k], r);
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void gate_absnorm_kernel4(const float* __restrict__ g, float* __restrict__ w, size_t V4, size_t total4) {
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;   // quad of the N V / 4
+    if (i >= total4) return;
+    const size_t n = i / V4, p = i - n * V4;
+    const float4* gb = reinterpret_cast<const float4*>(g) + n * K * V4 + p;
+    float4* wb = reinterpret_cast<float4*>(w) + n * K * V4 + p;
+    float4 x[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) x[k] = gb[(size_t)k * V4];
+    const float r0 = absnorm_rcp<K>([&](int k) { return x[k].x; }), r1 = absnorm_rcp<K>([&](int k) { return x[k].y; });
+    const float r2 = absnorm_rcp<K>([&](int k) { return x[k].z; }), r3 = absnorm_rcp<K>([&](int k) { return x[k].w; });
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        wb[(size_t)k * V4] = make_float4(absnorm_gate(x[k].x, r0), absnorm_gate(x[k].y, r1), absnorm_gate(x[k].z, r2), absnorm_gate(x[k].w, r3));
+}
+
+// one voxel's adjoint: x = raw gates, d = dL/dw in, out = dL/dg (d may be overwritten)
+template <int K>
+__device__ __forceinline__ void absnorm_adjoint(const float (&x)[K], float (&d)[K]) {
+    const float r = absnorm_rcp<K>([&](int k) { return x[k]; });
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) t = fmaf(absnorm_gate(x[k], r), d[k], t);
+#pragma unroll
+    for (int k = 0; k < K; ++k) d[k] = sign0(x[k]) * ((d[k] - t) * r);
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void gate_absnorm_backward_kernel(const float* __restrict__ g, const float* __restrict__ gw, float* __restrict__ gg,
+                                                                   size_t V, size_t total) {
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= total) return;
+    const size_t n = i / V, p = i - n * V, o = n * K * V + p;
+    float x[K], d[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        x[k] = g[o + (size_t)k * V];
+        d[k] = gw[o + (size_t)k * V];
+    }
+    absnorm_adjoint<K>(x, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) gg[o + (size_t)k * V] = d[k];
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void gate_absnorm_backward_kernel4(const float* __restrict__ g, const float* __restrict__ gw, float* __restrict__ gg,
+                                                                    size_t V4, size_t total4) {
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= total4) return;
+    const size_t n = i / V4, p = i - n * V4, o = n * K * V4 + p;
+    const float4* gb = reinterpret_cast<const float4*>(g) + o;
+    const float4* db = reinterpret_cast<const float4*>(gw) + o;
+    float4* ob = reinterpret_cast<float4*>(gg) + o;
+    float4 x4[K], d4[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        x4[k] = gb[(size_t)k * V4];
+        d4[k] = db[(size_t)k * V4];
+    }
+    float x[K], d[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { x[k] = x4[k].x; d[k] = d4[k].x; }
+    absnorm_adjoint<K>(x, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) { d4[k].x = d[k]; x[k] = x4[k].y; d[k] = d4[k].y; }
+    absnorm_adjoint<K>(x, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) { d4[k].y = d[k]; x[k] = x4[k].z; d[k] = d4[k].z; }
+    absnorm_adjoint<K>(x, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) { d4[k].z = d[k]; x[k] = x4[k].w; d[k] = d4[k].w; }
+    absnorm_adjoint<K>(x, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) { d4[k].w = d[k]; ob[(size_t)k * V4] = d4[k]; }
+}
+
+bool vec4_ok(size_t V, std::initializer_list<const void*> ptrs) {
+    if (V % 4) return false;
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 15u) return false;
+    return true;
+}
+
+template <int K>
+int absnorm_launch(const float* g, float* w, int N, size_t V, hipStream_t st) {
+    if (vec4_ok(V, {g, w})) {
+        const size_t t4 = (size_t)N * (V / 4);
+        hipLaunchKernelGGL(gate_absnorm_kernel4<K>, dim3((unsigned)((t4 + NT - 1) / NT)), dim3(NT), 0, st, g, w, V / 4, t4);
+    } else {
+        const size_t t = (size_t)N * V;
+        hipLaunchKernelGGL(gate_absnorm_kernel<K>, dim3((unsigned)((t + NT - 1) / NT)), dim3(NT), 0, st, g, w, V, t);
+    }
+    return check_launch("gate_absnorm_kernel");
+}
+
+template <int K>
+int absnorm_backward_launch(const float* g, const float* gw, float* gg, int N, size_t V, hipStream_t st) {
+    if (vec4_ok(V, {g, gw, gg})) {
+        const size_t t4 = (size_t)N * (V / 4);
+        hipLaunchKernelGGL(gate_absnorm_backward_kernel4<K>, dim3((unsigned)((t4 + NT - 1) / NT)), dim3(NT), 0, st, g, gw, gg, V / 4, t4);
+    } else {
+        const size_t t = (size_t)N * V;
+        hipLaunchKernelGGL(gate_absnorm_backward_kernel<K>, dim3((unsigned)((t + NT - 1) / NT)), dim3(NT), 0, st, g, gw, gg, V, t);
+    }
+    return check_launch("gate_absnorm_backward_kernel");
+}
+
+}  // namespace
+
+// K in {8, 26}, N >= 1, V >= 1, N V < 2^31 * 256 (one thread per voxel or quad): checked by the caller (cspn_abi.cpp)
+int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t st) {
+    return K == 26 ? absnorm_launch<26>(g, w, N, V, st) : absnorm_launch<8>(g, w, N, V, st);
+}
+
+int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st) {
+    return K == 26 ? absnorm_backward_launch<26>(g, gw, gg, N, V, st) : absnorm_backward_launch<8>(g, gw, gg, N, V, st);
+}
+
+}  // namespace cspn

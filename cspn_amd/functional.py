@@ -552,3 +552,169 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
         else:
             outs.append(cspn3d_forward(gate_weight, x, None, n_iter, "none"))
     return outs[0] if C == 1 else torch.cat(outs, 1)
+
+
+# ---- the demo's module (reference cspn_paddle/demo.py:20-54): abs (:24), each channel's slice of K = 3^d - 1 gates divided by its own
+# channel sum (:25,31-36,47-49), prop_step chained propagations (:40-43,50-52) ----
+def _absnorm_flat(guide, K):
+    """guide [N, M, *S] with M % K == 0 -> the flat (N M / K, V) the C ABI takes"""
+    if not isinstance(guide, torch.Tensor):
+        raise TypeError("guide must be a torch.Tensor")
+    if K not in (8, 26):
+        raise ValueError("K must be 8 (2D) or 26 (3D), got %r" % (K,))
+    if guide.dim() < 3 or guide.shape[1] % K != 0 or guide.shape[1] == 0:
+        raise ValueError("guide must be [N, C*%d, *S], got %s" % (K, tuple(guide.shape)))
+    V = 1
+    for s in guide.shape[2:]:
+        V *= int(s)
+    return guide.shape[0] * (guide.shape[1] // K), V
+
+
+def _gate_absnorm(guide, K):
+    S, V = _absnorm_flat(guide, K)
+    g = _prep(guide, "guide")
+    out = torch.empty_like(g)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(g.device):
+        rc = _lib.late_symbol("cspn_gate_absnorm_f32")(g.data_ptr(), out.data_ptr(), S, K, V, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn_gate_absnorm_f32")
+    return out
+
+
+def gate_absnorm_backward(guide, grad_gate, K):
+    """The adjoint of gate_absnorm (cspn_gate_absnorm_backward_f32): guide raw, grad_gate = dL/dw, both [N, C*K, *S] -> dL/dguide,
+    sign(g_k) (dL/dw_k - sum_j w_j dL/dw_j) / sum_j |g_j| per slice (sign(0) = 0, torch's abs backward; NaN for an all-zero voxel)."""
+    S, V = _absnorm_flat(guide, K)
+    g = _prep(guide, "guide")
+    r = _prep(grad_gate, "grad_gate", tuple(g.shape))
+    if r.device != g.device:
+        raise _lib.CspnError("cspn_amd: guide is on %s, grad_gate on %s: all tensors must live on the same device" % (g.device, r.device))
+    out = torch.empty_like(g)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(g.device):
+        rc = _lib.late_symbol("cspn_gate_absnorm_backward_f32")(g.data_ptr(), r.data_ptr(), out.data_ptr(), S, K, V,
+                                                                torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn_gate_absnorm_backward_f32")
+    return out
+
+
+class _GateAbsnormFunction(torch.autograd.Function):
+    """gate_absnorm under autograd: keeps the raw guide, the backward is one cspn_gate_absnorm_backward_f32 launch"""
+
+    @staticmethod
+    def forward(ctx, guide, K):
+        ctx.K = K
+        ctx.save_for_backward(guide)
+        return _gate_absnorm(guide, K)
+
+    @staticmethod
+    def backward(ctx, grad_gate):
+        guide, = ctx.saved_tensors
+        return gate_absnorm_backward(guide, grad_gate, ctx.K), None
+
+
+def gate_absnorm(guide, K):
+    """The demo's gate normalisation (reference cspn_paddle/demo.py:24,34-36,47-49) as one HIP pass: guide [N, C*K, *S] -> w of the same
+    shape, w_k = |g_k| / sum_j |g_j| per voxel over each channel's slice of K gates (K = 26 in 3D, 8 in 2D; the sum in channel order;
+    NaN where a slice is all zero, as torch's 0 / 0).  Differentiable w.r.t. guide when grad mode is on and guide requires grad."""
+    if torch.is_grad_enabled() and isinstance(guide, torch.Tensor) and guide.requires_grad:
+        return _GateAbsnormFunction.apply(guide, K)
+    return _gate_absnorm(guide, K)
+
+
+def cspn3d_forward_absnorm(guide, feat, n_iter=12, algo="auto"):
+    """guide [B,26,D,H,W] RAW, feat [B,1,D,H,W] -> [B,1,D,H,W]: gate_absnorm(guide, 26), then cspn3d_forward(..., 'none') -- one engine call
+    (cspn3d_forward_absnorm_f32).  algo 'auto' normalises the resident gates inside the persistent kernel wherever the NONE op would take
+    it; 'stepwise' normalises into the workspace and steps; 'persistent' raises CspnError where the kernel cannot take the call."""
+    if guide.dim() != 5 or guide.shape[1] != 26:
+        raise ValueError("guide must be [B,26,D,H,W], got %s" % (tuple(guide.shape),))
+    B, _, D, H, W = guide.shape
+    g = _prep(guide, "guide")
+    h = _prep(feat, "feat", (B, 1, D, H, W))
+    if h.device != g.device:
+        raise _lib.CspnError("cspn_amd: guide is on %s, feat on %s: all tensors must live on the same device" % (g.device, h.device))
+    if h.data_ptr() % 16:
+        h = h.clone()   # (an aligned copy: misaligned values would need the folding path's workspace)
+    out = torch.empty_like(h)
+    if B == 0:
+        return out
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn3d_forward_absnorm_workspace_bytes")(B, D, H, W, int(n_iter))
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn3d_forward_absnorm_f32")(g.data_ptr(), h.data_ptr(), out.data_ptr(), B, D, H, W, int(n_iter),
+                                                            _lib.ALGOS_3D[algo], ws.data_ptr(), ws_bytes,
+                                                            torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn3d_forward_absnorm_f32")
+    return out
+
+
+def _absnorm_fold(guide, feat):
+    """per-channel gates are batch folding: [N, C*K, *S] -> [N*C, K, *S] and [N, C, *S] -> [N*C, 1, *S] (views, no copy)"""
+    N, C = feat.shape[:2]
+    S = tuple(feat.shape[2:])
+    K = 3 ** len(S) - 1
+    return guide.view(N * C, K, *S), feat.view(N * C, 1, *S), K
+
+
+def _absnorm_forward(guide, feat, n_iter):
+    g, x, K = _absnorm_fold(guide, feat)
+    if K == 26:
+        out = cspn3d_forward_absnorm(g, x, n_iter)
+    else:   # 2D: the normaliser, then the NONE op (the 2D loop is generated assembly: no fused normalisation there)
+        out = cspn2d_forward(_gate_absnorm(g, 8), x, None, n_iter, "none")
+    return out.view(feat.shape)
+
+
+class _AbsnormPropagateFunction(torch.autograd.Function):
+    """the demo's module under autograd: the backward recomputes w with the normaliser, runs the NONE op's backward on the folded N*C
+    batch and chains the gate gradient through cspn_gate_absnorm_backward_f32"""
+
+    @staticmethod
+    def forward(ctx, guide, feat, n_iter):
+        ctx.n_iter = n_iter
+        ctx.save_for_backward(guide, feat)
+        return _absnorm_forward(guide, feat, n_iter)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guide, feat = ctx.saved_tensors
+        need_g, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g, x, K = _absnorm_fold(guide, feat)
+        w = _gate_absnorm(g, K)
+        go = grad_out.contiguous().view(x.shape)
+        if K == 26:
+            gw, gx = cspn3d_backward(w, x, go, ctx.n_iter, need_g, need_x)
+        else:
+            gw, gx = cspn2d_backward(w, x, None, go, ctx.n_iter, "none", need_g, need_x)
+        gg = gate_absnorm_backward(g, gw, K).view(guide.shape) if need_g else None
+        return gg, gx.view(feat.shape) if need_x else None, None
+
+
+def absnorm_propagate(guide, feat, n_iter):
+    """The demo's CSPN.cspn (reference cspn_paddle/demo.py:20-54) as a function: feat [N,C,*S] (len(S) = 2 or 3), guide [N, C*K, *S] raw
+    with K = 3^len(S) - 1; channel c is propagated on its OWN slice guide[:, c*K:(c+1)*K], normalised by its abs-sum at every voxel, for
+    n_iter chained steps.  One engine call for all channels (they fold into the batch).  3D: cspn3d_forward_absnorm_f32 (the
+    normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none').  Differentiable
+    w.r.t. guide and feat.  n_iter == 0 returns feat itself."""
+    for t, name in ((guide, "guide"), (feat, "feat")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    if feat.dim() not in (4, 5):
+        raise ValueError("feat must be [N,C,H,W] or [N,C,D,H,W], got %s" % (tuple(feat.shape),))
+    K = 3 ** (feat.dim() - 2) - 1
+    N, C = feat.shape[:2]
+    if tuple(guide.shape) != (N, C * K) + tuple(feat.shape[2:]):
+        raise ValueError("guide has shape %s, expected (N, C*%d, *S) = %s" % (tuple(guide.shape), K, (N, C * K) + tuple(feat.shape[2:])))
+    if int(n_iter) < 0:
+        raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
+    if int(n_iter) == 0:
+        return feat
+    g = _prep(guide, "guide")
+    x = _prep(feat, "feat")
+    if g.device != x.device:
+        raise _lib.CspnError("cspn_amd: guide is on %s, feat on %s: all tensors must live on the same device" % (g.device, x.device))
+    if torch.is_grad_enabled() and (guide.requires_grad or feat.requires_grad):
+        return _AbsnormPropagateFunction.apply(g, x, int(n_iter))
+    return _absnorm_forward(g, x, int(n_iter))

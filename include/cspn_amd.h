@@ -46,7 +46,8 @@ extern "C" {
                               *    (what AUTO returns for W % 4 != 0; cspn2d_workspace_bytes grows accordingly for such widths);
                               * 5: cspn_guidance_head_f32 (the producer of the path's inputs) and cspn_guidance_head_backward_f32; CSPN_NORM_PRENORM on the 2D backward entry points;
                               *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32,
-                              *    the cspn2d_*_multi entry points (C channels on shared 2D guidance) */
+                              *    the cspn2d_*_multi entry points (C channels on shared 2D guidance), the demo's gate normalisation
+                              *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -218,6 +219,33 @@ size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, 
 int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat,
                               int B, int C, int D, int H, int W, int n_iter,
                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the demo's module (reference cspn_paddle/demo.py:20-54, CSPN.cspn): guide = abs(guide) (:24), each slice of K = 3^d - 1 gate
+ * channels divided by its own channel sum at the voxel (:34-36,47-49), then the chained propagation (:40-43,50-52) -- what a port of the
+ * demo otherwise writes in torch in front of cspn3d_forward_f32 with CSPN_NORM_NONE.  Throughout w_k = |g_k| * r, r = 1 / S,
+ * S = sum_{j=0..K-1} |g_j| added in channel order (one arithmetic form for the stand-alone and the fused kernel: bitwise equal);
+ * an all-zero voxel gives 0 * inf = NaN, where torch's 0 / 0 gives NaN.
+ * cspn_gate_absnorm_f32: guide [N,K,V] raw -> gate [N,K,V] = w (K = 8 or 26; V = voxels of a slice).  K * 4 B read + K * 4 B written per voxel.
+ * cspn_gate_absnorm_backward_f32: the adjoint, guide [N,K,V] raw, grad_gate = dL/dw -> grad_guide = dL/dguide
+ *   dL/dg_k = sign(g_k) (dL/dw_k - sum_j w_j dL/dw_j) * r, sign(0) = 0 (torch's abs backward): S and w are recomputed from guide, no
+ *   workspace, no atomics (every output element written once); NaN in all K gradients of an all-zero voxel, as torch.
+ * Both: any N, V >= 1 and 4-byte-aligned pointers (16-byte loads where V % 4 == 0 and every pointer is 16-byte aligned); K other than
+ * 8 / 26, a null pointer or an output that overlaps an input: CSPN_E_BADARG.
+ * cspn3d_forward_absnorm_f32: guide [B,26,D,H,W] RAW, feat / out [B,1,D,H,W]: the result of cspn_gate_absnorm_f32 followed by
+ *   cspn3d_forward_f32(..., CSPN_NORM_NONE).  algo (CSPN_ALGO3D_*): AUTO normalises the resident gates inside the persistent kernel
+ *   (no HBM bytes for it) wherever the NONE op would take the persistent kernel (W % 4 == 0, 2 <= n_iter <= 60, 16-byte aligned
+ *   guide / feat / out / workspace, the volume fits the device), and elsewhere normalises into the workspace and runs the NONE op on it;
+ *   STEPWISE always takes that second route (one launch per step); PERSISTENT returns CSPN_E_UNSUPPORTED where the kernel cannot take
+ *   the call.  Workspace: cspn3d_forward_absnorm_workspace_bytes() covers both routes for 16-byte aligned feat / out (misaligned ones
+ *   need cspn3d_workspace_bytes() more, as the folding path after the normaliser).  n_iter = 0 copies feat to out.  Failures of the
+ *   persistent kernel are reported as for cspn3d_forward_f32: CSPN_E_ASYNC and cspn3d_check_status.  Gradients: the backward of the
+ *   NONE op on w (cspn3d_backward_f32) chained through cspn_gate_absnorm_backward_f32. */
+int cspn_gate_absnorm_f32(const float* guide, float* gate, int N, int K, size_t V, cspn_stream_t stream);
+int cspn_gate_absnorm_backward_f32(const float* guide, const float* grad_gate, float* grad_guide, int N, int K, size_t V,
+                                   cspn_stream_t stream);
+size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_iter);
+int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
+                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
