@@ -144,6 +144,14 @@ _LATE_SYMBOLS = {
     "cspn_gate_absnorm_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
     "cspn3d_forward_absnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cspn3d_forward_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (fluid.layers.affinity_propagate's kernel_size)
+    "cspn2d_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "cspn2d_kxk_history_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "cspn2d_forward_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 6
+                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "cspn2d_backward_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
+                                + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

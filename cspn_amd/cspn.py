@@ -130,14 +130,15 @@ class Affinity_Propagate(nn.Module):
 
 class CSPN(nn.Module):
     """reference cspn_paddle/demo.py:10-54 (the demo's module): same constructor, same cspn(guide, feat) -- also the forward.  guide
-    [N, feat_chan*K, *S] raw (K = 3^dim_num - 1), feat [N, feat_chan, *S]: abs, each channel's slice of K gates divided by its abs-sum,
-    prop_step chained propagations (F.absnorm_propagate: one engine call for all channels, the 3D normalisation inside the persistent
-    kernel).  A port of demo.py changes its imports and tensor types, nothing else."""
+    [N, feat_chan*K, *S] raw (K = prop_kernel^dim_num - 1; prop_kernel 3, or 5 / 7 in 2D), feat [N, feat_chan, *S]: abs, each channel's
+    slice of K gates divided by its abs-sum, prop_step chained propagations (F.absnorm_propagate: one engine call for all channels, the 3D
+    normalisation inside the persistent kernel, the K x K engine for prop_kernel 5 / 7).  A port of demo.py changes its imports and tensor types, nothing else."""
 
     def __init__(self, dim_num, feat_chan, prop_kernel, prop_step):
         super(CSPN, self).__init__()
-        assert prop_kernel == 3, 'only the 3 x 3 (x 3) neighbourhood is supported'   # (demo.py:90)
         assert dim_num in (2, 3), 'dim_num must be 2 or 3'   # (demo.py:87)
+        assert prop_kernel == 3 or (dim_num == 2 and prop_kernel in (5, 7)), \
+            'the neighbourhood is 3 x 3 (x 3), or 5 x 5 / 7 x 7 in 2D'   # (demo.py:90)
         self.dim_num = dim_num
         self.feat_chan = feat_chan
         self.prop_kernel = prop_kernel
@@ -146,7 +147,7 @@ class CSPN(nn.Module):
     def cspn(self, guide, feat):
         if feat.dim() != self.dim_num + 2:
             raise ValueError("feat must have %d dimensions for dim_num %d, got %s" % (self.dim_num + 2, self.dim_num, tuple(feat.shape)))
-        return F.absnorm_propagate(guide, feat, self.prop_step)
+        return F.absnorm_propagate(guide, feat, self.prop_step, self.prop_kernel)
 
     def forward(self, guide, feat):
         return self.cspn(guide, feat)

@@ -5,6 +5,8 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
+#include <utility>
 
 #include "cspn_common.h"
 
@@ -64,7 +66,10 @@ static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
 static int absnorm_check(const char* what, const float* guide, const float* a, const float* out, int N, int K, size_t V) {
     if (!guide || !a || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (N <= 0 || V == 0) { set_error("%s: bad shape N=%d V=%zu", what, N, V); return CSPN_E_BADARG; }
-    if (K != 8 && K != 26) { set_error("%s: K must be 8 (2D) or 26 (3D), got %d", what, K); return CSPN_E_BADARG; }
+    if (K != 8 && K != 26 && K != 24 && K != 48) {
+        set_error("%s: K must be 8 (2D), 26 (3D), 24 or 48 (2D 5 x 5 / 7 x 7), got %d", what, K);
+        return CSPN_E_BADARG;
+    }
     if ((size_t)N * V > ((size_t)1 << 39)) { set_error("%s: N * V = %zu voxels is beyond the launch grid", what, (size_t)N * V); return CSPN_E_UNSUPPORTED; }
     const size_t bytes = sizeof(float) * (size_t)N * K * V;
     if (overlaps(out, bytes, guide, bytes) || overlaps(out, bytes, a, bytes)) { set_error("%s: the output must not alias an input", what); return CSPN_E_BADARG; }
@@ -73,6 +78,38 @@ static int absnorm_check(const char* what, const float* guide, const float* a, c
 
 static size_t absnorm_planes_bytes(int B, int D, int H, int W) {   // the normalised gates of the unfused path, 256-byte multiple
     return (26 * sizeof(float) * (size_t)B * D * H * W + 255) & ~(size_t)255;
+}
+
+// ---- the K x K entry points (cspn2d_*_kxk*) ----
+static bool kxk_shape_ok(int B, int C, int H, int W, int K, int n_iter) {
+    return B > 0 && C > 0 && H > 0 && W > 0 && (K == 5 || K == 7) && n_iter >= 0 && (long long)B * C * H * W <= 0x7fffffffLL &&
+           (long long)B * (K * K - 1) * H * W <= 0x7fffffffLL;
+}
+
+static int kxk_check_shape(const char* what, int B, int C, int H, int W, int K, int n_iter) {
+    if (K != 5 && K != 7) { set_error("%s: K must be 5 or 7, got %d", what, K); return CSPN_E_BADARG; }
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (n_iter < 0) { set_error("%s: n_iter must be >= 0 (got %d)", what, n_iter); return CSPN_E_BADARG; }
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter)) { set_error("%s: tensor too large for 32-bit element indexing", what); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
+static size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static size_t kxk_values_bytes(int B, int C, int H, int W) { return sizeof(float) * (size_t)B * C * H * W; }
+
+static int kxk_check_ws(const char* what, const void* ws, size_t ws_bytes, size_t need) {
+    if (need && (!ws || ws_bytes < need)) { set_error("%s: workspace too small: need %zu bytes, got %zu", what, need, ws_bytes); return CSPN_E_WORKSPACE; }
+    if (need && ((uintptr_t)ws & 255u)) { set_error("%s: workspace must be 256-byte aligned", what); return CSPN_E_WORKSPACE; }
+    return 0;
+}
+
+// an output range that overlaps any of the (pointer, bytes) ranges given; null pointers and empty ranges are skipped
+static bool kxk_overlaps(const void* out, size_t out_bytes, std::initializer_list<std::pair<const void*, size_t>> others) {
+    if (!out || !out_bytes) return false;
+    for (const auto& o : others)
+        if (o.first && o.second && overlaps(out, out_bytes, o.first, o.second)) return true;
+    return false;
 }
 
 }  // namespace cspn
@@ -590,6 +627,81 @@ int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out
     float* gate = (float*)ws;
     if (int e = gate_absnorm(guide, gate, B, 26, (size_t)D * H * W, st)) return e;
     return stepwise3d_forward(gate, feat, nullptr, out, B, D, H, W, n_iter, CSPN_NORM_NONE, (char*)ws + absnorm_planes_bytes(B, D, H, W), st, algo);
+}
+
+
+// ---- the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (cspn2d_kxk.hip) ----
+size_t cspn2d_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
+    return sizeof(float) * kxk_level_floats((size_t)B * C * H * W) * (n_iter == 2 ? 1 : 2);
+}
+
+size_t cspn2d_kxk_history_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
+    return kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1);
+}
+
+int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H, int W,
+                           int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_forward_kxk_f32";
+    if (!gate || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1);
+    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = history ? 0 : cspn2d_kxk_workspace_bytes(B, C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{gate, gb}, {x, vb}, {history, hb}, {ws, wb}}) || kxk_overlaps(history, hb, {{gate, gb}, {x, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {
+        hipError_t e = hipMemcpyAsync(out, x, vb, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_forward(gate, x, out, history, B, C, H, W, K, n_iter, ws, st);
+}
+
+size_t cspn2d_backward_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
+    return round256(kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1));
+}
+
+int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                            float* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                            cspn_stream_t stream) {
+    static const char* what = "cspn2d_backward_kxk_f32";
+    if (!gate || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1);
+    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
+    if (grad_gate && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the gate gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_workspace_bytes(B, C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = grad_gate ? hb : 0;
+    if (grad_gate && grad_gate == grad_x) { set_error("%s: grad_gate and grad_x must not alias", what); return CSPN_E_BADARG; }
+    if (kxk_overlaps(grad_gate, gb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_x, vb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_gate, grad_x and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_gate && !grad_x) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {   // the identity: dL/dx = dL/dout, no gate is read
+        hipError_t e = grad_x ? hipMemcpyAsync(grad_x, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, gb, st);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_backward(gate, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
 }
 
 }  // extern "C"

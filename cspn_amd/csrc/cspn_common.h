@@ -77,9 +77,20 @@ int persistent3d_forward_absnorm(const float* guide, const float* feat, float* o
 // neighbour: not all workgroups resident); read without synchronisation from a pinned host word, cleared by the read
 int persistent3d_take_status();
 
-// ---- the demo's gate normalisation (cspn_gate_norm.hip): guide [N][K][V] -> w_k = |g_k| / sum_j |g_j|, and its adjoint; K = 8 or 26 ----
+// ---- the demo's gate normalisation (cspn_gate_norm.hip): guide [N][K][V] -> w_k = |g_k| / sum_j |g_j|, and its adjoint; K = 8, 24, 26
+// or 48 ----
 int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t st);
 int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st);
+
+// ---- the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (cspn2d_kxk.hip): gate [N][K*K-1][H][W], values [N][C][H][W] ----
+// a level of the forward's ping-pong workspace, rounded to 64 floats so that both levels stay 256-byte aligned
+inline size_t kxk_level_floats(size_t L) { return (L + 63) & ~(size_t)63; }
+// hist: NULL (the levels ping-pong in ws: 2 levels of kxk_level_floats) or H_1 .. H_{n-1}, level t at hist + (t - 1) N C H W
+int kxk_forward(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
+                hipStream_t st);
+// ws: A_1 .. A_{n-1} ((n - 1) N C H W floats); gg (summed over C) and gx may each be NULL; hist as the forward kept it
+int kxk_backward(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W, int K,
+                 int n_iter, void* ws, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

@@ -1,6 +1,6 @@
 // cspn_gate_norm.hip -- the demo's gate normalisation as a stand-alone streaming pass and its adjoint (reference cspn_paddle/demo.py:24,
 // 34-36,47-49): guide [N][K][V] raw -> gate [N][K][V], w_k(p) = |g_k(p)| / sum_j |g_j(p)| per voxel p over the K = 3^d - 1 gate channels of
-// one slice (K = 26 in 3D, 8 in 2D).  The arithmetic form is cspn_gate_norm.h's, which the fused persistent 3D instance uses as well.
+// one slice (K = 26 in 3D, 8 in 2D; 24 and 48 for the 2D 5 x 5 and 7 x 7 neighbourhoods of cspn2d_kxk.hip).  The arithmetic form is cspn_gate_norm.h's, which the fused persistent 3D instance uses as well.
 //   forward   K * 4 B read + K * 4 B written per voxel
 //   backward  dL/dg_k = sign(g_k) (dL/dw_k - sum_j w_j dL/dw_j) / S, S = sum_j |g_j|, sign(0) = 0 (torch's abs backward): S and w are
 //             recomputed from g (no saved w, no workspace), every output element is written once (no atomics); 2 K * 4 B read +
@@ -143,15 +143,32 @@ int absnorm_backward_launch(const float* g, const float* gw, float* gg, int N, s
     return check_launch("gate_absnorm_backward_kernel");
 }
 
+// K = 48 (7 x 7): one voxel per thread in the adjoint -- four voxels' raw gates and gradients would not fit the registers
+int absnorm_backward_launch48(const float* g, const float* gw, float* gg, int N, size_t V, hipStream_t st) {
+    const size_t t = (size_t)N * V;
+    hipLaunchKernelGGL(gate_absnorm_backward_kernel<48>, dim3((unsigned)((t + NT - 1) / NT)), dim3(NT), 0, st, g, gw, gg, V, t);
+    return check_launch("gate_absnorm_backward_kernel");
+}
+
 }  // namespace
 
-// K in {8, 26}, N >= 1, V >= 1, N V < 2^31 * 256 (one thread per voxel or quad): checked by the caller (cspn_abi.cpp)
+// K in {8, 24, 26, 48}, N >= 1, V >= 1, N V < 2^31 * 256 (one thread per voxel or quad): checked by the caller (cspn_abi.cpp)
 int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t st) {
-    return K == 26 ? absnorm_launch<26>(g, w, N, V, st) : absnorm_launch<8>(g, w, N, V, st);
+    switch (K) {
+        case 26: return absnorm_launch<26>(g, w, N, V, st);
+        case 24: return absnorm_launch<24>(g, w, N, V, st);
+        case 48: return absnorm_launch<48>(g, w, N, V, st);
+        default: return absnorm_launch<8>(g, w, N, V, st);
+    }
 }
 
 int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st) {
-    return K == 26 ? absnorm_backward_launch<26>(g, gw, gg, N, V, st) : absnorm_backward_launch<8>(g, gw, gg, N, V, st);
+    switch (K) {
+        case 26: return absnorm_backward_launch<26>(g, gw, gg, N, V, st);
+        case 24: return absnorm_backward_launch<24>(g, gw, gg, N, V, st);
+        case 48: return absnorm_backward_launch48(g, gw, gg, N, V, st);
+        default: return absnorm_backward_launch<8>(g, gw, gg, N, V, st);
+    }
 }
 
 }  // namespace cspn

@@ -514,14 +514,137 @@ class _AffinityPropagateFunction(torch.autograd.Function):
         return gx, gg, None
 
 
+# ---- the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (cspn2d_kxk.hip): gate channel k is the k-th pair (t, l) in raster order over
+# {0..K-1}^2 without the centre, neighbour offset (K//2 - t, K//2 - l) ----
+def _kxk_shape(gate, x, kernel_size, extra=()):
+    K = _check_kernel_size(kernel_size, x.dim() if isinstance(x, torch.Tensor) else 4)
+    if K == 3:
+        raise ValueError("the K x K engine takes kernel_size 5 or 7; 3 x 3 is cspn2d_forward / affinity_propagate")
+    if gate.dim() != 4 or gate.shape[1] != K * K - 1:
+        raise ValueError("gate must be [N,%d,H,W] for kernel_size %d, got %s" % (K * K - 1, K, tuple(gate.shape)))
+    N, _, H, W = gate.shape
+    if x.dim() != 4 or x.shape[0] != N or tuple(x.shape[2:]) != (H, W) or x.shape[1] < 1:
+        raise ValueError("x has shape %s, expected (N,C,H,W) = (%d,C,%d,%d)" % (tuple(x.shape), N, H, W))
+    C = x.shape[1]
+    for t, name in extra:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (N, C, H, W):
+            raise ValueError("%s must be a tensor of shape %s" % (name, (N, C, H, W)))
+    return K, N, C, H, W
+
+
+def _kxk_args(gate, x, kernel_size, extra=()):
+    K, N, C, H, W = _kxk_shape(gate, x, kernel_size, extra)
+    g = _prep(gate, "gate")
+    h = _prep(x, "x")
+    rest = [_prep(t, name, (N, C, H, W)) for t, name in extra]
+    if any(t.device != g.device for t in [h] + rest):
+        raise ValueError("all tensors must live on the same device")
+    return (g, h, K, N, C, H, W) + tuple(rest)
+
+
+def _check_kernel_size(kernel_size, dim):
+    if isinstance(kernel_size, bool) or not isinstance(kernel_size, int):
+        raise ValueError("kernel_size must be an int, got %r" % (kernel_size,))
+    if kernel_size < 3 or kernel_size > 7 or kernel_size % 2 == 0:
+        raise ValueError("kernel_size must be 3, 5 or 7 (odd, 3 <= K <= 7), got %d" % kernel_size)
+    if kernel_size != 3 and dim != 4:
+        raise ValueError("kernel_size %d is 2D only (input [N,C,H,W]); 3D takes the 3 x 3 x 3 neighbourhood" % kernel_size)
+    return kernel_size
+
+
+def cspn2d_forward_kxk(gate, x, kernel_size, n_iter, return_history=False):
+    """gate [N,K*K-1,H,W] used as given (centre-sited, no centre term, any sign), x [N,C,H,W] -> H_n [N,C,H,W] with
+    H_{t+1}(p) = sum_k gate_k(p) H_t(p + off_k), zero outside, the C channels on the shared gates (cspn2d_forward_kxk_f32).
+    K = kernel_size in {5, 7}.  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk.  n_iter == 0 returns x."""
+    _kxk_shape(gate, x, kernel_size)
+    n = int(n_iter)
+    if n < 0:
+        raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
+    if n == 0:
+        return (x, None) if return_history else x
+    g, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size)
+    out = torch.empty_like(h)
+    hist = None
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    with torch.cuda.device(g.device):
+        if return_history:
+            hb = _lib.late_symbol("cspn2d_kxk_history_bytes")(N, C, H, W, K, n)
+            hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+            ws_bytes, ws = 0, None
+        else:
+            hb = 0
+            ws_bytes = _lib.late_symbol("cspn2d_kxk_workspace_bytes")(N, C, H, W, K, n)
+            ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_forward_kxk_f32")(
+            g.data_ptr(), h.data_ptr(), out.data_ptr(), hist.data_ptr() if hist is not None else None, hb, N, C, H, W, K, n,
+            ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_forward_kxk_f32")
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk(gate, x, grad_out, kernel_size, n_iter, history=None, need_gate=True, need_x=True):
+    """Gradient of cspn2d_forward_kxk -> (dL/dgate [N,K*K-1,H,W] summed over the C channels or None, dL/dx [N,C,H,W] or None);
+    cspn2d_backward_kxk_f32.  history: what cspn2d_forward_kxk(..., return_history=True) returned; None runs that forward first
+    where the gate gradient needs it."""
+    g, h, K, N, C, H, W, go = _kxk_args(gate, x, kernel_size, ((grad_out, "grad_out"),))
+    n = int(n_iter)
+    if n < 0:
+        raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
+    gg = torch.empty_like(g) if need_gate else None
+    gx = torch.empty_like(h) if need_x else None
+    if not (need_gate or need_x):
+        return gg, gx
+    if h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), gx
+    if need_gate and n >= 2 and history is None:
+        _, history = cspn2d_forward_kxk(g, h, K, n, return_history=True)
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_workspace_bytes")(N, C, H, W, K, n)
+        ws = _workspace(ws_bytes, g.device)
+        hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
+        rc = _lib.late_symbol("cspn2d_backward_kxk_f32")(
+            g.data_ptr(), h.data_ptr(), hp, hb, go.data_ptr(), gg.data_ptr() if gg is not None else None,
+            gx.data_ptr() if gx is not None else None, N, C, H, W, K, n, ws.data_ptr(), ws_bytes,
+            torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_backward_kxk_f32")
+    return gg, gx
+
+
+class _AffinityPropagateKxKFunction(torch.autograd.Function):
+    """2D K x K, any C on shared gates: the forward keeps H_1 .. H_{n-1}, the backward is one cspn2d_backward_kxk_f32 call"""
+
+    @staticmethod
+    def forward(ctx, x, gate_weight, kernel_size, n_iter):
+        ctx.kernel_size, ctx.n_iter = kernel_size, n_iter
+        out, hist = cspn2d_forward_kxk(gate_weight, x, kernel_size, n_iter, return_history=True)
+        ctx.save_for_backward(x, gate_weight, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gate_weight, hist = ctx.saved_tensors
+        gg, gx = cspn2d_backward_kxk(gate_weight, x, grad_out, ctx.kernel_size, ctx.n_iter, hist, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gx, gg, None, None
+
+
 def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     """Mirror of fluid.layers.affinity_propagate (reference cspn_paddle/demo.py:41-43,50-52;
-    contract cspn_paddle/README.md:54-56): input [N,C,...], gate_weight [N,3**d-1,...] already
+    contract cspn_paddle/README.md:54-56): input [N,C,...], gate_weight [N,kernel_size**d-1,...] already
     normalised over the channel dim by the caller, shared across the C input channels.
-    d = 2 or 3.  n_iter > 1 fuses that many chained calls (demo.py:39,50).  Differentiable w.r.t. input and
-    gate_weight like the reference op (the demo trains through it, demo.py:65-75)."""
+    d = 2 or 3; kernel_size 3, or 5 / 7 in 2D (the K x K engine, cspn2d_forward_kxk).  n_iter > 1 fuses that many chained calls
+    (demo.py:39,50).  Differentiable w.r.t. input and gate_weight like the reference op (the demo trains through it, demo.py:65-75)."""
     if kernel_size != 3:
-        raise ValueError("only kernel_size == 3 is supported (reference cspn_paddle/demo.py:90)")
+        if not isinstance(input, torch.Tensor) or not isinstance(gate_weight, torch.Tensor):
+            raise TypeError("input and gate_weight must be torch.Tensor")
+        K = _check_kernel_size(kernel_size, input.dim())
+        if gate_weight.dim() != 4 or gate_weight.shape[1] != K * K - 1:
+            raise ValueError("gate_weight must have %d channels for kernel_size %d, got %s" % (K * K - 1, K, tuple(gate_weight.shape)))
+        if int(n_iter) == 0:
+            return input
+        if torch.is_grad_enabled() and (input.requires_grad or gate_weight.requires_grad):
+            return _AffinityPropagateKxKFunction.apply(input, gate_weight, K, int(n_iter))
+        return cspn2d_forward_kxk(gate_weight, input, K, n_iter)
     d = input.dim() - 2
     if d not in (2, 3):
         raise ValueError("input must be [N,C,H,W] or [N,C,D,H,W]")
@@ -560,8 +683,8 @@ def _absnorm_flat(guide, K):
     """guide [N, M, *S] with M % K == 0 -> the flat (N M / K, V) the C ABI takes"""
     if not isinstance(guide, torch.Tensor):
         raise TypeError("guide must be a torch.Tensor")
-    if K not in (8, 26):
-        raise ValueError("K must be 8 (2D) or 26 (3D), got %r" % (K,))
+    if K not in (8, 26, 24, 48):
+        raise ValueError("K must be 8 (2D), 26 (3D), 24 or 48 (2D 5 x 5 / 7 x 7), got %r" % (K,))
     if guide.dim() < 3 or guide.shape[1] % K != 0 or guide.shape[1] == 0:
         raise ValueError("guide must be [N, C*%d, *S], got %s" % (K, tuple(guide.shape)))
     V = 1
@@ -617,7 +740,8 @@ class _GateAbsnormFunction(torch.autograd.Function):
 
 def gate_absnorm(guide, K):
     """The demo's gate normalisation (reference cspn_paddle/demo.py:24,34-36,47-49) as one HIP pass: guide [N, C*K, *S] -> w of the same
-    shape, w_k = |g_k| / sum_j |g_j| per voxel over each channel's slice of K gates (K = 26 in 3D, 8 in 2D; the sum in channel order;
+    shape, w_k = |g_k| / sum_j |g_j| per voxel over each channel's slice of K gates (K = 26 in 3D, 8 in 2D, 24 / 48 for the 2D 5 x 5 / 7 x 7
+    neighbourhoods; the sum in channel order;
     NaN where a slice is all zero, as torch's 0 / 0).  Differentiable w.r.t. guide when grad mode is on and guide requires grad."""
     if torch.is_grad_enabled() and isinstance(guide, torch.Tensor) and guide.requires_grad:
         return _GateAbsnormFunction.apply(guide, K)
@@ -650,60 +774,71 @@ def cspn3d_forward_absnorm(guide, feat, n_iter=12, algo="auto"):
     return out
 
 
-def _absnorm_fold(guide, feat):
+def _absnorm_fold(guide, feat, kernel_size=3):
     """per-channel gates are batch folding: [N, C*K, *S] -> [N*C, K, *S] and [N, C, *S] -> [N*C, 1, *S] (views, no copy)"""
     N, C = feat.shape[:2]
     S = tuple(feat.shape[2:])
-    K = 3 ** len(S) - 1
+    K = kernel_size ** len(S) - 1
     return guide.view(N * C, K, *S), feat.view(N * C, 1, *S), K
 
 
-def _absnorm_forward(guide, feat, n_iter):
-    g, x, K = _absnorm_fold(guide, feat)
+def _absnorm_forward(guide, feat, n_iter, kernel_size=3, keep_history=False):
+    """-> (out, history): history is the K x K forward's H_1 .. H_{n-1} where keep_history asks for it, else None"""
+    g, x, K = _absnorm_fold(guide, feat, kernel_size)
+    hist = None
     if K == 26:
         out = cspn3d_forward_absnorm(g, x, n_iter)
-    else:   # 2D: the normaliser, then the NONE op (the 2D loop is generated assembly: no fused normalisation there)
+    elif K == 8:   # 2D: the normaliser, then the NONE op (the 2D loop is generated assembly: no fused normalisation there)
         out = cspn2d_forward(_gate_absnorm(g, 8), x, None, n_iter, "none")
-    return out.view(feat.shape)
+    else:          # 2D K x K: the normaliser, then the K x K engine
+        out = cspn2d_forward_kxk(_gate_absnorm(g, K), x, kernel_size, n_iter, return_history=keep_history)
+        if keep_history:
+            out, hist = out
+    return out.view(feat.shape), hist
 
 
 class _AbsnormPropagateFunction(torch.autograd.Function):
     """the demo's module under autograd: the backward recomputes w with the normaliser, runs the NONE op's backward on the folded N*C
-    batch and chains the gate gradient through cspn_gate_absnorm_backward_f32"""
+    batch and chains the gate gradient through cspn_gate_absnorm_backward_f32 (K x K: the forward keeps its levels for the backward)"""
 
     @staticmethod
-    def forward(ctx, guide, feat, n_iter):
-        ctx.n_iter = n_iter
-        ctx.save_for_backward(guide, feat)
-        return _absnorm_forward(guide, feat, n_iter)
+    def forward(ctx, guide, feat, n_iter, kernel_size):
+        ctx.n_iter, ctx.kernel_size = n_iter, kernel_size
+        out, hist = _absnorm_forward(guide, feat, n_iter, kernel_size, keep_history=kernel_size != 3)
+        ctx.save_for_backward(guide, feat, hist)
+        return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        guide, feat = ctx.saved_tensors
+        guide, feat, hist = ctx.saved_tensors
         need_g, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g, x, K = _absnorm_fold(guide, feat)
+        g, x, K = _absnorm_fold(guide, feat, ctx.kernel_size)
         w = _gate_absnorm(g, K)
         go = grad_out.contiguous().view(x.shape)
         if K == 26:
             gw, gx = cspn3d_backward(w, x, go, ctx.n_iter, need_g, need_x)
-        else:
+        elif K == 8:
             gw, gx = cspn2d_backward(w, x, None, go, ctx.n_iter, "none", need_g, need_x)
+        else:
+            gw, gx = cspn2d_backward_kxk(w, x, go, ctx.kernel_size, ctx.n_iter, hist, need_g, need_x)
         gg = gate_absnorm_backward(g, gw, K).view(guide.shape) if need_g else None
-        return gg, gx.view(feat.shape) if need_x else None, None
+        return gg, gx.view(feat.shape) if need_x else None, None, None
 
 
-def absnorm_propagate(guide, feat, n_iter):
+def absnorm_propagate(guide, feat, n_iter, kernel_size=3):
     """The demo's CSPN.cspn (reference cspn_paddle/demo.py:20-54) as a function: feat [N,C,*S] (len(S) = 2 or 3), guide [N, C*K, *S] raw
-    with K = 3^len(S) - 1; channel c is propagated on its OWN slice guide[:, c*K:(c+1)*K], normalised by its abs-sum at every voxel, for
-    n_iter chained steps.  One engine call for all channels (they fold into the batch).  3D: cspn3d_forward_absnorm_f32 (the
-    normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none').  Differentiable
-    w.r.t. guide and feat.  n_iter == 0 returns feat itself."""
+    with K = kernel_size^len(S) - 1; channel c is propagated on its OWN slice guide[:, c*K:(c+1)*K], normalised by its abs-sum at every
+    voxel, for n_iter chained steps.  One engine call for all channels (they fold into the batch).  3D: cspn3d_forward_absnorm_f32 (the
+    normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none'), or with kernel_size
+    5 / 7 (2D only) cspn2d_forward_kxk.  Differentiable w.r.t. guide and feat.  n_iter == 0 returns feat itself."""
     for t, name in ((guide, "guide"), (feat, "feat")):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor" % name)
     if feat.dim() not in (4, 5):
         raise ValueError("feat must be [N,C,H,W] or [N,C,D,H,W], got %s" % (tuple(feat.shape),))
-    K = 3 ** (feat.dim() - 2) - 1
+    if kernel_size != 3:
+        _check_kernel_size(kernel_size, feat.dim())
+    K = kernel_size ** (feat.dim() - 2) - 1
     N, C = feat.shape[:2]
     if tuple(guide.shape) != (N, C * K) + tuple(feat.shape[2:]):
         raise ValueError("guide has shape %s, expected (N, C*%d, *S) = %s" % (tuple(guide.shape), K, (N, C * K) + tuple(feat.shape[2:])))
@@ -716,5 +851,5 @@ def absnorm_propagate(guide, feat, n_iter):
     if g.device != x.device:
         raise _lib.CspnError("cspn_amd: guide is on %s, feat on %s: all tensors must live on the same device" % (g.device, x.device))
     if torch.is_grad_enabled() and (guide.requires_grad or feat.requires_grad):
-        return _AbsnormPropagateFunction.apply(g, x, int(n_iter))
-    return _absnorm_forward(g, x, int(n_iter))
+        return _AbsnormPropagateFunction.apply(g, x, int(n_iter), kernel_size)
+    return _absnorm_forward(g, x, int(n_iter), kernel_size)[0]

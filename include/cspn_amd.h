@@ -47,7 +47,8 @@ extern "C" {
                               * 5: cspn_guidance_head_f32 (the producer of the path's inputs) and cspn_guidance_head_backward_f32; CSPN_NORM_PRENORM on the 2D backward entry points;
                               *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32,
                               *    the cspn2d_*_multi entry points (C channels on shared 2D guidance), the demo's gate normalisation
-                              *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32) */
+                              *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32), the 2D K x K entry points
+                              *    (cspn2d_*_kxk*, K = 5 / 7) and K = 24 / 48 on the gate normaliser */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -225,12 +226,12 @@ int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float*
  * demo otherwise writes in torch in front of cspn3d_forward_f32 with CSPN_NORM_NONE.  Throughout w_k = |g_k| * r, r = 1 / S,
  * S = sum_{j=0..K-1} |g_j| added in channel order (one arithmetic form for the stand-alone and the fused kernel: bitwise equal);
  * an all-zero voxel gives 0 * inf = NaN, where torch's 0 / 0 gives NaN.
- * cspn_gate_absnorm_f32: guide [N,K,V] raw -> gate [N,K,V] = w (K = 8 or 26; V = voxels of a slice).  K * 4 B read + K * 4 B written per voxel.
+ * cspn_gate_absnorm_f32: guide [N,K,V] raw -> gate [N,K,V] = w (K = 8 or 26; 24 or 48 for the 2D K x K op below; V = voxels of a slice).  K * 4 B read + K * 4 B written per voxel.
  * cspn_gate_absnorm_backward_f32: the adjoint, guide [N,K,V] raw, grad_gate = dL/dw -> grad_guide = dL/dguide
  *   dL/dg_k = sign(g_k) (dL/dw_k - sum_j w_j dL/dw_j) * r, sign(0) = 0 (torch's abs backward): S and w are recomputed from guide, no
  *   workspace, no atomics (every output element written once); NaN in all K gradients of an all-zero voxel, as torch.
  * Both: any N, V >= 1 and 4-byte-aligned pointers (16-byte loads where V % 4 == 0 and every pointer is 16-byte aligned); K other than
- * 8 / 26, a null pointer or an output that overlaps an input: CSPN_E_BADARG.
+ * 8 / 24 / 26 / 48, a null pointer or an output that overlaps an input: CSPN_E_BADARG.
  * cspn3d_forward_absnorm_f32: guide [B,26,D,H,W] RAW, feat / out [B,1,D,H,W]: the result of cspn_gate_absnorm_f32 followed by
  *   cspn3d_forward_f32(..., CSPN_NORM_NONE).  algo (CSPN_ALGO3D_*): AUTO normalises the resident gates inside the persistent kernel
  *   (no HBM bytes for it) wherever the NONE op would take the persistent kernel (W % 4 == 0, 2 <= n_iter <= 60, 16-byte aligned
@@ -246,6 +247,33 @@ int cspn_gate_absnorm_backward_f32(const float* guide, const float* grad_gate, f
 size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_iter);
 int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- 2D over a K x K neighbourhood, K = 2R+1 in {5, 7}: fluid.layers.affinity_propagate(input, gate_weight, kernel_size) with
+ * kernel_size 5 or 7, the NONE contract (gates used as given, centre-sited, no centre term, any sign; reference cspn_paddle/README.md:54-56).
+ *   gate [B,KK,H,W], KK = K*K - 1; x / out [B,C,H,W], the C channels share the gates.
+ *   Channel order: gate channel k is the k-th pair (t, l) in raster order over {0..K-1}^2 skipping the centre (R, R); its neighbour
+ *   offset is (dy, dx) = (R - t, R - l) (with K = 3 this is the order of the 3 x 3 op).
+ *   H_0 = x, H_{t+1}(p) = sum_{k=0..KK-1} g_k(p) H_t(p + off_k) (zero outside the image, summed in channel order), out = H_n.
+ * cspn2d_forward_kxk_f32: history NULL -> the levels ping-pong in the workspace (cspn2d_kxk_workspace_bytes); history non-NULL ->
+ *   H_1 .. H_{n-1} are kept there ([n-1][B][C][H][W], cspn2d_kxk_history_bytes; no workspace needed) for cspn2d_backward_kxk_f32.
+ *   n_iter = 0 copies x to out.  One launch per step; per step and pixel 4 KK + 8 C bytes.
+ * cspn2d_backward_kxk_f32: grad_out = dL/dout -> grad_x = dL/dx = A_0 and grad_gate = dL/dgate, summed over the C channels; either may
+ *   be NULL.  A_n = grad_out, A_t(q) = sum_k g_k(q - off_k) A_{t+1}(q - off_k); dL/dg_k(p) = sum_{t<n} sum_c A_{t+1}(p) H_t(p + off_k),
+ *   accumulated in registers over t, then c, every element written once (no atomics: deterministic).  The workspace
+ *   (cspn2d_backward_kxk_workspace_bytes) keeps A_1 .. A_{n-1}; grad_gate needs the history of a forward with the same arguments.
+ * All four: any 4-byte aligned pointers (16-byte loads and stores where W % 4 == 0 and the pointer is 16-byte aligned), any
+ * H, W >= 1.  K other than 5 / 7, a null input, a size <= 0, an output, history or workspace overlapping an input or another output:
+ * CSPN_E_BADARG; B C H W or B KK H W above 2^31 - 1 elements: CSPN_E_UNSUPPORTED; a workspace or history too small, or a workspace
+ * not 256-byte aligned: CSPN_E_WORKSPACE.  The byte-count queries return 0 where the call needs nothing or the shape is invalid. */
+size_t cspn2d_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter);
+size_t cspn2d_kxk_history_bytes(int B, int C, int H, int W, int K, int n_iter);
+int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float* history, size_t history_bytes,
+                           int B, int C, int H, int W, int K, int n_iter,
+                           void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter);
+int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                            float* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
