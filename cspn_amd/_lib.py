@@ -152,6 +152,14 @@ _LATE_SYMBOLS = {
     "cspn2d_backward_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "cspn2d_backward_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the depth-completion contract (Affinity_Propagate's normalisation, siting, blur term and pinning) over K x K, K = 3, 5 or 7
+    "cspn2d_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
+    "cspn2d_kxk_norm_history_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "cspn2d_forward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_int] * 8
+                                    + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
+    "cspn2d_backward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 8
+                                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

@@ -128,6 +128,60 @@ class Affinity_Propagate(nn.Module):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
 
 
+class _CSPN2dKxKNormFunction(torch.autograd.Function):
+    """Affinity_PropagateKxK with prop_kernel 5 / 7: the forward keeps H_1 .. H_{n-1} where the guidance gradient needs them, the
+    backward is one cspn2d_backward_kxk_norm_f32 call (the fold is recomputed there)"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type):
+        ctx.kernel_size, ctx.n_iter, ctx.norm_type = kernel_size, n_iter, norm_type
+        hist = None
+        if ctx.needs_input_grad[0] and n_iter >= 2:
+            out, hist = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, return_history=True)
+        else:
+            out = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type)
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
+        gg, gh = F.cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type, hist,
+                                            need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
+        return gg, gh, None, None, None, None
+
+
+class Affinity_PropagateKxK(nn.Module):
+    """Affinity_Propagate (same constructor, same forward) with prop_kernel 3, 5 or 7 -- what cspn_config['kernel'] asks of the reference
+    (torch_resnet_cspn_nyu.py:281,344-347; cspn.py:24 "current only support 3x3").  guidance [B, K*K-1, H, W] raw, channel k the k-th
+    pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour (K//2 - t, K//2 - l): at K = 3 the
+    reference's gate1 .. gate8.  prop_kernel 3 runs today's 3 x 3 path (bitwise Affinity_Propagate); 5 and 7 the K x K engine
+    (F.cspn2d_forward_kxk_norm), differentiable w.r.t. guidance and blur_depth."""
+
+    def __init__(self, prop_time, prop_kernel, norm_type='8sum'):
+        super(Affinity_PropagateKxK, self).__init__()
+        assert prop_kernel in (3, 5, 7), 'the neighbourhood is 3 x 3, 5 x 5 or 7 x 7'
+        assert norm_type in ['8sum', '8sum_abs']
+        self.prop_time = prop_time
+        self.prop_kernel = prop_kernel
+        self.norm_type = norm_type
+        self.algo = "auto"          # prop_kernel 3: as Affinity_Propagate
+        self.keep_history = True
+
+    def forward(self, guidance, blur_depth, sparse_depth=None, n_iter=None):
+        n = self.prop_time if n_iter is None else int(n_iter)
+        if n == 0:
+            return blur_depth
+        if self.prop_kernel == 3:
+            return _apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
+        if torch.is_grad_enabled() and (guidance.requires_grad or blur_depth.requires_grad):
+            return _CSPN2dKxKNormFunction.apply(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
+        return F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
+
+    def extra_repr(self):
+        return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
+
+
 class CSPN(nn.Module):
     """reference cspn_paddle/demo.py:10-54 (the demo's module): same constructor, same cspn(guide, feat) -- also the forward.  guide
     [N, feat_chan*K, *S] raw (K = prop_kernel^dim_num - 1; prop_kernel 3, or 5 / 7 in 2D), feat [N, feat_chan, *S]: abs, each channel's

@@ -10,6 +10,9 @@
 // tile plus an R-wide halo (zeros outside the image) are staged in LDS once per channel.  The forward and the adjoint step hold the
 // KK x 4 gates a thread needs in registers and loop over the C channels, so the gates are read once per step for all channels.
 // Bytes per pixel: forward step 4 KK + 8 C; adjoint step the same; gate gradient 8 n C + 4 KK.
+// Below them, the depth-completion contract of Affinity_Propagate over K x K (K = 3, 5 or 7): folded into w' and a bias b by kxk_fold,
+// run by the same step with BIAS, and differentiated by the same adjoint step, the gate gradient with BIAS, kxk_unfold_pixel and
+// kxk_unsite.
 #include "cspn_common.h"
 
 namespace cspn {
@@ -81,9 +84,10 @@ template <int K>
 __host__ __device__ constexpr int chan(int t, int l) { return t * K + l - (t * K + l > (K / 2) * (K + 1) ? 1 : 0); }
 
 // one forward step for all C channels: dst = step(src).  VEC: W % 4 == 0, gate and dst 16-byte aligned
-template <int K, bool VEC>
+// BIAS: the accumulator starts from bias [N][C][H][W] (the folded normalising contract, kxk_fold), 16-byte aligned where VEC
+template <int K, bool VEC, bool BIAS = false>
 __global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
-                                                       int C, int H, int W, int tiles_x, int tiles_y) {
+                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -100,6 +104,7 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__
         stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
         __syncthreads();
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (BIAS) load4<VEC>(acc, bias + plane + pix, row_in, T.x0, W);
 #pragma unroll
         for (int t = 0; t < K; ++t) {
             float row[4 + 2 * R];   // row y + R - t, columns x0 - R .. x0 + 3 + R
@@ -168,11 +173,13 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__
 }
 
 // dL/dg for all KK channels of the tile: the levels H_0 = x, H_t = hist + (t - 1) L (t >= 1) and A_t = alev + (t - 1) L (t < n),
-// A_n = gout, L = N C H W.  Accumulated over t = 0 .. n-1, then c = 0 .. C-1, written once.  VEC: W % 4 == 0 and gg 16-byte aligned
-template <int K, bool VEC>
+// A_n = gout, L = N C H W.  Accumulated over t = 0 .. n-1, then c = 0 .. C-1, written once.  VEC: W % 4 == 0 and gg 16-byte aligned.
+// BIAS: also db [N][C][H][W] = sum_t A_{t+1} (dL/dbias of the folded contract); the loops then run over c, then t, and GATES = false
+// leaves out the gate gradient (no H level is read, gg and hist unused); db 16-byte aligned where VEC
+template <int K, bool VEC, bool BIAS = false, bool GATES = true>
 __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x, const float* __restrict__ hist, const float* __restrict__ alev,
                                                     const float* __restrict__ gout, float* __restrict__ gg, int n_iter, size_t L, int C, int H,
-                                                    int W, int tiles_x, int tiles_y) {
+                                                    int W, int tiles_x, int tiles_y, float* __restrict__ db) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -184,34 +191,70 @@ __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x,
     for (int k = 0; k < KK; ++k)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[k][j] = 0.f;
-    for (int it = 0; it < n_iter; ++it) {
-        const float* hl = it == 0 ? x : hist + (size_t)(it - 1) * L;
-        const float* al = it + 1 == n_iter ? gout : alev + (size_t)it * L;
-        for (int c = 0; c < C; ++c) {
-            const size_t plane = ((size_t)T.n * C + c) * HW;
-            __syncthreads();
-            stage<R>(lds, hl + plane, T.y0, T.xt0, H, W);
-            float a[4];
-            load4<false>(a, al + plane + pix, row_in, T.x0, W);
-            __syncthreads();
+    if constexpr (!BIAS) {
+        for (int it = 0; it < n_iter; ++it) {
+            const float* hl = it == 0 ? x : hist + (size_t)(it - 1) * L;
+            const float* al = it + 1 == n_iter ? gout : alev + (size_t)it * L;
+            for (int c = 0; c < C; ++c) {
+                const size_t plane = ((size_t)T.n * C + c) * HW;
+                __syncthreads();
+                stage<R>(lds, hl + plane, T.y0, T.xt0, H, W);
+                float a[4];
+                load4<false>(a, al + plane + pix, row_in, T.x0, W);
+                __syncthreads();
 #pragma unroll
-            for (int t = 0; t < K; ++t) {
-                float row[4 + 2 * R];
+                for (int t = 0; t < K; ++t) {
+                    float row[4 + 2 * R];
 #pragma unroll
-                for (int i = 0; i < 4 + 2 * R; ++i) row[i] = lds[(T.ly + 2 * R - t) * SW + 4 * T.lq + i];
+                    for (int i = 0; i < 4 + 2 * R; ++i) row[i] = lds[(T.ly + 2 * R - t) * SW + 4 * T.lq + i];
 #pragma unroll
-                for (int l = 0; l < K; ++l) {
-                    if (t == R && l == R) continue;
-                    const int k = chan<K>(t, l);
+                    for (int l = 0; l < K; ++l) {
+                        if (t == R && l == R) continue;
+                        const int k = chan<K>(t, l);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(a[j], row[j + 2 * R - l], acc[k][j]);
+                        for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(a[j], row[j + 2 * R - l], acc[k][j]);
+                    }
                 }
             }
         }
-    }
-    float* gp = gg + (size_t)T.n * KK * HW + pix;
+    } else {
+        for (int c = 0; c < C; ++c) {
+            const size_t plane = ((size_t)T.n * C + c) * HW;
+            float d[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int it = 0; it < n_iter; ++it) {
+                const float* al = it + 1 == n_iter ? gout : alev + (size_t)it * L;
+                float a[4];
+                load4<false>(a, al + plane + pix, row_in, T.x0, W);
 #pragma unroll
-    for (int k = 0; k < KK; ++k) store4<VEC>(gp + (size_t)k * HW, acc[k], row_in, T.x0, W);
+                for (int j = 0; j < 4; ++j) d[j] += a[j];
+                if constexpr (GATES) {
+                    const float* hl = it == 0 ? x : hist + (size_t)(it - 1) * L;
+                    __syncthreads();
+                    stage<R>(lds, hl + plane, T.y0, T.xt0, H, W);
+                    __syncthreads();
+#pragma unroll
+                    for (int t = 0; t < K; ++t) {
+                        float row[4 + 2 * R];
+#pragma unroll
+                        for (int i = 0; i < 4 + 2 * R; ++i) row[i] = lds[(T.ly + 2 * R - t) * SW + 4 * T.lq + i];
+#pragma unroll
+                        for (int l = 0; l < K; ++l) {
+                            if (t == R && l == R) continue;
+                            const int k = chan<K>(t, l);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(a[j], row[j + 2 * R - l], acc[k][j]);
+                        }
+                    }
+                }
+            }
+            store4<VEC>(db + plane + pix, d, row_in, T.x0, W);
+        }
+    }
+    if constexpr (GATES) {
+        float* gp = gg + (size_t)T.n * KK * HW + pix;
+#pragma unroll
+        for (int k = 0; k < KK; ++k) store4<VEC>(gp + (size_t)k * HW, acc[k], row_in, T.x0, W);
+    }
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -229,8 +272,243 @@ Grid grid_of(int N, int H, int W) {
     return g;
 }
 
+// ---- the depth-completion contract (reference cspn.py:42-144 generalised to K x K) folded into the step above:
+//   G_k(p) = g_k(p + off_k) (|g| for 8SUM_ABS), wb_k = G_k / sum_j |G_j|, c = 1 - sum_k wb_k, m = sign(sparse), u = 1 - m
+//   H_{t+1}(p) = sum_k w'_k(p) H_t(p + off_k) + b(p),   w'_k = u wb_k (centre-sited, what kxk_forward_step reads), b = (u c + m) blur
+// A mask of one plane per image (none, or [B,1]) keeps one w' for the C channels; a mask per channel ([B,C], C > 1) folds the channels into
+// the batch: N' = B C images of one channel, each with its own w', cpg = C images per guidance image.
+
+// G_k of the four pixels x0 .. x0+3 of row y: the guidance read at the neighbour (zero outside the image), abs for 8SUM_ABS
 template <int K>
-int forward_steps(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
+__device__ __forceinline__ void sited_gates(float (&G)[K * K - 1][4], const float* __restrict__ gb, bool row_in, int y, int x0, int H, int W,
+                                            bool ab) {
+    constexpr int R = K / 2;
+    const int HW = H * W;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const int py = y + R - t;
+        const bool yin = row_in && py >= 0 && py < H;
+#pragma unroll
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            const int k = chan<K>(t, l);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int px = x0 + j + R - l;
+                const float v = (yin && x0 + j < W && px >= 0 && px < W) ? gb[(size_t)k * HW + py * W + px] : 0.f;
+                G[k][j] = ab ? fabsf(v) : v;
+            }
+        }
+    }
+}
+
+// m = sign(sparse) and u = 1 - m of image n (one plane per image, or none)
+__device__ __forceinline__ void mask4(float (&m)[4], float (&u)[4], const float* __restrict__ sparse, int n, int HW, int pix, bool row_in, int x0,
+                                      int W) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    if (sparse) load4<false>(s, sparse + (size_t)n * HW + pix, row_in, x0, W);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m[j] = signf(s[j]);
+        u[j] = 1.f - m[j];
+    }
+}
+
+// w' [N'][KK][H][W] and b [N'][Cv][H][W] of image n' (guidance image n' / cpg).  VEC: W % 4 == 0, blur 16-byte aligned
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void kxk_fold(const float* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
+                                               float* __restrict__ wp, float* __restrict__ bias, int Cv, int cpg, int norm, int H, int W, int tiles_x,
+                                               int tiles_y) {
+    constexpr int KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    float G[KK][4];
+    sited_gates<K>(G, guid + (size_t)(T.n / cpg) * KK * HW, row_in, T.y, T.x0, H, W, norm == CSPN_NORM_8SUM_ABS);
+    float S[4] = {0.f, 0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f}, m[4], u[4];
+#pragma unroll
+    for (int k = 0; k < KK; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[j] += fabsf(G[k][j]);
+    mask4(m, u, sparse, T.n, HW, pix, row_in, T.x0, W);
+    float* wq = wp + (size_t)T.n * KK * HW + pix;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float wb = G[k][j] / S[j];   // 0 / 0 = NaN, as the reference's torch.div
+            gs[j] += wb;
+            G[k][j] = u[j] * wb;
+        }
+        store4<VEC>(wq + (size_t)k * HW, G[k], row_in, T.x0, W);
+    }
+    float f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = u[j] * (1.f - gs[j]) + m[j];
+    for (int c = 0; c < Cv; ++c) {
+        const size_t plane = ((size_t)T.n * Cv + c) * HW + pix;
+        float v[4];
+        load4<VEC>(v, blur + plane, row_in, T.x0, W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= f[j];
+        store4<VEC>(bias + plane, v, row_in, T.x0, W);
+    }
+}
+
+// the pixel-local part of the fold's adjoint, per guidance image b and pixel p, images n' = b cpg + i:
+//   dwb_k = sum_i u_i (dw'_{n',k} - sum_c blur_{n',c} db_{n',c}),  dG_k = (dwb_k - sign(G_k) sum_j wb_j dwb_j) / S  -> dw' of image b cpg
+//   (in place: every element is read and written by the same thread), and where gx is given
+//   gx_{n',c} = A_0 + (u_i c + m_i) db_{n',c} (gx holds A_0).  need_g = false: only the second.  VEC: W % 4 == 0, blur and gx 16-byte aligned
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void kxk_unfold_pixel(const float* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
+                                                       float* __restrict__ dwp, const float* __restrict__ db, float* __restrict__ gx, int need_g, int Cv,
+                                                       int cpg, int norm, int H, int W, int tiles_x, int tiles_y) {
+    constexpr int R = K / 2, KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    const float* gb = guid + (size_t)T.n * KK * HW;
+    const bool ab = norm == CSPN_NORM_8SUM_ABS;
+    // G_k of the four pixels (kxk_fold's sited_gates, one channel at a time: the passes below re-read it from the cache rather than
+    // keep KK x 4 values live)
+    auto gate = [&](int t, int l, float (&v)[4]) {
+        const int k = chan<K>(t, l), py = T.y + R - t;
+        const bool yin = row_in && py >= 0 && py < H;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int px = T.x0 + j + R - l;
+            const float g = (yin && T.x0 + j < W && px >= 0 && px < W) ? gb[(size_t)k * HW + py * W + px] : 0.f;
+            v[j] = ab ? fabsf(g) : g;
+        }
+    };
+    float S[4] = {0.f, 0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < K; ++t)
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            float v[4];
+            gate(t, l, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) S[j] += fabsf(v[j]);
+        }
+    const int n0 = T.n * cpg;
+    if (need_g) {
+        // u_i and sum_c blur db of image n0 + i
+        auto ubd = [&](int i, float (&u)[4], float (&bd)[4]) {
+            float m[4];
+            mask4(m, u, sparse, n0 + i, HW, pix, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bd[j] = 0.f;
+            for (int c = 0; c < Cv; ++c) {
+                const size_t plane = ((size_t)(n0 + i) * Cv + c) * HW + pix;
+                float v[4], d[4];
+                load4<VEC>(v, blur + plane, row_in, T.x0, W);
+                load4<VEC>(d, db + plane, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bd[j] = fmaf(v[j], d[j], bd[j]);
+            }
+        };
+        float u0[4], bd0[4];
+        ubd(0, u0, bd0);
+        auto dwb = [&](int k, float (&d)[4]) {
+            load4<VEC>(d, dwp + ((size_t)n0 * KK + k) * HW + pix, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = u0[j] * (d[j] - bd0[j]);
+            for (int i = 1; i < cpg; ++i) {
+                float u[4], bd[4], e[4];
+                ubd(i, u, bd);
+                load4<VEC>(e, dwp + ((size_t)(n0 + i) * KK + k) * HW + pix, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[j] = fmaf(u[j], e[j] - bd[j], d[j]);
+            }
+        };
+        float dot[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < K; ++t)
+            for (int l = 0; l < K; ++l) {
+                if (t == R && l == R) continue;
+                float v[4], d[4];
+                gate(t, l, v);
+                dwb(chan<K>(t, l), d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dot[j] = fmaf(v[j] / S[j], d[j], dot[j]);
+            }
+        for (int t = 0; t < K; ++t)
+            for (int l = 0; l < K; ++l) {
+                if (t == R && l == R) continue;
+                const int k = chan<K>(t, l);
+                float v[4], d[4];
+                gate(t, l, v);
+                dwb(k, d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[j] = (d[j] - signf(v[j]) * dot[j]) / S[j];
+                store4<VEC>(dwp + ((size_t)n0 * KK + k) * HW + pix, d, row_in, T.x0, W);
+            }
+    }
+    if (!gx) return;
+    for (int t = 0; t < K; ++t)
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            float v[4];
+            gate(t, l, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gs[j] += v[j] / S[j];   // c = 1 - sum_k wb_k, in channel order as kxk_fold
+        }
+    for (int i = 0; i < cpg; ++i) {
+        float m[4], u[4];
+        mask4(m, u, sparse, n0 + i, HW, pix, row_in, T.x0, W);
+        for (int c = 0; c < Cv; ++c) {
+            const size_t plane = ((size_t)(n0 + i) * Cv + c) * HW + pix;
+            float a[4], d[4];
+            load4<VEC>(a, gx + plane, row_in, T.x0, W);
+            load4<VEC>(d, db + plane, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = fmaf(u[j] * (1.f - gs[j]) + m[j], d[j], a[j]);
+            store4<VEC>(gx + plane, a, row_in, T.x0, W);
+        }
+    }
+}
+
+// un-siting, a gather: dL/dguidance_k(q) = dG_k(q - off_k) (zero outside the image), times sign(g_k(q)) for 8SUM_ABS; dG of image b at
+// dg + b cpg KK H W.  VEC: W % 4 == 0, guid and gg 16-byte aligned
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, const float* __restrict__ guid, float* __restrict__ gg, int cpg, int norm,
+                                                 int H, int W, int tiles_x, int tiles_y) {
+    constexpr int R = K / 2, KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    const float* db = dg + (size_t)T.n * cpg * KK * HW;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const int py = T.y - R + t;
+        const bool yin = row_in && py >= 0 && py < H;
+#pragma unroll
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            const int k = chan<K>(t, l);
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int px = T.x0 + j - R + l;
+                v[j] = (yin && T.x0 + j < W && px >= 0 && px < W) ? db[(size_t)k * HW + py * W + px] : 0.f;
+            }
+            const size_t at = ((size_t)T.n * KK + k) * HW + pix;
+            if (norm == CSPN_NORM_8SUM_ABS) {
+                float g[4];
+                load4<VEC>(g, guid + at, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] *= signf(g[j]);
+            }
+            store4<VEC>(gg + at, v, row_in, T.x0, W);
+        }
+    }
+}
+
+template <int K, bool BIAS = false>
+int forward_steps(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
+                  const float* bias = nullptr) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
     float* ping = (float*)ws;
@@ -238,12 +516,29 @@ int forward_steps(const float* gate, const float* x, float* out, float* hist, in
     const float* src = x;
     for (int it = 1; it <= n_iter; ++it) {
         float* dst = it == n_iter ? out : (hist ? hist + (size_t)(it - 1) * L : ((it & 1) ? ping : pong));
-        if (W % 4 == 0 && aligned16(gate) && aligned16(dst))
-            hipLaunchKernelGGL((kxk_forward_step<K, true>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+        if (W % 4 == 0 && aligned16(gate) && aligned16(dst) && (!BIAS || aligned16(bias)))
+            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         else
-            hipLaunchKernelGGL((kxk_forward_step<K, false>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         if (int e = check_launch("kxk_forward_step")) return e;
         src = dst;
+    }
+    return 0;
+}
+
+// the adjoint steps A_{n-1} .. A_last into alev (A_t at alev + (t - 1) L), A_0 into gx
+template <int K>
+int adjoint_steps(const float* gate, const float* gout, float* gx, float* alev, int last, int N, int C, int H, int W, int n_iter, hipStream_t st) {
+    const Grid G = grid_of(N, H, W);
+    const size_t L = (size_t)N * C * H * W;
+    for (int t = n_iter - 1; t >= last; --t) {
+        const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
+        float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
+        if (W % 4 == 0 && aligned16(dst))
+            hipLaunchKernelGGL((kxk_adjoint_step<K, true>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+        else
+            hipLaunchKernelGGL((kxk_adjoint_step<K, false>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+        if (int e = check_launch("kxk_adjoint_step")) return e;
     }
     return 0;
 }
@@ -255,22 +550,92 @@ int backward_run(const float* gate, const float* x, const float* hist, const flo
     const size_t L = (size_t)N * C * H * W;
     float* alev = (float*)ws;   // A_1 .. A_{n-1}, level t at alev + (t - 1) L
     // the adjoint steps: A_{n-1} .. A_1 always (the gate gradient reads them), A_0 = dL/dx where asked for
-    const int last = gx ? 0 : (gg ? 1 : n_iter);
-    for (int t = n_iter - 1; t >= last; --t) {
-        const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
-        float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
-        if (W % 4 == 0 && aligned16(dst))
-            hipLaunchKernelGGL((kxk_adjoint_step<K, true>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
-        else
-            hipLaunchKernelGGL((kxk_adjoint_step<K, false>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
-        if (int e = check_launch("kxk_adjoint_step")) return e;
-    }
+    if (int e = adjoint_steps<K>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st)) return e;
     if (!gg) return 0;
     if (W % 4 == 0 && aligned16(gg))
-        hipLaunchKernelGGL((kxk_gate_grad<K, true>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty);
+        hipLaunchKernelGGL((kxk_gate_grad<K, true>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty, nullptr);
     else
-        hipLaunchKernelGGL((kxk_gate_grad<K, false>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty);
+        hipLaunchKernelGGL((kxk_gate_grad<K, false>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty, nullptr);
     return check_launch("kxk_gate_grad");
+}
+
+// the views of the folded contract: N' images of Cv channels, cpg of them per guidance image
+struct NormGeo {
+    int N, Cv, cpg;
+    size_t L;
+};
+
+NormGeo norm_geo(int B, int C, int sparse_C, int H, int W) {
+    const bool pc = sparse_C > 1;
+    return NormGeo{pc ? B * C : B, pc ? 1 : C, pc ? C : 1, (size_t)B * C * H * W};
+}
+
+template <int K>
+int fold(const float* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st) {
+    const Grid G = grid_of(g.N, H, W);
+    if (W % 4 == 0 && aligned16(blur))
+        hipLaunchKernelGGL((kxk_fold<K, true>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
+    else
+        hipLaunchKernelGGL((kxk_fold<K, false>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
+    return check_launch("kxk_fold");
+}
+
+template <int K>
+int norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
+                 int n_iter, int norm, void* ws, hipStream_t st) {
+    constexpr int KK = K * K - 1;
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    float* wp = (float*)ws;
+    float* bias = wp + kxk_level_floats((size_t)g.N * KK * H * W);
+    if (int e = fold<K>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    return forward_steps<K, true>(wp, blur, out, hist, g.N, g.Cv, H, W, n_iter, bias + kxk_level_floats(g.L), st, bias);
+}
+
+template <int K>
+int norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B, int C,
+                  int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+    constexpr int KK = K * K - 1;
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    const size_t P = kxk_level_floats((size_t)g.N * KK * H * W);
+    float* wp = (float*)ws;
+    float* bias = wp + P;
+    float* dwp = bias + kxk_level_floats(g.L);
+    float* dbp = dwp + P;
+    float* alev = dbp + kxk_level_floats(g.L);
+    if (int e = fold<K>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    if (int e = adjoint_steps<K>(wp, gout, gx, alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
+    const Grid G = grid_of(g.N, H, W);
+    const bool vec = W % 4 == 0;   // dwp and dbp: workspace
+    if (gg) {
+        if (vec)
+            hipLaunchKernelGGL((kxk_gate_grad<K, true, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H, W,
+                               G.tx, G.ty, dbp);
+        else
+            hipLaunchKernelGGL((kxk_gate_grad<K, false, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
+                               W, G.tx, G.ty, dbp);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((kxk_gate_grad<K, true, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
+                               W, G.tx, G.ty, dbp);
+        else
+            hipLaunchKernelGGL((kxk_gate_grad<K, false, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
+                               W, G.tx, G.ty, dbp);
+    }
+    if (int e = check_launch("kxk_gate_grad")) return e;
+    const Grid GB = grid_of(B, H, W);
+    if (vec && aligned16(blur) && (!gx || aligned16(gx)))
+        hipLaunchKernelGGL((kxk_unfold_pixel<K, true>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
+                           H, W, GB.tx, GB.ty);
+    else
+        hipLaunchKernelGGL((kxk_unfold_pixel<K, false>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
+                           H, W, GB.tx, GB.ty);
+    if (int e = check_launch("kxk_unfold_pixel")) return e;
+    if (!gg) return 0;
+    if (vec && aligned16(guid) && aligned16(gg))
+        hipLaunchKernelGGL((kxk_unsite<K, true>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+    else
+        hipLaunchKernelGGL((kxk_unsite<K, false>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+    return check_launch("kxk_unsite");
 }
 
 }  // namespace
@@ -286,6 +651,35 @@ int kxk_backward(const float* gate, const float* x, const float* hist, const flo
                  int n_iter, void* ws, hipStream_t st) {
     return K == 5 ? backward_run<5>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st)
                   : backward_run<7>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st);
+}
+
+}  // namespace cspn
+
+namespace cspn {
+
+size_t kxk_norm_fold_floats(int B, int C, int sparse_C, int H, int W, int K) {
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    return kxk_level_floats((size_t)g.N * (K * K - 1) * H * W) + kxk_level_floats(g.L);
+}
+
+// arguments checked by the caller (cspn_abi.cpp): K in {3, 5, 7}, n_iter >= 1, norm 8SUM / 8SUM_ABS, sparse_C 0 / 1 / C (0 <=> sparse NULL),
+// every view below 2^31 elements, no aliasing, the workspace as cspn2d_kxk_norm_workspace_bytes / cspn2d_backward_kxk_norm_workspace_bytes
+int kxk_norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
+                     int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    switch (K) {
+        case 3: return norm_forward<3>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        case 5: return norm_forward<5>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        default: return norm_forward<7>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+    }
+}
+
+int kxk_norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B,
+                      int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    switch (K) {
+        case 3: return norm_backward<3>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        case 5: return norm_backward<5>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        default: return norm_backward<7>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+    }
 }
 
 }  // namespace cspn

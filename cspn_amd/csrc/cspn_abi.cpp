@@ -112,6 +112,26 @@ static bool kxk_overlaps(const void* out, size_t out_bytes, std::initializer_lis
     return false;
 }
 
+// the depth-completion contract over K x K (cspn2d_*_kxk_norm*): K = 3 as well, a mask of 0, 1 or C planes
+static bool kxk_norm_shape_ok(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
+    const long long px = (long long)H * W, N = sparse_C > 1 ? (long long)B * C : B;
+    return B > 0 && C > 0 && H > 0 && W > 0 && (K == 3 || K == 5 || K == 7) && n_iter >= 0 && (sparse_C == 0 || sparse_C == 1 || sparse_C == C) &&
+           (long long)B * C * px <= 0x7fffffffLL && N * (K * K - 1) * px <= 0x7fffffffLL;
+}
+
+static int kxk_norm_check(const char* what, const float* sparse, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm) {
+    if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (n_iter < 0) { set_error("%s: n_iter must be >= 0 (got %d)", what, n_iter); return CSPN_E_BADARG; }
+    if (norm != CSPN_NORM_8SUM && norm != CSPN_NORM_8SUM_ABS) { set_error("%s: norm must be CSPN_NORM_8SUM or CSPN_NORM_8SUM_ABS, got %d", what, norm); return CSPN_E_BADARG; }
+    if ((sparse_C != 0 && sparse_C != 1 && sparse_C != C) || (sparse_C == 0) != (sparse == nullptr)) {
+        set_error("%s: sparse_C must be 0 (sparse NULL), 1 or C = %d (sparse given), got %d", what, C, sparse_C);
+        return CSPN_E_BADARG;
+    }
+    if (!kxk_norm_shape_ok(B, C, sparse_C, H, W, K, n_iter)) { set_error("%s: tensor too large for 32-bit element indexing", what); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
 }  // namespace cspn
 
 using namespace cspn;
@@ -702,6 +722,84 @@ int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* hist
         return 0;
     }
     return kxk_backward(gate, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
+// ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip) ----
+size_t cspn2d_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
+    if (!kxk_norm_shape_ok(B, C, sparse_C, H, W, K, n_iter) || n_iter < 1) return 0;
+    const size_t levels = n_iter < 2 ? 0 : kxk_level_floats((size_t)B * C * H * W) * (n_iter == 2 ? 1 : 2);
+    return sizeof(float) * (kxk_norm_fold_floats(B, C, sparse_C, H, W, K) + levels);
+}
+
+size_t cspn2d_kxk_norm_history_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_norm_shape_ok(B, C, 0, H, W, K, n_iter) || n_iter < 2) return 0;
+    return kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1);
+}
+
+int cspn2d_forward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, float* out, float* history, size_t history_bytes, int B,
+                                int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_forward_kxk_norm_f32";
+    if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1), sb = vb / C * sparse_C;
+    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = n_iter == 0 ? 0
+                        : (history ? sizeof(float) * kxk_norm_fold_floats(B, C, sparse_C, H, W, K)
+                                   : cspn2d_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter));
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hb}, {ws, wb}}) ||
+        kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {
+        hipError_t e = hipMemcpyAsync(out, blur, vb, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_norm_forward(guidance, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+}
+
+size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
+    if (!kxk_norm_shape_ok(B, C, sparse_C, H, W, K, n_iter) || n_iter < 1) return 0;
+    return sizeof(float) * 2 * kxk_norm_fold_floats(B, C, sparse_C, H, W, K) + round256(kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1));
+}
+
+int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, const float* history, size_t history_bytes,
+                                 const float* grad_out, float* grad_guidance, float* grad_blur, int B, int C, int sparse_C, int H, int W, int K,
+                                 int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_backward_kxk_norm_f32";
+    if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1), sb = vb / C * sparse_C;
+    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
+    if (grad_guidance && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the guidance gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = grad_guidance ? hb : 0;
+    if (grad_guidance && (const void*)grad_guidance == (const void*)grad_blur) { set_error("%s: grad_guidance and grad_blur must not alias", what); return CSPN_E_BADARG; }
+    if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_blur, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_blur, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_guidance, grad_blur and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_guidance && !grad_blur) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {   // the identity: dL/dblur = dL/dout, no gate is read
+        hipError_t e = grad_blur ? hipMemcpyAsync(grad_blur, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_guidance) e = hipMemsetAsync(grad_guidance, 0, gb, st);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_norm_backward(guidance, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
 }  // extern "C"

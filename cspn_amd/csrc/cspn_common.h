@@ -92,6 +92,17 @@ int kxk_forward(const float* gate, const float* x, float* out, float* hist, int 
 int kxk_backward(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W, int K,
                  int n_iter, void* ws, hipStream_t st);
 
+// ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip): guidance [B][K*K-1][H][W] raw, blur
+// [B][C][H][W], sparse NULL (sparse_C 0) or [B][sparse_C][H][W] with sparse_C 1 or C; normalised, neighbour-sited, pinned, folded into w' and b ----
+// the folded w' and b in front of each workspace (floats)
+size_t kxk_norm_fold_floats(int B, int C, int sparse_C, int H, int W, int K);
+// ws: the fold, then (hist NULL) the two ping-pong levels of kxk_forward; hist as kxk_forward
+int kxk_norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
+                     int K, int n_iter, int norm, void* ws, hipStream_t st);
+// ws: the fold, dL/dw', dL/db (one fold's size), then A_1 .. A_{n-1}; gg needs hist (n >= 2), gx and gg may each be NULL
+int kxk_norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B,
+                      int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels
 size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C = 1);

@@ -677,6 +677,105 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     return outs[0] if C == 1 else torch.cat(outs, 1)
 
 
+# ---- the depth-completion contract of Affinity_Propagate (reference cspn.py:42-144) over a K x K neighbourhood, K = 3, 5 or 7
+# (cspn2d_*_kxk_norm_f32): guidance [B,K*K-1,H,W] raw in the K x K op's channel order, normalised, each gate sited at its neighbour, a
+# (1 - gate_sum) blur term and sparse depth pinned ----
+def _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter):
+    if isinstance(kernel_size, bool) or not isinstance(kernel_size, int) or kernel_size not in (3, 5, 7):
+        raise ValueError("kernel_size must be 3, 5 or 7, got %r" % (kernel_size,))
+    if norm_type not in ("8sum", "8sum_abs"):
+        raise ValueError("norm_type must be '8sum' or '8sum_abs', got %r" % (norm_type,))
+    if int(n_iter) < 0:
+        raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
+    for t, name in ((guidance, "guidance"), (blur_depth, "blur_depth")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    K = kernel_size
+    if guidance.dim() != 4 or guidance.shape[1] != K * K - 1:
+        raise ValueError("guidance must be [B,%d,H,W] for kernel_size %d, got %s" % (K * K - 1, K, tuple(guidance.shape)))
+    B, _, H, W = guidance.shape
+    if blur_depth.dim() != 4 or blur_depth.shape[0] != B or tuple(blur_depth.shape[2:]) != (H, W) or blur_depth.shape[1] < 1:
+        raise ValueError("blur_depth has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(blur_depth.shape), B, H, W))
+    C = blur_depth.shape[1]
+    sc = 0
+    if sparse_depth is not None:
+        if not isinstance(sparse_depth, torch.Tensor) or sparse_depth.dim() != 4 or sparse_depth.shape[1] not in (1, C) \
+                or sparse_depth.shape[0] != B or tuple(sparse_depth.shape[2:]) != (H, W):
+            raise ValueError("sparse_depth must be None, (B,1,H,W) or (B,C,H,W) = (%d,%d,%d,%d), got %s"
+                             % (B, C, H, W, tuple(getattr(sparse_depth, "shape", ()))))
+        sc = sparse_depth.shape[1]
+    return K, B, C, H, W, sc
+
+
+def _kxk_norm_args(guidance, blur_depth, sparse_depth, extra=()):
+    g = _prep(guidance, "guidance")
+    h = _prep(blur_depth, "blur_depth")
+    s = _prep(sparse_depth, "sparse_depth") if sparse_depth is not None else None
+    rest = [_prep(t, name, tuple(h.shape)) for t, name in extra]
+    if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
+        raise ValueError("all tensors must live on the same device")
+    return (g, h, s) + tuple(rest)
+
+
+def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False):
+    """Affinity_Propagate's forward (reference cspn.py:42-144) over a kernel_size x kernel_size neighbourhood: guidance [B,K*K-1,H,W] raw
+    (channel k = the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour
+    (K//2 - t, K//2 - l)), blur_depth [B,C,H,W] on the shared guidance, sparse_depth None, [B,1,H,W] or [B,C,H,W] -> [B,C,H,W]
+    (cspn2d_forward_kxk_norm_f32).  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_norm.  n_iter == 0
+    returns blur_depth itself."""
+    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    n = int(n_iter)
+    if n == 0:
+        return (blur_depth, None) if return_history else blur_depth
+    g, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
+    out = torch.empty_like(h)
+    hist = None
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    with torch.cuda.device(g.device):
+        hb = _lib.late_symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n) if return_history else 0
+        if return_history:
+            hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+        # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
+        ws_bytes = _lib.late_symbol("cspn2d_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, 1 if return_history else n)
+        ws = _workspace(ws_bytes, g.device)
+        rc = _lib.late_symbol("cspn2d_forward_kxk_norm_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), hist.data_ptr() if hist is not None else None,
+            hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_forward_kxk_norm_f32")
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
+                             need_guidance=True, need_blur=True):
+    """Gradient of cspn2d_forward_kxk_norm -> (dL/dguidance [B,K*K-1,H,W] summed over the C channels or None, dL/dblur_depth [B,C,H,W]
+    or None); sparse_depth gets none (cspn.py uses its sign only).  cspn2d_backward_kxk_norm_f32.  history: what
+    cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it."""
+    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
+        raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
+    g, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    n = int(n_iter)
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    if not (need_guidance or need_blur):
+        return gg, gh
+    if h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), gh
+    if need_guidance and n >= 2 and history is None:
+        _, history = cspn2d_forward_kxk_norm(g, h, s, K, n, norm_type, return_history=True)
+    with torch.cuda.device(g.device):
+        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, n)
+        ws = _workspace(ws_bytes, g.device)
+        hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
+        rc = _lib.late_symbol("cspn2d_backward_kxk_norm_f32")(
+            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, hp, hb, go.data_ptr(),
+            gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None, B, C, sc, H, W, K, n,
+            _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, "cspn2d_backward_kxk_norm_f32")
+    return gg, gh
+
+
 # ---- the demo's module (reference cspn_paddle/demo.py:20-54): abs (:24), each channel's slice of K = 3^d - 1 gates divided by its own
 # channel sum (:25,31-36,47-49), prop_step chained propagations (:40-43,50-52) ----
 def _absnorm_flat(guide, K):

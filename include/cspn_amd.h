@@ -48,7 +48,8 @@ extern "C" {
                               *    later, purely additive (no signature or behaviour changed, so the version stays): cspn2d_normalize_backward_f32,
                               *    the cspn2d_*_multi entry points (C channels on shared 2D guidance), the demo's gate normalisation
                               *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32), the 2D K x K entry points
-                              *    (cspn2d_*_kxk*, K = 5 / 7) and K = 24 / 48 on the gate normaliser */
+                              *    (cspn2d_*_kxk*, K = 5 / 7), K = 24 / 48 on the gate normaliser and the depth-completion contract over
+                              *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -274,6 +275,36 @@ size_t cspn2d_backward_kxk_workspace_bytes(int B, int C, int H, int W, int K, in
 int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* history, size_t history_bytes, const float* grad_out,
                             float* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
                             void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the depth-completion contract of Affinity_Propagate (reference cspn_pytorch/models/cspn.py:42-144) over a K x K neighbourhood,
+ * K = 2R+1 in {3, 5, 7}: the guidance normalised, each gate sited at its neighbour, a (1 - gate_sum) blur term, sparse depth pinned.
+ *   guidance [B,KK,H,W] raw, KK = K*K - 1, in the channel order of the NONE op above: channel k is the k-th pair (t, l) in raster order
+ *   over {0..K-1}^2 skipping the centre, offset off_k = (R - t, R - l); the reference's padding generalised is ZeroPad2d((l, K-1-l, t, K-1-t))
+ *   followed by a crop of R on each side (K = 3: gate1 .. gate8 of cspn.py:104-131).  blur / out [B,C,H,W], the C channels share the
+ *   guidance (the reference's broadcast); sparse NULL with sparse_C = 0, or [B,sparse_C,H,W] with sparse_C 1 (one mask for all channels) or C.
+ *   norm CSPN_NORM_8SUM or CSPN_NORM_8SUM_ABS (g = |guidance|).  Per pixel p, zero outside the image:
+ *     G_k(p) = g_k(p + off_k), wb_k = G_k / sum_j |G_j| (channel order; 0 / 0 = NaN as in the reference), c = 1 - sum_k wb_k,
+ *     m = sign(sparse), u = 1 - m, H_0 = blur, H_{t+1} = u (sum_k wb_k H_t(p + off_k) + c blur) + m blur, out = H_n.
+ *   The engine folds this into w'_k = u wb_k and b = (u c + m) blur (one launch) and runs the K x K step with b as its start value;
+ *   with sparse_C = C > 1 the channels become images of their own w'.
+ * cspn2d_forward_kxk_norm_f32: history NULL -> the workspace holds the fold and two ping-pong levels (cspn2d_kxk_norm_workspace_bytes);
+ *   history non-NULL -> H_1 .. H_{n-1} are kept there ([n-1][B][C][H][W], cspn2d_kxk_norm_history_bytes) and the workspace needs only the
+ *   fold (what cspn2d_kxk_norm_workspace_bytes returns for n_iter = 1).  n_iter = 0 copies blur to out.  Per step and pixel 4 KK + 12 C bytes.
+ * cspn2d_backward_kxk_norm_f32: grad_out = dL/dout -> grad_guidance = dL/dguidance (summed over the C channels) and grad_blur = dL/dblur;
+ *   either may be NULL; sparse gets no gradient (only its sign is used, cspn.py:64).  It recomputes the fold, runs the adjoint steps on w',
+ *   one gate-gradient pass that also sums dL/db, then the fold's adjoint per pixel and a gather back to the raw guidance: every element
+ *   written once (no atomics: deterministic).  grad_guidance with n_iter >= 2 needs the history of a forward with the same arguments.
+ * Argument errors as the NONE op's block above, plus: K other than 3 / 5 / 7, norm other than 8SUM / 8SUM_ABS, sparse_C other than
+ * 0 / 1 / C or not matching a NULL / non-NULL sparse: CSPN_E_BADARG.  cspn2d_forward_kxk_f32 still takes K = 5 / 7 only. */
+size_t cspn2d_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter);
+size_t cspn2d_kxk_norm_history_bytes(int B, int C, int H, int W, int K, int n_iter);
+int cspn2d_forward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, float* out, float* history, size_t history_bytes,
+                                int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm,
+                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter);
+int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, const float* history, size_t history_bytes,
+                                 const float* grad_out, float* grad_guidance, float* grad_blur, int B, int C, int sparse_C, int H, int W, int K,
+                                 int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
