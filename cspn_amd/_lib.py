@@ -160,6 +160,11 @@ _LATE_SYMBOLS = {
     "cspn2d_backward_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
     "cspn2d_backward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 8
                                      + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
+    "cspn_guidance_head_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn_guidance_head_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn_guidance_head_kxk_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn_guidance_head_kxk_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

@@ -802,4 +802,63 @@ int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const
     return kxk_norm_backward(guidance, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
+// ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----
+static int head_kxk_check(const char* what, int B, int C, int h, int w, int H, int W, int K) {
+    if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }
+    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d h=%d w=%d H=%d W=%d", what, B, C, h, w, H, W); return CSPN_E_BADARG; }
+    if (H > 2 * h || W > 2 * w) { set_error("%s: H x W = %d x %d exceeds the unpooled %d x %d", what, H, W, 2 * h, 2 * w); return CSPN_E_BADARG; }
+    return 0;
+}
+
+static int head_kxk_check_ws(const char* what, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255u) != 0) { set_error("%s: workspace: need %zu bytes, 256-byte aligned", what, need); return CSPN_E_WORKSPACE; }
+    return 0;
+}
+
+static bool head_kxk_too_large(int B, int C, int h, int w, int H, int W, int K) {
+    return (long long)B * (K * K - 1) * H * W >= (1ll << 40) || (long long)C * h * w >= (1ll << 31) || (long long)(K * K - 1) * H * W >= (1ll << 31);
+}
+
+size_t cspn_guidance_head_kxk_workspace_bytes(int B, int C, int h, int w, int K) {
+    (void)B; (void)h; (void)w;
+    if (C <= 0) return 0;
+    return K == 3 ? cspn_guidance_head_workspace_bytes(C) : ((K == 5 || K == 7) ? head_kxk_workspace(C, K) : 0);
+}
+
+int cspn_guidance_head_kxk_f32(const float* x, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out, int B, int C, int h, int w,
+                               int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn_guidance_head_kxk_f32";
+    if (!x || !w_guidance || !guidance_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
+    if ((w_blur != nullptr) != (blur_out != nullptr)) { set_error("%s: w_blur and blur_out come together", what); return CSPN_E_BADARG; }
+    if (int e = head_kxk_check_ws(what, workspace, workspace_bytes, cspn_guidance_head_kxk_workspace_bytes(B, C, h, w, K))) return e;
+    if (K == 3) return cspn_guidance_head_f32(x, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, CSPN_NORM_NONE, workspace, workspace_bytes, stream);
+    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
+    if (B == 0) return 0;
+    return head_kxk_forward(x, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, K, workspace, (hipStream_t)stream);
+}
+
+size_t cspn_guidance_head_kxk_backward_workspace_bytes(int B, int C, int h, int w, int K) {
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
+    return K == 3 ? cspn_guidance_head_backward_workspace_bytes(B, C, h, w) : ((K == 5 || K == 7) ? head_kxk_backward_workspace(B, C, h, w, K) : 0);
+}
+
+int cspn_guidance_head_kxk_backward_f32(const float* x, const float* w_guidance, const float* w_blur, const float* grad_guidance, const float* grad_blur,
+                                        float* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W, int K,
+                                        void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn_guidance_head_kxk_backward_f32";
+    if (!x || !w_guidance || !grad_guidance) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
+    if ((w_blur != nullptr) != (grad_blur != nullptr)) { set_error("%s: w_blur and grad_blur come together", what); return CSPN_E_BADARG; }
+    if (grad_w_blur && !w_blur) { set_error("%s: grad_w_blur without a blur head", what); return CSPN_E_BADARG; }
+    if (B == 0 || (!grad_x && !grad_w_guidance && !grad_w_blur)) return 0;
+    if (int e = head_kxk_check_ws(what, workspace, workspace_bytes, cspn_guidance_head_kxk_backward_workspace_bytes(B, C, h, w, K))) return e;
+    if (K == 3)
+        return cspn_guidance_head_backward_f32(x, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, workspace,
+                                               workspace_bytes, stream);
+    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
+    return head_kxk_backward(x, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, K, workspace,
+                             (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -118,6 +118,14 @@ int head_backward(const float* x, const float* w6, const float* w5, const float*
 int head_forward(const float* x, const float* w6, const float* w5, float* gout, float* bout, int B, int C, int h, int w, int H, int W, int mode,
                  void* ws, hipStream_t st);
 
+// ---- the heads for K x K propagation, K = 5 or 7 (cspn_head_kxk.hip): C -> K*K-1 (raw guidance) and C -> 1 (blur) on the matrix cores ----
+size_t head_kxk_workspace(int C, int K);
+int head_kxk_forward(const float* x, const float* wg, const float* wb, float* gout, float* bout, int B, int C, int h, int w, int H, int W, int K, void* ws,
+                     hipStream_t st);
+size_t head_kxk_backward_workspace(int B, int C, int h, int w, int K);
+int head_kxk_backward(const float* x, const float* wg, const float* wb, const float* gg, const float* gb, float* dx, float* dwg, float* dwb, int B, int C,
+                      int h, int w, int H, int W, int K, void* ws, hipStream_t st);
+
 // ---- fused path (all iterations in one launch; time-skewed wave ring) ----
 bool fused2d_supported(int B, int H, int W, int n_iter);
 size_t fused2d_workspace(int B, int H, int W, int n_iter);

@@ -141,6 +141,57 @@ def createSparseDepthImage(depth_image, n_sample, mode="nyu", seed=0):
     return out
 
 
+_PLANES_TO_K = {8: 3, 24: 5, 48: 7}
+
+
+def _head_planes(x, weight_guidance, *others):
+    """the argument checks guidance_heads and guidance_heads_backward share -> the guidance head's plane count: 8, 24 or 48 (prop_kernel 3, 5 or 7)"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("x must be [B,C,h,w], got %s" % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__,))
+    if not isinstance(weight_guidance, torch.Tensor) or weight_guidance.dim() != 4 or int(weight_guidance.shape[0]) not in _PLANES_TO_K:
+        raise ValueError("weight_guidance must be [8 | 24 | 48, C, 3, 3] (prop_kernel 3, 5 or 7: K*K-1 planes), got %s"
+                         % (tuple(weight_guidance.shape) if isinstance(weight_guidance, torch.Tensor) else type(weight_guidance).__name__,))
+    for t in (weight_guidance,) + others:
+        if isinstance(t, torch.Tensor) and t.device != x.device:
+            raise ValueError("all tensors must live on the same device")
+    return int(weight_guidance.shape[0])
+
+
+def _heads_kxk_forward(xx, wg, wb, H, W):
+    """cspn_guidance_head_kxk_f32: the 24- / 48-plane guidance head and the blur head, raw, on the matrix cores"""
+    B, C, h, w = xx.shape
+    P = int(wg.shape[0])
+    K = _PLANES_TO_K[P]
+    g = torch.empty(B, P, H, W, dtype=torch.float32, device=xx.device)
+    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk_workspace_bytes")(B, C, h, w, K)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.late_symbol("cspn_guidance_head_kxk_f32")(xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
+                                                            b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
+                                                            torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_kxk_f32")
+    return g, b
+
+
+def _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w):
+    B, C, h, w = xx.shape
+    K = _PLANES_TO_K[int(wg.shape[0])]
+    H, W = int(gg.shape[2]), int(gg.shape[3])
+    dx = torch.empty_like(xx) if need_x else None
+    dwg = torch.empty_like(wg) if need_w else None
+    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward_workspace_bytes")(B, C, h, w, K)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.late_symbol("cspn_guidance_head_kxk_backward_f32")(
+            xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(), gb.data_ptr() if gb is not None else None,
+            dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None, dwb.data_ptr() if dwb is not None else None,
+            B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_kxk_backward_f32")
+    return dx, dwg, dwb
+
+
 def _heads_forward(xx, wg, wb, H, W, norm):
     lib = _lib.load()
     B, C, h, w = xx.shape
@@ -158,15 +209,21 @@ def _heads_forward(xx, wg, wb, H, W, norm):
 
 def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad_blur, need_x=True, need_w=True):
     """cspn_guidance_head_backward_f32: (dL/dx, dL/dweight_guidance, dL/dweight_blur) of the RAW heads -- what torch autograd computes through the two reference
-    layers (torch_resnet_cspn_nyu.py:187-206) -- from dL/dguidance [B,8,H,W] and dL/dblur [B,1,H,W] (None without a blur head); skipped outputs are None."""
+    layers (torch_resnet_cspn_nyu.py:187-206) -- from dL/dguidance [B,8,H,W] and dL/dblur [B,1,H,W] (None without a blur head); skipped outputs are None.
+    weight_guidance [24 | 48, C, 3, 3] with dL/dguidance [B, 24 | 48, H, W]: cspn_guidance_head_kxk_backward_f32, the heads of prop_kernel 5 / 7."""
     lib = _lib.load()
+    P = _head_planes(x, weight_guidance, weight_blur, grad_guidance, grad_blur)
     xx = _prep(x, "x")
     B, C, h, w = xx.shape
-    wg = _prep(weight_guidance, "weight_guidance", (8, C, 3, 3))
+    wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
     wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
+    if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
+        raise ValueError("grad_guidance must be [B,%d,H,W]" % P)
     H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
-    gg = _prep(grad_guidance, "grad_guidance", (B, 8, H, W))
+    gg = _prep(grad_guidance, "grad_guidance", (B, P, H, W))
     gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
+    if P != 8:
+        return _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w)
     dx = torch.empty_like(xx) if need_x else None
     dwg = torch.empty_like(wg) if need_w else None
     dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
@@ -200,6 +257,26 @@ class _GuidanceHeadsFunction(torch.autograd.Function):
         return dx, dwg if ctx.needs_input_grad[1] else None, dwb if (wb is not None and ctx.needs_input_grad[2]) else None, None, None
 
 
+class _GuidanceHeadsKxKFunction(torch.autograd.Function):
+    """the 24- / 48-plane guidance head + the blur head: cspn_guidance_head_kxk_f32 and its backward"""
+
+    @staticmethod
+    def forward(ctx, x, wg, wb, H, W):
+        ctx.save_for_backward(x, wg, wb)
+        return _heads_kxk_forward(x, wg, wb, H, W)
+
+    @staticmethod
+    def backward(ctx, grad_g, grad_b):
+        x, wg, wb = ctx.saved_tensors
+        if grad_g is None:
+            grad_g = torch.zeros(x.shape[0], wg.shape[0], grad_b.shape[2], grad_b.shape[3], device=x.device)
+        if wb is not None and grad_b is None:
+            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], device=x.device)
+        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
+        dx, dwg, dwb = _heads_kxk_backward(x, wg, wb, grad_g.contiguous(), grad_b.contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
+        return dx, dwg if ctx.needs_input_grad[1] else None, dwb if (wb is not None and ctx.needs_input_grad[2]) else None, None, None
+
+
 def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, norm_type=None):
     """The producer of the propagation's inputs: what the reference computes as
         guidance = self.gud_up_proj_layer6(x); x = self.gud_up_proj_layer5(x)          (torch_resnet_cspn_nyu.py:372-373)
@@ -210,7 +287,23 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     norm_type '8sum' | '8sum_abs': the guidance comes back normalised -- gate_wb of affinity_normalization (cspn.py:85-144) -- for
     cspn2d_forward(gate_wb, blur, sparse, n_iter, 'prenorm') / cspn_amd.propagate_prenorm.  With grad off the normalisation runs fused behind the conv
     (one kernel); with grad on and any input requiring grad, the raw heads (_GuidanceHeadsFunction) then the differentiable cspn2d_normalize: autograd chains
-    cspn2d_normalize_backward_f32 into cspn_guidance_head_backward_f32, so dL/dgate_wb from propagate_prenorm reaches x and both weights."""
+    cspn2d_normalize_backward_f32 into cspn_guidance_head_backward_f32, so dL/dgate_wb from propagate_prenorm reaches x and both weights.
+    weight_guidance [24 | 48, C, 3, 3] (Simple_Gudi_UpConv_Block_Last_Layer(C, 24 | 48, ...): prop_kernel 5 / 7): -> (guidance [B, 24 | 48, H, W], blur), the
+    inputs of Affinity_PropagateKxK(prop_time, 5 | 7, norm_type)(guidance, blur, sparse); cspn_guidance_head_kxk_f32, three GEMMs on the matrix cores forward
+    and backward (one autograd Function); raw only: a norm_type raises ValueError, the K x K contract normalises in its own fold."""
+    P = _head_planes(x, weight_guidance, weight_blur)
+    if P != 8:
+        if norm_type is not None:
+            raise ValueError("the %d-plane guidance head returns raw guidance only (norm_type=None): Affinity_PropagateKxK(prop_time, %d, norm_type) "
+                             "normalises it" % (P, _PLANES_TO_K[P]))
+        xx = _prep(x, "x")
+        B, C, h, w = xx.shape
+        wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
+        wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
+        H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
+        if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
+            return _GuidanceHeadsKxKFunction.apply(xx, wg, wb, H, W)
+        return _heads_kxk_forward(xx, wg, wb, H, W)
     if norm_type is not None and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, weight_guidance, weight_blur)):
         return _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth, norm_type)
     xx = _prep(x, "x")

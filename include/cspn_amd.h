@@ -49,7 +49,7 @@ extern "C" {
                               *    the cspn2d_*_multi entry points (C channels on shared 2D guidance), the demo's gate normalisation
                               *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32), the 2D K x K entry points
                               *    (cspn2d_*_kxk*, K = 5 / 7), K = 24 / 48 on the gate normaliser and the depth-completion contract over
-                              *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7) */
+                              *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -388,6 +388,23 @@ size_t cspn_guidance_head_backward_workspace_bytes(int B, int C, int h, int w);
 int cspn_guidance_head_backward_f32(const float* x, const float* w_guidance, const float* w_blur, const float* grad_guidance, const float* grad_blur,
                                     float* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W,
                                     void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the guidance heads for K x K propagation: Simple_Gudi_UpConv_Block_Last_Layer(C, K*K-1, ...) (the class takes the plane count as an argument) with the
+ * 1-plane blur head riding along -- the producer of what cspn2d_forward_kxk_norm_f32 consumes.  Raw guidance only (the K x K contract normalises in its own fold).
+ *   x [B,C,h,w];  w_guidance [K*K-1,C,3,3];  w_blur [1,C,3,3] or NULL;  guidance_out / grad_guidance [B,K*K-1,H,W];  blur_out / grad_blur [B,1,H,W] or NULL
+ *   (with w_blur: both or neither);  H <= 2h, W <= 2w;  grad_x [B,C,h,w], grad_w_guidance [K*K-1,C,3,3], grad_w_blur [1,C,3,3]: each may be NULL (skipped).
+ *   K = 5 or 7: three GEMMs on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32); the weight gradients' partial sums are added in a fixed order (no
+ *   atomics: deterministic).  K = 3 forwards to cspn_guidance_head_f32 (CSPN_NORM_NONE) / cspn_guidance_head_backward_f32: bitwise their results.
+ *   Any other K, H > 2h, W > 2w or a w_blur without blur_out / grad_blur: CSPN_E_BADARG.
+ * workspace: the matching *_workspace_bytes(B, C, h, w, K) bytes, 256-byte aligned; too small or misaligned: CSPN_E_WORKSPACE from both calls. */
+size_t cspn_guidance_head_kxk_workspace_bytes(int B, int C, int h, int w, int K);
+int cspn_guidance_head_kxk_f32(const float* x, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out,
+                               int B, int C, int h, int w, int H, int W, int K,
+                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn_guidance_head_kxk_backward_workspace_bytes(int B, int C, int h, int w, int K);
+int cspn_guidance_head_kxk_backward_f32(const float* x, const float* w_guidance, const float* w_blur, const float* grad_guidance, const float* grad_blur,
+                                        float* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W, int K,
+                                        void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 #ifdef __cplusplus
 }
