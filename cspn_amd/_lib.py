@@ -14,6 +14,7 @@ NORM_TYPES = {"8sum": 0, "8sum_abs": 1, "none": 2, "prenorm": 3}
 ALGOS = {"auto": 0, "stepwise": 1, "fused": 2, "fused_cxx": 3, "fused_padded": 4}
 ALGOS_3D = {"auto": 0, "stepwise": 1, "persistent": 2}
 ABI_VERSION = 5
+DTYPES = {"float16": 1, "bfloat16": 2}   # CSPN_DTYPE_F16 / CSPN_DTYPE_BF16: the gate storage types of the *_g16 entry points
 
 HOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libcspn_amd_hooks.so")
 
@@ -160,6 +161,15 @@ _LATE_SYMBOLS = {
     "cspn2d_backward_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
     "cspn2d_backward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 8
                                      + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the same four on fp16 / bf16 gates or guidance (gate_dtype DTYPES[...]); values, workspace and history stay float32
+    "cspn2d_forward_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_int] * 6
+                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
+                                + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_forward_kxk_norm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 8
+                                    + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_norm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
+                                     + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
     "cspn_guidance_head_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cspn_guidance_head_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

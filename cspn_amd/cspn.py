@@ -18,7 +18,10 @@ Differences a caller can observe, all deliberate:
     sparse_depth gets no gradient (only its sign is used, cspn.py:64);
   * blur_depth [B,C,H,W] with C > 1 is propagated on the shared affinities like the reference's broadcast (cspn.py:58-81), with
     sparse_depth None, [B,1,H,W] or [B,C,H,W]: one engine call each way (cspn2d_forward_multi_f32 / cspn2d_backward_multi_f32),
-    dL/dguidance summed over the channels."""
+    dL/dguidance summed over the channels;
+  * float16 / bfloat16 inputs (heads under torch.autocast) are taken and the result is float32: Affinity_PropagateKxK with prop_kernel
+    5 / 7 hands 16-bit guidance to the engine as it is (widened exactly where used, dL/dguidance in its dtype); everything without a 16-bit
+    kernel (Affinity_Propagate, prop_kernel 3, propagate_prenorm, CSPN) widens with a differentiable .float() first."""
 import torch
 import torch.nn as nn
 
@@ -99,6 +102,7 @@ def propagate_prenorm(gate_wb, blur_depth, sparse_depth=None, n_iter=24, algo="a
     train_utils.guidance_heads(..., norm_type='8sum' | '8sum_abs') (that, then cspn_guidance_head_backward_f32)."""
     if n_iter == 0:
         return blur_depth
+    gate_wb, blur_depth, sparse_depth = F.widen16(gate_wb, blur_depth, sparse_depth)
     return _apply(gate_wb, blur_depth, sparse_depth, int(n_iter), "prenorm", algo, keep_history)
 
 
@@ -122,6 +126,7 @@ class Affinity_Propagate(nn.Module):
             raise ValueError('unknown norm %s' % self.norm_type)
         if n == 0:
             return blur_depth  # cspn.py:61,66,83: the very same tensor object
+        guidance, blur_depth, sparse_depth = F.widen16(guidance, blur_depth, sparse_depth)   # no 16-bit 3 x 3 kernel: float32 from here on
         return _apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
 
     def extra_repr(self):
@@ -156,7 +161,8 @@ class Affinity_PropagateKxK(nn.Module):
     (torch_resnet_cspn_nyu.py:281,344-347; cspn.py:24 "current only support 3x3").  guidance [B, K*K-1, H, W] raw, channel k the k-th
     pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour (K//2 - t, K//2 - l): at K = 3 the
     reference's gate1 .. gate8.  prop_kernel 3 runs today's 3 x 3 path (bitwise Affinity_Propagate); 5 and 7 the K x K engine
-    (F.cspn2d_forward_kxk_norm), differentiable w.r.t. guidance and blur_depth."""
+    (F.cspn2d_forward_kxk_norm), differentiable w.r.t. guidance and blur_depth.  float16 / bfloat16 guidance goes to the K x K engine as it
+    is (prop_kernel 3: widened first); the result is float32."""
 
     def __init__(self, prop_time, prop_kernel, norm_type='8sum'):
         super(Affinity_PropagateKxK, self).__init__()
@@ -172,8 +178,9 @@ class Affinity_PropagateKxK(nn.Module):
         n = self.prop_time if n_iter is None else int(n_iter)
         if n == 0:
             return blur_depth
+        blur_depth, sparse_depth = F.widen16(blur_depth, sparse_depth)
         if self.prop_kernel == 3:
-            return _apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
+            return _apply(F.widen16(guidance), blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
         if torch.is_grad_enabled() and (guidance.requires_grad or blur_depth.requires_grad):
             return _CSPN2dKxKNormFunction.apply(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
         return F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
@@ -201,6 +208,7 @@ class CSPN(nn.Module):
     def cspn(self, guide, feat):
         if feat.dim() != self.dim_num + 2:
             raise ValueError("feat must have %d dimensions for dim_num %d, got %s" % (self.dim_num + 2, self.dim_num, tuple(feat.shape)))
+        guide, feat = F.widen16(guide, feat)   # the gate normaliser has no 16-bit kernel: float32 from here on
         return F.absnorm_propagate(guide, feat, self.prop_step, self.prop_kernel)
 
     def forward(self, guide, feat):

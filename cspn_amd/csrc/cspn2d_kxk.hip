@@ -13,6 +13,15 @@
 // Below them, the depth-completion contract of Affinity_Propagate over K x K (K = 3, 5 or 7): folded into w' and a bias b by kxk_fold,
 // run by the same step with BIAS, and differentiated by the same adjoint step, the gate gradient with BIAS, kxk_unfold_pixel and
 // kxk_unsite.
+// Gate storage type GT: float, or __half / __hip_bfloat16 (the *_g16 entry points).  A 16-bit gate is widened to float32 exactly where
+// it is used, every multiply-add and sum is the float32 one in the same order, so the results are bitwise those of the float instance
+// on the widened gates; a gradient with respect to a 16-bit tensor is accumulated in float32 and rounded once (to nearest even,
+// subnormals kept) at its single store.  Values, levels, w', b, the mask and grad_x are float32 throughout.
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+
+#include <type_traits>
+
 #include "cspn_common.h"
 
 namespace cspn {
@@ -55,27 +64,130 @@ __device__ __forceinline__ void stage(float* lds, const float* __restrict__ s, i
     }
 }
 
-// four pixels x0 .. x0+3 of row y (p = row offset of x0); VEC: W % 4 == 0 and the plane 16-byte aligned (a quad is then all in or all out)
-template <bool VEC>
-__device__ __forceinline__ void load4(float (&v)[4], const float* __restrict__ p, bool row_in, int x0, int W) {
-    if (VEC) {
-        const float4 q = (row_in && x0 < W) ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (row_in && x0 + j < W) ? p[j] : 0.f;
+// ---- the gate storage type.  A 16-bit gate travels as its bit pattern (unsigned short); float gates as themselves ----
+template <class GT>
+struct Store {
+    using type = unsigned short;
+};
+template <>
+struct Store<float> {
+    using type = float;
+};
+template <class GT>
+using store_t = typename Store<GT>::type;
+
+// exact widening of a stored gate
+template <class GT>
+__device__ __forceinline__ float widen(store_t<GT> v) {
+    if constexpr (std::is_same<GT, float>::value) return v;
+    else if constexpr (std::is_same<GT, __half>::value) return (float)__builtin_bit_cast(_Float16, v);
+    else return __uint_as_float((uint32_t)v << 16);
+}
+
+// the single rounding of a float32 gradient to the storage type: to nearest even, subnormals kept, NaN stays NaN
+template <class GT>
+__device__ __forceinline__ store_t<GT> narrow(float v) {
+    if constexpr (std::is_same<GT, float>::value) return v;
+    else if constexpr (std::is_same<GT, __half>::value) return __builtin_bit_cast(unsigned short, (_Float16)v);
+    else {
+        const uint32_t u = __float_as_uint(v);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0;
+        return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
     }
 }
 
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ p, const float (&v)[4], bool row_in, int x0, int W) {
-    if (!row_in) return;
-    if (VEC) {
-        if (x0 < W) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
+// the four gates of pixels x0 .. x0+3 as a thread holds them: float as four registers, 16-bit packed two to a register and widened at
+// the multiply-add (fp16 by the mixed-precision FMA's operand select, bf16 by a shift or a mask)
+template <class GT>
+struct Quad {
+    uint32_t p[2];
+    __device__ __forceinline__ void clear() { p[0] = p[1] = 0u; }
+    // keeps the packed form live across the channel loop: without it the compiler hoists the widening out of the loop and holds four
+    // registers per quad, as the float instance does
+    __device__ __forceinline__ void pin() { asm volatile("" : "+v"(p[0]), "+v"(p[1])); }
+    __device__ __forceinline__ void put(int j, unsigned short v) { p[j >> 1] |= (uint32_t)v << (16 * (j & 1)); }
+    __device__ __forceinline__ float get(int j) const {
+        if constexpr (std::is_same<GT, __half>::value) return widen<GT>((unsigned short)(p[j >> 1] >> (16 * (j & 1))));
+        else return __uint_as_float((j & 1) ? (p[j >> 1] & 0xffff0000u) : (p[j >> 1] << 16));
+    }
+};
+template <>
+struct Quad<float> {
+    float v[4];
+    __device__ __forceinline__ void clear() { v[0] = v[1] = v[2] = v[3] = 0.f; }
+    __device__ __forceinline__ void pin() {}
+    __device__ __forceinline__ void put(int j, float x) { v[j] = x; }
+    __device__ __forceinline__ float get(int j) const { return v[j]; }
+};
+
+// four pixels x0 .. x0+3 of row y (p = row offset of x0), widened; VEC: W % 4 == 0 and the plane aligned to four elements (16 bytes
+// for float, 8 for a 16-bit type; a quad is then all in or all out)
+template <bool VEC, class T = float>
+__device__ __forceinline__ void load4(float (&v)[4], const store_t<T>* __restrict__ p, bool row_in, int x0, int W) {
+    if constexpr (std::is_same<T, float>::value) {
+        if (VEC) {
+            const float4 q = (row_in && x0 < W) ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (x0 + j < W) p[j] = v[j];
+            for (int j = 0; j < 4; ++j) v[j] = (row_in && x0 + j < W) ? p[j] : 0.f;
+        }
+    } else {
+        if (VEC) {
+            const uint2 q = (row_in && x0 < W) ? *reinterpret_cast<const uint2*>(p) : make_uint2(0u, 0u);
+            v[0] = widen<T>((unsigned short)q.x); v[1] = widen<T>((unsigned short)(q.x >> 16));
+            v[2] = widen<T>((unsigned short)q.y); v[3] = widen<T>((unsigned short)(q.y >> 16));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (row_in && x0 + j < W) ? widen<T>(p[j]) : 0.f;
+        }
+    }
+}
+
+// a guarded 2-byte gate load without a branch: the address is p where ok, else safe (any element inside the tensor), the value selected
+// afterwards.  A load inside the guard's branch has its pack behind a full vmcnt wait, which serialises a thread's gate loads
+__device__ __forceinline__ unsigned short load16(const unsigned short* __restrict__ p, bool ok, const unsigned short* __restrict__ safe) {
+    const unsigned short v = *(ok ? p : safe);
+    return ok ? v : (unsigned short)0;
+}
+
+// the same four gates as the thread keeps them over the channel loop; safe: an element inside the gate tensor (16-bit scalar path)
+template <bool VEC, class GT>
+__device__ __forceinline__ void load_quad(Quad<GT>& g, const store_t<GT>* __restrict__ p, bool row_in, int x0, int W,
+                                          const store_t<GT>* __restrict__ safe) {
+    if constexpr (std::is_same<GT, float>::value) {
+        load4<VEC>(g.v, p, row_in, x0, W);
+    } else if (VEC) {
+        const uint2 q = (row_in && x0 < W) ? *reinterpret_cast<const uint2*>(p) : make_uint2(0u, 0u);
+        g.p[0] = q.x; g.p[1] = q.y;
+    } else {
+        g.clear();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g.put(j, load16(p + j, row_in && x0 + j < W, safe));
+    }
+}
+
+template <bool VEC, class T = float>
+__device__ __forceinline__ void store4(store_t<T>* __restrict__ p, const float (&v)[4], bool row_in, int x0, int W) {
+    if (!row_in) return;
+    if constexpr (std::is_same<T, float>::value) {
+        if (VEC) {
+            if (x0 < W) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < W) p[j] = v[j];
+        }
+    } else {
+        if (VEC) {
+            if (x0 < W)
+                *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)narrow<T>(v[0]) | ((uint32_t)narrow<T>(v[1]) << 16),
+                                                          (uint32_t)narrow<T>(v[2]) | ((uint32_t)narrow<T>(v[3]) << 16));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < W) p[j] = narrow<T>(v[j]);
+        }
     }
 }
 
@@ -83,10 +195,10 @@ __device__ __forceinline__ void store4(float* __restrict__ p, const float (&v)[4
 template <int K>
 __host__ __device__ constexpr int chan(int t, int l) { return t * K + l - (t * K + l > (K / 2) * (K + 1) ? 1 : 0); }
 
-// one forward step for all C channels: dst = step(src).  VEC: W % 4 == 0, gate and dst 16-byte aligned
+// one forward step for all C channels: dst = step(src).  VEC: W % 4 == 0, dst 16-byte aligned, gate aligned to four elements
 // BIAS: the accumulator starts from bias [N][C][H][W] (the folded normalising contract, kxk_fold), 16-byte aligned where VEC
-template <int K, bool VEC, bool BIAS = false>
-__global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
+template <int K, bool VEC, bool BIAS = false, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
                                                        int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
@@ -94,15 +206,17 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__
     const int HW = H * W;
     const bool row_in = T.y < H;
     const int pix = T.y * W + T.x0;
-    float g[KK][4];
-    const float* gp = gate + (size_t)T.n * KK * HW + pix;
+    Quad<GT> g[KK];
+    const store_t<GT>* gp = gate + (size_t)T.n * KK * HW + pix;
 #pragma unroll
-    for (int k = 0; k < KK; ++k) load4<VEC>(g[k], gp + (size_t)k * HW, row_in, T.x0, W);
+    for (int k = 0; k < KK; ++k) load_quad<VEC, GT>(g[k], gp + (size_t)k * HW, row_in, T.x0, W, gate);
     for (int c = 0; c < C; ++c) {
         const size_t plane = ((size_t)T.n * C + c) * HW;
         __syncthreads();   // the previous channel's reads of lds are done
         stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
         __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KK; ++k) g[k].pin();
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if constexpr (BIAS) load4<VEC>(acc, bias + plane + pix, row_in, T.x0, W);
 #pragma unroll
@@ -115,7 +229,7 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__
                 if (t == R && l == R) continue;
                 const int k = chan<K>(t, l);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k][j], row[j + 2 * R - l], acc[j]);
+                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k].get(j), row[j + 2 * R - l], acc[j]);
             }
         }
         store4<VEC>(dst + plane + pix, acc, row_in, T.x0, W);
@@ -123,17 +237,17 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const float* __restrict__
 }
 
 // one adjoint step for all C channels: dst = step^T(src).  The gate of pixel q and channel k is read at q - off_k (zero outside the
-// image); VEC: W % 4 == 0 and dst 16-byte aligned
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
+// image); VEC: W % 4 == 0 and dst 16-byte aligned, 16-bit gates 8-byte aligned
+template <int K, bool VEC, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
                                                        int C, int H, int W, int tiles_x, int tiles_y) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
     const int HW = H * W;
     const bool row_in = T.y < H;
-    float g[KK][4];
-    const float* gb = gate + (size_t)T.n * KK * HW;
+    Quad<GT> g[KK];
+    const store_t<GT>* gb = gate + (size_t)T.n * KK * HW;
 #pragma unroll
     for (int t = 0; t < K; ++t) {
         const int py = T.y - R + t;
@@ -142,10 +256,44 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__
         for (int l = 0; l < K; ++l) {
             if (t == R && l == R) continue;
             const int k = chan<K>(t, l);
+            if constexpr (VEC && !std::is_same<GT, float>::value) {
+                // 16-bit, W % 4 == 0 and the gates 8-byte aligned: the four gates x0 + d .. x0 + d + 3 (d = l - R) are a 64-bit window of
+                // the aligned quads at x0 - 4, x0 and x0 + 4 (each all inside the row or all outside: zero): one or two 8-byte loads and
+                // a funnel shift, no 2-byte load and no pack
+                const store_t<GT>* row = gb + (size_t)k * HW + py * W;
+                auto quad = [&](int x) {
+                    return (yin && T.x0 < W && x >= 0 && x < W) ? *reinterpret_cast<const uint2*>(row + x) : make_uint2(0u, 0u);
+                };
+                const int s = l - R;   // compile-time after unrolling
+                const uint2 b = quad(T.x0);
+                uint32_t w[4];
+                if (s < 0) {
+                    const uint2 a = quad(T.x0 - 4);
+                    w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y;
+                } else {
+                    const uint2 a = s > 0 ? quad(T.x0 + 4) : make_uint2(0u, 0u);
+                    w[0] = b.x; w[1] = b.y; w[2] = a.x; w[3] = a.y;
+                }
+                const int e = s < 0 ? 4 + s : s, i = e >> 1;   // first element of the window in w, its word
+                if (e & 1) {
+                    g[k].p[0] = (w[i] >> 16) | (w[i + 1] << 16);
+                    g[k].p[1] = (w[i + 1] >> 16) | (w[i + 2] << 16);
+                } else {
+                    g[k].p[0] = w[i];
+                    g[k].p[1] = w[i + 1];
+                }
+                continue;
+            }
+            g[k].clear();
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int px = T.x0 + j - R + l;
-                g[k][j] = (yin && T.x0 + j < W && px >= 0 && px < W) ? gb[(size_t)k * HW + py * W + px] : 0.f;
+                const bool ok = yin && T.x0 + j < W && px >= 0 && px < W;
+                if constexpr (std::is_same<GT, float>::value) {
+                    if (ok) g[k].put(j, gb[(size_t)k * HW + py * W + px]);
+                } else {
+                    g[k].put(j, load16(gb + (size_t)k * HW + py * W + px, ok, gb));
+                }
             }
         }
     }
@@ -154,6 +302,8 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__
         __syncthreads();
         stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
         __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KK; ++k) g[k].pin();
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < K; ++t) {
@@ -165,7 +315,7 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__
                 if (t == R && l == R) continue;
                 const int k = chan<K>(t, l);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k][j], row[j + l], acc[j]);
+                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k].get(j), row[j + l], acc[j]);
             }
         }
         store4<VEC>(dst + plane + T.y * W + T.x0, acc, row_in, T.x0, W);
@@ -173,12 +323,13 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const float* __restrict__
 }
 
 // dL/dg for all KK channels of the tile: the levels H_0 = x, H_t = hist + (t - 1) L (t >= 1) and A_t = alev + (t - 1) L (t < n),
-// A_n = gout, L = N C H W.  Accumulated over t = 0 .. n-1, then c = 0 .. C-1, written once.  VEC: W % 4 == 0 and gg 16-byte aligned.
+// A_n = gout, L = N C H W.  Accumulated over t = 0 .. n-1, then c = 0 .. C-1, written once (a 16-bit gg: rounded once, there).
+// VEC: W % 4 == 0 and gg aligned to four elements.
 // BIAS: also db [N][C][H][W] = sum_t A_{t+1} (dL/dbias of the folded contract); the loops then run over c, then t, and GATES = false
 // leaves out the gate gradient (no H level is read, gg and hist unused); db 16-byte aligned where VEC
-template <int K, bool VEC, bool BIAS = false, bool GATES = true>
+template <int K, bool VEC, bool BIAS = false, bool GATES = true, class GT = float>
 __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x, const float* __restrict__ hist, const float* __restrict__ alev,
-                                                    const float* __restrict__ gout, float* __restrict__ gg, int n_iter, size_t L, int C, int H,
+                                                    const float* __restrict__ gout, store_t<GT>* __restrict__ gg, int n_iter, size_t L, int C, int H,
                                                     int W, int tiles_x, int tiles_y, float* __restrict__ db) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
@@ -251,13 +402,16 @@ __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x,
         }
     }
     if constexpr (GATES) {
-        float* gp = gg + (size_t)T.n * KK * HW + pix;
+        store_t<GT>* gp = gg + (size_t)T.n * KK * HW + pix;
 #pragma unroll
-        for (int k = 0; k < KK; ++k) store4<VEC>(gp + (size_t)k * HW, acc[k], row_in, T.x0, W);
+        for (int k = 0; k < KK; ++k) store4<VEC, GT>(gp + (size_t)k * HW, acc[k], row_in, T.x0, W);
     }
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// four elements of the gate storage type: 16 bytes for float, 8 for a 16-bit type
+template <class GT>
+bool aligned_quad(const void* p) { return ((uintptr_t)p & (4 * sizeof(store_t<GT>) - 1)) == 0; }
 
 struct Grid {
     int tx, ty;
@@ -279,8 +433,8 @@ Grid grid_of(int N, int H, int W) {
 // the batch: N' = B C images of one channel, each with its own w', cpg = C images per guidance image.
 
 // G_k of the four pixels x0 .. x0+3 of row y: the guidance read at the neighbour (zero outside the image), abs for 8SUM_ABS
-template <int K>
-__device__ __forceinline__ void sited_gates(float (&G)[K * K - 1][4], const float* __restrict__ gb, bool row_in, int y, int x0, int H, int W,
+template <int K, class GT>
+__device__ __forceinline__ void sited_gates(float (&G)[K * K - 1][4], const store_t<GT>* __restrict__ gb, bool row_in, int y, int x0, int H, int W,
                                             bool ab) {
     constexpr int R = K / 2;
     const int HW = H * W;
@@ -295,7 +449,7 @@ __device__ __forceinline__ void sited_gates(float (&G)[K * K - 1][4], const floa
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int px = x0 + j + R - l;
-                const float v = (yin && x0 + j < W && px >= 0 && px < W) ? gb[(size_t)k * HW + py * W + px] : 0.f;
+                const float v = (yin && x0 + j < W && px >= 0 && px < W) ? widen<GT>(gb[(size_t)k * HW + py * W + px]) : 0.f;
                 G[k][j] = ab ? fabsf(v) : v;
             }
         }
@@ -315,8 +469,8 @@ __device__ __forceinline__ void mask4(float (&m)[4], float (&u)[4], const float*
 }
 
 // w' [N'][KK][H][W] and b [N'][Cv][H][W] of image n' (guidance image n' / cpg).  VEC: W % 4 == 0, blur 16-byte aligned
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void kxk_fold(const float* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
+template <int K, bool VEC, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_fold(const store_t<GT>* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
                                                float* __restrict__ wp, float* __restrict__ bias, int Cv, int cpg, int norm, int H, int W, int tiles_x,
                                                int tiles_y) {
     constexpr int KK = K * K - 1;
@@ -325,7 +479,7 @@ __global__ __launch_bounds__(NT) void kxk_fold(const float* __restrict__ guid, c
     const bool row_in = T.y < H;
     const int pix = T.y * W + T.x0;
     float G[KK][4];
-    sited_gates<K>(G, guid + (size_t)(T.n / cpg) * KK * HW, row_in, T.y, T.x0, H, W, norm == CSPN_NORM_8SUM_ABS);
+    sited_gates<K, GT>(G, guid + (size_t)(T.n / cpg) * KK * HW, row_in, T.y, T.x0, H, W, norm == CSPN_NORM_8SUM_ABS);
     float S[4] = {0.f, 0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f}, m[4], u[4];
 #pragma unroll
     for (int k = 0; k < KK; ++k)
@@ -360,8 +514,8 @@ __global__ __launch_bounds__(NT) void kxk_fold(const float* __restrict__ guid, c
 //   dwb_k = sum_i u_i (dw'_{n',k} - sum_c blur_{n',c} db_{n',c}),  dG_k = (dwb_k - sign(G_k) sum_j wb_j dwb_j) / S  -> dw' of image b cpg
 //   (in place: every element is read and written by the same thread), and where gx is given
 //   gx_{n',c} = A_0 + (u_i c + m_i) db_{n',c} (gx holds A_0).  need_g = false: only the second.  VEC: W % 4 == 0, blur and gx 16-byte aligned
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void kxk_unfold_pixel(const float* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
+template <int K, bool VEC, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_unfold_pixel(const store_t<GT>* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
                                                        float* __restrict__ dwp, const float* __restrict__ db, float* __restrict__ gx, int need_g, int Cv,
                                                        int cpg, int norm, int H, int W, int tiles_x, int tiles_y) {
     constexpr int R = K / 2, KK = K * K - 1;
@@ -369,7 +523,7 @@ __global__ __launch_bounds__(NT) void kxk_unfold_pixel(const float* __restrict__
     const int HW = H * W;
     const bool row_in = T.y < H;
     const int pix = T.y * W + T.x0;
-    const float* gb = guid + (size_t)T.n * KK * HW;
+    const store_t<GT>* gb = guid + (size_t)T.n * KK * HW;
     const bool ab = norm == CSPN_NORM_8SUM_ABS;
     // G_k of the four pixels (kxk_fold's sited_gates, one channel at a time: the passes below re-read it from the cache rather than
     // keep KK x 4 values live)
@@ -379,7 +533,7 @@ __global__ __launch_bounds__(NT) void kxk_unfold_pixel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int px = T.x0 + j + R - l;
-            const float g = (yin && T.x0 + j < W && px >= 0 && px < W) ? gb[(size_t)k * HW + py * W + px] : 0.f;
+            const float g = (yin && T.x0 + j < W && px >= 0 && px < W) ? widen<GT>(gb[(size_t)k * HW + py * W + px]) : 0.f;
             v[j] = ab ? fabsf(g) : g;
         }
     };
@@ -470,9 +624,9 @@ __global__ __launch_bounds__(NT) void kxk_unfold_pixel(const float* __restrict__
 }
 
 // un-siting, a gather: dL/dguidance_k(q) = dG_k(q - off_k) (zero outside the image), times sign(g_k(q)) for 8SUM_ABS; dG of image b at
-// dg + b cpg KK H W.  VEC: W % 4 == 0, guid and gg 16-byte aligned
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, const float* __restrict__ guid, float* __restrict__ gg, int cpg, int norm,
+// dg + b cpg KK H W.  VEC: W % 4 == 0, guid and gg aligned to four elements.  A 16-bit gg is rounded here, at its only store
+template <int K, bool VEC, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, const store_t<GT>* __restrict__ guid, store_t<GT>* __restrict__ gg, int cpg, int norm,
                                                  int H, int W, int tiles_x, int tiles_y) {
     constexpr int R = K / 2, KK = K * K - 1;
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -497,17 +651,17 @@ __global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, c
             const size_t at = ((size_t)T.n * KK + k) * HW + pix;
             if (norm == CSPN_NORM_8SUM_ABS) {
                 float g[4];
-                load4<VEC>(g, guid + at, row_in, T.x0, W);
+                load4<VEC, GT>(g, guid + at, row_in, T.x0, W);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] *= signf(g[j]);
             }
-            store4<VEC>(gg + at, v, row_in, T.x0, W);
+            store4<VEC, GT>(gg + at, v, row_in, T.x0, W);
         }
     }
 }
 
-template <int K, bool BIAS = false>
-int forward_steps(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
+template <int K, bool BIAS = false, class GT = float>
+int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
                   const float* bias = nullptr) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
@@ -516,10 +670,10 @@ int forward_steps(const float* gate, const float* x, float* out, float* hist, in
     const float* src = x;
     for (int it = 1; it <= n_iter; ++it) {
         float* dst = it == n_iter ? out : (hist ? hist + (size_t)(it - 1) * L : ((it & 1) ? ping : pong));
-        if (W % 4 == 0 && aligned16(gate) && aligned16(dst) && (!BIAS || aligned16(bias)))
-            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
+        if (W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)))
+            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         else
-            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
+            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         if (int e = check_launch("kxk_forward_step")) return e;
         src = dst;
     }
@@ -527,35 +681,37 @@ int forward_steps(const float* gate, const float* x, float* out, float* hist, in
 }
 
 // the adjoint steps A_{n-1} .. A_last into alev (A_t at alev + (t - 1) L), A_0 into gx
-template <int K>
-int adjoint_steps(const float* gate, const float* gout, float* gx, float* alev, int last, int N, int C, int H, int W, int n_iter, hipStream_t st) {
+template <int K, class GT = float>
+int adjoint_steps(const store_t<GT>* gate, const float* gout, float* gx, float* alev, int last, int N, int C, int H, int W, int n_iter, hipStream_t st) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
     for (int t = n_iter - 1; t >= last; --t) {
         const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
         float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
-        if (W % 4 == 0 && aligned16(dst))
-            hipLaunchKernelGGL((kxk_adjoint_step<K, true>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+        if (W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)))
+            hipLaunchKernelGGL((kxk_adjoint_step<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
         else
-            hipLaunchKernelGGL((kxk_adjoint_step<K, false>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+            hipLaunchKernelGGL((kxk_adjoint_step<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
         if (int e = check_launch("kxk_adjoint_step")) return e;
     }
     return 0;
 }
 
-template <int K>
-int backward_run(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W,
+template <int K, class GT = float>
+int backward_run(const store_t<GT>* gate, const float* x, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int N, int C, int H, int W,
                  int n_iter, void* ws, hipStream_t st) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
     float* alev = (float*)ws;   // A_1 .. A_{n-1}, level t at alev + (t - 1) L
     // the adjoint steps: A_{n-1} .. A_1 always (the gate gradient reads them), A_0 = dL/dx where asked for
-    if (int e = adjoint_steps<K>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st)) return e;
+    if (int e = adjoint_steps<K, GT>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st)) return e;
     if (!gg) return 0;
-    if (W % 4 == 0 && aligned16(gg))
-        hipLaunchKernelGGL((kxk_gate_grad<K, true>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty, nullptr);
+    if (W % 4 == 0 && aligned_quad<GT>(gg))
+        hipLaunchKernelGGL((kxk_gate_grad<K, true, false, true, GT>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx,
+                           G.ty, nullptr);
     else
-        hipLaunchKernelGGL((kxk_gate_grad<K, false>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx, G.ty, nullptr);
+        hipLaunchKernelGGL((kxk_gate_grad<K, false, false, true, GT>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx,
+                           G.ty, nullptr);
     return check_launch("kxk_gate_grad");
 }
 
@@ -570,29 +726,29 @@ NormGeo norm_geo(int B, int C, int sparse_C, int H, int W) {
     return NormGeo{pc ? B * C : B, pc ? 1 : C, pc ? C : 1, (size_t)B * C * H * W};
 }
 
-template <int K>
-int fold(const float* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st) {
+template <int K, class GT = float>
+int fold(const store_t<GT>* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st) {
     const Grid G = grid_of(g.N, H, W);
     if (W % 4 == 0 && aligned16(blur))
-        hipLaunchKernelGGL((kxk_fold<K, true>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
+        hipLaunchKernelGGL((kxk_fold<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
     else
-        hipLaunchKernelGGL((kxk_fold<K, false>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
+        hipLaunchKernelGGL((kxk_fold<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
     return check_launch("kxk_fold");
 }
 
-template <int K>
-int norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
+template <int K, class GT = float>
+int norm_forward(const store_t<GT>* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
                  int n_iter, int norm, void* ws, hipStream_t st) {
     constexpr int KK = K * K - 1;
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     float* wp = (float*)ws;
     float* bias = wp + kxk_level_floats((size_t)g.N * KK * H * W);
-    if (int e = fold<K>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
     return forward_steps<K, true>(wp, blur, out, hist, g.N, g.Cv, H, W, n_iter, bias + kxk_level_floats(g.L), st, bias);
 }
 
-template <int K>
-int norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B, int C,
+template <int K, class GT = float>
+int norm_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int B, int C,
                   int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
     constexpr int KK = K * K - 1;
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
@@ -602,7 +758,7 @@ int norm_backward(const float* guid, const float* blur, const float* sparse, con
     float* dwp = bias + kxk_level_floats(g.L);
     float* dbp = dwp + P;
     float* alev = dbp + kxk_level_floats(g.L);
-    if (int e = fold<K>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
     if (int e = adjoint_steps<K>(wp, gout, gx, alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
     const Grid G = grid_of(g.N, H, W);
     const bool vec = W % 4 == 0;   // dwp and dbp: workspace
@@ -624,17 +780,17 @@ int norm_backward(const float* guid, const float* blur, const float* sparse, con
     if (int e = check_launch("kxk_gate_grad")) return e;
     const Grid GB = grid_of(B, H, W);
     if (vec && aligned16(blur) && (!gx || aligned16(gx)))
-        hipLaunchKernelGGL((kxk_unfold_pixel<K, true>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
+        hipLaunchKernelGGL((kxk_unfold_pixel<K, true, GT>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
                            H, W, GB.tx, GB.ty);
     else
-        hipLaunchKernelGGL((kxk_unfold_pixel<K, false>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
+        hipLaunchKernelGGL((kxk_unfold_pixel<K, false, GT>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
                            H, W, GB.tx, GB.ty);
     if (int e = check_launch("kxk_unfold_pixel")) return e;
     if (!gg) return 0;
-    if (vec && aligned16(guid) && aligned16(gg))
-        hipLaunchKernelGGL((kxk_unsite<K, true>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+    if (vec && aligned_quad<GT>(guid) && aligned_quad<GT>(gg))
+        hipLaunchKernelGGL((kxk_unsite<K, true, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
     else
-        hipLaunchKernelGGL((kxk_unsite<K, false>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+        hipLaunchKernelGGL((kxk_unsite<K, false, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
     return check_launch("kxk_unsite");
 }
 
@@ -651,6 +807,28 @@ int kxk_backward(const float* gate, const float* x, const float* hist, const flo
                  int n_iter, void* ws, hipStream_t st) {
     return K == 5 ? backward_run<5>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st)
                   : backward_run<7>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st);
+}
+
+// the same on 16-bit gates (dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16, checked by the caller); gg in the gates' type
+int kxk_forward_g16(const void* gate, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
+                    hipStream_t st) {
+    const unsigned short* g = (const unsigned short*)gate;
+    if (dtype == CSPN_DTYPE_F16)
+        return K == 5 ? forward_steps<5, false, __half>(g, x, out, hist, N, C, H, W, n_iter, ws, st)
+                      : forward_steps<7, false, __half>(g, x, out, hist, N, C, H, W, n_iter, ws, st);
+    return K == 5 ? forward_steps<5, false, __hip_bfloat16>(g, x, out, hist, N, C, H, W, n_iter, ws, st)
+                  : forward_steps<7, false, __hip_bfloat16>(g, x, out, hist, N, C, H, W, n_iter, ws, st);
+}
+
+int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
+                     int W, int K, int n_iter, void* ws, hipStream_t st) {
+    const unsigned short* g = (const unsigned short*)gate;
+    unsigned short* d = (unsigned short*)gg;
+    if (dtype == CSPN_DTYPE_F16)
+        return K == 5 ? backward_run<5, __half>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st)
+                      : backward_run<7, __half>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
+    return K == 5 ? backward_run<5, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st)
+                  : backward_run<7, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
 }
 
 }  // namespace cspn
@@ -680,6 +858,44 @@ int kxk_norm_backward(const float* guid, const float* blur, const float* sparse,
         case 5: return norm_backward<5>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
         default: return norm_backward<7>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
     }
+}
+
+// the same on 16-bit guidance (dtype as kxk_forward_g16); w' and b stay float32, gg in the guidance's type
+template <class GT>
+static int norm_forward_g16(const unsigned short* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
+                            int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    switch (K) {
+        case 3: return norm_forward<3, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        case 5: return norm_forward<5, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        default: return norm_forward<7, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+    }
+}
+
+template <class GT>
+static int norm_backward_g16(const unsigned short* guid, const float* blur, const float* sparse, const float* hist, const float* gout,
+                             unsigned short* gg, float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                             hipStream_t st) {
+    switch (K) {
+        case 3: return norm_backward<3, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        case 5: return norm_backward<5, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        default: return norm_backward<7, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+    }
+}
+
+int kxk_norm_forward_g16(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
+                         int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    const unsigned short* g = (const unsigned short*)guid;
+    return dtype == CSPN_DTYPE_F16 ? norm_forward_g16<__half>(g, blur, sparse, out, hist, B, C, sparse_C, H, W, K, n_iter, norm, ws, st)
+                                   : norm_forward_g16<__hip_bfloat16>(g, blur, sparse, out, hist, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+}
+
+int kxk_norm_backward_g16(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg,
+                          float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    const unsigned short* g = (const unsigned short*)guid;
+    unsigned short* d = (unsigned short*)gg;
+    return dtype == CSPN_DTYPE_F16
+               ? norm_backward_g16<__half>(g, blur, sparse, hist, gout, d, gx, B, C, sparse_C, H, W, K, n_iter, norm, ws, st)
+               : norm_backward_g16<__hip_bfloat16>(g, blur, sparse, hist, gout, d, gx, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
 }  // namespace cspn

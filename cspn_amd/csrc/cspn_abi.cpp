@@ -802,6 +802,142 @@ int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const
     return kxk_norm_backward(guidance, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
+// ---- the four K x K entry points on 16-bit gates / guidance (cspn2d_*_kxk*_g16): the checks of the _f32 twins, the gate tensor and its
+// gradient sized and aligned as 2-byte elements ----
+static int g16_check(const char* what, int dtype, const void* gate, const void* grad_gate) {
+    if (dtype != CSPN_DTYPE_F16 && dtype != CSPN_DTYPE_BF16) {
+        set_error("%s: gate_dtype must be CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dtype);
+        return CSPN_E_BADARG;
+    }
+    if (((uintptr_t)gate & 1u) || ((uintptr_t)grad_gate & 1u)) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
+    return 0;
+}
+
+int cspn2d_forward_kxk_g16(const void* gate, int gate_dtype, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H,
+                           int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_forward_kxk_g16";
+    if (!gate || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = g16_check(what, gate_dtype, gate, nullptr)) return e;
+    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2;
+    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = history ? 0 : cspn2d_kxk_workspace_bytes(B, C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{gate, gb}, {x, vb}, {history, hb}, {ws, wb}}) || kxk_overlaps(history, hb, {{gate, gb}, {x, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {
+        hipError_t e = hipMemcpyAsync(out, x, vb, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_forward_g16(gate, gate_dtype, x, out, history, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_backward_kxk_g16(const void* gate, int gate_dtype, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                            void* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                            cspn_stream_t stream) {
+    static const char* what = "cspn2d_backward_kxk_g16";
+    if (!gate || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = g16_check(what, gate_dtype, gate, grad_gate)) return e;
+    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2;
+    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
+    if (grad_gate && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the gate gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_workspace_bytes(B, C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = grad_gate ? hb : 0;
+    if (grad_gate && grad_gate == (void*)grad_x) { set_error("%s: grad_gate and grad_x must not alias", what); return CSPN_E_BADARG; }
+    if (kxk_overlaps(grad_gate, gb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_x, vb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_gate, grad_x and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_gate && !grad_x) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {   // the identity: dL/dx = dL/dout, no gate is read
+        hipError_t e = grad_x ? hipMemcpyAsync(grad_x, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, gb, st);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_backward_g16(gate, gate_dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_forward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,
+                                size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                                size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_forward_kxk_norm_g16";
+    if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = g16_check(what, gate_dtype, guidance, nullptr)) return e;
+    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2, sb = vb / C * sparse_C;
+    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = n_iter == 0 ? 0
+                        : (history ? sizeof(float) * kxk_norm_fold_floats(B, C, sparse_C, H, W, K)
+                                   : cspn2d_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter));
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hb}, {ws, wb}}) ||
+        kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {
+        hipError_t e = hipMemcpyAsync(out, blur, vb, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_norm_forward_g16(guidance, gate_dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+}
+
+int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
+                                 size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
+                                 int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    static const char* what = "cspn2d_backward_kxk_norm_g16";
+    if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = g16_check(what, gate_dtype, guidance, grad_guidance)) return e;
+    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2, sb = vb / C * sparse_C;
+    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
+    if (grad_guidance && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the guidance gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = grad_guidance ? hb : 0;
+    if (grad_guidance && (const void*)grad_guidance == (const void*)grad_blur) { set_error("%s: grad_guidance and grad_blur must not alias", what); return CSPN_E_BADARG; }
+    if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_blur, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_blur, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_guidance, grad_blur and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_guidance && !grad_blur) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {   // the identity: dL/dblur = dL/dout, no gate is read
+        hipError_t e = grad_blur ? hipMemcpyAsync(grad_blur, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_guidance) e = hipMemsetAsync(grad_guidance, 0, gb, st);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return kxk_norm_backward_g16(guidance, gate_dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm,
+                                 ws, st);
+}
+
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----
 static int head_kxk_check(const char* what, int B, int C, int h, int w, int H, int W, int K) {
     if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }

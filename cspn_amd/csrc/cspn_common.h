@@ -91,6 +91,12 @@ int kxk_forward(const float* gate, const float* x, float* out, float* hist, int 
 // ws: A_1 .. A_{n-1} ((n - 1) N C H W floats); gg (summed over C) and gx may each be NULL; hist as the forward kept it
 int kxk_backward(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W, int K,
                  int n_iter, void* ws, hipStream_t st);
+// the same on 16-bit gates: dtype CSPN_DTYPE_F16 / CSPN_DTYPE_BF16, widened exactly where used (bitwise the float32 results on the widened
+// gates); gg in the gates' type, the float32 sum rounded once at its store
+int kxk_forward_g16(const void* gate, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
+                    hipStream_t st);
+int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
+                     int W, int K, int n_iter, void* ws, hipStream_t st);
 
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip): guidance [B][K*K-1][H][W] raw, blur
 // [B][C][H][W], sparse NULL (sparse_C 0) or [B][sparse_C][H][W] with sparse_C 1 or C; normalised, neighbour-sited, pinned, folded into w' and b ----
@@ -102,6 +108,11 @@ int kxk_norm_forward(const float* guid, const float* blur, const float* sparse, 
 // ws: the fold, dL/dw', dL/db (one fold's size), then A_1 .. A_{n-1}; gg needs hist (n >= 2), gx and gg may each be NULL
 int kxk_norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B,
                       int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+// the same on 16-bit guidance (w' and b stay float32 in the workspace: the workspace sizes are those above)
+int kxk_norm_forward_g16(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
+                         int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_norm_backward_g16(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg,
+                          float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

@@ -20,6 +20,31 @@ def _prep(t, name, shape=None):
     return t.contiguous()
 
 
+_GATE16 = {torch.float16: _lib.DTYPES["float16"], torch.bfloat16: _lib.DTYPES["bfloat16"]}
+
+
+def _prep_gate(t, name):
+    """a gate / guidance tensor of the K x K engine: float32, or float16 / bfloat16 as it is (the *_g16 entry points widen it exactly
+    where it is used) -> (tensor, gate_dtype code or None for float32)"""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in _GATE16:
+        return t.contiguous(), _GATE16[t.dtype]
+    return _prep(t, name), None
+
+
+def _prep_value(t, name, shape=None):
+    """a value tensor of the K x K engine (one plane per channel): float32; float16 / bfloat16 is widened with one torch cast"""
+    if isinstance(t, torch.Tensor) and t.dtype in _GATE16:
+        t = t.float()
+    return _prep(t, name, shape)
+
+
+def widen16(*tensors):
+    """float16 / bfloat16 tensors widened with a differentiable .float() (autograd carries the gradient back through the cast), everything
+    else as it is: what the modules and mirrors do in front of the paths that have no 16-bit kernel (3 x 3 in 2D, 3D, the gate normaliser)"""
+    out = tuple(t.float() if isinstance(t, torch.Tensor) and t.dtype in _GATE16 else t for t in tensors)
+    return out[0] if len(out) == 1 else out
+
+
 def _workspace(nbytes, device):
     # torch's caching allocator: stream-ordered reuse is safe, base is >=512-B aligned
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
@@ -534,12 +559,12 @@ def _kxk_shape(gate, x, kernel_size, extra=()):
 
 def _kxk_args(gate, x, kernel_size, extra=()):
     K, N, C, H, W = _kxk_shape(gate, x, kernel_size, extra)
-    g = _prep(gate, "gate")
-    h = _prep(x, "x")
-    rest = [_prep(t, name, (N, C, H, W)) for t, name in extra]
+    g, dt = _prep_gate(gate, "gate")
+    h = _prep_value(x, "x")
+    rest = [_prep_value(t, name, (N, C, H, W)) for t, name in extra]
     if any(t.device != g.device for t in [h] + rest):
         raise ValueError("all tensors must live on the same device")
-    return (g, h, K, N, C, H, W) + tuple(rest)
+    return (g, dt, h, K, N, C, H, W) + tuple(rest)
 
 
 def _check_kernel_size(kernel_size, dim):
@@ -555,14 +580,16 @@ def _check_kernel_size(kernel_size, dim):
 def cspn2d_forward_kxk(gate, x, kernel_size, n_iter, return_history=False):
     """gate [N,K*K-1,H,W] used as given (centre-sited, no centre term, any sign), x [N,C,H,W] -> H_n [N,C,H,W] with
     H_{t+1}(p) = sum_k gate_k(p) H_t(p + off_k), zero outside, the C channels on the shared gates (cspn2d_forward_kxk_f32).
-    K = kernel_size in {5, 7}.  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk.  n_iter == 0 returns x."""
+    K = kernel_size in {5, 7}.  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk.  n_iter == 0 returns x.
+    gate may be float16 / bfloat16 (cspn2d_forward_kxk_g16: widened exactly where used, out is float32 and bitwise the float32 call on
+    gate.float()); a 16-bit x is widened with one cast."""
     _kxk_shape(gate, x, kernel_size)
     n = int(n_iter)
     if n < 0:
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
     if n == 0:
         return (x, None) if return_history else x
-    g, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size)
+    g, dt, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size)
     out = torch.empty_like(h)
     hist = None
     if out.numel() == 0:
@@ -576,18 +603,20 @@ def cspn2d_forward_kxk(gate, x, kernel_size, n_iter, return_history=False):
             hb = 0
             ws_bytes = _lib.late_symbol("cspn2d_kxk_workspace_bytes")(N, C, H, W, K, n)
             ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_forward_kxk_f32")(
-            g.data_ptr(), h.data_ptr(), out.data_ptr(), hist.data_ptr() if hist is not None else None, hb, N, C, H, W, K, n,
-            ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_forward_kxk_f32")
+        name = "cspn2d_forward_kxk_f32" if dt is None else "cspn2d_forward_kxk_g16"
+        rc = _lib.late_symbol(name)(
+            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), out.data_ptr(), hist.data_ptr() if hist is not None else None, hb,
+            N, C, H, W, K, n, ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, name)
     return (out, hist) if return_history else out
 
 
 def cspn2d_backward_kxk(gate, x, grad_out, kernel_size, n_iter, history=None, need_gate=True, need_x=True):
     """Gradient of cspn2d_forward_kxk -> (dL/dgate [N,K*K-1,H,W] summed over the C channels or None, dL/dx [N,C,H,W] or None);
     cspn2d_backward_kxk_f32.  history: what cspn2d_forward_kxk(..., return_history=True) returned; None runs that forward first
-    where the gate gradient needs it."""
-    g, h, K, N, C, H, W, go = _kxk_args(gate, x, kernel_size, ((grad_out, "grad_out"),))
+    where the gate gradient needs it.  A float16 / bfloat16 gate (cspn2d_backward_kxk_g16): dL/dx is float32 and bitwise the float32 call's,
+    dL/dgate comes back in the gate's dtype, the float32 sum rounded once."""
+    g, dt, h, K, N, C, H, W, go = _kxk_args(gate, x, kernel_size, ((grad_out, "grad_out"),))
     n = int(n_iter)
     if n < 0:
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
@@ -603,11 +632,12 @@ def cspn2d_backward_kxk(gate, x, grad_out, kernel_size, n_iter, history=None, ne
         ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_workspace_bytes")(N, C, H, W, K, n)
         ws = _workspace(ws_bytes, g.device)
         hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
-        rc = _lib.late_symbol("cspn2d_backward_kxk_f32")(
-            g.data_ptr(), h.data_ptr(), hp, hb, go.data_ptr(), gg.data_ptr() if gg is not None else None,
+        name = "cspn2d_backward_kxk_f32" if dt is None else "cspn2d_backward_kxk_g16"
+        rc = _lib.late_symbol(name)(
+            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), hp, hb, go.data_ptr(), gg.data_ptr() if gg is not None else None,
             gx.data_ptr() if gx is not None else None, N, C, H, W, K, n, ws.data_ptr(), ws_bytes,
             torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_backward_kxk_f32")
+    _lib.check(rc, name)
     return gg, gx
 
 
@@ -633,7 +663,10 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     contract cspn_paddle/README.md:54-56): input [N,C,...], gate_weight [N,kernel_size**d-1,...] already
     normalised over the channel dim by the caller, shared across the C input channels.
     d = 2 or 3; kernel_size 3, or 5 / 7 in 2D (the K x K engine, cspn2d_forward_kxk).  n_iter > 1 fuses that many chained calls
-    (demo.py:39,50).  Differentiable w.r.t. input and gate_weight like the reference op (the demo trains through it, demo.py:65-75)."""
+    (demo.py:39,50).  Differentiable w.r.t. input and gate_weight like the reference op (the demo trains through it, demo.py:65-75).
+    float16 / bfloat16 (a head under torch.autocast): with kernel_size 5 / 7 the gates go to the engine as they are (widened exactly where
+    used; the gate gradient comes back in their dtype) and a 16-bit input is widened with one cast; with kernel_size 3 (2D and 3D, no 16-bit
+    kernel) both are widened with a differentiable .float().  The result is float32 either way."""
     if kernel_size != 3:
         if not isinstance(input, torch.Tensor) or not isinstance(gate_weight, torch.Tensor):
             raise TypeError("input and gate_weight must be torch.Tensor")
@@ -642,9 +675,11 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
             raise ValueError("gate_weight must have %d channels for kernel_size %d, got %s" % (K * K - 1, K, tuple(gate_weight.shape)))
         if int(n_iter) == 0:
             return input
+        input = widen16(input)
         if torch.is_grad_enabled() and (input.requires_grad or gate_weight.requires_grad):
             return _AffinityPropagateKxKFunction.apply(input, gate_weight, K, int(n_iter))
         return cspn2d_forward_kxk(gate_weight, input, K, n_iter)
+    input, gate_weight = widen16(input, gate_weight)
     d = input.dim() - 2
     if d not in (2, 3):
         raise ValueError("input must be [N,C,H,W] or [N,C,D,H,W]")
@@ -708,13 +743,13 @@ def _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, 
 
 
 def _kxk_norm_args(guidance, blur_depth, sparse_depth, extra=()):
-    g = _prep(guidance, "guidance")
-    h = _prep(blur_depth, "blur_depth")
-    s = _prep(sparse_depth, "sparse_depth") if sparse_depth is not None else None
-    rest = [_prep(t, name, tuple(h.shape)) for t, name in extra]
+    g, dt = _prep_gate(guidance, "guidance")
+    h = _prep_value(blur_depth, "blur_depth")
+    s = _prep_value(sparse_depth, "sparse_depth") if sparse_depth is not None else None
+    rest = [_prep_value(t, name, tuple(h.shape)) for t, name in extra]
     if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
         raise ValueError("all tensors must live on the same device")
-    return (g, h, s) + tuple(rest)
+    return (g, dt, h, s) + tuple(rest)
 
 
 def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False):
@@ -722,12 +757,14 @@ def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size
     (channel k = the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour
     (K//2 - t, K//2 - l)), blur_depth [B,C,H,W] on the shared guidance, sparse_depth None, [B,1,H,W] or [B,C,H,W] -> [B,C,H,W]
     (cspn2d_forward_kxk_norm_f32).  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_norm.  n_iter == 0
-    returns blur_depth itself."""
+    returns blur_depth itself.  guidance may be float16 / bfloat16 (cspn2d_forward_kxk_norm_g16, K = 3 included: the fold widens it exactly,
+    w' stays float32; out is float32 and bitwise the float32 call on guidance.float()); 16-bit blur_depth / sparse_depth are widened with
+    one cast."""
     K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
     n = int(n_iter)
     if n == 0:
         return (blur_depth, None) if return_history else blur_depth
-    g, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
+    g, dt, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
     out = torch.empty_like(h)
     hist = None
     if out.numel() == 0:
@@ -739,10 +776,12 @@ def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size
         # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
         ws_bytes = _lib.late_symbol("cspn2d_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, 1 if return_history else n)
         ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_forward_kxk_norm_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), hist.data_ptr() if hist is not None else None,
-            hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_forward_kxk_norm_f32")
+        name = "cspn2d_forward_kxk_norm_f32" if dt is None else "cspn2d_forward_kxk_norm_g16"
+        rc = _lib.late_symbol(name)(
+            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(),
+            hist.data_ptr() if hist is not None else None, hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes,
+            torch.cuda.current_stream(g.device).cuda_stream)
+    _lib.check(rc, name)
     return (out, hist) if return_history else out
 
 
@@ -750,11 +789,13 @@ def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kerne
                              need_guidance=True, need_blur=True):
     """Gradient of cspn2d_forward_kxk_norm -> (dL/dguidance [B,K*K-1,H,W] summed over the C channels or None, dL/dblur_depth [B,C,H,W]
     or None); sparse_depth gets none (cspn.py uses its sign only).  cspn2d_backward_kxk_norm_f32.  history: what
-    cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it."""
+    cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it.
+    A float16 / bfloat16 guidance (cspn2d_backward_kxk_norm_g16): dL/dblur_depth is float32 and bitwise the float32 call's, dL/dguidance comes
+    back in the guidance's dtype, the float32 value rounded once."""
     K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
     if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
         raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
-    g, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    g, dt, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
     n = int(n_iter)
     gg = torch.empty_like(g) if need_guidance else None
     gh = torch.empty_like(h) if need_blur else None
@@ -768,11 +809,12 @@ def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kerne
         ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, n)
         ws = _workspace(ws_bytes, g.device)
         hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
-        rc = _lib.late_symbol("cspn2d_backward_kxk_norm_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, hp, hb, go.data_ptr(),
+        name = "cspn2d_backward_kxk_norm_f32" if dt is None else "cspn2d_backward_kxk_norm_g16"
+        rc = _lib.late_symbol(name)(
+            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), s.data_ptr() if s is not None else None, hp, hb, go.data_ptr(),
             gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None, B, C, sc, H, W, K, n,
             _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_backward_kxk_norm_f32")
+    _lib.check(rc, name)
     return gg, gh
 
 

@@ -49,7 +49,8 @@ extern "C" {
                               *    the cspn2d_*_multi entry points (C channels on shared 2D guidance), the demo's gate normalisation
                               *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32), the 2D K x K entry points
                               *    (cspn2d_*_kxk*, K = 5 / 7), K = 24 / 48 on the gate normaliser and the depth-completion contract over
-                              *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*) */
+                              *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*),
+                              *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -69,6 +70,9 @@ enum { CSPN_ALGO_AUTO = 0, CSPN_ALGO_STEPWISE = 1, CSPN_ALGO_FUSED = 2, CSPN_ALG
        CSPN_ALGO_FUSED_PADDED = 4 /* W % 4 != 0 (what AUTO picks there, round 5): the inputs are laid out once in the workspace with rows padded to a
                                     * multiple of 4 columns (zeros; 8SUM / 8SUM_ABS are normalised on the way, for the real width), the fused path
                                     * runs on those and the output is copied back: three more passes over the data instead of one launch per iteration */ };
+
+/* gate_dtype of the *_g16 entry points: the storage type of the gate / guidance tensor and of its gradient */
+enum { CSPN_DTYPE_F16 = 1 /* IEEE binary16 */, CSPN_DTYPE_BF16 = 2 /* bfloat16 */ };
 
 enum {
     CSPN_E_BADARG = -1,   /* null pointer, non-positive size, unknown enum      */
@@ -305,6 +309,29 @@ size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int 
 int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, const float* history, size_t history_bytes,
                                  const float* grad_out, float* grad_guidance, float* grad_blur, int B, int C, int sparse_C, int H, int W, int K,
                                  int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the four K x K entry points above on 16-bit gates / guidance (what a head under autocast emits), gate_dtype CSPN_DTYPE_F16 or
+ * CSPN_DTYPE_BF16.  gate / guidance and grad_gate / grad_guidance are of that type; x, blur, sparse, out, history, grad_out, grad_x /
+ * grad_blur and the workspace (w' and b of the folded contract included) stay float32, and the byte-count queries above apply unchanged.
+ *   Exact widening: a 16-bit gate is widened to float32 where it is used and every multiply-add and sum is the float32 one of the _f32
+ *   entry point in the same order, so out and grad_x / grad_blur are bitwise what the _f32 entry point returns for the widened tensor.
+ *   grad_gate / grad_guidance is accumulated in float32 exactly as there and rounded once, to nearest even with subnormals kept, at its
+ *   single store: bitwise the _f32 gradient converted to gate_dtype.  No atomics; every element written once.
+ *   Per step and pixel the NONE op reads 2 KK + 8 C bytes.  The 16-bit tensors need 2-byte alignment (8-byte loads and stores where
+ *   W % 4 == 0 and the pointer is 8-byte aligned).  Argument errors as the _f32 twins, plus: any other gate_dtype: CSPN_E_BADARG ("dtype"
+ *   in cspn_last_error()); a 16-bit tensor at an odd address: CSPN_E_BADARG. */
+int cspn2d_forward_kxk_g16(const void* gate, int gate_dtype, const float* x, float* out, float* history, size_t history_bytes,
+                           int B, int C, int H, int W, int K, int n_iter,
+                           void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_g16(const void* gate, int gate_dtype, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                            void* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_forward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,
+                                size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm,
+                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
+                                 size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
+                                 int H, int W, int K, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
