@@ -175,6 +175,13 @@ _LATE_SYMBOLS = {
     "cspn_guidance_head_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "cspn_guidance_head_kxk_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cspn_guidance_head_kxk_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the same heads on an fp16 / bf16 feature map (dtype DTYPES[...] after x), K = 5 or 7: 16-bit x, guidance, dL/dguidance, dL/dx; float32 weights, blur, dL/dW
+    "cspn_guidance_head_kxk_g16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn_guidance_head_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7
+                                   + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn_guidance_head_kxk_backward_g16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cspn_guidance_head_kxk_backward_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7
+                                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

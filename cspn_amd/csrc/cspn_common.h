@@ -136,6 +136,14 @@ int head_kxk_forward(const float* x, const float* wg, const float* wb, float* go
 size_t head_kxk_backward_workspace(int B, int C, int h, int w, int K);
 int head_kxk_backward(const float* x, const float* wg, const float* wb, const float* gg, const float* gb, float* dx, float* dwg, float* dwb, int B, int C,
                       int h, int w, int H, int W, int K, void* ws, hipStream_t st);
+// the same on fp16 / bf16 x, guidance, dL/dguidance and dL/dx (cspn_head_kxk_g16.hip; dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16, checked by the caller):
+// float32 master weights rounded once per call, float32 blur, dL/dblur (rounded once as it enters the GEMMs) and weight gradients
+size_t head_kxk_g16_workspace(int C, int K);
+int head_kxk_g16_forward(const void* x, int dtype, const float* wg, const float* wb, void* gout, float* bout, int B, int C, int h, int w, int H, int W, int K,
+                         void* ws, hipStream_t st);
+size_t head_kxk_g16_backward_workspace(int B, int C, int h, int w, int K);
+int head_kxk_g16_backward(const void* x, int dtype, const float* wg, const float* wb, const void* gg, const float* gb, void* dx, float* dwg, float* dwb, int B,
+                          int C, int h, int w, int H, int W, int K, void* ws, hipStream_t st);
 
 // ---- fused path (all iterations in one launch; time-skewed wave ring) ----
 bool fused2d_supported(int B, int H, int W, int n_iter);

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .functional import _prep, _workspace, cspn2d_normalize
+from .functional import _GATE16, _prep, _workspace, cspn2d_normalize
 
 _KEYS = ['MSE', 'RMSE', 'ABS_REL', 'LG10', 'MAE', 'DELTA1.02', 'DELTA1.05', 'DELTA1.10', 'DELTA1.25', 'DELTA1.25^2',
          'DELTA1.25^3']
@@ -192,6 +192,77 @@ def _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w):
     return dx, dwg, dwb
 
 
+def _head_dtype16(x, weight_guidance, weight_blur, P):
+    """-> the 16-bit dtype of x (float16 / bfloat16: the heads of cspn_guidance_head_kxk_g16), or None for every other x.  Raised before any device check:
+    TypeError for a 16-bit x with 8-plane weights, and for 16-bit weights whose dtype differs from x's"""
+    if x.dtype not in _GATE16:
+        return None
+    if P == 8:
+        raise TypeError("the 3 x 3 guidance head (weight_guidance [8, C, 3, 3]) is float32 only: its ring has no 16-bit consumer; x is %s -- pass x.float(), "
+                        "or use the 24- / 48-plane heads of prop_kernel 5 / 7" % (x.dtype,))
+    for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
+        if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
+            raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
+    return x.dtype
+
+
+def _prep16(t, name, dt, shape=None):
+    """a 16-bit tensor of the heads (x, dL/dguidance): on the GPU, of dtype dt, contiguous"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if not t.is_cuda:
+        raise _lib.CspnError("cspn_amd: %s is on %s; the engine is GPU-only (hand-written HIP for gfx950) and has no CPU path" % (name, t.device))
+    if t.dtype != dt:
+        raise TypeError("%s must be %s as x (got %s)" % (name, dt, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t.contiguous()
+
+
+def _prep_w16(t, name, dt, shape):
+    """a weight of the 16-bit heads: the float32 master weights, or dt weights widened with .float() (exact) -> float32"""
+    if isinstance(t, torch.Tensor) and t.dtype == dt:
+        t = t.float()
+    return _prep(t, name, shape)
+
+
+def _heads_kxk_forward16(xx, wg, wb, H, W):
+    """cspn_guidance_head_kxk_g16: x fp16 / bf16, float32 weights (rounded once to x's dtype in the engine) -> guidance in x's dtype, blur float32"""
+    B, C, h, w = xx.shape
+    P = int(wg.shape[0])
+    K = _PLANES_TO_K[P]
+    g = torch.empty(B, P, H, W, dtype=xx.dtype, device=xx.device)
+    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk_g16_workspace_bytes")(B, C, h, w, K)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.late_symbol("cspn_guidance_head_kxk_g16")(xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None,
+                                                            g.data_ptr(), b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
+                                                            torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_kxk_g16")
+    return g, b
+
+
+def _heads_kxk_backward16(xx, wg, wb, gg, gb, need_x, need_w):
+    """cspn_guidance_head_kxk_backward_g16: dL/dguidance in x's dtype, dL/dblur float32 (rounded once to x's dtype as it enters the GEMMs) -> dL/dx in x's
+    dtype, the weight gradients float32"""
+    B, C, h, w = xx.shape
+    K = _PLANES_TO_K[int(wg.shape[0])]
+    H, W = int(gg.shape[2]), int(gg.shape[3])
+    dx = torch.empty_like(xx) if need_x else None
+    dwg = torch.empty_like(wg) if need_w else None
+    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward_g16_workspace_bytes")(B, C, h, w, K)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.late_symbol("cspn_guidance_head_kxk_backward_g16")(
+            xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
+            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
+            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_kxk_backward_g16")
+    return dx, dwg, dwb
+
+
 def _heads_forward(xx, wg, wb, H, W, norm):
     lib = _lib.load()
     B, C, h, w = xx.shape
@@ -210,9 +281,29 @@ def _heads_forward(xx, wg, wb, H, W, norm):
 def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad_blur, need_x=True, need_w=True):
     """cspn_guidance_head_backward_f32: (dL/dx, dL/dweight_guidance, dL/dweight_blur) of the RAW heads -- what torch autograd computes through the two reference
     layers (torch_resnet_cspn_nyu.py:187-206) -- from dL/dguidance [B,8,H,W] and dL/dblur [B,1,H,W] (None without a blur head); skipped outputs are None.
-    weight_guidance [24 | 48, C, 3, 3] with dL/dguidance [B, 24 | 48, H, W]: cspn_guidance_head_kxk_backward_f32, the heads of prop_kernel 5 / 7."""
+    weight_guidance [24 | 48, C, 3, 3] with dL/dguidance [B, 24 | 48, H, W]: cspn_guidance_head_kxk_backward_f32, the heads of prop_kernel 5 / 7.
+    With those weights x may be float16 / bfloat16 = dt (cspn_guidance_head_kxk_backward_g16): grad_guidance is dt (what cspn2d_backward_kxk_norm returns for a
+    dt guidance), grad_blur is float32 and is ROUNDED ONCE TO dt as it enters the GEMMs (what a 16-bit convolution's backward would have received); dL/dx comes
+    back in dt (rounded once), the weight gradients in float32 (the accumulators) -- or in dt, the float32 ones .to(dt), for weights that are dt themselves."""
     lib = _lib.load()
     P = _head_planes(x, weight_guidance, weight_blur, grad_guidance, grad_blur)
+    dt = _head_dtype16(x, weight_guidance, weight_blur, P)
+    if dt is not None:
+        xx = _prep16(x, "x", dt)
+        B, C, h, w = xx.shape
+        wg = _prep_w16(weight_guidance, "weight_guidance", dt, (P, C, 3, 3))
+        wb = _prep_w16(weight_blur, "weight_blur", dt, (1, C, 3, 3)) if weight_blur is not None else None
+        if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
+            raise ValueError("grad_guidance must be [B,%d,H,W]" % P)
+        H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
+        gg = _prep16(grad_guidance, "grad_guidance", dt, (B, P, H, W))
+        gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
+        dx, dwg, dwb = _heads_kxk_backward16(xx, wg, wb, gg, gb, need_x, need_w)
+        if dwg is not None and weight_guidance.dtype == dt:
+            dwg = dwg.to(dt)
+        if dwb is not None and weight_blur.dtype == dt:
+            dwb = dwb.to(dt)
+        return dx, dwg, dwb
     xx = _prep(x, "x")
     B, C, h, w = xx.shape
     wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
@@ -277,6 +368,29 @@ class _GuidanceHeadsKxKFunction(torch.autograd.Function):
         return dx, dwg if ctx.needs_input_grad[1] else None, dwb if (wb is not None and ctx.needs_input_grad[2]) else None, None, None
 
 
+class _GuidanceHeadsKxK16Function(torch.autograd.Function):
+    """the 24- / 48-plane guidance head + the blur head on a float16 / bfloat16 x: cspn_guidance_head_kxk_g16 and its backward.  wg / wb: float32 master
+    weights, or weights of x's dtype (widened exactly; their gradients are the float32 ones .to(dtype))"""
+
+    @staticmethod
+    def forward(ctx, x, wg, wb, H, W):
+        ctx.save_for_backward(x, wg, wb)
+        return _heads_kxk_forward16(x, wg.float(), wb.float() if wb is not None else None, H, W)
+
+    @staticmethod
+    def backward(ctx, grad_g, grad_b):
+        x, wg, wb = ctx.saved_tensors
+        if grad_g is None:
+            grad_g = torch.zeros(x.shape[0], wg.shape[0], grad_b.shape[2], grad_b.shape[3], dtype=x.dtype, device=x.device)
+        if wb is not None and grad_b is None:
+            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], dtype=torch.float32, device=x.device)
+        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
+        dx, dwg, dwb = _heads_kxk_backward16(x, wg.float(), wb.float() if wb is not None else None, grad_g.contiguous(),
+                                             grad_b.float().contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
+        return (dx, dwg.to(wg.dtype) if ctx.needs_input_grad[1] else None,
+                dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
+
+
 def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, norm_type=None):
     """The producer of the propagation's inputs: what the reference computes as
         guidance = self.gud_up_proj_layer6(x); x = self.gud_up_proj_layer5(x)          (torch_resnet_cspn_nyu.py:372-373)
@@ -290,12 +404,32 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     cspn2d_normalize_backward_f32 into cspn_guidance_head_backward_f32, so dL/dgate_wb from propagate_prenorm reaches x and both weights.
     weight_guidance [24 | 48, C, 3, 3] (Simple_Gudi_UpConv_Block_Last_Layer(C, 24 | 48, ...): prop_kernel 5 / 7): -> (guidance [B, 24 | 48, H, W], blur), the
     inputs of Affinity_PropagateKxK(prop_time, 5 | 7, norm_type)(guidance, blur, sparse); cspn_guidance_head_kxk_f32, three GEMMs on the matrix cores forward
-    and backward (one autograd Function); raw only: a norm_type raises ValueError, the K x K contract normalises in its own fold."""
+    and backward (one autograd Function); raw only: a norm_type raises ValueError, the K x K contract normalises in its own fold.
+    With the 24- / 48-plane weights x may be float16 / bfloat16 = dt, as a backbone under torch.autocast emits it (cspn_guidance_head_kxk_g16): the weights are
+    the float32 master weights (rounded once to dt in the engine) or dt weights (passed as .float(), exact; their gradients come back .to(dt)); products of two
+    dt values accumulate in float32 on the matrix cores; guidance comes back in dt (the accumulator rounded once) -- what Affinity_PropagateKxK takes as it is
+    --, blur in float32 (the accumulator: the engine's value tensors are float32); dL/dx comes back in dt.  A dt that differs between x and 16-bit weights
+    raises TypeError, and so does a 16-bit x with the 8-plane weights: the 3 x 3 head is float32 only."""
     P = _head_planes(x, weight_guidance, weight_blur)
+    dt = _head_dtype16(x, weight_guidance, weight_blur, P)
     if P != 8:
         if norm_type is not None:
             raise ValueError("the %d-plane guidance head returns raw guidance only (norm_type=None): Affinity_PropagateKxK(prop_time, %d, norm_type) "
                              "normalises it" % (P, _PLANES_TO_K[P]))
+        if dt is not None:
+            xx = _prep16(x, "x", dt)
+            B, C, h, w = xx.shape
+            H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
+            for t, name, shape in ((weight_guidance, "weight_guidance", (P, C, 3, 3)), (weight_blur, "weight_blur", (1, C, 3, 3))):
+                if t is not None and t.dtype == dt:
+                    _prep16(t, name, dt, shape)
+                elif t is not None:
+                    _prep(t, name, shape)
+            wg = weight_guidance.contiguous()
+            wb = weight_blur.contiguous() if weight_blur is not None else None
+            if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
+                return _GuidanceHeadsKxK16Function.apply(xx, wg, wb, H, W)
+            return _heads_kxk_forward16(xx, wg.float(), wb.float() if wb is not None else None, H, W)
         xx = _prep(x, "x")
         B, C, h, w = xx.shape
         wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))

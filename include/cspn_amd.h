@@ -433,6 +433,26 @@ int cspn_guidance_head_kxk_backward_f32(const float* x, const float* w_guidance,
                                         float* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W, int K,
                                         void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
+/* ---- the same heads on a 16-bit feature map (what a backbone under autocast hands over), dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16 = DT, K = 5 or 7 only (the
+ * 8-plane head of K = 3 is float32 only: its ring has no 16-bit consumer) -- the producer of what cspn2d_forward_kxk_norm_g16 consumes.
+ *   x [B,C,h,w], guidance_out / grad_guidance [B,K*K-1,H,W] and grad_x [B,C,h,w] are DT;  w_guidance, w_blur (the master weights), blur_out / grad_blur
+ *   [B,1,H,W] and grad_w_guidance / grad_w_blur are float32.
+ *   The weights are rounded once to DT (to nearest even) in the per-call repack; every product is of two DT values, exact in float32; the sums accumulate in
+ *   float32 on the matrix cores (v_mfma_f32_32x32x16_f16 / _bf16).  guidance_out is the accumulator rounded once to DT (to nearest even, overflow to +-inf as
+ *   a cast); blur_out is the accumulator, unrounded.  grad_guidance arrives in DT (what cspn2d_backward_kxk_norm_g16 returns); grad_blur arrives in float32
+ *   and is ROUNDED ONCE TO DT as it enters the GEMMs -- what a 16-bit convolution's backward would have received; grad_x is rounded once to DT; the weight
+ *   gradients are the float32 accumulators, their partial sums added in a fixed order (no atomics: deterministic, every element written once).
+ *   All checks of the _f32 twins apply; K = 3 or any other K, an unknown dtype or a 16-bit pointer that is not 2-byte aligned: CSPN_E_BADARG.
+ * workspace: the matching *_g16_workspace_bytes(B, C, h, w, K) bytes, 256-byte aligned; too small or misaligned: CSPN_E_WORKSPACE. */
+size_t cspn_guidance_head_kxk_g16_workspace_bytes(int B, int C, int h, int w, int K);
+int cspn_guidance_head_kxk_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, void* guidance_out, float* blur_out,
+                               int B, int C, int h, int w, int H, int W, int K,
+                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn_guidance_head_kxk_backward_g16_workspace_bytes(int B, int C, int h, int w, int K);
+int cspn_guidance_head_kxk_backward_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, const void* grad_guidance,
+                                        const float* grad_blur, void* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w,
+                                        int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
