@@ -3,7 +3,8 @@ gate [N, K*K-1, H, W] used as given, x [N, C, H, W] on shared gates.  Gate chann
 without the centre, neighbour offset (K//2 - t, K//2 - l).  Pinned against a float64 torch statement of that recurrence, whose K = 3 form is
 today's 3 x 3 op, and whose autograd gives the reference gradients.
 CPU: exports, header, ABI version, C and Python argument errors, the module's constructor.  GPU: forward, C channels, gradients, the
-public routes (affinity_propagate, CSPN, gate_absnorm with K = 24 / 48)."""
+public routes (affinity_propagate, CSPN, gate_absnorm with K = 24 / 48).  The gradient cases here fit one 64 x 16 tile; tile seams and
+tile grids that are not square are covered in tests/test_kxk_tilegrid.py."""
 import ctypes
 import os
 import re

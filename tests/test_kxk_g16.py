@@ -277,6 +277,8 @@ SHAPES = [
     (1, 3, 18, 68, 24, True),     # W % 4 == 0 behind a gate pointer that is 2-byte but not 8-byte aligned; 24 steps
     (1, 1, 5, 8, 24, False),      # smaller than one tile, vector path
     (2, 3, 33, 192, 1, False),    # three tiles each way, one step
+    (2, 2, 35, 196, 3, False),    # 3 x 4 tiles, two images: a grid that is not square (tests/test_kxk_tilegrid.py), vector path
+    (1, 2, 67, 70, 3, False),     # 5 x 2 tiles, the guarded path
 ]
 
 
