@@ -170,6 +170,16 @@ _LATE_SYMBOLS = {
                                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "cspn2d_backward_kxk_norm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
                                      + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
+    "cspn2d_forward_kxk_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 6
+                                       + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_forward_kxk_absnorm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_int] * 6
+                                       + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_absnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "cspn2d_backward_kxk_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
+                                        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "cspn2d_backward_kxk_absnorm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t]
+                                        + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
     "cspn_guidance_head_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cspn_guidance_head_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -20,8 +20,9 @@ Differences a caller can observe, all deliberate:
     sparse_depth None, [B,1,H,W] or [B,C,H,W]: one engine call each way (cspn2d_forward_multi_f32 / cspn2d_backward_multi_f32),
     dL/dguidance summed over the channels;
   * float16 / bfloat16 inputs (heads under torch.autocast) are taken and the result is float32: Affinity_PropagateKxK with prop_kernel
-    5 / 7 hands 16-bit guidance to the engine as it is (widened exactly where used, dL/dguidance in its dtype); everything without a 16-bit
-    kernel (Affinity_Propagate, prop_kernel 3, propagate_prenorm, CSPN) widens with a differentiable .float() first."""
+    5 / 7 and CSPN in 2D with prop_kernel 5 / 7 hand a 16-bit guidance / guide to the engine as it is (widened exactly where used, its
+    gradient in its dtype); everything without a 16-bit kernel (Affinity_Propagate, prop_kernel 3, propagate_prenorm, CSPN in 3D) widens
+    with a differentiable .float() first."""
 import torch
 import torch.nn as nn
 
@@ -193,7 +194,9 @@ class CSPN(nn.Module):
     """reference cspn_paddle/demo.py:10-54 (the demo's module): same constructor, same cspn(guide, feat) -- also the forward.  guide
     [N, feat_chan*K, *S] raw (K = prop_kernel^dim_num - 1; prop_kernel 3, or 5 / 7 in 2D), feat [N, feat_chan, *S]: abs, each channel's
     slice of K gates divided by its abs-sum, prop_step chained propagations (F.absnorm_propagate: one engine call for all channels, the 3D
-    normalisation inside the persistent kernel, the K x K engine for prop_kernel 5 / 7).  A port of demo.py changes its imports and tensor types, nothing else."""
+    normalisation inside the persistent kernel; for prop_kernel 5 / 7 inside the K x K engine's step, F.cspn2d_forward_kxk_absnorm, which
+    stores no normalised gate and takes a float16 / bfloat16 guide as it is).  The result is float32.  A port of demo.py changes its
+    imports and tensor types, nothing else."""
 
     def __init__(self, dim_num, feat_chan, prop_kernel, prop_step):
         super(CSPN, self).__init__()
@@ -208,7 +211,10 @@ class CSPN(nn.Module):
     def cspn(self, guide, feat):
         if feat.dim() != self.dim_num + 2:
             raise ValueError("feat must have %d dimensions for dim_num %d, got %s" % (self.dim_num + 2, self.dim_num, tuple(feat.shape)))
-        guide, feat = F.widen16(guide, feat)   # the gate normaliser has no 16-bit kernel: float32 from here on
+        if self.dim_num == 2 and self.prop_kernel != 3:
+            feat = F.widen16(feat)   # the K x K engine widens a 16-bit guide where it uses it; values are float32
+        else:
+            guide, feat = F.widen16(guide, feat)   # the gate_absnorm tensor op has no 16-bit kernel: float32 from here on
         return F.absnorm_propagate(guide, feat, self.prop_step, self.prop_kernel)
 
     def forward(self, guide, feat):

@@ -13,6 +13,10 @@
 // Below them, the depth-completion contract of Affinity_Propagate over K x K (K = 3, 5 or 7): folded into w' and a bias b by kxk_fold,
 // run by the same step with BIAS, and differentiated by the same adjoint step, the gate gradient with BIAS, kxk_unfold_pixel and
 // kxk_unsite.
+// Last, the demo module's contract (ABS): the guide is raw, a_k = |g_k| enters the multiply-add and the sum is scaled by 1 / S,
+// S(p) = sum_k a_k(p) in channel order, after it.  The gates are centre-sited, so the thread that steps a pixel holds all of its gates
+// and forms S from them; the adjoint step holds the gates of shifted pixels and reads 1 / S from a plane (kxk_rsum) while it stages
+// A; the gate gradient's epilogue re-reads the guide a channel at a time: no normalised gate and no dL/dw is ever stored.
 // Gate storage type GT: float, or __half / __hip_bfloat16 (the *_g16 entry points).  A 16-bit gate is widened to float32 exactly where
 // it is used, every multiply-add and sum is the float32 one in the same order, so the results are bitwise those of the float instance
 // on the widened gates; a gradient with respect to a 16-bit tensor is accumulated in float32 and rounded once (to nearest even,
@@ -105,10 +109,16 @@ struct Quad {
     // keeps the packed form live across the channel loop: without it the compiler hoists the widening out of the loop and holds four
     // registers per quad, as the float instance does
     __device__ __forceinline__ void pin() { asm volatile("" : "+v"(p[0]), "+v"(p[1])); }
+    __device__ __forceinline__ void pin_sign() {}
     __device__ __forceinline__ void put(int j, unsigned short v) { p[j >> 1] |= (uint32_t)v << (16 * (j & 1)); }
     __device__ __forceinline__ float get(int j) const {
         if constexpr (std::is_same<GT, __half>::value) return widen<GT>((unsigned short)(p[j >> 1] >> (16 * (j & 1))));
         else return __uint_as_float((j & 1) ? (p[j >> 1] & 0xffff0000u) : (p[j >> 1] << 16));
+    }
+    // |gate|: the odd bf16 element drops its sign in the mask that widens it, the rest as a source modifier of the multiply-add
+    __device__ __forceinline__ float mag(int j) const {
+        if constexpr (std::is_same<GT, __half>::value) return fabsf(get(j));
+        else return (j & 1) ? __uint_as_float(p[j >> 1] & 0x7fff0000u) : fabsf(__uint_as_float(p[j >> 1] << 16));
     }
 };
 template <>
@@ -116,9 +126,39 @@ struct Quad<float> {
     float v[4];
     __device__ __forceinline__ void clear() { v[0] = v[1] = v[2] = v[3] = 0.f; }
     __device__ __forceinline__ void pin() {}
+    // ABS: keeps |gate| from being computed once in front of the channel loop, so that it folds into the multiply-add as a source modifier
+    __device__ __forceinline__ void pin_sign() { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])); }
     __device__ __forceinline__ void put(int j, float x) { v[j] = x; }
     __device__ __forceinline__ float get(int j) const { return v[j]; }
+    __device__ __forceinline__ float mag(int j) const { return fabsf(v[j]); }
 };
+
+// stage for the adjoint of the ABS contract: A / S as A * (1 / S).  rs: the plane [H][W] of 1 / S that kxk_rsum wrote, or NULL (a single
+// step, which has no workspace): 1 / S is then formed here from the pixel's KK gates gb [KK][H][W], the same sum and division
+template <int R, int KK, class GT>
+__device__ __forceinline__ void stage_scaled(float* lds, const float* __restrict__ s, const float* __restrict__ rs, const store_t<GT>* __restrict__ gb,
+                                             int y0, int xt0, int H, int W) {
+    constexpr int SW = TW + 2 * R, SH = TH + 2 * R;
+    if (rs) {
+        for (int i = threadIdx.x; i < SW * SH; i += NT) {
+            const int r = i / SW, c = i - r * SW;
+            const int gy = y0 - R + r, gx = xt0 - R + c;
+            lds[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? s[gy * W + gx] * rs[gy * W + gx] : 0.f;
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < SW * SH; i += NT) {
+        const int r = i / SW, c = i - r * SW;
+        const int gy = y0 - R + r, gx = xt0 - R + c;
+        float v = 0.f;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            float S = 0.f;
+            for (int k = 0; k < KK; ++k) S += fabsf(widen<GT>(gb[(size_t)k * H * W + gy * W + gx]));
+            v = s[gy * W + gx] * (1.f / S);
+        }
+        lds[i] = v;
+    }
+}
 
 // four pixels x0 .. x0+3 of row y (p = row offset of x0), widened; VEC: W % 4 == 0 and the plane aligned to four elements (16 bytes
 // for float, 8 for a 16-bit type; a quad is then all in or all out)
@@ -197,7 +237,8 @@ __host__ __device__ constexpr int chan(int t, int l) { return t * K + l - (t * K
 
 // one forward step for all C channels: dst = step(src).  VEC: W % 4 == 0, dst 16-byte aligned, gate aligned to four elements
 // BIAS: the accumulator starts from bias [N][C][H][W] (the folded normalising contract, kxk_fold), 16-byte aligned where VEC
-template <int K, bool VEC, bool BIAS = false, class GT = float>
+// ABS: gate is the raw guide; |gate| in the multiply-add, the sum times 1 / S before the store (0 * inf = NaN where a pixel's gates are all zero)
+template <int K, bool VEC, bool BIAS = false, class GT = float, bool ABS = false>
 __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
                                                        int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
@@ -210,6 +251,16 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
     const store_t<GT>* gp = gate + (size_t)T.n * KK * HW + pix;
 #pragma unroll
     for (int k = 0; k < KK; ++k) load_quad<VEC, GT>(g[k], gp + (size_t)k * HW, row_in, T.x0, W, gate);
+    // 1 / S of the thread's four pixels waits in LDS while the stencil runs: K = 7 in float32 has no register left for it
+    __shared__ float4 rsl[ABS ? NT : 1];
+    if constexpr (ABS) {
+        float S[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < KK; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) S[j] += g[k].mag(j);
+        rsl[threadIdx.x] = make_float4(1.f / S[0], 1.f / S[1], 1.f / S[2], 1.f / S[3]);   // read back by this thread alone
+    }
     for (int c = 0; c < C; ++c) {
         const size_t plane = ((size_t)T.n * C + c) * HW;
         __syncthreads();   // the previous channel's reads of lds are done
@@ -217,6 +268,10 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < KK; ++k) g[k].pin();
+        if constexpr (ABS) {
+#pragma unroll
+            for (int k = 0; k < KK; ++k) g[k].pin_sign();
+        }
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if constexpr (BIAS) load4<VEC>(acc, bias + plane + pix, row_in, T.x0, W);
 #pragma unroll
@@ -229,8 +284,12 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
                 if (t == R && l == R) continue;
                 const int k = chan<K>(t, l);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k].get(j), row[j + 2 * R - l], acc[j]);
+                for (int j = 0; j < 4; ++j) acc[j] = fmaf(ABS ? g[k].mag(j) : g[k].get(j), row[j + 2 * R - l], acc[j]);
             }
+        }
+        if constexpr (ABS) {
+            const float4 q = rsl[threadIdx.x];
+            acc[0] *= q.x; acc[1] *= q.y; acc[2] *= q.z; acc[3] *= q.w;
         }
         store4<VEC>(dst + plane + pix, acc, row_in, T.x0, W);
     }
@@ -238,9 +297,10 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
 
 // one adjoint step for all C channels: dst = step^T(src).  The gate of pixel q and channel k is read at q - off_k (zero outside the
 // image); VEC: W % 4 == 0 and dst 16-byte aligned, 16-bit gates 8-byte aligned
-template <int K, bool VEC, class GT = float>
+// ABS: gate is the raw guide; src is staged times 1 / S (rs [N][H][W], or NULL: stage_scaled) and the stencil runs on |gate|
+template <int K, bool VEC, class GT = float, bool ABS = false>
 __global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
-                                                       int C, int H, int W, int tiles_x, int tiles_y) {
+                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ rs) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -300,10 +360,15 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __rest
     for (int c = 0; c < C; ++c) {
         const size_t plane = ((size_t)T.n * C + c) * HW;
         __syncthreads();
-        stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
+        if constexpr (ABS) stage_scaled<R, KK, GT>(lds, src + plane, rs ? rs + (size_t)T.n * HW : nullptr, gb, T.y0, T.xt0, H, W);
+        else stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < KK; ++k) g[k].pin();
+        if constexpr (ABS) {
+#pragma unroll
+            for (int k = 0; k < KK; ++k) g[k].pin_sign();
+        }
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < K; ++t) {
@@ -315,7 +380,7 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __rest
                 if (t == R && l == R) continue;
                 const int k = chan<K>(t, l);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(g[k].get(j), row[j + l], acc[j]);
+                for (int j = 0; j < 4; ++j) acc[j] = fmaf(ABS ? g[k].mag(j) : g[k].get(j), row[j + l], acc[j]);
             }
         }
         store4<VEC>(dst + plane + T.y * W + T.x0, acc, row_in, T.x0, W);
@@ -327,10 +392,12 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __rest
 // VEC: W % 4 == 0 and gg aligned to four elements.
 // BIAS: also db [N][C][H][W] = sum_t A_{t+1} (dL/dbias of the folded contract); the loops then run over c, then t, and GATES = false
 // leaves out the gate gradient (no H level is read, gg and hist unused); db 16-byte aligned where VEC
-template <int K, bool VEC, bool BIAS = false, bool GATES = true, class GT = float>
+// ABS: the sums are dW of the ABS contract; the epilogue re-reads the raw guide (aligned to four elements where VEC) one channel at a
+// time, twice, and writes dL/dg_k = sign(g_k) (dW_k - (sum_j |g_j| dW_j) r) r, r = 1 / S, sign(0) = 0
+template <int K, bool VEC, bool BIAS = false, bool GATES = true, class GT = float, bool ABS = false>
 __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x, const float* __restrict__ hist, const float* __restrict__ alev,
                                                     const float* __restrict__ gout, store_t<GT>* __restrict__ gg, int n_iter, size_t L, int C, int H,
-                                                    int W, int tiles_x, int tiles_y, float* __restrict__ db) {
+                                                    int W, int tiles_x, int tiles_y, float* __restrict__ db, const store_t<GT>* __restrict__ guide) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -401,11 +468,76 @@ __global__ __launch_bounds__(NT) void kxk_gate_grad(const float* __restrict__ x,
             store4<VEC>(db + plane + pix, d, row_in, T.x0, W);
         }
     }
+    if constexpr (ABS) {
+        // four channels of the guide at a time, each group's loads through a pointer laundered after the group before it: left alone
+        // the compiler gathers all KK loads above the sums and keeps their values for the second pass, in registers the kernel does not have
+        constexpr int GB = 4;
+        static_assert(KK % GB == 0, "the epilogue walks the guide four channels at a time");
+        const store_t<GT>* up = guide + (size_t)T.n * KK * HW + pix;
+        store_t<GT>* gp = gg + (size_t)T.n * KK * HW + pix;
+        float S[4] = {0.f, 0.f, 0.f, 0.f}, dot[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k0 = 0; k0 < KK; k0 += GB) {
+            float g[GB][4];
+#pragma unroll
+            for (int i = 0; i < GB; ++i) load4<VEC, GT>(g[i], up + (size_t)(k0 + i) * HW, row_in, T.x0, W);
+#pragma unroll
+            for (int i = 0; i < GB; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    S[j] += fabsf(g[i][j]);
+                    dot[j] = fmaf(fabsf(g[i][j]), acc[k0 + i][j], dot[j]);
+                }
+            asm volatile("" : "+v"(up), "+v"(dot[3]));   // the next four loads wait for these sums
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            S[j] = 1.f / S[j];
+            dot[j] *= S[j];
+        }
+#pragma unroll
+        for (int k0 = 0; k0 < KK; k0 += GB) {
+            float g[GB][4];
+#pragma unroll
+            for (int i = 0; i < GB; ++i) load4<VEC, GT>(g[i], up + (size_t)(k0 + i) * HW, row_in, T.x0, W);
+#pragma unroll
+            for (int i = 0; i < GB; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[i][j] = signf(g[i][j]) * ((acc[k0 + i][j] - dot[j]) * S[j]);
+                store4<VEC, GT>(gp + (size_t)(k0 + i) * HW, g[i], row_in, T.x0, W);
+            }
+            asm volatile("" : "+v"(up) : "v"(g[GB - 1][3]));
+        }
+        return;
+    }
     if constexpr (GATES) {
         store_t<GT>* gp = gg + (size_t)T.n * KK * HW + pix;
 #pragma unroll
         for (int k = 0; k < KK; ++k) store4<VEC, GT>(gp + (size_t)k * HW, acc[k], row_in, T.x0, W);
     }
+}
+
+// 1 / S of the ABS contract for the adjoint steps: rs [N][H][W] = 1 / sum_k |guide_k|, the sum and the division of kxk_forward_step.
+// VEC: W % 4 == 0, guide aligned to four elements, rs 16-byte aligned
+template <int K, bool VEC, class GT = float>
+__global__ __launch_bounds__(NT) void kxk_rsum(const store_t<GT>* __restrict__ guide, float* __restrict__ rs, int H, int W, int tiles_x, int tiles_y) {
+    constexpr int KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    const store_t<GT>* up = guide + (size_t)T.n * KK * HW + pix;
+    float S[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+        float g[4];
+        load4<VEC, GT>(g, up + (size_t)k * HW, row_in, T.x0, W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[j] += fabsf(g[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) S[j] = 1.f / S[j];
+    store4<VEC>(rs + (size_t)T.n * HW + pix, S, row_in, T.x0, W);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -660,7 +792,7 @@ __global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, c
     }
 }
 
-template <int K, bool BIAS = false, class GT = float>
+template <int K, bool BIAS = false, class GT = float, bool ABS = false>
 int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
                   const float* bias = nullptr) {
     const Grid G = grid_of(N, H, W);
@@ -671,47 +803,59 @@ int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hi
     for (int it = 1; it <= n_iter; ++it) {
         float* dst = it == n_iter ? out : (hist ? hist + (size_t)(it - 1) * L : ((it & 1) ? ping : pong));
         if (W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)))
-            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
+            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         else
-            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
+            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
         if (int e = check_launch("kxk_forward_step")) return e;
         src = dst;
     }
     return 0;
 }
 
-// the adjoint steps A_{n-1} .. A_last into alev (A_t at alev + (t - 1) L), A_0 into gx
-template <int K, class GT = float>
-int adjoint_steps(const store_t<GT>* gate, const float* gout, float* gx, float* alev, int last, int N, int C, int H, int W, int n_iter, hipStream_t st) {
+// the adjoint steps A_{n-1} .. A_last into alev (A_t at alev + (t - 1) L), A_0 into gx; ABS: rs as kxk_adjoint_step takes it
+template <int K, class GT = float, bool ABS = false>
+int adjoint_steps(const store_t<GT>* gate, const float* gout, float* gx, float* alev, int last, int N, int C, int H, int W, int n_iter, hipStream_t st,
+                  const float* rs = nullptr) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
     for (int t = n_iter - 1; t >= last; --t) {
         const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
         float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
         if (W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)))
-            hipLaunchKernelGGL((kxk_adjoint_step<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+            hipLaunchKernelGGL((kxk_adjoint_step<K, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, rs);
         else
-            hipLaunchKernelGGL((kxk_adjoint_step<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty);
+            hipLaunchKernelGGL((kxk_adjoint_step<K, false, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, rs);
         if (int e = check_launch("kxk_adjoint_step")) return e;
     }
     return 0;
 }
 
-template <int K, class GT = float>
+// ABS: gate is the raw guide; with n_iter >= 2 the plane of 1 / S follows the adjoint levels in ws (kxk_absnorm_alev_bytes)
+template <int K, class GT = float, bool ABS = false>
 int backward_run(const store_t<GT>* gate, const float* x, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int N, int C, int H, int W,
                  int n_iter, void* ws, hipStream_t st) {
     const Grid G = grid_of(N, H, W);
     const size_t L = (size_t)N * C * H * W;
     float* alev = (float*)ws;   // A_1 .. A_{n-1}, level t at alev + (t - 1) L
+    const float* rs = nullptr;
+    if (ABS && n_iter >= 2) {
+        float* r = (float*)((char*)ws + kxk_absnorm_alev_bytes(L, n_iter));
+        if (W % 4 == 0 && aligned_quad<GT>(gate))
+            hipLaunchKernelGGL((kxk_rsum<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, r, H, W, G.tx, G.ty);
+        else
+            hipLaunchKernelGGL((kxk_rsum<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, r, H, W, G.tx, G.ty);
+        if (int e = check_launch("kxk_rsum")) return e;
+        rs = r;
+    }
     // the adjoint steps: A_{n-1} .. A_1 always (the gate gradient reads them), A_0 = dL/dx where asked for
-    if (int e = adjoint_steps<K, GT>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st)) return e;
+    if (int e = adjoint_steps<K, GT, ABS>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st, rs)) return e;
     if (!gg) return 0;
-    if (W % 4 == 0 && aligned_quad<GT>(gg))
-        hipLaunchKernelGGL((kxk_gate_grad<K, true, false, true, GT>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx,
-                           G.ty, nullptr);
+    if (W % 4 == 0 && aligned_quad<GT>(gg) && (!ABS || aligned_quad<GT>(gate)))
+        hipLaunchKernelGGL((kxk_gate_grad<K, true, false, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W,
+                           G.tx, G.ty, nullptr, gate);
     else
-        hipLaunchKernelGGL((kxk_gate_grad<K, false, false, true, GT>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W, G.tx,
-                           G.ty, nullptr);
+        hipLaunchKernelGGL((kxk_gate_grad<K, false, false, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W,
+                           G.tx, G.ty, nullptr, gate);
     return check_launch("kxk_gate_grad");
 }
 
@@ -765,17 +909,17 @@ int norm_backward(const store_t<GT>* guid, const float* blur, const float* spars
     if (gg) {
         if (vec)
             hipLaunchKernelGGL((kxk_gate_grad<K, true, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H, W,
-                               G.tx, G.ty, dbp);
+                               G.tx, G.ty, dbp, nullptr);
         else
             hipLaunchKernelGGL((kxk_gate_grad<K, false, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp);
+                               W, G.tx, G.ty, dbp, nullptr);
     } else {
         if (vec)
             hipLaunchKernelGGL((kxk_gate_grad<K, true, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp);
+                               W, G.tx, G.ty, dbp, nullptr);
         else
             hipLaunchKernelGGL((kxk_gate_grad<K, false, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp);
+                               W, G.tx, G.ty, dbp, nullptr);
     }
     if (int e = check_launch("kxk_gate_grad")) return e;
     const Grid GB = grid_of(B, H, W);
@@ -829,6 +973,33 @@ int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* h
                       : backward_run<7, __half>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
     return K == 5 ? backward_run<5, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st)
                   : backward_run<7, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
+}
+
+// the demo module's contract on the raw guide (dtype 0: float32, else as kxk_forward_g16); gg in the guide's type
+template <bool FWD, class GT>
+static int absnorm_run(const void* guide, const float* x, const float* hist, float* out, float* hout, const float* gout, void* gg, float* gx, int N, int C,
+                       int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+    const store_t<GT>* g = (const store_t<GT>*)guide;
+    if constexpr (FWD)
+        return K == 5 ? forward_steps<5, false, GT, true>(g, x, out, hout, N, C, H, W, n_iter, ws, st)
+                      : forward_steps<7, false, GT, true>(g, x, out, hout, N, C, H, W, n_iter, ws, st);
+    else
+        return K == 5 ? backward_run<5, GT, true>(g, x, hist, gout, (store_t<GT>*)gg, gx, N, C, H, W, n_iter, ws, st)
+                      : backward_run<7, GT, true>(g, x, hist, gout, (store_t<GT>*)gg, gx, N, C, H, W, n_iter, ws, st);
+}
+
+int kxk_absnorm_forward(const void* guide, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
+                        hipStream_t st) {
+    if (dtype == 0) return absnorm_run<true, float>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
+    if (dtype == CSPN_DTYPE_F16) return absnorm_run<true, __half>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
+    return absnorm_run<true, __hip_bfloat16>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
+}
+
+int kxk_absnorm_backward(const void* guide, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
+                         int W, int K, int n_iter, void* ws, hipStream_t st) {
+    if (dtype == 0) return absnorm_run<false, float>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
+    if (dtype == CSPN_DTYPE_F16) return absnorm_run<false, __half>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
+    return absnorm_run<false, __hip_bfloat16>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
 }
 
 }  // namespace cspn

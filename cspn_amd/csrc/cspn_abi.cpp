@@ -112,6 +112,16 @@ static bool kxk_overlaps(const void* out, size_t out_bytes, std::initializer_lis
     return false;
 }
 
+// the *_g16 entry points: the gate dtype, and the 16-bit tensors at even addresses
+static int g16_check(const char* what, int dtype, const void* gate, const void* grad_gate) {
+    if (dtype != CSPN_DTYPE_F16 && dtype != CSPN_DTYPE_BF16) {
+        set_error("%s: gate_dtype must be CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dtype);
+        return CSPN_E_BADARG;
+    }
+    if (((uintptr_t)gate & 1u) || ((uintptr_t)grad_gate & 1u)) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
+    return 0;
+}
+
 // the depth-completion contract over K x K (cspn2d_*_kxk_norm*): K = 3 as well, a mask of 0, 1 or C planes
 static bool kxk_norm_shape_ok(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
     const long long px = (long long)H * W, N = sparse_C > 1 ? (long long)B * C : B;
@@ -661,12 +671,15 @@ size_t cspn2d_kxk_history_bytes(int B, int C, int H, int W, int K, int n_iter) {
     return kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1);
 }
 
-int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H, int W,
-                           int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_forward_kxk_f32";
+// the checks of the eight cspn2d_{forward,backward}_kxk[_absnorm]_{f32,g16} entry points, then the engine.  g16: 16-bit gates of dtype, else dtype 0;
+// absnorm: the gates are the raw guide of the demo module's contract (the backward's workspace then also holds 1 / S)
+static int kxk_forward_entry(const char* what, const void* gate, bool g16, int dtype, bool absnorm, const float* x, float* out, float* history,
+                             size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (!gate || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (g16)
+        if (int e = g16_check(what, dtype, gate, nullptr)) return e;
     if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1);
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1);
     const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
     if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
     const size_t need = history ? 0 : cspn2d_kxk_workspace_bytes(B, C, H, W, K, n_iter);
@@ -683,30 +696,29 @@ int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float*
         if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return kxk_forward(gate, x, out, history, B, C, H, W, K, n_iter, ws, st);
+    if (absnorm) return kxk_absnorm_forward(gate, dtype, x, out, history, B, C, H, W, K, n_iter, ws, st);
+    return g16 ? kxk_forward_g16(gate, dtype, x, out, history, B, C, H, W, K, n_iter, ws, st)
+                 : kxk_forward((const float*)gate, x, out, history, B, C, H, W, K, n_iter, ws, st);
 }
 
-size_t cspn2d_backward_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter) {
-    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
-    return round256(kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1));
-}
-
-int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* history, size_t history_bytes, const float* grad_out,
-                            float* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
-                            cspn_stream_t stream) {
-    static const char* what = "cspn2d_backward_kxk_f32";
+static int kxk_backward_entry(const char* what, const void* gate, bool g16, int dtype, bool absnorm, const float* x, const float* history, size_t history_bytes,
+                              const float* grad_out, void* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws,
+                              size_t ws_bytes, cspn_stream_t stream) {
     if (!gate || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (g16)
+        if (int e = g16_check(what, dtype, gate, grad_gate)) return e;
     if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1);
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1);
     const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
     if (grad_gate && hb && (!history || history_bytes < hb)) {
         set_error("%s: the gate gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
         return CSPN_E_BADARG;
     }
-    const size_t need = cspn2d_backward_kxk_workspace_bytes(B, C, H, W, K, n_iter);
+    const size_t need = absnorm ? cspn2d_backward_kxk_absnorm_workspace_bytes(B, C, H, W, K, n_iter)
+                                : cspn2d_backward_kxk_workspace_bytes(B, C, H, W, K, n_iter);
     if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
     const size_t wb = need ? ws_bytes : 0, hbu = grad_gate ? hb : 0;
-    if (grad_gate && grad_gate == grad_x) { set_error("%s: grad_gate and grad_x must not alias", what); return CSPN_E_BADARG; }
+    if (grad_gate && grad_gate == (void*)grad_x) { set_error("%s: grad_gate and grad_x must not alias", what); return CSPN_E_BADARG; }
     if (kxk_overlaps(grad_gate, gb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
         kxk_overlaps(grad_x, vb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
         kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}})) {
@@ -721,7 +733,57 @@ int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* hist
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return kxk_backward(gate, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+    if (absnorm) return kxk_absnorm_backward(gate, dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+    return g16 ? kxk_backward_g16(gate, dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st)
+                 : kxk_backward((const float*)gate, x, history, grad_out, (float*)grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H, int W,
+                           int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_forward_entry("cspn2d_forward_kxk_f32", gate, false, 0, false, x, out, history, history_bytes, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+size_t cspn2d_backward_kxk_workspace_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
+    return round256(kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1));
+}
+
+int cspn2d_backward_kxk_f32(const float* gate, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                            float* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                            cspn_stream_t stream) {
+    return kxk_backward_entry("cspn2d_backward_kxk_f32", gate, false, 0, false, x, history, history_bytes, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter,
+                              ws, ws_bytes, stream);
+}
+
+// ---- the demo module's contract in the K x K engine (cspn2d_kxk.hip): the raw guide in the gates' place, the checks of the twins above ----
+size_t cspn2d_backward_kxk_absnorm_workspace_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;   // a single step forms 1 / S as it stages: no plane
+    return kxk_absnorm_alev_bytes((size_t)B * C * H * W, n_iter) + round256(sizeof(float) * (size_t)B * H * W);
+}
+
+int cspn2d_forward_kxk_absnorm_f32(const float* guide, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H, int W,
+                                   int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_forward_entry("cspn2d_forward_kxk_absnorm_f32", guide, false, 0, true, x, out, history, history_bytes, B, C, H, W, K, n_iter, ws, ws_bytes,
+                             stream);
+}
+
+int cspn2d_forward_kxk_absnorm_g16(const void* guide, int gate_dtype, const float* x, float* out, float* history, size_t history_bytes, int B, int C,
+                                   int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_forward_entry("cspn2d_forward_kxk_absnorm_g16", guide, true, gate_dtype, true, x, out, history, history_bytes, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_kxk_absnorm_f32(const float* guide, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                                    float* grad_guide, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                                    cspn_stream_t stream) {
+    return kxk_backward_entry("cspn2d_backward_kxk_absnorm_f32", guide, false, 0, true, x, history, history_bytes, grad_out, grad_guide, grad_x, B, C, H, W, K,
+                              n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_kxk_absnorm_g16(const void* guide, int gate_dtype, const float* x, const float* history, size_t history_bytes,
+                                    const float* grad_out, void* grad_guide, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws,
+                                    size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_backward_entry("cspn2d_backward_kxk_absnorm_g16", guide, true, gate_dtype, true, x, history, history_bytes, grad_out, grad_guide, grad_x, B, C, H, W, K, n_iter, ws,
+                              ws_bytes, stream);
 }
 
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip) ----
@@ -804,73 +866,17 @@ int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const
 
 // ---- the four K x K entry points on 16-bit gates / guidance (cspn2d_*_kxk*_g16): the checks of the _f32 twins, the gate tensor and its
 // gradient sized and aligned as 2-byte elements ----
-static int g16_check(const char* what, int dtype, const void* gate, const void* grad_gate) {
-    if (dtype != CSPN_DTYPE_F16 && dtype != CSPN_DTYPE_BF16) {
-        set_error("%s: gate_dtype must be CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dtype);
-        return CSPN_E_BADARG;
-    }
-    if (((uintptr_t)gate & 1u) || ((uintptr_t)grad_gate & 1u)) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
-    return 0;
-}
 
 int cspn2d_forward_kxk_g16(const void* gate, int gate_dtype, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H,
                            int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_forward_kxk_g16";
-    if (!gate || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = g16_check(what, gate_dtype, gate, nullptr)) return e;
-    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2;
-    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
-    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
-    const size_t need = history ? 0 : cspn2d_kxk_workspace_bytes(B, C, H, W, K, n_iter);
-    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0;
-    if (kxk_overlaps(out, vb, {{gate, gb}, {x, vb}, {history, hb}, {ws, wb}}) || kxk_overlaps(history, hb, {{gate, gb}, {x, vb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}})) {
-        set_error("%s: out, history and the workspace must not alias an input or each other", what);
-        return CSPN_E_BADARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (n_iter == 0) {
-        hipError_t e = hipMemcpyAsync(out, x, vb, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return kxk_forward_g16(gate, gate_dtype, x, out, history, B, C, H, W, K, n_iter, ws, st);
+    return kxk_forward_entry("cspn2d_forward_kxk_g16", gate, true, gate_dtype, false, x, out, history, history_bytes, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
 }
 
 int cspn2d_backward_kxk_g16(const void* gate, int gate_dtype, const float* x, const float* history, size_t history_bytes, const float* grad_out,
                             void* grad_gate, float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
                             cspn_stream_t stream) {
-    static const char* what = "cspn2d_backward_kxk_g16";
-    if (!gate || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = g16_check(what, gate_dtype, gate, grad_gate)) return e;
-    if (int e = kxk_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2;
-    const size_t hb = cspn2d_kxk_history_bytes(B, C, H, W, K, n_iter);
-    if (grad_gate && hb && (!history || history_bytes < hb)) {
-        set_error("%s: the gate gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
-        return CSPN_E_BADARG;
-    }
-    const size_t need = cspn2d_backward_kxk_workspace_bytes(B, C, H, W, K, n_iter);
-    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0, hbu = grad_gate ? hb : 0;
-    if (grad_gate && grad_gate == (void*)grad_x) { set_error("%s: grad_gate and grad_x must not alias", what); return CSPN_E_BADARG; }
-    if (kxk_overlaps(grad_gate, gb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
-        kxk_overlaps(grad_x, vb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{gate, gb}, {x, vb}, {history, hbu}, {grad_out, vb}})) {
-        set_error("%s: grad_gate, grad_x and the workspace must not alias an input or each other", what);
-        return CSPN_E_BADARG;
-    }
-    if (!grad_gate && !grad_x) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_iter == 0) {   // the identity: dL/dx = dL/dout, no gate is read
-        hipError_t e = grad_x ? hipMemcpyAsync(grad_x, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
-        if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, gb, st);
-        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return kxk_backward_g16(gate, gate_dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+    return kxk_backward_entry("cspn2d_backward_kxk_g16", gate, true, gate_dtype, false, x, history, history_bytes, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, ws_bytes,
+                              stream);
 }
 
 int cspn2d_forward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,

@@ -97,6 +97,15 @@ int kxk_forward_g16(const void* gate, int dtype, const float* x, float* out, flo
                     hipStream_t st);
 int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
                      int W, int K, int n_iter, void* ws, hipStream_t st);
+// the demo module's contract (cspn_paddle/demo.py:20-54) inside the same engine: guide raw, a_k = |g_k|, S = sum_k a_k per pixel,
+// H_{t+1} = (sum_k a_k H_t(p + off_k)) / S; dtype 0 (float32), CSPN_DTYPE_F16 or CSPN_DTYPE_BF16; gg = dL/dguide in the guide's type.
+// The forward's ws and hist as kxk_forward.  The backward's ws: A_1 .. A_{n-1} (kxk_absnorm_alev_bytes), then with n_iter >= 2 the
+// float32 plane [N][H][W] of 1 / S
+inline size_t kxk_absnorm_alev_bytes(size_t L, int n_iter) { return (sizeof(float) * L * (size_t)(n_iter - 1) + 255) & ~(size_t)255; }
+int kxk_absnorm_forward(const void* guide, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
+                        hipStream_t st);
+int kxk_absnorm_backward(const void* guide, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
+                         int W, int K, int n_iter, void* ws, hipStream_t st);
 
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip): guidance [B][K*K-1][H][W] raw, blur
 // [B][C][H][W], sparse NULL (sparse_C 0) or [B][sparse_C][H][W] with sparse_C 1 or C; normalised, neighbour-sited, pinned, folded into w' and b ----

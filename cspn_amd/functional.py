@@ -40,7 +40,7 @@ def _prep_value(t, name, shape=None):
 
 def widen16(*tensors):
     """float16 / bfloat16 tensors widened with a differentiable .float() (autograd carries the gradient back through the cast), everything
-    else as it is: what the modules and mirrors do in front of the paths that have no 16-bit kernel (3 x 3 in 2D, 3D, the gate normaliser)"""
+    else as it is: what the modules and mirrors do in front of the paths that have no 16-bit kernel (3 x 3 in 2D, 3D, the gate_absnorm tensor op)"""
     out = tuple(t.float() if isinstance(t, torch.Tensor) and t.dtype in _GATE16 else t for t in tensors)
     return out[0] if len(out) == 1 else out
 
@@ -557,9 +557,9 @@ def _kxk_shape(gate, x, kernel_size, extra=()):
     return K, N, C, H, W
 
 
-def _kxk_args(gate, x, kernel_size, extra=()):
+def _kxk_args(gate, x, kernel_size, extra=(), gate_name="gate"):
     K, N, C, H, W = _kxk_shape(gate, x, kernel_size, extra)
-    g, dt = _prep_gate(gate, "gate")
+    g, dt = _prep_gate(gate, gate_name)
     h = _prep_value(x, "x")
     rest = [_prep_value(t, name, (N, C, H, W)) for t, name in extra]
     if any(t.device != g.device for t in [h] + rest):
@@ -583,13 +583,18 @@ def cspn2d_forward_kxk(gate, x, kernel_size, n_iter, return_history=False):
     K = kernel_size in {5, 7}.  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk.  n_iter == 0 returns x.
     gate may be float16 / bfloat16 (cspn2d_forward_kxk_g16: widened exactly where used, out is float32 and bitwise the float32 call on
     gate.float()); a 16-bit x is widened with one cast."""
+    return _kxk_forward(gate, x, kernel_size, n_iter, return_history, "")
+
+
+def _kxk_forward(gate, x, kernel_size, n_iter, return_history, contract):
+    """cspn2d_forward_kxk<contract>_f32 / _g16: contract "" (gates as given) or "_absnorm" (the raw guide in their place)"""
     _kxk_shape(gate, x, kernel_size)
     n = int(n_iter)
     if n < 0:
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
     if n == 0:
         return (x, None) if return_history else x
-    g, dt, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size)
+    g, dt, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size, gate_name="guide" if contract else "gate")
     out = torch.empty_like(h)
     hist = None
     if out.numel() == 0:
@@ -603,7 +608,7 @@ def cspn2d_forward_kxk(gate, x, kernel_size, n_iter, return_history=False):
             hb = 0
             ws_bytes = _lib.late_symbol("cspn2d_kxk_workspace_bytes")(N, C, H, W, K, n)
             ws = _workspace(ws_bytes, g.device)
-        name = "cspn2d_forward_kxk_f32" if dt is None else "cspn2d_forward_kxk_g16"
+        name = "cspn2d_forward_kxk%s_%s" % (contract, "f32" if dt is None else "g16")
         rc = _lib.late_symbol(name)(
             g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), out.data_ptr(), hist.data_ptr() if hist is not None else None, hb,
             N, C, H, W, K, n, ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
@@ -616,7 +621,12 @@ def cspn2d_backward_kxk(gate, x, grad_out, kernel_size, n_iter, history=None, ne
     cspn2d_backward_kxk_f32.  history: what cspn2d_forward_kxk(..., return_history=True) returned; None runs that forward first
     where the gate gradient needs it.  A float16 / bfloat16 gate (cspn2d_backward_kxk_g16): dL/dx is float32 and bitwise the float32 call's,
     dL/dgate comes back in the gate's dtype, the float32 sum rounded once."""
-    g, dt, h, K, N, C, H, W, go = _kxk_args(gate, x, kernel_size, ((grad_out, "grad_out"),))
+    return _kxk_backward(gate, x, grad_out, kernel_size, n_iter, history, need_gate, need_x, "")
+
+
+def _kxk_backward(gate, x, grad_out, kernel_size, n_iter, history, need_gate, need_x, contract):
+    """cspn2d_backward_kxk<contract>_f32 / _g16, contract as _kxk_forward"""
+    g, dt, h, K, N, C, H, W, go = _kxk_args(gate, x, kernel_size, ((grad_out, "grad_out"),), "guide" if contract else "gate")
     n = int(n_iter)
     if n < 0:
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
@@ -627,18 +637,39 @@ def cspn2d_backward_kxk(gate, x, grad_out, kernel_size, n_iter, history=None, ne
     if h.numel() == 0:
         return (gg.zero_() if gg is not None else None), gx
     if need_gate and n >= 2 and history is None:
-        _, history = cspn2d_forward_kxk(g, h, K, n, return_history=True)
+        _, history = _kxk_forward(g, h, K, n, True, contract)
     with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_workspace_bytes")(N, C, H, W, K, n)
+        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk%s_workspace_bytes" % contract)(N, C, H, W, K, n)
         ws = _workspace(ws_bytes, g.device)
         hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
-        name = "cspn2d_backward_kxk_f32" if dt is None else "cspn2d_backward_kxk_g16"
+        name = "cspn2d_backward_kxk%s_%s" % (contract, "f32" if dt is None else "g16")
         rc = _lib.late_symbol(name)(
             g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), hp, hb, go.data_ptr(), gg.data_ptr() if gg is not None else None,
             gx.data_ptr() if gx is not None else None, N, C, H, W, K, n, ws.data_ptr(), ws_bytes,
             torch.cuda.current_stream(g.device).cuda_stream)
     _lib.check(rc, name)
     return gg, gx
+
+
+def cspn2d_forward_kxk_absnorm(guide, x, kernel_size, n_iter, return_history=False):
+    """The demo module's step inside the K x K engine (cspn2d_forward_kxk_absnorm_f32): guide [N,K*K-1,H,W] raw, any sign, in the gate
+    channel order of cspn2d_forward_kxk; x [N,C,H,W], the C channels on the shared guide -> H_n [N,C,H,W] with
+    H_{t+1}(p) = (sum_k |guide_k(p)| H_t(p + off_k)) / S(p), S(p) = sum_k |guide_k(p)|: what cspn2d_forward_kxk(gate_absnorm(guide, K*K-1),
+    x, ...) computes up to rounding (the scale is applied once, after the sum), with no normalised gate stored.  NaN where a pixel's
+    gates are all zero.  K = kernel_size in {5, 7}; return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_absnorm;
+    n_iter == 0 returns x.  guide may be float16 / bfloat16 (cspn2d_forward_kxk_absnorm_g16: widened exactly where used, out is float32 and
+    bitwise the float32 call on guide.float()); a 16-bit x is widened with one cast."""
+    return _kxk_forward(guide, x, kernel_size, n_iter, return_history, "_absnorm")
+
+
+def cspn2d_backward_kxk_absnorm(guide, x, grad_out, kernel_size, n_iter, history=None, need_guide=True, need_x=True):
+    """Gradient of cspn2d_forward_kxk_absnorm -> (dL/dguide [N,K*K-1,H,W] summed over the C channels or None, dL/dx [N,C,H,W] or None);
+    cspn2d_backward_kxk_absnorm_f32.  The adjoint steps read 1 / S from one float32 plane, the gate-gradient pass keeps its K*K-1 sums in
+    registers and chains them through the normalisation as it writes: no dL/dw tensor exists.  history: what
+    cspn2d_forward_kxk_absnorm(..., return_history=True) returned; None runs that forward first where the guide gradient needs it.
+    A float16 / bfloat16 guide (cspn2d_backward_kxk_absnorm_g16): dL/dx is float32 and bitwise the float32 call's, dL/dguide comes back in
+    the guide's dtype, the float32 value rounded once."""
+    return _kxk_backward(guide, x, grad_out, kernel_size, n_iter, history, need_guide, need_x, "_absnorm")
 
 
 class _AffinityPropagateKxKFunction(torch.autograd.Function):
@@ -931,21 +962,22 @@ def _absnorm_forward(guide, feat, n_iter, kernel_size=3, keep_history=False):
         out = cspn3d_forward_absnorm(g, x, n_iter)
     elif K == 8:   # 2D: the normaliser, then the NONE op (the 2D loop is generated assembly: no fused normalisation there)
         out = cspn2d_forward(_gate_absnorm(g, 8), x, None, n_iter, "none")
-    else:          # 2D K x K: the normaliser, then the K x K engine
-        out = cspn2d_forward_kxk(_gate_absnorm(g, K), x, kernel_size, n_iter, return_history=keep_history)
+    else:          # 2D K x K: the K x K engine normalises the resident gates in its step
+        out = cspn2d_forward_kxk_absnorm(g, x, kernel_size, n_iter, return_history=keep_history)
         if keep_history:
             out, hist = out
     return out.view(feat.shape), hist
 
 
 class _AbsnormPropagateFunction(torch.autograd.Function):
-    """the demo's module under autograd: the backward recomputes w with the normaliser, runs the NONE op's backward on the folded N*C
-    batch and chains the gate gradient through cspn_gate_absnorm_backward_f32 (K x K: the forward keeps its levels for the backward)"""
+    """the demo's module under autograd.  3 x 3 (x 3): the backward recomputes w with the normaliser, runs the NONE op's backward on the
+    folded N*C batch and chains the gate gradient through cspn_gate_absnorm_backward_f32.  K x K: the forward keeps its levels where the
+    guide gradient needs them, the backward is one cspn2d_backward_kxk_absnorm call on the raw guide (float32, float16 or bfloat16)"""
 
     @staticmethod
     def forward(ctx, guide, feat, n_iter, kernel_size):
         ctx.n_iter, ctx.kernel_size = n_iter, kernel_size
-        out, hist = _absnorm_forward(guide, feat, n_iter, kernel_size, keep_history=kernel_size != 3)
+        out, hist = _absnorm_forward(guide, feat, n_iter, kernel_size, keep_history=kernel_size != 3 and ctx.needs_input_grad[0] and n_iter >= 2)
         ctx.save_for_backward(guide, feat, hist)
         return out
 
@@ -954,14 +986,15 @@ class _AbsnormPropagateFunction(torch.autograd.Function):
         guide, feat, hist = ctx.saved_tensors
         need_g, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g, x, K = _absnorm_fold(guide, feat, ctx.kernel_size)
-        w = _gate_absnorm(g, K)
         go = grad_out.contiguous().view(x.shape)
+        if K not in (8, 26):
+            gg, gx = cspn2d_backward_kxk_absnorm(g, x, go, ctx.kernel_size, ctx.n_iter, hist, need_g, need_x)
+            return gg.view(guide.shape) if need_g else None, gx.view(feat.shape) if need_x else None, None, None
+        w = _gate_absnorm(g, K)
         if K == 26:
             gw, gx = cspn3d_backward(w, x, go, ctx.n_iter, need_g, need_x)
-        elif K == 8:
-            gw, gx = cspn2d_backward(w, x, None, go, ctx.n_iter, "none", need_g, need_x)
         else:
-            gw, gx = cspn2d_backward_kxk(w, x, go, ctx.kernel_size, ctx.n_iter, hist, need_g, need_x)
+            gw, gx = cspn2d_backward(w, x, None, go, ctx.n_iter, "none", need_g, need_x)
         gg = gate_absnorm_backward(g, gw, K).view(guide.shape) if need_g else None
         return gg, gx.view(feat.shape) if need_x else None, None, None
 
@@ -970,8 +1003,11 @@ def absnorm_propagate(guide, feat, n_iter, kernel_size=3):
     """The demo's CSPN.cspn (reference cspn_paddle/demo.py:20-54) as a function: feat [N,C,*S] (len(S) = 2 or 3), guide [N, C*K, *S] raw
     with K = kernel_size^len(S) - 1; channel c is propagated on its OWN slice guide[:, c*K:(c+1)*K], normalised by its abs-sum at every
     voxel, for n_iter chained steps.  One engine call for all channels (they fold into the batch).  3D: cspn3d_forward_absnorm_f32 (the
-    normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none'), or with kernel_size
-    5 / 7 (2D only) cspn2d_forward_kxk.  Differentiable w.r.t. guide and feat.  n_iter == 0 returns feat itself."""
+    normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none'); with kernel_size
+    5 / 7 (2D only) cspn2d_forward_kxk_absnorm / cspn2d_backward_kxk_absnorm on the folded views, which normalise the gates inside the
+    K x K step and store no normalised gate.  That route alone takes a float16 / bfloat16 guide as it is (dL/dguide comes back in its
+    dtype) and widens a 16-bit feat with one differentiable cast; the result is float32.  Differentiable w.r.t. guide and feat.
+    n_iter == 0 returns feat itself."""
     for t, name in ((guide, "guide"), (feat, "feat")):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor" % name)
@@ -987,8 +1023,12 @@ def absnorm_propagate(guide, feat, n_iter, kernel_size=3):
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
     if int(n_iter) == 0:
         return feat
-    g = _prep(guide, "guide")
-    x = _prep(feat, "feat")
+    if kernel_size != 3:
+        g = _prep_gate(guide, "guide")[0]
+        x = _prep(widen16(feat), "feat")
+    else:
+        g = _prep(guide, "guide")
+        x = _prep(feat, "feat")
     if g.device != x.device:
         raise _lib.CspnError("cspn_amd: guide is on %s, feat on %s: all tensors must live on the same device" % (g.device, x.device))
     if torch.is_grad_enabled() and (guide.requires_grad or feat.requires_grad):

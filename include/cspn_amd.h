@@ -50,7 +50,8 @@ extern "C" {
                               *    (cspn_gate_absnorm_f32 / _backward_f32, cspn3d_forward_absnorm_f32), the 2D K x K entry points
                               *    (cspn2d_*_kxk*, K = 5 / 7), K = 24 / 48 on the gate normaliser and the depth-completion contract over
                               *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*),
-                              *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*) */
+                              *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*), the demo module's
+                              *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -332,6 +333,34 @@ int cspn2d_forward_kxk_norm_g16(const void* guidance, int gate_dtype, const floa
 int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
                                  size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
                                  int H, int W, int K, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
+ * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
+ * S(p) = sum_k a_k(p), summed in channel order in float32:
+ *     H_{t+1}(p) = (sum_k a_k(p) H_t(p + off_k)) * (1 / S(p))      H_0 = x, out = H_n, zero outside the image
+ *     A_t(q)     = sum_k a_k(q - off_k) A_{t+1}(q - off_k) * (1 / S(q - off_k)),   A_n = grad_out, grad_x = A_0
+ *     dW_k(p)    = sum_{t<n} sum_c A_{t+1}(p) H_t(p + off_k),   grad_guide_k = sign(g_k) (dW_k - (sum_j a_j dW_j) / S) / S,  sign(0) = 0
+ *   what cspn_gate_absnorm_f32 followed by cspn2d_forward_kxk_f32 computes, up to rounding (the scale is applied once, after the sum),
+ *   without the normalised gates: no tensor of the guide's size is written, read back or kept.  A pixel whose KK gates are all zero
+ *   gives NaN (0 * inf), as 0 / 0 there.
+ * history, the forward's workspace and their byte counts are those of cspn2d_forward_kxk_f32 (cspn2d_kxk_workspace_bytes,
+ * cspn2d_kxk_history_bytes).  The backward's workspace (cspn2d_backward_kxk_absnorm_workspace_bytes) keeps A_1 .. A_{n-1} and one
+ * float32 plane [B,H,W] of 1 / S; 0 for n_iter <= 1.  The _g16 twins take a guide of gate_dtype under the rule of the 16-bit block above:
+ * out and grad_x bitwise the _f32 entry point's on the widened guide, grad_guide its float32 value rounded once.  No atomics.
+ * Arguments, alignment and error codes exactly as cspn2d_forward_kxk_f32 / _g16 and cspn2d_backward_kxk_f32 / _g16. */
+int cspn2d_forward_kxk_absnorm_f32(const float* guide, const float* x, float* out, float* history, size_t history_bytes,
+                                   int B, int C, int H, int W, int K, int n_iter,
+                                   void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_forward_kxk_absnorm_g16(const void* guide, int gate_dtype, const float* x, float* out, float* history, size_t history_bytes,
+                                   int B, int C, int H, int W, int K, int n_iter,
+                                   void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_kxk_absnorm_workspace_bytes(int B, int C, int H, int W, int K, int n_iter);
+int cspn2d_backward_kxk_absnorm_f32(const float* guide, const float* x, const float* history, size_t history_bytes, const float* grad_out,
+                                    float* grad_guide, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                                    void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_absnorm_g16(const void* guide, int gate_dtype, const float* x, const float* history, size_t history_bytes,
+                                    const float* grad_out, void* grad_guide, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                                    void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
