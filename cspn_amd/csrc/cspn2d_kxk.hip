@@ -792,6 +792,34 @@ __global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, c
     }
 }
 
+// ---- the host dispatch: a runtime value as a template argument of a generic lambda ----
+template <class T>
+struct Tag {
+    using type = T;
+};
+
+// the gate storage type of dtype: 0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16 (checked by the caller)
+template <class F>
+int with_gate_type(int dtype, F&& f) {
+    if (dtype == 0) return f(Tag<float>{});
+    if (dtype == CSPN_DTYPE_F16) return f(Tag<__half>{});
+    return f(Tag<__hip_bfloat16>{});
+}
+
+// K as a constant out of the contract's list (checked by the caller to be one of them)
+template <int K0, int... Ks, class F>
+int with_k(int K, F&& f) {
+    if constexpr (sizeof...(Ks) == 0) return f(std::integral_constant<int, K0>{});
+    else return K == K0 ? f(std::integral_constant<int, K0>{}) : with_k<Ks...>(K, f);
+}
+
+// a flag as std::bool_constant: VEC of a launch, which is then written once
+template <class F>
+auto with_bool(bool b, F&& f) {
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
+}
+
 template <int K, bool BIAS = false, class GT = float, bool ABS = false>
 int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
                   const float* bias = nullptr) {
@@ -802,10 +830,10 @@ int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hi
     const float* src = x;
     for (int it = 1; it <= n_iter; ++it) {
         float* dst = it == n_iter ? out : (hist ? hist + (size_t)(it - 1) * L : ((it & 1) ? ping : pong));
-        if (W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)))
-            hipLaunchKernelGGL((kxk_forward_step<K, true, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
-        else
-            hipLaunchKernelGGL((kxk_forward_step<K, false, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, bias);
+        with_bool(W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_forward_step<K, decltype(vec)::value, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx,
+                               G.ty, bias);
+        });
         if (int e = check_launch("kxk_forward_step")) return e;
         src = dst;
     }
@@ -821,10 +849,10 @@ int adjoint_steps(const store_t<GT>* gate, const float* gout, float* gx, float* 
     for (int t = n_iter - 1; t >= last; --t) {
         const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
         float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
-        if (W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)))
-            hipLaunchKernelGGL((kxk_adjoint_step<K, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, rs);
-        else
-            hipLaunchKernelGGL((kxk_adjoint_step<K, false, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, rs);
+        with_bool(W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_adjoint_step<K, decltype(vec)::value, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty,
+                               rs);
+        });
         if (int e = check_launch("kxk_adjoint_step")) return e;
     }
     return 0;
@@ -840,22 +868,19 @@ int backward_run(const store_t<GT>* gate, const float* x, const float* hist, con
     const float* rs = nullptr;
     if (ABS && n_iter >= 2) {
         float* r = (float*)((char*)ws + kxk_absnorm_alev_bytes(L, n_iter));
-        if (W % 4 == 0 && aligned_quad<GT>(gate))
-            hipLaunchKernelGGL((kxk_rsum<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, r, H, W, G.tx, G.ty);
-        else
-            hipLaunchKernelGGL((kxk_rsum<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, r, H, W, G.tx, G.ty);
+        with_bool(W % 4 == 0 && aligned_quad<GT>(gate), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_rsum<K, decltype(vec)::value, GT>), dim3(G.blocks), dim3(NT), 0, st, gate, r, H, W, G.tx, G.ty);
+        });
         if (int e = check_launch("kxk_rsum")) return e;
         rs = r;
     }
     // the adjoint steps: A_{n-1} .. A_1 always (the gate gradient reads them), A_0 = dL/dx where asked for
     if (int e = adjoint_steps<K, GT, ABS>(gate, gout, gx, alev, gx ? 0 : (gg ? 1 : n_iter), N, C, H, W, n_iter, st, rs)) return e;
     if (!gg) return 0;
-    if (W % 4 == 0 && aligned_quad<GT>(gg) && (!ABS || aligned_quad<GT>(gate)))
-        hipLaunchKernelGGL((kxk_gate_grad<K, true, false, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W,
-                           G.tx, G.ty, nullptr, gate);
-    else
-        hipLaunchKernelGGL((kxk_gate_grad<K, false, false, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L, C, H, W,
-                           G.tx, G.ty, nullptr, gate);
+    with_bool(W % 4 == 0 && aligned_quad<GT>(gg) && (!ABS || aligned_quad<GT>(gate)), [&](auto vec) {
+        hipLaunchKernelGGL((kxk_gate_grad<K, decltype(vec)::value, false, true, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, x, hist, alev, gout, gg, n_iter, L,
+                           C, H, W, G.tx, G.ty, nullptr, gate);
+    });
     return check_launch("kxk_gate_grad");
 }
 
@@ -873,13 +898,14 @@ NormGeo norm_geo(int B, int C, int sparse_C, int H, int W) {
 template <int K, class GT = float>
 int fold(const store_t<GT>* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st) {
     const Grid G = grid_of(g.N, H, W);
-    if (W % 4 == 0 && aligned16(blur))
-        hipLaunchKernelGGL((kxk_fold<K, true, GT>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
-    else
-        hipLaunchKernelGGL((kxk_fold<K, false, GT>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W, G.tx, G.ty);
+    with_bool(W % 4 == 0 && aligned16(blur), [&](auto vec) {
+        hipLaunchKernelGGL((kxk_fold<K, decltype(vec)::value, GT>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W,
+                           G.tx, G.ty);
+    });
     return check_launch("kxk_fold");
 }
 
+// the steps run on the float32 w' and b whatever the guidance's type
 template <int K, class GT = float>
 int norm_forward(const store_t<GT>* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
                  int n_iter, int norm, void* ws, hipStream_t st) {
@@ -906,167 +932,83 @@ int norm_backward(const store_t<GT>* guid, const float* blur, const float* spars
     if (int e = adjoint_steps<K>(wp, gout, gx, alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
     const Grid G = grid_of(g.N, H, W);
     const bool vec = W % 4 == 0;   // dwp and dbp: workspace
-    if (gg) {
-        if (vec)
-            hipLaunchKernelGGL((kxk_gate_grad<K, true, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H, W,
-                               G.tx, G.ty, dbp, nullptr);
-        else
-            hipLaunchKernelGGL((kxk_gate_grad<K, false, true, true>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp, nullptr);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((kxk_gate_grad<K, true, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp, nullptr);
-        else
-            hipLaunchKernelGGL((kxk_gate_grad<K, false, true, false>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout, dwp, n_iter, g.L, g.Cv, H,
-                               W, G.tx, G.ty, dbp, nullptr);
-    }
+    with_bool(vec, [&](auto v) {
+        with_bool(gg != nullptr, [&](auto gates) {
+            hipLaunchKernelGGL((kxk_gate_grad<K, decltype(v)::value, true, decltype(gates)::value>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout,
+                               dwp, n_iter, g.L, g.Cv, H, W, G.tx, G.ty, dbp, nullptr);
+        });
+    });
     if (int e = check_launch("kxk_gate_grad")) return e;
     const Grid GB = grid_of(B, H, W);
-    if (vec && aligned16(blur) && (!gx || aligned16(gx)))
-        hipLaunchKernelGGL((kxk_unfold_pixel<K, true, GT>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
-                           H, W, GB.tx, GB.ty);
-    else
-        hipLaunchKernelGGL((kxk_unfold_pixel<K, false, GT>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv, g.cpg, norm,
-                           H, W, GB.tx, GB.ty);
+    with_bool(vec && aligned16(blur) && (!gx || aligned16(gx)), [&](auto v) {
+        hipLaunchKernelGGL((kxk_unfold_pixel<K, decltype(v)::value, GT>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv,
+                           g.cpg, norm, H, W, GB.tx, GB.ty);
+    });
     if (int e = check_launch("kxk_unfold_pixel")) return e;
     if (!gg) return 0;
-    if (vec && aligned_quad<GT>(guid) && aligned_quad<GT>(gg))
-        hipLaunchKernelGGL((kxk_unsite<K, true, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
-    else
-        hipLaunchKernelGGL((kxk_unsite<K, false, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+    with_bool(vec && aligned_quad<GT>(guid) && aligned_quad<GT>(gg), [&](auto v) {
+        hipLaunchKernelGGL((kxk_unsite<K, decltype(v)::value, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
+    });
     return check_launch("kxk_unsite");
 }
 
 }  // namespace
 
-// arguments checked by the caller (cspn_abi.cpp): K in {5, 7}, n_iter >= 1, N C H W and N KK H W below 2^31, no aliasing, the
-// workspace as kxk_workspace_floats / kxk_backward_workspace_floats
-int kxk_forward(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                hipStream_t st) {
-    return K == 5 ? forward_steps<5>(gate, x, out, hist, N, C, H, W, n_iter, ws, st) : forward_steps<7>(gate, x, out, hist, N, C, H, W, n_iter, ws, st);
+// ---- the four entries.  gate / guid in the type of dtype: 0 float32, CSPN_DTYPE_F16 or CSPN_DTYPE_BF16; gg in the same type.  The
+// arguments are checked by the caller (cspn_abi.cpp): n_iter >= 1, every view below 2^31 elements, no aliasing, the workspaces as the
+// cspn2d_*kxk*_workspace_bytes functions size them ----
+
+// K in {5, 7}; absnorm: the demo module's contract on the raw guide, else the gates as given
+int kxk_forward(const void* gate, int dtype, bool absnorm, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter,
+                void* ws, hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<5, 7>(K, [&](auto k) {
+            return with_bool(absnorm, [&](auto abs) {
+                return forward_steps<decltype(k)::value, false, GT, decltype(abs)::value>((const store_t<GT>*)gate, x, out, hist, N, C, H, W, n_iter, ws, st);
+            });
+        });
+    });
 }
 
-int kxk_backward(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W, int K,
-                 int n_iter, void* ws, hipStream_t st) {
-    return K == 5 ? backward_run<5>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st)
-                  : backward_run<7>(gate, x, hist, gout, gg, gx, N, C, H, W, n_iter, ws, st);
+int kxk_backward(const void* gate, int dtype, bool absnorm, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C,
+                 int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<5, 7>(K, [&](auto k) {
+            return with_bool(absnorm, [&](auto abs) {
+                return backward_run<decltype(k)::value, GT, decltype(abs)::value>((const store_t<GT>*)gate, x, hist, gout, (store_t<GT>*)gg, gx, N, C, H, W,
+                                                                                 n_iter, ws, st);
+            });
+        });
+    });
 }
-
-// the same on 16-bit gates (dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16, checked by the caller); gg in the gates' type
-int kxk_forward_g16(const void* gate, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                    hipStream_t st) {
-    const unsigned short* g = (const unsigned short*)gate;
-    if (dtype == CSPN_DTYPE_F16)
-        return K == 5 ? forward_steps<5, false, __half>(g, x, out, hist, N, C, H, W, n_iter, ws, st)
-                      : forward_steps<7, false, __half>(g, x, out, hist, N, C, H, W, n_iter, ws, st);
-    return K == 5 ? forward_steps<5, false, __hip_bfloat16>(g, x, out, hist, N, C, H, W, n_iter, ws, st)
-                  : forward_steps<7, false, __hip_bfloat16>(g, x, out, hist, N, C, H, W, n_iter, ws, st);
-}
-
-int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
-                     int W, int K, int n_iter, void* ws, hipStream_t st) {
-    const unsigned short* g = (const unsigned short*)gate;
-    unsigned short* d = (unsigned short*)gg;
-    if (dtype == CSPN_DTYPE_F16)
-        return K == 5 ? backward_run<5, __half>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st)
-                      : backward_run<7, __half>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
-    return K == 5 ? backward_run<5, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st)
-                  : backward_run<7, __hip_bfloat16>(g, x, hist, gout, d, gx, N, C, H, W, n_iter, ws, st);
-}
-
-// the demo module's contract on the raw guide (dtype 0: float32, else as kxk_forward_g16); gg in the guide's type
-template <bool FWD, class GT>
-static int absnorm_run(const void* guide, const float* x, const float* hist, float* out, float* hout, const float* gout, void* gg, float* gx, int N, int C,
-                       int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
-    const store_t<GT>* g = (const store_t<GT>*)guide;
-    if constexpr (FWD)
-        return K == 5 ? forward_steps<5, false, GT, true>(g, x, out, hout, N, C, H, W, n_iter, ws, st)
-                      : forward_steps<7, false, GT, true>(g, x, out, hout, N, C, H, W, n_iter, ws, st);
-    else
-        return K == 5 ? backward_run<5, GT, true>(g, x, hist, gout, (store_t<GT>*)gg, gx, N, C, H, W, n_iter, ws, st)
-                      : backward_run<7, GT, true>(g, x, hist, gout, (store_t<GT>*)gg, gx, N, C, H, W, n_iter, ws, st);
-}
-
-int kxk_absnorm_forward(const void* guide, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                        hipStream_t st) {
-    if (dtype == 0) return absnorm_run<true, float>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
-    if (dtype == CSPN_DTYPE_F16) return absnorm_run<true, __half>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
-    return absnorm_run<true, __hip_bfloat16>(guide, x, nullptr, out, hist, nullptr, nullptr, nullptr, N, C, H, W, K, n_iter, ws, st);
-}
-
-int kxk_absnorm_backward(const void* guide, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
-                         int W, int K, int n_iter, void* ws, hipStream_t st) {
-    if (dtype == 0) return absnorm_run<false, float>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
-    if (dtype == CSPN_DTYPE_F16) return absnorm_run<false, __half>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
-    return absnorm_run<false, __hip_bfloat16>(guide, x, hist, nullptr, nullptr, gout, gg, gx, N, C, H, W, K, n_iter, ws, st);
-}
-
-}  // namespace cspn
-
-namespace cspn {
 
 size_t kxk_norm_fold_floats(int B, int C, int sparse_C, int H, int W, int K) {
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     return kxk_level_floats((size_t)g.N * (K * K - 1) * H * W) + kxk_level_floats(g.L);
 }
 
-// arguments checked by the caller (cspn_abi.cpp): K in {3, 5, 7}, n_iter >= 1, norm 8SUM / 8SUM_ABS, sparse_C 0 / 1 / C (0 <=> sparse NULL),
-// every view below 2^31 elements, no aliasing, the workspace as cspn2d_kxk_norm_workspace_bytes / cspn2d_backward_kxk_norm_workspace_bytes
-int kxk_norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
-                     int K, int n_iter, int norm, void* ws, hipStream_t st) {
-    switch (K) {
-        case 3: return norm_forward<3>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        case 5: return norm_forward<5>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        default: return norm_forward<7>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-    }
+// K in {3, 5, 7}, norm 8SUM / 8SUM_ABS, sparse_C 0 / 1 / C (0 <=> sparse NULL)
+int kxk_norm_forward(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H,
+                     int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<3, 5, 7>(K, [&](auto k) {
+            return norm_forward<decltype(k)::value, GT>((const store_t<GT>*)guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
+        });
+    });
 }
 
-int kxk_norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B,
-                      int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
-    switch (K) {
-        case 3: return norm_backward<3>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        case 5: return norm_backward<5>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        default: return norm_backward<7>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-    }
-}
-
-// the same on 16-bit guidance (dtype as kxk_forward_g16); w' and b stay float32, gg in the guidance's type
-template <class GT>
-static int norm_forward_g16(const unsigned short* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
-                            int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
-    switch (K) {
-        case 3: return norm_forward<3, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        case 5: return norm_forward<5, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        default: return norm_forward<7, GT>(guid, blur, sparse, out, hist, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-    }
-}
-
-template <class GT>
-static int norm_backward_g16(const unsigned short* guid, const float* blur, const float* sparse, const float* hist, const float* gout,
-                             unsigned short* gg, float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
-                             hipStream_t st) {
-    switch (K) {
-        case 3: return norm_backward<3, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        case 5: return norm_backward<5, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-        default: return norm_backward<7, GT>(guid, blur, sparse, hist, gout, gg, gx, B, C, sparse_C, H, W, n_iter, norm, ws, st);
-    }
-}
-
-int kxk_norm_forward_g16(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
-                         int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
-    const unsigned short* g = (const unsigned short*)guid;
-    return dtype == CSPN_DTYPE_F16 ? norm_forward_g16<__half>(g, blur, sparse, out, hist, B, C, sparse_C, H, W, K, n_iter, norm, ws, st)
-                                   : norm_forward_g16<__hip_bfloat16>(g, blur, sparse, out, hist, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
-}
-
-int kxk_norm_backward_g16(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg,
-                          float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
-    const unsigned short* g = (const unsigned short*)guid;
-    unsigned short* d = (unsigned short*)gg;
-    return dtype == CSPN_DTYPE_F16
-               ? norm_backward_g16<__half>(g, blur, sparse, hist, gout, d, gx, B, C, sparse_C, H, W, K, n_iter, norm, ws, st)
-               : norm_backward_g16<__hip_bfloat16>(g, blur, sparse, hist, gout, d, gx, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+int kxk_norm_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg, float* gx,
+                      int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<3, 5, 7>(K, [&](auto k) {
+            return norm_backward<decltype(k)::value, GT>((const store_t<GT>*)guid, blur, sparse, hist, gout, (store_t<GT>*)gg, gx, B, C, sparse_C, H, W,
+                                                        n_iter, norm, ws, st);
+        });
+    });
 }
 
 }  // namespace cspn

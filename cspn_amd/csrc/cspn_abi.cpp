@@ -77,7 +77,7 @@ static int absnorm_check(const char* what, const float* guide, const float* a, c
 }
 
 static size_t absnorm_planes_bytes(int B, int D, int H, int W) {   // the normalised gates of the unfused path, 256-byte multiple
-    return (26 * sizeof(float) * (size_t)B * D * H * W + 255) & ~(size_t)255;
+    return round256(26 * sizeof(float) * (size_t)B * D * H * W);
 }
 
 // ---- the K x K entry points (cspn2d_*_kxk*) ----
@@ -93,8 +93,6 @@ static int kxk_check_shape(const char* what, int B, int C, int H, int W, int K, 
     if (!kxk_shape_ok(B, C, H, W, K, n_iter)) { set_error("%s: tensor too large for 32-bit element indexing", what); return CSPN_E_UNSUPPORTED; }
     return 0;
 }
-
-static size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static size_t kxk_values_bytes(int B, int C, int H, int W) { return sizeof(float) * (size_t)B * C * H * W; }
 
@@ -287,7 +285,6 @@ int cspn2d_backward_history_f32(const float* guidance, const float* blur, const 
 }
 
 // ---- C channels on shared 2D guidance (include/cspn_amd.h: the cspn2d_*_multi entry points) ----
-static size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 static int check_multi(int B, int C, int sparse_channels, const float* sparse, int H, int W) {
     if (B < 0 || C <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d C=%d H=%d W=%d", B, C, H, W); return CSPN_E_BADARG; }
@@ -318,7 +315,7 @@ static hipError_t scatter_channel(float* dst, const float* src, int B, int C, in
     } while (0)
 
 // a shared mask widened to [B][C][HW] at the front of the workspace (the fast paths)
-static size_t widened_bytes(int B, int C, int H, int W) { return al256(sizeof(float) * (size_t)B * C * H * W); }
+static size_t widened_bytes(int B, int C, int H, int W) { return round256(sizeof(float) * (size_t)B * C * H * W); }
 
 static int widen_if_shared(const float*& sparse, int sparse_channels, int B, int C, int H, int W, void* ws, hipStream_t st) {
     if (!sparse || sparse_channels == C) return 0;
@@ -335,8 +332,8 @@ int cspn2d_multi_supported(int B, int C, int H, int W, int n_iter) {
 size_t cspn2d_workspace_bytes_multi(int B, int C, int H, int W, int n_iter) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
     if (C == 1) return cspn2d_workspace_bytes(B, H, W, n_iter);
-    const size_t plane = al256(sizeof(float) * (size_t)B * H * W);
-    const size_t loop = 3 * plane + al256(cspn2d_workspace_bytes(B, H, W, n_iter));   // blur, mask and out of one channel + its call's workspace
+    const size_t plane = round256(sizeof(float) * (size_t)B * H * W);
+    const size_t loop = 3 * plane + round256(cspn2d_workspace_bytes(B, H, W, n_iter));   // blur, mask and out of one channel + its call's workspace
     const size_t fast = multi_fast(B, C, H, W, n_iter) ? widened_bytes(B, C, H, W) + fused2d_workspace(B * C, H, W, n_iter) : 0;
     return loop > fast ? loop : fast;
 }
@@ -362,7 +359,7 @@ int cspn2d_forward_multi_f32(const float* guidance, const float* blur, const flo
         return fused2d_forward(guidance, blur, sparse, out, B * C, H, W, n_iter, norm_type, (char*)ws + widened_bytes(B, C, H, W), st, true, 0, C);
     }
     // everything else: channel by channel through the single-channel entry point
-    const size_t plane = al256(sizeof(float) * (size_t)B * HW);
+    const size_t plane = round256(sizeof(float) * (size_t)B * HW);
     float* blur_c = (float*)ws;
     float* sp_c = (float*)((char*)ws + plane);
     float* out_c = (float*)((char*)ws + 2 * plane);
@@ -404,8 +401,8 @@ size_t cspn2d_backward_multi_workspace_bytes(int B, int C, int H, int W, int n_i
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
     if (C == 1) return cspn2d_backward_workspace_bytes(B, H, W, n_iter);
     if (backward2d_multi_supported(B * C, H, W, n_iter)) return widened_bytes(B, C, H, W) + backward2d_workspace(B * C, H, W, n_iter);
-    const size_t plane = al256(sizeof(float) * (size_t)B * H * W);
-    return 4 * plane + 8 * plane + al256(backward2d_workspace(B, H, W, n_iter));   // blur, mask, grad_out, grad_blur of one channel; its grad_guidance
+    const size_t plane = round256(sizeof(float) * (size_t)B * H * W);
+    return 4 * plane + 8 * plane + round256(backward2d_workspace(B, H, W, n_iter));   // blur, mask, grad_out, grad_blur of one channel; its grad_guidance
 }
 
 int cspn2d_backward_multi_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out, float* grad_guidance,
@@ -426,7 +423,7 @@ int cspn2d_backward_multi_f32(const float* guidance, const float* blur, const fl
         return backward2d(guidance, blur, sparse, grad_out, grad_guidance, grad_blur, B * C, H, W, n_iter, norm_type,
                           (char*)ws + widened_bytes(B, C, H, W), st, C);
     }
-    const size_t plane = al256(sizeof(float) * (size_t)B * HW);
+    const size_t plane = round256(sizeof(float) * (size_t)B * HW);
     float* blur_c = (float*)ws;
     float* sp_c = (float*)((char*)ws + plane);
     float* go_c = (float*)((char*)ws + 2 * plane);
@@ -696,9 +693,7 @@ static int kxk_forward_entry(const char* what, const void* gate, bool g16, int d
         if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    if (absnorm) return kxk_absnorm_forward(gate, dtype, x, out, history, B, C, H, W, K, n_iter, ws, st);
-    return g16 ? kxk_forward_g16(gate, dtype, x, out, history, B, C, H, W, K, n_iter, ws, st)
-                 : kxk_forward((const float*)gate, x, out, history, B, C, H, W, K, n_iter, ws, st);
+    return kxk_forward(gate, dtype, absnorm, x, out, history, B, C, H, W, K, n_iter, ws, st);
 }
 
 static int kxk_backward_entry(const char* what, const void* gate, bool g16, int dtype, bool absnorm, const float* x, const float* history, size_t history_bytes,
@@ -733,9 +728,7 @@ static int kxk_backward_entry(const char* what, const void* gate, bool g16, int 
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    if (absnorm) return kxk_absnorm_backward(gate, dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
-    return g16 ? kxk_backward_g16(gate, dtype, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st)
-                 : kxk_backward((const float*)gate, x, history, grad_out, (float*)grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
+    return kxk_backward(gate, dtype, absnorm, x, history, grad_out, grad_gate, grad_x, B, C, H, W, K, n_iter, ws, st);
 }
 
 int cspn2d_forward_kxk_f32(const float* gate, const float* x, float* out, float* history, size_t history_bytes, int B, int C, int H, int W,
@@ -798,12 +791,15 @@ size_t cspn2d_kxk_norm_history_bytes(int B, int C, int H, int W, int K, int n_it
     return kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1);
 }
 
-int cspn2d_forward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, float* out, float* history, size_t history_bytes, int B,
-                                int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_forward_kxk_norm_f32";
+// the checks of the four cspn2d_{forward,backward}_kxk_norm_{f32,g16} entry points, then the engine; g16 and dtype as kxk_forward_entry
+static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, float* out,
+                                  float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                                  size_t ws_bytes, cspn_stream_t stream) {
     if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (g16)
+        if (int e = g16_check(what, dtype, guidance, nullptr)) return e;
     if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1), sb = vb / C * sparse_C;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C;
     const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
     if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
     const size_t need = n_iter == 0 ? 0
@@ -823,7 +819,13 @@ int cspn2d_forward_kxk_norm_f32(const float* guidance, const float* blur, const 
         if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return kxk_norm_forward(guidance, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+    return kxk_norm_forward(guidance, dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+}
+
+int cspn2d_forward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, float* out, float* history, size_t history_bytes, int B,
+                                int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_norm_forward_entry("cspn2d_forward_kxk_norm_f32", guidance, false, 0, blur, sparse, out, history, history_bytes, B, C, sparse_C, H, W, K,
+                                  n_iter, norm, ws, ws_bytes, stream);
 }
 
 size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
@@ -831,13 +833,14 @@ size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int 
     return sizeof(float) * 2 * kxk_norm_fold_floats(B, C, sparse_C, H, W, K) + round256(kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1));
 }
 
-int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, const float* history, size_t history_bytes,
-                                 const float* grad_out, float* grad_guidance, float* grad_blur, int B, int C, int sparse_C, int H, int W, int K,
-                                 int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_backward_kxk_norm_f32";
+static int kxk_norm_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse,
+                                   const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C,
+                                   int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (g16)
+        if (int e = g16_check(what, dtype, guidance, grad_guidance)) return e;
     if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1), sb = vb / C * sparse_C;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C;
     const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
     if (grad_guidance && hb && (!history || history_bytes < hb)) {
         set_error("%s: the guidance gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
@@ -861,7 +864,14 @@ int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return kxk_norm_backward(guidance, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+    return kxk_norm_backward(guidance, dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+}
+
+int cspn2d_backward_kxk_norm_f32(const float* guidance, const float* blur, const float* sparse, const float* history, size_t history_bytes,
+                                 const float* grad_out, float* grad_guidance, float* grad_blur, int B, int C, int sparse_C, int H, int W, int K,
+                                 int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_norm_backward_entry("cspn2d_backward_kxk_norm_f32", guidance, false, 0, blur, sparse, history, history_bytes, grad_out, grad_guidance, grad_blur,
+                                   B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
 }
 
 // ---- the four K x K entry points on 16-bit gates / guidance (cspn2d_*_kxk*_g16): the checks of the _f32 twins, the gate tensor and its
@@ -882,66 +892,15 @@ int cspn2d_backward_kxk_g16(const void* gate, int gate_dtype, const float* x, co
 int cspn2d_forward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,
                                 size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
                                 size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_forward_kxk_norm_g16";
-    if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = g16_check(what, gate_dtype, guidance, nullptr)) return e;
-    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2, sb = vb / C * sparse_C;
-    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
-    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
-    const size_t need = n_iter == 0 ? 0
-                        : (history ? sizeof(float) * kxk_norm_fold_floats(B, C, sparse_C, H, W, K)
-                                   : cspn2d_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter));
-    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0;
-    if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hb}, {ws, wb}}) ||
-        kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}})) {
-        set_error("%s: out, history and the workspace must not alias an input or each other", what);
-        return CSPN_E_BADARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (n_iter == 0) {
-        hipError_t e = hipMemcpyAsync(out, blur, vb, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return kxk_norm_forward_g16(guidance, gate_dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
+    return kxk_norm_forward_entry("cspn2d_forward_kxk_norm_g16", guidance, true, gate_dtype, blur, sparse, out, history, history_bytes, B, C, sparse_C, H, W,
+                                  K, n_iter, norm, ws, ws_bytes, stream);
 }
 
 int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
                                  size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
                                  int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    static const char* what = "cspn2d_backward_kxk_norm_g16";
-    if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = g16_check(what, gate_dtype, guidance, grad_guidance)) return e;
-    if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / 2, sb = vb / C * sparse_C;
-    const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
-    if (grad_guidance && hb && (!history || history_bytes < hb)) {
-        set_error("%s: the guidance gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
-        return CSPN_E_BADARG;
-    }
-    const size_t need = cspn2d_backward_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
-    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0, hbu = grad_guidance ? hb : 0;
-    if (grad_guidance && (const void*)grad_guidance == (const void*)grad_blur) { set_error("%s: grad_guidance and grad_blur must not alias", what); return CSPN_E_BADARG; }
-    if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_blur, vb}, {ws, wb}}) ||
-        kxk_overlaps(grad_blur, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}})) {
-        set_error("%s: grad_guidance, grad_blur and the workspace must not alias an input or each other", what);
-        return CSPN_E_BADARG;
-    }
-    if (!grad_guidance && !grad_blur) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_iter == 0) {   // the identity: dL/dblur = dL/dout, no gate is read
-        hipError_t e = grad_blur ? hipMemcpyAsync(grad_blur, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
-        if (e == hipSuccess && grad_guidance) e = hipMemsetAsync(grad_guidance, 0, gb, st);
-        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return kxk_norm_backward_g16(guidance, gate_dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm,
-                                 ws, st);
+    return kxk_norm_backward_entry("cspn2d_backward_kxk_norm_g16", guidance, true, gate_dtype, blur, sparse, history, history_bytes, grad_out, grad_guidance,
+                                   grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
 }
 
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----

@@ -83,45 +83,34 @@ int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t s
 int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st);
 
 // ---- the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (cspn2d_kxk.hip): gate [N][K*K-1][H][W], values [N][C][H][W] ----
+// gate and gg in the type of dtype: 0 (float32), CSPN_DTYPE_F16 or CSPN_DTYPE_BF16.  A 16-bit gate is widened exactly where it is used
+// (bitwise the float32 results on the widened gates); a 16-bit gg is the float32 sum rounded once at its store
+// absnorm: the demo module's contract (cspn_paddle/demo.py:20-54) inside the same engine: gate is the raw guide, a_k = |g_k|,
+// S = sum_k a_k per pixel, H_{t+1} = (sum_k a_k H_t(p + off_k)) / S; gg = dL/dguide
+// a workspace part's bytes, rounded so that the part behind it stays 256-byte aligned
+inline size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 // a level of the forward's ping-pong workspace, rounded to 64 floats so that both levels stay 256-byte aligned
 inline size_t kxk_level_floats(size_t L) { return (L + 63) & ~(size_t)63; }
 // hist: NULL (the levels ping-pong in ws: 2 levels of kxk_level_floats) or H_1 .. H_{n-1}, level t at hist + (t - 1) N C H W
-int kxk_forward(const float* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                hipStream_t st);
-// ws: A_1 .. A_{n-1} ((n - 1) N C H W floats); gg (summed over C) and gx may each be NULL; hist as the forward kept it
-int kxk_backward(const float* gate, const float* x, const float* hist, const float* gout, float* gg, float* gx, int N, int C, int H, int W, int K,
-                 int n_iter, void* ws, hipStream_t st);
-// the same on 16-bit gates: dtype CSPN_DTYPE_F16 / CSPN_DTYPE_BF16, widened exactly where used (bitwise the float32 results on the widened
-// gates); gg in the gates' type, the float32 sum rounded once at its store
-int kxk_forward_g16(const void* gate, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                    hipStream_t st);
-int kxk_backward_g16(const void* gate, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
-                     int W, int K, int n_iter, void* ws, hipStream_t st);
-// the demo module's contract (cspn_paddle/demo.py:20-54) inside the same engine: guide raw, a_k = |g_k|, S = sum_k a_k per pixel,
-// H_{t+1} = (sum_k a_k H_t(p + off_k)) / S; dtype 0 (float32), CSPN_DTYPE_F16 or CSPN_DTYPE_BF16; gg = dL/dguide in the guide's type.
-// The forward's ws and hist as kxk_forward.  The backward's ws: A_1 .. A_{n-1} (kxk_absnorm_alev_bytes), then with n_iter >= 2 the
-// float32 plane [N][H][W] of 1 / S
-inline size_t kxk_absnorm_alev_bytes(size_t L, int n_iter) { return (sizeof(float) * L * (size_t)(n_iter - 1) + 255) & ~(size_t)255; }
-int kxk_absnorm_forward(const void* guide, int dtype, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter, void* ws,
-                        hipStream_t st);
-int kxk_absnorm_backward(const void* guide, int dtype, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C, int H,
-                         int W, int K, int n_iter, void* ws, hipStream_t st);
+int kxk_forward(const void* gate, int dtype, bool absnorm, const float* x, float* out, float* hist, int N, int C, int H, int W, int K, int n_iter,
+                void* ws, hipStream_t st);
+// ws: A_1 .. A_{n-1} ((n - 1) N C H W floats: kxk_absnorm_alev_bytes), then with absnorm and n_iter >= 2 the float32 plane [N][H][W] of 1 / S;
+// gg (summed over C) and gx may each be NULL; hist as the forward kept it
+inline size_t kxk_absnorm_alev_bytes(size_t L, int n_iter) { return round256(sizeof(float) * L * (size_t)(n_iter - 1)); }
+int kxk_backward(const void* gate, int dtype, bool absnorm, const float* x, const float* hist, const float* gout, void* gg, float* gx, int N, int C,
+                 int H, int W, int K, int n_iter, void* ws, hipStream_t st);
 
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip): guidance [B][K*K-1][H][W] raw, blur
-// [B][C][H][W], sparse NULL (sparse_C 0) or [B][sparse_C][H][W] with sparse_C 1 or C; normalised, neighbour-sited, pinned, folded into w' and b ----
+// [B][C][H][W], sparse NULL (sparse_C 0) or [B][sparse_C][H][W] with sparse_C 1 or C; normalised, neighbour-sited, pinned, folded into w' and b.
+// guid and gg in the type of dtype as above; w' and b stay float32 in the workspace, so the workspace sizes do not depend on it ----
 // the folded w' and b in front of each workspace (floats)
 size_t kxk_norm_fold_floats(int B, int C, int sparse_C, int H, int W, int K);
 // ws: the fold, then (hist NULL) the two ping-pong levels of kxk_forward; hist as kxk_forward
-int kxk_norm_forward(const float* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
-                     int K, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_norm_forward(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H,
+                     int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
 // ws: the fold, dL/dw', dL/db (one fold's size), then A_1 .. A_{n-1}; gg needs hist (n >= 2), gx and gg may each be NULL
-int kxk_norm_backward(const float* guid, const float* blur, const float* sparse, const float* hist, const float* gout, float* gg, float* gx, int B,
-                      int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
-// the same on 16-bit guidance (w' and b stay float32 in the workspace: the workspace sizes are those above)
-int kxk_norm_forward_g16(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C,
-                         int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
-int kxk_norm_backward_g16(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg,
-                          float* gx, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_norm_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg, float* gx,
+                      int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

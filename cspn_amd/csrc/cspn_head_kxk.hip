@@ -22,13 +22,12 @@
 //     waves add their blocks in wave order through LDS, hk_bwd_w_reduce_kernel adds the workgroups' blocks in workgroup order: no atomics, deterministic.
 #include <cstdint>
 
-#include "cspn_common.h"
+#include "cspn_head_kxk_common.h"
 
 namespace cspn {
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 constexpr int REC = 12;            // floats per (plane, channel) weight record: the 9 taps [ky][kx] + 3 of padding (three 16-byte loads)
 
@@ -49,13 +48,6 @@ __global__ __launch_bounds__(256) void hk_pack_kernel(const float* __restrict__ 
 }
 
 __device__ __forceinline__ f16v mfma(float a, float b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-// a wave's unit of work: workgroup ids go round the 8 XCDs, each XCD takes a contiguous eighth of the units (neighbouring rows share a row of their input in one L2)
-__device__ __forceinline__ int wave_unit() {
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int per_xcd = gridDim.x >> 3;
-    return (((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3)) * 4 + wv;
-}
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------
 // One wave = PT input rows (i0 .. i0 + PT - 1) x 32 columns x all O planes (OB blocks of 32).  wp: hk_pack_kernel c_major, [C rounded up to even][OB * 32][12].
@@ -261,9 +253,7 @@ __global__ __launch_bounds__(256, 2) void hk_bwd_x_kernel(const float* __restric
 // take pixels jb .. jb + 3, lanes 32-63 the next four, four matrix steps per (row block, channel block); a lane reads its row's four window values (8 consecutive
 // floats, every other one a pixel's) and its channel's four pixels, the next tile's reads are issued before the current tile's matrix instructions.  blockIdx.y
 // = the group of DW_TB row blocks; a wave takes a contiguous share of the tiles.
-constexpr int DW_TB = 4, DW_PX = 4, DW_TILE = 2 * DW_PX;
-template <int NB>
-struct DwSize { static constexpr int floats = DW_TB * NB * 16 * 64; };
+constexpr int DW_PX = 4, DW_TILE = 2 * DW_PX;
 
 template <int NB>
 __global__ __launch_bounds__(256, 2) void hk_bwd_w_kernel(const float* __restrict__ x, const float* __restrict__ gg, const float* __restrict__ gb,
@@ -410,19 +400,13 @@ __global__ __launch_bounds__(256) void hk_bwd_w_reduce_kernel(const float* __res
     else if (dwb) dwb[(size_t)ch * 9 + tap] = v;
 }
 
-constexpr int DW_MAX_WG = 256;        // workgroups per group of row blocks (one per CU)
-
-size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-int row_groups(int O) { return ((9 * O + 31) / 32 + DW_TB - 1) / DW_TB; }
 size_t bwd_x_pack_bytes(int C, int O) { return round256((size_t)((O + 1) & ~1) * ((C + 31) & ~31) * REC * sizeof(float)); }
 
-// waves -> workgroups, a multiple of 8 (wave_unit's XCD mapping; the spare waves return at once); 0: does not fit an int
-unsigned groups_of(long long units) {
-    const long long groups = ((units + 3) / 4 + 7) / 8 * 8;
-    return groups * 4 >= (1ll << 31) ? 0u : (unsigned)groups;      // (the kernels number the waves with an int)
-}
-
 }  // namespace
+
+void head_kxk_dw_reduce(const float* part, float* dwg, float* dwb, int C, int c0, int NB, int O, int nwg, hipStream_t st) {
+    hipLaunchKernelGGL(hk_bwd_w_reduce_kernel, dim3((9 * O * NB * 32 + 255) / 256), dim3(256), 0, st, part, dwg, dwb, C, c0, NB, O, nwg);
+}
 
 // the forward's weight records ([C rounded up to even][32 or 64][12] floats)
 size_t head_kxk_workspace(int C, int K) {
@@ -471,19 +455,13 @@ int head_kxk_backward(const float* x, const float* wg, const float* wb, const fl
         float* zero = (float*)((char*)ws + bwd_x_pack_bytes(C, O));        // what a tile reads for positions outside the tensors
         float* part = zero + 64;
         hipLaunchKernelGGL(hk_zero_line_kernel, dim3(1), dim3(64), 0, st, zero);
-        const int hfed = (H + 1) / 2 < h ? (H + 1) / 2 : h;     // input rows whose unpooled row lies inside the (narrowed) output
-        const int wfed = (W + 1) / 2 < w ? (W + 1) / 2 : w;
-        const int tiles_w = (wfed + DW_TILE - 1) / DW_TILE;
-        const long long tiles_ll = (long long)B * hfed * tiles_w;
-        if (tiles_ll >= (1ll << 31)) { set_error("%s: too many pixels", what); return CSPN_E_UNSUPPORTED; }
-        const int tiles = (int)tiles_ll;
-        const int nwave = tiles < 4 * DW_MAX_WG ? tiles : 4 * DW_MAX_WG;
-        const int nwg = (nwave + 3) / 4, ng = row_groups(O);
+        const DwGeo G(B, h, w, H, W, O, DW_TILE);
+        if (!G.fits) { set_error("%s: too many pixels", what); return CSPN_E_UNSUPPORTED; }
         for (int c0 = 0; c0 < C; c0 += 64) {                     // 64 channels at a time (two column blocks of the matrix core)
             const int NB = C - c0 > 32 ? 2 : 1;
-            if (NB == 2) hipLaunchKernelGGL(hk_bwd_w_kernel<2>, dim3(nwg, ng), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, O, tiles, tiles_w, hfed, nwave);
-            else hipLaunchKernelGGL(hk_bwd_w_kernel<1>, dim3(nwg, ng), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, O, tiles, tiles_w, hfed, nwave);
-            hipLaunchKernelGGL(hk_bwd_w_reduce_kernel, dim3((9 * O * NB * 32 + 255) / 256), dim3(256), 0, st, part, dwg, dwb, C, c0, NB, O, nwg);
+            if (NB == 2) hipLaunchKernelGGL(hk_bwd_w_kernel<2>, dim3(G.nwg, G.ng), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, O, G.tiles, G.tiles_w, G.hfed, G.nwave);
+            else hipLaunchKernelGGL(hk_bwd_w_kernel<1>, dim3(G.nwg, G.ng), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, O, G.tiles, G.tiles_w, G.hfed, G.nwave);
+            head_kxk_dw_reduce(part, dwg, dwb, C, c0, NB, O, G.nwg, st);
         }
         if (int e = check_launch("hk_bwd_w_kernel")) return e;
     }

@@ -12,12 +12,11 @@
 // Addresses are clamped and values selected: nothing is read outside a tensor, whatever lies outside feeds a zero.
 #include <cstdint>
 
-#include "cspn_common.h"
+#include "cspn_head_kxk_common.h"
 
 namespace cspn {
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
@@ -71,13 +70,6 @@ template <bool BF>
 __global__ __launch_bounds__(256) void hk16_round_kernel(const float* __restrict__ in, us* __restrict__ out, size_t n) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx < n) out[idx] = narrow<BF>(in[idx]);
-}
-
-// a wave's unit of work: workgroup ids go round the 8 XCDs, each XCD takes a contiguous eighth of the units
-__device__ __forceinline__ int wave_unit() {
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int per_xcd = gridDim.x >> 3;
-    return (((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3)) * 4 + wv;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------
@@ -294,9 +286,7 @@ __global__ __launch_bounds__(256, 2) void hk16_bwd_x_kernel(const us* __restrict
 // D[row T = o * 9 + r * 3 + k][channel] += sum over pixels g[o][2i - 1 + r][2j - 1 + k] x[channel][i][j].  A tile = 16 consecutive pixels of an input row: lanes
 // 0-31 take pixels jb .. jb + 7, lanes 32-63 the next eight: one matrix step per (row block, channel block).  blockIdx.y = the group of DW_TB row blocks; a wave
 // takes a contiguous share of the tiles.
-constexpr int DW_TB = 4, DW_TILE = 16;
-template <int NB>
-struct DwSize { static constexpr int floats = DW_TB * NB * 16 * 64; };
+constexpr int DW_TILE = 16;
 
 template <bool BF, int NB>
 __global__ __launch_bounds__(256, 2) void hk16_bwd_w_kernel(const us* __restrict__ x, const us* __restrict__ gg, const us* __restrict__ gb, float* __restrict__ part,
@@ -426,41 +416,8 @@ __global__ __launch_bounds__(256, 2) void hk16_bwd_w_kernel(const us* __restrict
     for (int e = threadIdx.x; e < DwSize<NB>::floats; e += 256) dst[e] = red[e];
 }
 
-// dW[o][c][ky][kx] = sum over the workgroups' blocks, in workgroup order (deterministic); float32, the accumulators
-__global__ __launch_bounds__(256) void hk16_bwd_w_reduce_kernel(const float* __restrict__ part, float* __restrict__ dwg, float* __restrict__ dwb, int C, int c0,
-                                                                 int NB, int O, int nwg) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int nch = NB * 32;
-    if (idx >= 9 * O * nch) return;
-    const int t = idx / nch, cl = idx - t * nch, ch = c0 + cl;
-    if (ch >= C) return;
-    const int tbg = t >> 5, tg = tbg / DW_TB, tb = tbg - tg * DW_TB, i = t & 31, nb = cl >> 5, jc = cl & 31;
-    const int q = (i >> 3) * 4 + (i & 3), l = ((i & 7) >> 2) * 32 + jc;
-    const size_t stride = (size_t)DW_TB * NB * 16 * 64;
-    const float* p = part + (size_t)tg * nwg * stride + ((size_t)(tb * NB + nb) * 16 + q) * 64 + l;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int g = 0;
-    for (; g + 3 < nwg; g += 4) { s0 += p[(size_t)g * stride]; s1 += p[(size_t)(g + 1) * stride]; s2 += p[(size_t)(g + 2) * stride]; s3 += p[(size_t)(g + 3) * stride]; }
-    for (; g < nwg; ++g) s0 += p[(size_t)g * stride];
-    const float v = (s0 + s1) + (s2 + s3);
-    const int o = t / 9, r = (t - o * 9) / 3, k = t - o * 9 - r * 3;
-    const int tap = (2 - r) * 3 + (2 - k);
-    if (o < O - 1) { if (dwg) dwg[((size_t)o * C + ch) * 9 + tap] = v; }
-    else if (dwb) dwb[(size_t)ch * 9 + tap] = v;
-}
-
-constexpr int DW_MAX_WG = 256;        // workgroups per group of row blocks (one per CU)
-
-size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-int row_groups(int O) { return ((9 * O + 31) / 32 + DW_TB - 1) / DW_TB; }
 size_t bwd_x_pack_bytes(int C, int O) { return round256((size_t)((O + 15) >> 4) * 2 * 9 * ((C + 31) & ~31) * 16); }
 size_t blur16_bytes(int B, int h, int w) { return round256((size_t)B * (2 * h) * (2 * w) * 2); }
-
-// waves -> workgroups, a multiple of 8 (wave_unit's XCD mapping; the spare waves return at once); 0: does not fit an int
-unsigned groups_of(long long units) {
-    const long long groups = ((units + 3) / 4 + 7) / 8 * 8;
-    return groups * 4 >= (1ll << 31) ? 0u : (unsigned)groups;
-}
 
 template <bool BF>
 int forward_g16(const us* x, const float* wg, const float* wb, us* gout, float* bout, int B, int C, int h, int w, int H, int W, int K, void* ws, hipStream_t st) {
@@ -502,19 +459,13 @@ int backward_g16(const us* x, const float* wg, const float* wb, const us* gg, co
     }
     if (dwg || dwb) {
         float* part = (float*)((char*)ws + bwd_x_pack_bytes(C, O) + blur16_bytes(B, h, w));
-        const int hfed = (H + 1) / 2 < h ? (H + 1) / 2 : h;     // input rows whose unpooled row lies inside the (narrowed) output
-        const int wfed = (W + 1) / 2 < w ? (W + 1) / 2 : w;
-        const int tiles_w = (wfed + DW_TILE - 1) / DW_TILE;
-        const long long tiles_ll = (long long)B * hfed * tiles_w;
-        if (tiles_ll >= (1ll << 31)) { set_error("%s: too many pixels", what); return CSPN_E_UNSUPPORTED; }
-        const int tiles = (int)tiles_ll;
-        const int nwave = tiles < 4 * DW_MAX_WG ? tiles : 4 * DW_MAX_WG;
-        const int nwg = (nwave + 3) / 4, ng = row_groups(O);
+        const DwGeo G(B, h, w, H, W, O, DW_TILE);
+        if (!G.fits) { set_error("%s: too many pixels", what); return CSPN_E_UNSUPPORTED; }
         for (int c0 = 0; c0 < C; c0 += 64) {                     // 64 channels at a time (two column blocks of the matrix core)
             const int NB = C - c0 > 32 ? 2 : 1;
-            if (NB == 2) hipLaunchKernelGGL((hk16_bwd_w_kernel<BF, 2>), dim3(nwg, ng), dim3(256), 0, st, x, gg, gb16, part, C, c0, h, w, H, W, O, tiles, tiles_w, hfed, nwave);
-            else hipLaunchKernelGGL((hk16_bwd_w_kernel<BF, 1>), dim3(nwg, ng), dim3(256), 0, st, x, gg, gb16, part, C, c0, h, w, H, W, O, tiles, tiles_w, hfed, nwave);
-            hipLaunchKernelGGL(hk16_bwd_w_reduce_kernel, dim3((9 * O * NB * 32 + 255) / 256), dim3(256), 0, st, part, dwg, dwb, C, c0, NB, O, nwg);
+            if (NB == 2) hipLaunchKernelGGL((hk16_bwd_w_kernel<BF, 2>), dim3(G.nwg, G.ng), dim3(256), 0, st, x, gg, gb16, part, C, c0, h, w, H, W, O, G.tiles, G.tiles_w, G.hfed, G.nwave);
+            else hipLaunchKernelGGL((hk16_bwd_w_kernel<BF, 1>), dim3(G.nwg, G.ng), dim3(256), 0, st, x, gg, gb16, part, C, c0, h, w, H, W, O, G.tiles, G.tiles_w, G.hfed, G.nwave);
+            head_kxk_dw_reduce(part, dwg, dwb, C, c0, NB, O, G.nwg, st);
         }
         if (int e = check_launch("hk16_bwd_w_kernel")) return e;
     }

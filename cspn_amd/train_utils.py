@@ -158,37 +158,44 @@ def _head_planes(x, weight_guidance, *others):
 
 
 def _heads_kxk_forward(xx, wg, wb, H, W):
-    """cspn_guidance_head_kxk_f32: the 24- / 48-plane guidance head and the blur head, raw, on the matrix cores"""
+    """cspn_guidance_head_kxk_f32: the 24- / 48-plane guidance head and the blur head, raw, on the matrix cores.  xx float16 / bfloat16:
+    cspn_guidance_head_kxk_g16, float32 weights (rounded once to xx's dtype in the engine) -> guidance in xx's dtype, blur float32"""
     B, C, h, w = xx.shape
     P = int(wg.shape[0])
     K = _PLANES_TO_K[P]
-    g = torch.empty(B, P, H, W, dtype=torch.float32, device=xx.device)
+    dt = _GATE16.get(xx.dtype)
+    g = torch.empty(B, P, H, W, dtype=xx.dtype, device=xx.device)
     b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
+    name = "cspn_guidance_head_kxk_f32" if dt is None else "cspn_guidance_head_kxk_g16"
     with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk_workspace_bytes")(B, C, h, w, K)
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk%s_workspace_bytes" % ("" if dt is None else "_g16"))(B, C, h, w, K)
         ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol("cspn_guidance_head_kxk_f32")(xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
-                                                            b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
-                                                            torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_kxk_f32")
+        rc = _lib.late_symbol(name)(xx.data_ptr(), *(() if dt is None else (dt,)), wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
+                                    b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
+                                    torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, name)
     return g, b
 
 
 def _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w):
+    """cspn_guidance_head_kxk_backward_f32.  xx float16 / bfloat16: cspn_guidance_head_kxk_backward_g16, dL/dguidance in xx's dtype, dL/dblur float32
+    (rounded once to xx's dtype as it enters the GEMMs) -> dL/dx in xx's dtype, the weight gradients float32"""
     B, C, h, w = xx.shape
     K = _PLANES_TO_K[int(wg.shape[0])]
     H, W = int(gg.shape[2]), int(gg.shape[3])
+    dt = _GATE16.get(xx.dtype)
     dx = torch.empty_like(xx) if need_x else None
     dwg = torch.empty_like(wg) if need_w else None
     dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
+    name = "cspn_guidance_head_kxk_backward_%s" % ("f32" if dt is None else "g16")
     with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward_workspace_bytes")(B, C, h, w, K)
+        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward%s_workspace_bytes" % ("" if dt is None else "_g16"))(B, C, h, w, K)
         ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol("cspn_guidance_head_kxk_backward_f32")(
-            xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(), gb.data_ptr() if gb is not None else None,
-            dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None, dwb.data_ptr() if dwb is not None else None,
-            B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_kxk_backward_f32")
+        rc = _lib.late_symbol(name)(
+            xx.data_ptr(), *(() if dt is None else (dt,)), wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
+            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
+            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, name)
     return dx, dwg, dwb
 
 
@@ -226,43 +233,6 @@ def _prep_w16(t, name, dt, shape):
     return _prep(t, name, shape)
 
 
-def _heads_kxk_forward16(xx, wg, wb, H, W):
-    """cspn_guidance_head_kxk_g16: x fp16 / bf16, float32 weights (rounded once to x's dtype in the engine) -> guidance in x's dtype, blur float32"""
-    B, C, h, w = xx.shape
-    P = int(wg.shape[0])
-    K = _PLANES_TO_K[P]
-    g = torch.empty(B, P, H, W, dtype=xx.dtype, device=xx.device)
-    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
-    with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk_g16_workspace_bytes")(B, C, h, w, K)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol("cspn_guidance_head_kxk_g16")(xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None,
-                                                            g.data_ptr(), b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
-                                                            torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_kxk_g16")
-    return g, b
-
-
-def _heads_kxk_backward16(xx, wg, wb, gg, gb, need_x, need_w):
-    """cspn_guidance_head_kxk_backward_g16: dL/dguidance in x's dtype, dL/dblur float32 (rounded once to x's dtype as it enters the GEMMs) -> dL/dx in x's
-    dtype, the weight gradients float32"""
-    B, C, h, w = xx.shape
-    K = _PLANES_TO_K[int(wg.shape[0])]
-    H, W = int(gg.shape[2]), int(gg.shape[3])
-    dx = torch.empty_like(xx) if need_x else None
-    dwg = torch.empty_like(wg) if need_w else None
-    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
-    with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward_g16_workspace_bytes")(B, C, h, w, K)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol("cspn_guidance_head_kxk_backward_g16")(
-            xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
-            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
-            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_kxk_backward_g16")
-    return dx, dwg, dwb
-
-
 def _heads_forward(xx, wg, wb, H, W, norm):
     lib = _lib.load()
     B, C, h, w = xx.shape
@@ -298,7 +268,7 @@ def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad
         H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
         gg = _prep16(grad_guidance, "grad_guidance", dt, (B, P, H, W))
         gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
-        dx, dwg, dwb = _heads_kxk_backward16(xx, wg, wb, gg, gb, need_x, need_w)
+        dx, dwg, dwb = _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w)
         if dwg is not None and weight_guidance.dtype == dt:
             dwg = dwg.to(dt)
         if dwb is not None and weight_blur.dtype == dt:
@@ -375,7 +345,7 @@ class _GuidanceHeadsKxK16Function(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wg, wb, H, W):
         ctx.save_for_backward(x, wg, wb)
-        return _heads_kxk_forward16(x, wg.float(), wb.float() if wb is not None else None, H, W)
+        return _heads_kxk_forward(x, wg.float(), wb.float() if wb is not None else None, H, W)
 
     @staticmethod
     def backward(ctx, grad_g, grad_b):
@@ -385,7 +355,7 @@ class _GuidanceHeadsKxK16Function(torch.autograd.Function):
         if wb is not None and grad_b is None:
             grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], dtype=torch.float32, device=x.device)
         need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
-        dx, dwg, dwb = _heads_kxk_backward16(x, wg.float(), wb.float() if wb is not None else None, grad_g.contiguous(),
+        dx, dwg, dwb = _heads_kxk_backward(x, wg.float(), wb.float() if wb is not None else None, grad_g.contiguous(),
                                              grad_b.float().contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
         return (dx, dwg.to(wg.dtype) if ctx.needs_input_grad[1] else None,
                 dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
@@ -429,7 +399,7 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
             wb = weight_blur.contiguous() if weight_blur is not None else None
             if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
                 return _GuidanceHeadsKxK16Function.apply(xx, wg, wb, H, W)
-            return _heads_kxk_forward16(xx, wg.float(), wb.float() if wb is not None else None, H, W)
+            return _heads_kxk_forward(xx, wg.float(), wb.float() if wb is not None else None, H, W)
         xx = _prep(x, "x")
         B, C, h, w = xx.shape
         wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
