@@ -37,6 +37,104 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+c_int, c_size_t, vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
+_WS = [vp, c_size_t, vp]   # workspace, its bytes, stream: the tail of the entry points that take a workspace
+
+# every entry point the binding calls: name -> (restype, argtypes).  First ABI 5 as it was released: load() binds these, so a library
+# without one of them fails to load
+_SYMBOLS = {
+    "cspn2d_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn2d_auto_algo": (c_int, [c_int] * 4),
+    "cspn2d_forward_f32": (c_int, [vp] * 4 + [c_int] * 5 + _WS),
+    "cspn2d_forward_f32_algo": (c_int, [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_normalize_f32": (c_int, [vp] * 2 + [c_int] * 4 + [vp]),
+    "cspn2d_forward_prenorm_f32": (c_int, [vp] * 4 + [c_int] * 4 + _WS),
+    "cspn2d_backward_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn2d_backward_f32": (c_int, [vp] * 6 + [c_int] * 5 + _WS),
+    "cspn2d_history_bytes": (c_size_t, [c_int] * 4),
+    "cspn2d_forward_history_f32": (c_int, [vp] * 5 + [c_size_t] + [c_int] * 5 + _WS),
+    "cspn2d_backward_history_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn2d_backward_history_f32": (c_int, [vp] * 5 + [c_size_t, vp, vp] + [c_int] * 5 + _WS),
+    "cspn_metrics_workspace_bytes": (c_size_t, [c_size_t]),
+    "cspn_metrics_f32": (c_int, [vp, vp, c_size_t, vp, vp, c_size_t, vp]),
+    "cspn_l1_backward_f32": (c_int, [vp, vp, vp, vp, vp, c_size_t, vp]),
+    "cspn3d_backward_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn3d_backward_f32": (c_int, [vp] * 5 + [c_int] * 6 + _WS),
+    "cspn_unpool_f32": (c_int, [vp, vp, c_size_t, c_int, c_int, c_int, vp]),
+    "cspn_guidance_head_workspace_bytes": (c_size_t, [c_int]),
+    "cspn_guidance_head_f32": (c_int, [vp] * 5 + [c_int] * 7 + _WS),
+    "cspn_guidance_head_backward_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn_guidance_head_backward_f32": (c_int, [vp] * 8 + [c_int] * 6 + _WS),
+    "cspn_unpool_backward_f32": (c_int, [vp, vp, c_size_t, c_int, c_int, c_int, vp]),
+    "cspn_sparse_sample_workspace_bytes": (c_size_t, [c_size_t]),
+    "cspn_sparse_sample_f32": (c_int, [vp, vp, c_size_t, c_size_t, c_int, c_int, ctypes.c_ulonglong, vp, c_size_t, vp]),
+    "cspn3d_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn3d_forward_f32": (c_int, [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn3d_workspace_bytes_ex": (c_size_t, [c_int] * 7),
+    "cspn3d_forward_f32_algo": (c_int, [vp] * 4 + [c_int] * 7 + _WS),
+    "cspn3d_multi_supported": (c_int, [c_int] * 6),
+    "cspn3d_forward_multi_f32": (c_int, [vp] * 3 + [c_int] * 6 + _WS),
+    "cspn3d_backward_multi_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cspn3d_backward_multi_f32": (c_int, [vp] * 5 + [c_int] * 6 + _WS),
+    "cspn3d_check_status": (c_int, [vp]),
+}
+_BOUND_AT_LOAD = tuple(_SYMBOLS)
+# exports added to ABI 5 after its release (purely additive, the version stayed): looked up on first use, so that a library built before
+# them still loads and serves everything else, and a call of a missing one says to rebuild instead of raising AttributeError
+_SYMBOLS.update({
+    "cspn2d_normalize_backward_f32": (c_int, [vp] * 3 + [c_int] * 4 + [vp]),
+    # C channels on shared 2D guidance
+    "cspn2d_workspace_bytes_multi": (c_size_t, [c_int] * 5),
+    "cspn2d_multi_supported": (c_int, [c_int] * 5),
+    "cspn2d_forward_multi_f32": (c_int, [vp] * 4 + [c_int] * 8 + _WS),
+    "cspn2d_history_bytes_multi": (c_size_t, [c_int] * 5),
+    "cspn2d_forward_history_multi_f32": (c_int, [vp] * 5 + [c_size_t] + [c_int] * 7 + _WS),
+    "cspn2d_backward_multi_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn2d_backward_multi_f32": (c_int, [vp] * 6 + [c_int] * 7 + _WS),
+    "cspn2d_backward_history_multi_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn2d_backward_history_multi_f32": (c_int, [vp] * 5 + [c_size_t, vp, vp] + [c_int] * 7 + _WS),
+    # the demo's gate normalisation (reference cspn_paddle/demo.py:24,34-36,47-49) and the 3D module on raw gates
+    "cspn_gate_absnorm_f32": (c_int, [vp] * 2 + [c_int] * 2 + [c_size_t, vp]),
+    "cspn_gate_absnorm_backward_f32": (c_int, [vp] * 3 + [c_int] * 2 + [c_size_t, vp]),
+    "cspn3d_forward_absnorm_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn3d_forward_absnorm_f32": (c_int, [vp] * 3 + [c_int] * 6 + _WS),
+    # the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (fluid.layers.affinity_propagate's kernel_size)
+    "cspn2d_kxk_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_kxk_history_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_forward_kxk_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_kxk_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_backward_kxk_f32": (c_int, [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
+    # the depth-completion contract (Affinity_Propagate's normalisation, siting, blur term and pinning) over K x K, K = 3, 5 or 7
+    "cspn2d_kxk_norm_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_kxk_norm_history_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_forward_kxk_norm_f32": (c_int, [vp] * 5 + [c_size_t] + [c_int] * 8 + _WS),
+    "cspn2d_backward_kxk_norm_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_backward_kxk_norm_f32": (c_int, [vp] * 4 + [c_size_t] + [vp] * 3 + [c_int] * 8 + _WS),
+    # the same four on fp16 / bf16 gates or guidance (gate_dtype DTYPES[...]); values, workspace and history stay float32
+    "cspn2d_forward_kxk_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_kxk_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
+    "cspn2d_forward_kxk_norm_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_size_t] + [c_int] * 8 + _WS),
+    "cspn2d_backward_kxk_norm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 8 + _WS),
+    # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
+    "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_kxk_absnorm_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_backward_kxk_absnorm_f32": (c_int, [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
+    "cspn2d_backward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
+    # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
+    "cspn_guidance_head_kxk_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn_guidance_head_kxk_f32": (c_int, [vp] * 5 + [c_int] * 7 + _WS),
+    "cspn_guidance_head_kxk_backward_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn_guidance_head_kxk_backward_f32": (c_int, [vp] * 8 + [c_int] * 7 + _WS),
+    # the same heads on an fp16 / bf16 feature map (dtype DTYPES[...] after x), K = 5 or 7: 16-bit x, guidance, dL/dguidance, dL/dx; float32 weights, blur, dL/dW
+    "cspn_guidance_head_kxk_g16_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn_guidance_head_kxk_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 7 + _WS),
+    "cspn_guidance_head_kxk_backward_g16_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn_guidance_head_kxk_backward_g16": (c_int, [vp, c_int] + [vp] * 7 + [c_int] * 7 + _WS),
+})
+_LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -46,160 +144,24 @@ def load():
             "cspn_amd: %s not found -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C cspn_amd/csrc`). There is no fallback path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    c_int, c_size_t, vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
     lib.cspn_abi_version.restype = c_int
     v = lib.cspn_abi_version()
     if v != ABI_VERSION:   # (before any symbol lookup: a stale library must fail with this message, not an AttributeError)
         raise CspnError("cspn_amd: ABI version mismatch: library %d, binding %d -- rebuild with `make -C cspn_amd/csrc`" % (v, ABI_VERSION))
     lib.cspn_last_error.restype = ctypes.c_char_p
-    lib.cspn2d_workspace_bytes.restype = c_size_t
-    lib.cspn2d_workspace_bytes.argtypes = [c_int] * 4
-    lib.cspn2d_auto_algo.restype = c_int
-    lib.cspn2d_auto_algo.argtypes = [c_int] * 4
-    lib.cspn2d_forward_f32.restype = c_int
-    lib.cspn2d_forward_f32.argtypes = [vp, vp, vp, vp] + [c_int] * 5 + [vp, c_size_t, vp]
-    lib.cspn2d_forward_f32_algo.restype = c_int
-    lib.cspn2d_forward_f32_algo.argtypes = [vp, vp, vp, vp] + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn2d_normalize_f32.restype = c_int
-    lib.cspn2d_normalize_f32.argtypes = [vp, vp] + [c_int] * 4 + [vp]
-    lib.cspn2d_forward_prenorm_f32.restype = c_int
-    lib.cspn2d_forward_prenorm_f32.argtypes = [vp, vp, vp, vp] + [c_int] * 4 + [vp, c_size_t, vp]
-    lib.cspn2d_backward_workspace_bytes.restype = c_size_t
-    lib.cspn2d_backward_workspace_bytes.argtypes = [c_int] * 4
-    lib.cspn2d_backward_f32.restype = c_int
-    lib.cspn2d_backward_f32.argtypes = [vp] * 6 + [c_int] * 5 + [vp, c_size_t, vp]
-    lib.cspn2d_history_bytes.restype = c_size_t
-    lib.cspn2d_history_bytes.argtypes = [c_int] * 4
-    lib.cspn2d_forward_history_f32.restype = c_int
-    lib.cspn2d_forward_history_f32.argtypes = [vp] * 5 + [c_size_t] + [c_int] * 5 + [vp, c_size_t, vp]
-    lib.cspn2d_backward_history_workspace_bytes.restype = c_size_t
-    lib.cspn2d_backward_history_workspace_bytes.argtypes = [c_int] * 4
-    lib.cspn2d_backward_history_f32.restype = c_int
-    lib.cspn2d_backward_history_f32.argtypes = [vp] * 5 + [c_size_t, vp, vp] + [c_int] * 5 + [vp, c_size_t, vp]
-    lib.cspn_metrics_workspace_bytes.restype = c_size_t
-    lib.cspn_metrics_workspace_bytes.argtypes = [c_size_t]
-    lib.cspn_metrics_f32.restype = c_int
-    lib.cspn_metrics_f32.argtypes = [vp, vp, c_size_t, vp, vp, c_size_t, vp]
-    lib.cspn_l1_backward_f32.restype = c_int
-    lib.cspn_l1_backward_f32.argtypes = [vp, vp, vp, vp, vp, c_size_t, vp]
-    lib.cspn3d_backward_workspace_bytes.restype = c_size_t
-    lib.cspn3d_backward_workspace_bytes.argtypes = [c_int] * 5
-    lib.cspn3d_backward_f32.restype = c_int
-    lib.cspn3d_backward_f32.argtypes = [vp] * 5 + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn_unpool_f32.restype = c_int
-    lib.cspn_unpool_f32.argtypes = [vp, vp, c_size_t, c_int, c_int, c_int, vp]
-    lib.cspn_guidance_head_workspace_bytes.restype = c_size_t
-    lib.cspn_guidance_head_workspace_bytes.argtypes = [c_int]
-    lib.cspn_guidance_head_f32.restype = c_int
-    lib.cspn_guidance_head_f32.argtypes = [vp] * 5 + [c_int] * 7 + [vp, c_size_t, vp]
-    lib.cspn_guidance_head_backward_workspace_bytes.restype = c_size_t
-    lib.cspn_guidance_head_backward_workspace_bytes.argtypes = [c_int] * 4
-    lib.cspn_guidance_head_backward_f32.restype = c_int
-    lib.cspn_guidance_head_backward_f32.argtypes = [vp] * 8 + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn_unpool_backward_f32.restype = c_int
-    lib.cspn_unpool_backward_f32.argtypes = [vp, vp, c_size_t, c_int, c_int, c_int, vp]
-    lib.cspn_sparse_sample_workspace_bytes.restype = c_size_t
-    lib.cspn_sparse_sample_workspace_bytes.argtypes = [c_size_t]
-    lib.cspn_sparse_sample_f32.restype = c_int
-    lib.cspn_sparse_sample_f32.argtypes = [vp, vp, c_size_t, c_size_t, c_int, c_int, ctypes.c_ulonglong, vp, c_size_t, vp]
-    lib.cspn3d_workspace_bytes.restype = c_size_t
-    lib.cspn3d_workspace_bytes.argtypes = [c_int] * 5
-    lib.cspn3d_forward_f32.restype = c_int
-    lib.cspn3d_forward_f32.argtypes = [vp, vp, vp, vp] + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn3d_workspace_bytes_ex.restype = c_size_t
-    lib.cspn3d_workspace_bytes_ex.argtypes = [c_int] * 7
-    lib.cspn3d_forward_f32_algo.restype = c_int
-    lib.cspn3d_forward_f32_algo.argtypes = [vp, vp, vp, vp] + [c_int] * 7 + [vp, c_size_t, vp]
-    lib.cspn3d_multi_supported.restype = c_int
-    lib.cspn3d_multi_supported.argtypes = [c_int] * 6
-    lib.cspn3d_forward_multi_f32.restype = c_int
-    lib.cspn3d_forward_multi_f32.argtypes = [vp, vp, vp] + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn3d_backward_multi_workspace_bytes.restype = c_size_t
-    lib.cspn3d_backward_multi_workspace_bytes.argtypes = [c_int] * 6
-    lib.cspn3d_backward_multi_f32.restype = c_int
-    lib.cspn3d_backward_multi_f32.argtypes = [vp] * 5 + [c_int] * 6 + [vp, c_size_t, vp]
-    lib.cspn3d_check_status.restype = c_int
-    lib.cspn3d_check_status.argtypes = [vp]
+    for name in _BOUND_AT_LOAD:
+        f = getattr(lib, name)
+        f.restype, f.argtypes = _SYMBOLS[name]
     _lib = lib
     return lib
 
 
-# exports added to ABI 5 after its release (purely additive, the version stayed): looked up on first use, so that a library built before
-# them still loads and serves everything else, and a call of a missing one says to rebuild instead of raising AttributeError
-_LATE_SYMBOLS = {
-    "cspn2d_normalize_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
-    # C channels on shared 2D guidance
-    "cspn2d_workspace_bytes_multi": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn2d_multi_supported": (ctypes.c_int, [ctypes.c_int] * 5),
-    "cspn2d_forward_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_history_bytes_multi": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn2d_forward_history_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_int] * 7
-                                         + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn2d_backward_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_history_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn2d_backward_history_multi_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-                                          + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the demo's gate normalisation (reference cspn_paddle/demo.py:24,34-36,47-49) and the 3D module on raw gates
-    "cspn_gate_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn_gate_absnorm_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn3d_forward_absnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn3d_forward_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (fluid.layers.affinity_propagate's kernel_size)
-    "cspn2d_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
-    "cspn2d_kxk_history_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
-    "cspn2d_forward_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 6
-                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
-    "cspn2d_backward_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
-                                + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the depth-completion contract (Affinity_Propagate's normalisation, siting, blur term and pinning) over K x K, K = 3, 5 or 7
-    "cspn2d_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
-    "cspn2d_kxk_norm_history_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
-    "cspn2d_forward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_int] * 8
-                                    + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
-    "cspn2d_backward_kxk_norm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 8
-                                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the same four on fp16 / bf16 gates or guidance (gate_dtype DTYPES[...]); values, workspace and history stay float32
-    "cspn2d_forward_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_int] * 6
-                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
-                                + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_forward_kxk_norm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 8
-                                    + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_norm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
-                                     + [ctypes.c_int] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
-    "cspn2d_forward_kxk_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 6
-                                       + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_forward_kxk_absnorm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_int] * 6
-                                       + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_absnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
-    "cspn2d_backward_kxk_absnorm_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
-                                        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn2d_backward_kxk_absnorm_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t]
-                                        + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
-    "cspn_guidance_head_kxk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn_guidance_head_kxk_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn_guidance_head_kxk_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn_guidance_head_kxk_backward_f32": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    # the same heads on an fp16 / bf16 feature map (dtype DTYPES[...] after x), K = 5 or 7: 16-bit x, guidance, dL/dguidance, dL/dx; float32 weights, blur, dL/dW
-    "cspn_guidance_head_kxk_g16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn_guidance_head_kxk_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7
-                                   + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "cspn_guidance_head_kxk_backward_g16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
-    "cspn_guidance_head_kxk_backward_g16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7
-                                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-}
+_bound = {}
 
 
-_late = {}
-
-
-def late_symbol(name):
-    f = _late.get(name)
+def symbol(name):
+    """the entry point `name` of the loaded library with its types set: what every wrapper calls"""
+    f = _bound.get(name)
     if f is not None:
         return f
     lib = load()
@@ -208,9 +170,12 @@ def late_symbol(name):
     except AttributeError:
         raise CspnError("cspn_amd: %s does not export %s (a library built before it was added) -- rebuild with `make -C cspn_amd/csrc`"
                         % (LIB_PATH, name)) from None
-    f.restype, f.argtypes = _LATE_SYMBOLS[name]
-    _late[name] = f
+    f.restype, f.argtypes = _SYMBOLS[name]
+    _bound[name] = f
     return f
+
+
+late_symbol = symbol
 
 
 def load_hooks():
@@ -224,7 +189,6 @@ def load_hooks():
     if not os.path.exists(HOOKS_PATH):
         raise CspnError("cspn_amd: %s not found -- `make -C cspn_amd/csrc` builds it next to the product library" % HOOKS_PATH)
     h = ctypes.CDLL(HOOKS_PATH)
-    c_int, vp = ctypes.c_int, ctypes.c_void_p
     ip = ctypes.POINTER(c_int)
     h.cspn_debug_tsw_plan_geo.restype = c_int
     h.cspn_debug_tsw_plan_geo.argtypes = [c_int] * 5 + [ip]

@@ -29,69 +29,48 @@ import torch.nn as nn
 from . import functional as F
 
 
-class _CSPN2dMultiFunction(torch.autograd.Function):
-    """blur_depth [B,C,H,W], C > 1, on the shared guidance (reference cspn.py:58-81 broadcasts the affinities): one engine call each way,
-    dL/dguidance summed over the channels inside the engine"""
-
-    @staticmethod
-    def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo, keep_history):
-        ctx.n_iter, ctx.norm_type = n_iter, norm_type
-        needs_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        B, C, H, W = blur_depth.shape
-        if (keep_history and needs_grad and algo in ("auto", "fused") and guidance.is_cuda
-                and F.cspn2d_history_bytes_multi(B, C, H, W, n_iter) > 0):
-            out, hist = F.cspn2d_forward_with_history_multi(guidance, blur_depth, sparse_depth, n_iter, norm_type)
-            ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
-            return out
-        ctx.save_for_backward(guidance, blur_depth, sparse_depth, None)
-        return F.cspn2d_forward_multi(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
-        if hist is not None:
-            gg, gh = F.cspn2d_backward_from_history_multi(guidance, blur_depth, sparse_depth, grad_out, hist, ctx.n_iter, ctx.norm_type,
-                                                          need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
-        else:
-            gg, gh = F.cspn2d_backward_multi(guidance, blur_depth, sparse_depth, grad_out, ctx.n_iter, ctx.norm_type,
-                                             need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
-        return gg, gh, None, None, None, None, None
-
-
-def _apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history):
-    # blur_depth [B,C,H,W] with C > 1: the multi-channel call; C = 1 runs exactly the single-channel path
-    if isinstance(blur_depth, torch.Tensor) and blur_depth.dim() == 4 and blur_depth.shape[1] > 1:
-        return _CSPN2dMultiFunction.apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history)
-    return _CSPN2dFunction.apply(guidance, blur_depth, sparse_depth, n, norm_type, algo, keep_history)
+# the functional calls of one channel and of C > 1 channels on the shared guidance: history size query, forward keeping the history, backward from it,
+# plain forward, plain backward
+_CALLS = {False: (F.cspn2d_history_bytes, F.cspn2d_forward_with_history, F.cspn2d_backward_from_history, F.cspn2d_forward, F.cspn2d_backward),
+          True: (F.cspn2d_history_bytes_multi, F.cspn2d_forward_with_history_multi, F.cspn2d_backward_from_history_multi,
+                 F.cspn2d_forward_multi, F.cspn2d_backward_multi)}
 
 
 class _CSPN2dFunction(torch.autograd.Function):
+    """blur_depth [B,1,H,W] runs exactly the single-channel calls; [B,C,H,W] with C > 1 the multi-channel ones on the shared guidance (reference
+    cspn.py:58-81 broadcasts the affinities): one engine call each way, dL/dguidance summed over the channels inside the engine"""
+
     @staticmethod
     def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo, keep_history):
         ctx.n_iter, ctx.norm_type = n_iter, norm_type
+        ctx.multi = isinstance(blur_depth, torch.Tensor) and blur_depth.dim() == 4 and blur_depth.shape[1] > 1
+        history_bytes, forward_with_history, _, forward, _ = _CALLS[ctx.multi]
         needs_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        B, _, H, W = guidance.shape
+        shape = blur_depth.shape if ctx.multi else (guidance.shape[0],) + tuple(guidance.shape[2:])
         if (keep_history and needs_grad and algo in ("auto", "fused") and guidance.is_cuda
-                and F.cspn2d_history_bytes(B, H, W, n_iter) > 0):
-            # training: the forward keeps every FOURTH intermediate level (H_4 .. H_20) and the folded coefficients -- 13 planes,
-            # where autograd keeps ~27 temporaries per iteration for the reference --, the backward starts from them and
+                and history_bytes(*shape, n_iter) > 0):
+            # training: the forward keeps every FOURTH intermediate level (H_4 .. H_20) and the folded coefficients -- 13 planes per
+            # image-channel, where autograd keeps ~27 temporaries per iteration for the reference --, the backward starts from them and
             # recomputes the three levels in between
-            out, hist = F.cspn2d_forward_with_history(guidance, blur_depth, sparse_depth, n_iter, norm_type)
+            out, hist = forward_with_history(guidance, blur_depth, sparse_depth, n_iter, norm_type)
             ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
             return out
         ctx.save_for_backward(guidance, blur_depth, sparse_depth, None)
-        return F.cspn2d_forward(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
+        return forward(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
 
     @staticmethod
     def backward(ctx, grad_out):
         guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
+        _, _, backward_from_history, _, backward = _CALLS[ctx.multi]
+        need = dict(need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
         if hist is not None:
-            gg, gh = F.cspn2d_backward_from_history(guidance, blur_depth, sparse_depth, grad_out, hist, ctx.n_iter, ctx.norm_type,
-                                                    need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
+            gg, gh = backward_from_history(guidance, blur_depth, sparse_depth, grad_out, hist, ctx.n_iter, ctx.norm_type, **need)
         else:
-            gg, gh = F.cspn2d_backward(guidance, blur_depth, sparse_depth, grad_out, ctx.n_iter, ctx.norm_type,
-                                       need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
+            gg, gh = backward(guidance, blur_depth, sparse_depth, grad_out, ctx.n_iter, ctx.norm_type, **need)
         return gg, gh, None, None, None, None, None
+
+
+_apply = _CSPN2dFunction.apply
 
 
 def propagate_prenorm(gate_wb, blur_depth, sparse_depth=None, n_iter=24, algo="auto", keep_history=True):

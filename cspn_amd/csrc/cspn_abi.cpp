@@ -57,6 +57,42 @@ static int check_common(const void* a, const void* b, const void* out, int n_ite
     return 0;
 }
 
+// ---- the 3 x 3 entry points (cspn2d_* / cspn3d_*): the pieces their checks share ----
+// every dimension positive, the first (B) at least b_min; names: one letter per dimension for the text, "BHW" .. "BCDHW"
+static int check_shape(const char* names, std::initializer_list<int> dims, int b_min = 0) {
+    int i = 0, bad = 0;
+    for (int d : dims) bad |= d < (i++ ? 1 : b_min);
+    if (!bad) return 0;
+    char text[128] = "bad shape";
+    size_t n = 9;
+    for (int d : dims) n += snprintf(text + n, sizeof(text) - n, " %c=%d", *names++, d);
+    set_error("%s", text);
+    return CSPN_E_BADARG;
+}
+
+// elems values behind one 32-bit index that also counts `planes` planes of them
+static int check_index32(long long elems, int planes, const char* what = "") {
+    if (elems <= 0x7fffffffLL / planes) return 0;
+    set_error("tensor too large for 32-bit plane indexing%s", what);
+    return CSPN_E_UNSUPPORTED;
+}
+
+// n_iter == 0, forward: the loop body never runs (reference cspn.py:61,66,83)
+static int identity_copy(float* out, const float* in, size_t floats, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(out, in, sizeof(float) * floats, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+// n_iter == 0, backward: dL/dfeat = dL/dout, the gates are not used
+static int identity_backward(float* grad_feat, const float* grad_out, size_t floats, float* grad_gate, size_t gate_floats, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (grad_feat) e = hipMemcpyAsync(grad_feat, grad_out, sizeof(float) * floats, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, sizeof(float) * gate_floats, st);
+    if (e != hipSuccess) { set_error("hipMemcpyAsync / hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
 // argument checks of the gate normaliser entry points (cspn_gate_absnorm_f32 / _backward_f32)
 static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -165,9 +201,9 @@ size_t cspn2d_workspace_bytes(int B, int H, int W, int n_iter) {
 int cspn2d_forward_f32_algo(const float* guidance, const float* blur, const float* sparse, float* out, int B,
                             int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes,
                             cspn_stream_t stream) {
-    if (B < 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BHW", {B, H, W})) return e;
     if (B == 0) return 0;
-    if ((long long)B * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * H * W, 9)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (algo == CSPN_ALGO_AUTO) {
         algo = cspn2d_auto_algo(B, H, W, n_iter);
@@ -192,11 +228,7 @@ int cspn2d_forward_f32_algo(const float* guidance, const float* blur, const floa
                   : (fused ? fused2d_workspace(B, H, W, n_iter)
                                              : stepwise2d_workspace(B, H, W, n_iter));
     if (int e = check_common(guidance, blur, out, n_iter, norm_type, ws, ws_bytes, need, CSPN_NORM_PRENORM)) return e;
-    if (n_iter == 0) {  // reference cspn.py:61,66,83: the loop body never runs
-        hipError_t e = hipMemcpyAsync(out, blur, sizeof(float) * (size_t)B * H * W, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
+    if (n_iter == 0) return identity_copy(out, blur, (size_t)B * H * W, st);
     if (fused) return fused2d_forward(guidance, blur, sparse, out, B, H, W, n_iter, norm_type, ws, st, algo == CSPN_ALGO_FUSED);
     return stepwise2d_forward(guidance, blur, sparse, out, B, H, W, n_iter, norm_type, ws, st);
 }
@@ -211,7 +243,7 @@ int cspn2d_forward_f32(const float* guidance, const float* blur, const float* sp
 int cspn2d_normalize_f32(const float* guidance, float* wb, int B, int H, int W, int norm_type, cspn_stream_t stream) {
     if (!guidance || !wb || B <= 0 || H <= 0 || W <= 0) { set_error("bad argument"); return CSPN_E_BADARG; }
     if (norm_type != CSPN_NORM_8SUM && norm_type != CSPN_NORM_8SUM_ABS) { set_error("cspn2d_normalize_f32: norm_type must be 8SUM or 8SUM_ABS (got %d)", norm_type); return CSPN_E_BADARG; }
-    if ((long long)B * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * H * W, 9)) return e;
     return normalize2d(guidance, wb, B, H, W, norm_type, (hipStream_t)stream);
 }
 
@@ -221,7 +253,7 @@ int cspn2d_normalize_backward_f32(const float* guidance, const float* grad_wb, f
     if (B <= 0 || H <= 0 || W <= 0) { set_error("cspn2d_normalize_backward_f32: bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
     if (norm_type != CSPN_NORM_8SUM && norm_type != CSPN_NORM_8SUM_ABS) { set_error("cspn2d_normalize_backward_f32: norm_type must be 8SUM or 8SUM_ABS (got %d)", norm_type); return CSPN_E_BADARG; }
     if (grad_guidance == guidance || grad_guidance == grad_wb) { set_error("cspn2d_normalize_backward_f32: grad_guidance must not alias an input"); return CSPN_E_BADARG; }
-    if ((long long)B * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * H * W, 9)) return e;
     return normalize2d_backward(guidance, grad_wb, grad_guidance, B, H, W, norm_type, (hipStream_t)stream);
 }
 
@@ -238,10 +270,10 @@ size_t cspn2d_backward_workspace_bytes(int B, int H, int W, int n_iter) {
 int cspn2d_backward_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out,
                         float* grad_guidance, float* grad_blur, int B, int H, int W, int n_iter, int norm_type, void* ws,
                         size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BHW", {B, H, W})) return e;
     if (B == 0) return 0;
     if (n_iter < 1) { set_error("backward needs n_iter >= 1 (got %d)", n_iter); return CSPN_E_BADARG; }
-    if ((long long)B * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * H * W, 9)) return e;
     if (!grad_out) { set_error("null grad_out"); return CSPN_E_BADARG; }
     if (int e = check_common(guidance, blur, grad_out, n_iter, norm_type, ws, ws_bytes, backward2d_workspace(B, H, W, n_iter), CSPN_NORM_PRENORM)) return e;
     if (!grad_guidance && !grad_blur) return 0;
@@ -256,7 +288,7 @@ size_t cspn2d_history_bytes(int B, int H, int W, int n_iter) {
 int cspn2d_forward_history_f32(const float* guidance, const float* blur, const float* sparse, float* out, void* history,
                                size_t history_bytes, int B, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes,
                                cspn_stream_t stream) {
-    if (B <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BHW", {B, H, W}, 1)) return e;
     const size_t hb = history2d_bytes(B, H, W, n_iter);
     if (hb == 0) { set_error("no history mode for B=%d H=%d W=%d n_iter=%d", B, H, W, n_iter); return CSPN_E_UNSUPPORTED; }
     if (!history || history_bytes < hb || ((uintptr_t)history & 255u)) { set_error("history buffer too small or misaligned: need %zu bytes", hb); return CSPN_E_WORKSPACE; }
@@ -273,7 +305,7 @@ size_t cspn2d_backward_history_workspace_bytes(int B, int H, int W, int n_iter) 
 int cspn2d_backward_history_f32(const float* guidance, const float* blur, const float* sparse, const float* grad_out,
                                 const void* history, size_t history_bytes, float* grad_guidance, float* grad_blur, int B, int H,
                                 int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d H=%d W=%d", B, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BHW", {B, H, W}, 1)) return e;
     const size_t hb = history2d_bytes(B, H, W, n_iter);
     if (hb == 0) { set_error("no history mode for B=%d H=%d W=%d n_iter=%d", B, H, W, n_iter); return CSPN_E_UNSUPPORTED; }
     if (!grad_out) { set_error("null grad_out"); return CSPN_E_BADARG; }
@@ -287,13 +319,12 @@ int cspn2d_backward_history_f32(const float* guidance, const float* blur, const 
 // ---- C channels on shared 2D guidance (include/cspn_amd.h: the cspn2d_*_multi entry points) ----
 
 static int check_multi(int B, int C, int sparse_channels, const float* sparse, int H, int W) {
-    if (B < 0 || C <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d C=%d H=%d W=%d", B, C, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BCHW", {B, C, H, W})) return e;
     if (sparse && sparse_channels != 1 && sparse_channels != C) {
         set_error("sparse has %d channels: 1 (one mask for every channel) or C = %d expected", sparse_channels, C);
         return CSPN_E_BADARG;
     }
-    if ((long long)B * C * H * W > 0x7fffffffLL / 9) { set_error("tensor too large for 32-bit plane indexing (B*C*H*W)"); return CSPN_E_UNSUPPORTED; }
-    return 0;
+    return check_index32((long long)B * C * H * W, 9, " (B*C*H*W)");
 }
 
 // the shared-gate forward: one ring launch per pass over the B*C image-channels (the fused assembly path of the single-channel call)
@@ -348,11 +379,7 @@ int cspn2d_forward_multi_f32(const float* guidance, const float* blur, const flo
                              CSPN_NORM_PRENORM)) return e;
     hipStream_t st = (hipStream_t)stream;
     const size_t HW = (size_t)H * W;
-    if (n_iter == 0) {  // reference cspn.py:61,66,83: the loop body never runs
-        hipError_t e = hipMemcpyAsync(out, blur, sizeof(float) * (size_t)B * C * HW, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
+    if (n_iter == 0) return identity_copy(out, blur, (size_t)B * C * HW, st);
     // the fast path where the single-channel call would take the assembly ring too (AUTO / FUSED, 16-byte aligned output)
     if ((algo == CSPN_ALGO_AUTO || algo == CSPN_ALGO_FUSED) && multi_fast(B, C, H, W, n_iter) && ((uintptr_t)out & 15u) == 0) {
         if (int e = widen_if_shared(sparse, sparse_channels, B, C, H, W, ws, st)) return e;
@@ -506,9 +533,9 @@ int cspn3d_forward_f32(const float* gate, const float* feat, const float* sparse
 
 int cspn3d_forward_f32_algo(const float* gate, const float* feat, const float* sparse, float* out, int B, int D, int H,
                             int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d D=%d H=%d W=%d", B, D, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
-    if ((long long)B * D * H * W > 0x7fffffffLL / 27) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * D * H * W, 27)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
     if (int e = async_failure_of_earlier_call()) return e;
@@ -517,11 +544,7 @@ int cspn3d_forward_f32_algo(const float* gate, const float* feat, const float* s
     size_t need = n_iter == 0 ? 0 : (aligned ? forward3d_workspace(B, D, H, W, n_iter, norm_type, sparse != nullptr)
                                              : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(gate, feat, out, n_iter, norm_type, ws, ws_bytes, need)) return e;
-    if (n_iter == 0) {
-        hipError_t e = hipMemcpyAsync(out, feat, sizeof(float) * (size_t)B * D * H * W, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
+    if (n_iter == 0) return identity_copy(out, feat, (size_t)B * D * H * W, st);
     return stepwise3d_forward(gate, feat, sparse, out, B, D, H, W, n_iter, norm_type, ws, st, algo);
 }
 
@@ -532,7 +555,7 @@ int cspn3d_multi_supported(int B, int C, int D, int H, int W, int n_iter) {
 
 int cspn3d_forward_multi_f32(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
                              void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d C=%d D=%d H=%d W=%d", B, C, D, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BCDHW", {B, C, D, H, W})) return e;
     if (B == 0) return 0;
     if (int e = async_failure_of_earlier_call()) return e;
     if (int e = check_common(gate, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes,
@@ -552,28 +575,25 @@ size_t cspn3d_backward_workspace_bytes(int B, int D, int H, int W, int n_iter) {
     return backward3d_workspace(B, D, H, W, n_iter);
 }
 
+// the checks of cspn3d_backward_f32 (multi false, C = 1) and cspn3d_backward_multi_f32 (norm_type NONE), then the engine
+static int backward3d_entry(bool multi, const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B, int C,
+                            int D, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = multi ? check_shape("BCDHW", {B, C, D, H, W}) : check_shape("BDHW", {B, D, H, W})) return e;
+    if (B == 0) return 0;
+    const size_t V = (size_t)B * D * H * W;
+    if (int e = check_index32((long long)V, 27)) return e;
+    if (int e = check_index32((long long)V * C, 2)) return e;
+    if (norm_type != CSPN_NORM_NONE) { set_error("the 3D backward covers the Paddle contract only (norm_type NONE: gates used as given, no mask)"); return CSPN_E_UNSUPPORTED; }
+    if (int e = async_failure_of_earlier_call()) return e;
+    if (int e = check_common(gate, feat, grad_out, n_iter, norm_type, ws, ws_bytes, n_iter == 0 ? 0 : backward3d_workspace(B, D, H, W, n_iter, C))) return e;
+    if (!grad_gate && !grad_feat) return 0;
+    if (n_iter == 0) return identity_backward(grad_feat, grad_out, V * C, grad_gate, 26 * V, (hipStream_t)stream);
+    return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, (hipStream_t)stream, false, C);
+}
+
 int cspn3d_backward_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B,
                         int D, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d D=%d H=%d W=%d", B, D, H, W); return CSPN_E_BADARG; }
-    if (B == 0) return 0;
-    if ((long long)B * D * H * W > 0x7fffffffLL / 27) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
-    if (norm_type != CSPN_NORM_NONE) {
-        set_error("the 3D backward covers the Paddle contract only (norm_type NONE: gates used as given, no mask)");
-        return CSPN_E_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = async_failure_of_earlier_call()) return e;
-    if (int e = check_common(gate, feat, grad_out, n_iter, norm_type, ws, ws_bytes, n_iter == 0 ? 0 : backward3d_workspace(B, D, H, W, n_iter))) return e;
-    if (!grad_gate && !grad_feat) return 0;
-    const size_t bytes = sizeof(float) * (size_t)B * D * H * W;
-    if (n_iter == 0) {   // identity: dL/dfeat = dL/dout, the gates are not used
-        hipError_t e = hipSuccess;
-        if (grad_feat) e = hipMemcpyAsync(grad_feat, grad_out, bytes, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, 26 * bytes, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync / hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, st);
+    return backward3d_entry(false, gate, feat, grad_out, grad_gate, grad_feat, B, 1, D, H, W, n_iter, norm_type, ws, ws_bytes, stream);
 }
 
 size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter) {
@@ -583,26 +603,8 @@ size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, 
 
 int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B,
                               int C, int D, int H, int W, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d C=%d D=%d H=%d W=%d", B, C, D, H, W); return CSPN_E_BADARG; }
-    if (B == 0) return 0;
-    if ((long long)B * D * H * W > 0x7fffffffLL / 27 || (long long)B * C * D * H * W > 0x7fffffffLL / 2) {
-        set_error("tensor too large for 32-bit plane indexing");
-        return CSPN_E_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = async_failure_of_earlier_call()) return e;
-    if (int e = check_common(gate, feat, grad_out, n_iter, CSPN_NORM_NONE, ws, ws_bytes, n_iter == 0 ? 0 : backward3d_workspace(B, D, H, W, n_iter, C))) return e;
-    if (!grad_gate && !grad_feat) return 0;
-    if (n_iter == 0) {   // identity: dL/dfeat = dL/dout, the gates are not used
-        hipError_t e = hipSuccess;
-        if (grad_feat) e = hipMemcpyAsync(grad_feat, grad_out, sizeof(float) * (size_t)B * C * D * H * W, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, 26 * sizeof(float) * (size_t)B * D * H * W, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync / hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
-    return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, st, false, C);
+    return backward3d_entry(true, gate, feat, grad_out, grad_gate, grad_feat, B, C, D, H, W, n_iter, CSPN_NORM_NONE, ws, ws_bytes, stream);
 }
-
 
 // ---- the demo's module (reference cspn_paddle/demo.py:20-54): w = |g| / sum_k |g_k| per voxel over one slice's K gates, then the NONE op ----
 int cspn_gate_absnorm_f32(const float* guide, float* gate, int N, int K, size_t V, cspn_stream_t stream) {
@@ -623,9 +625,9 @@ size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_
 
 int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
                                void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0) { set_error("bad shape B=%d D=%d H=%d W=%d", B, D, H, W); return CSPN_E_BADARG; }
+    if (int e = check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
-    if ((long long)B * D * H * W > 0x7fffffffLL / 27) { set_error("tensor too large for 32-bit plane indexing"); return CSPN_E_UNSUPPORTED; }
+    if (int e = check_index32((long long)B * D * H * W, 27)) return e;
     if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
     const size_t total = (size_t)B * D * H * W;
     if (guide && feat && out && (overlaps(out, total * sizeof(float), guide, 26 * total * sizeof(float)) || overlaps(out, total * sizeof(float), feat, total * sizeof(float)))) {
@@ -639,11 +641,7 @@ int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out
     const size_t need = n_iter == 0 ? 0 : absnorm_planes_bytes(B, D, H, W) + (vals_aligned ? forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false)
                                                                                             : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(guide, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes, need)) return e;
-    if (n_iter == 0) {
-        hipError_t e = hipMemcpyAsync(out, feat, sizeof(float) * total, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-        return 0;
-    }
+    if (n_iter == 0) return identity_copy(out, feat, total, st);
     const bool fused = vals_aligned && ((((uintptr_t)guide | (uintptr_t)ws) & 15u) == 0) && persistent3d_supported(B, D, H, W, n_iter);
     if (algo == CSPN_ALGO3D_PERSISTENT && !fused) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");

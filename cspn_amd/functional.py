@@ -50,35 +50,25 @@ def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
-def cspn2d_forward(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum", algo="auto"):
-    """All n_iter steps of reference cspn_pytorch/models/cspn.py:42-83 in the HIP engine.
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
-    guidance [B,8,H,W], blur_depth [B,1,H,W], sparse_depth [B,1,H,W] or None -> [B,1,H,W]."""
-    lib = _lib.load()
-    if guidance.dim() != 4 or guidance.shape[1] != 8:
-        raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
-    B, _, H, W = guidance.shape
-    g = _prep(guidance, "guidance")
-    h = _prep(blur_depth, "blur_depth", (B, 1, H, W))
-    s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W)) if sparse_depth is not None else None
-    if h.device != g.device or (s is not None and s.device != g.device):
-        raise ValueError("all tensors must live on the same device")
-    out = torch.empty_like(h)
-    if B == 0:
-        return out
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn2d_workspace_bytes(B, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        rc = lib.cspn2d_forward_f32_algo(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None,
-                                         out.data_ptr(), B, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
-                                         _lib.ALGOS[algo], ws.data_ptr(), ws_bytes, stream)
-    _lib.check(rc, "cspn2d_forward_f32")
-    return out
+
+def _launch(name, device, args, ws_query=None, what=None):
+    """One engine call on `device` and its current stream: name(*args, [workspace, its bytes,] stream), then _lib.check under `what` (default:
+    name).  ws_query = (a size query's name, *its arguments): the workspace is allocated here and passed behind args.  -> the workspace"""
+    ws = None
+    with torch.cuda.device(device):
+        if ws_query is not None:
+            ws_bytes = _lib.symbol(ws_query[0])(*ws_query[1:])
+            ws = _workspace(ws_bytes, device)
+            args = (*args, ws.data_ptr(), ws_bytes)
+        rc = _lib.symbol(name)(*args, torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(rc, what or name)
+    return ws
 
 
 def _normalize(guidance, norm_type):
-    lib = _lib.load()
     if guidance.dim() != 4 or guidance.shape[1] != 8:
         raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
     g = _prep(guidance, "guidance")
@@ -86,10 +76,7 @@ def _normalize(guidance, norm_type):
     out = torch.empty_like(g)
     if B == 0:
         return out
-    with torch.cuda.device(g.device):
-        rc = lib.cspn2d_normalize_f32(g.data_ptr(), out.data_ptr(), B, H, W, _lib.NORM_TYPES[norm_type],
-                                      torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_normalize_f32")
+    _launch("cspn2d_normalize_f32", g.device, (_ptr(g), _ptr(out), B, H, W, _lib.NORM_TYPES[norm_type]))
     return out
 
 
@@ -98,7 +85,6 @@ def cspn2d_normalize_backward(guidance, grad_wb, norm_type="8sum"):
     grad_wb = dL/dgate_wb [B,8,H,W] (consumer-sited: what cspn2d_backward(..., 'prenorm') returns for its guidance) -> dL/dguidance
     [B,8,H,W], the gradient torch autograd computes through the reference's affinity_normalization (cspn.py:85-144).  Elements no pixel
     reads get 0; NaN where a pixel's neighbourhood sums to 0 (as the forward)."""
-    fn = _lib.late_symbol("cspn2d_normalize_backward_f32")
     if norm_type not in ("8sum", "8sum_abs"):
         raise ValueError("norm_type must be '8sum' or '8sum_abs' (got %r)" % (norm_type,))
     if guidance.dim() != 4 or guidance.shape[1] != 8:
@@ -111,10 +97,7 @@ def cspn2d_normalize_backward(guidance, grad_wb, norm_type="8sum"):
     out = torch.empty_like(g)
     if out.numel() == 0:
         return out
-    with torch.cuda.device(g.device):
-        rc = fn(g.data_ptr(), r.data_ptr(), out.data_ptr(), B, H, W, _lib.NORM_TYPES[norm_type],
-                torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_normalize_backward_f32")
+    _launch("cspn2d_normalize_backward_f32", g.device, (_ptr(g), _ptr(r), _ptr(out), B, H, W, _lib.NORM_TYPES[norm_type]))
     return out
 
 
@@ -169,7 +152,7 @@ def cspn2d_forward_sited8(guidance_s8, blur_depth, sparse_depth=None, n_iter=24,
     s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W)) if sparse_depth is not None else None
     out = torch.empty_like(h)
     with torch.cuda.device(g.device):
-        rc = hooks.cspn_debug_forward_sited8(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(),
+        rc = hooks.cspn_debug_forward_sited8(g.data_ptr(), h.data_ptr(), _ptr(s), out.data_ptr(),
                                              B, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
                                              torch.cuda.current_stream(g.device).cuda_stream)
     if rc != 0:
@@ -178,35 +161,96 @@ def cspn2d_forward_sited8(guidance_s8, blur_depth, sparse_depth=None, n_iter=24,
     return out
 
 
+# ---- the 3 x 3 engine in 2D: one body per operation; variant "" is one channel (cspn2d_*_f32, blur_depth [B,1,H,W]), "_multi" C >= 1 channels on shared
+# guidance (cspn2d_*_multi_f32: reference cspn.py:58-81 broadcasts the affinities over blur_depth's channels) ----
+def _args2d(variant, guidance, blur_depth, sparse_depth, extra=()):
+    """-> (g, h, s, the shape arguments of the variant's size queries, those of its entry points, *extra): checked, contiguous, on one device"""
+    if guidance.dim() != 4 or guidance.shape[1] != 8:
+        raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
+    B, _, H, W = guidance.shape
+    s, C, sc = None, 1, 1
+    if not variant:
+        g = _prep(guidance, "guidance")
+        h = _prep(blur_depth, "blur_depth", (B, 1, H, W))
+        if sparse_depth is not None:
+            s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W))
+    else:
+        if blur_depth.dim() != 4 or tuple(blur_depth.shape[:1]) + tuple(blur_depth.shape[2:]) != (B, H, W) or blur_depth.shape[1] < 1:
+            raise ValueError("blur_depth has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(blur_depth.shape), B, H, W))
+        C = blur_depth.shape[1]
+        g = _prep(guidance, "guidance")
+        h = _prep(blur_depth, "blur_depth", (B, C, H, W))
+        if sparse_depth is not None:
+            if sparse_depth.dim() != 4 or sparse_depth.shape[1] not in (1, C):
+                raise ValueError("sparse_depth has shape %s, expected (B,1,H,W) or (B,C,H,W) = (%d,%d,%d,%d)"
+                                 % (tuple(sparse_depth.shape), B, C, H, W))
+            sc = sparse_depth.shape[1]
+            s = _prep(sparse_depth, "sparse_depth", (B, sc, H, W))
+    rest = [_prep(t, name, (B, C, H, W)) for t, name in extra]
+    if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
+        raise ValueError("all tensors must live on the same device")
+    return (g, h, s) + (((B, C, H, W), (B, C, sc, H, W)) if variant else ((B, H, W), (B, H, W))) + tuple(rest)
+
+
+def _forward2d(variant, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo):
+    g, h, s, q, d = _args2d(variant, guidance, blur_depth, sparse_depth)
+    out = torch.empty_like(h)
+    if q[0] == 0:
+        return out
+    _launch("cspn2d_forward%s_f32%s" % (variant, "" if variant else "_algo"), g.device,
+            (_ptr(g), _ptr(h), _ptr(s), _ptr(out), *d, int(n_iter), _lib.NORM_TYPES[norm_type], _lib.ALGOS[algo]),
+            ("cspn2d_workspace_bytes" + variant, *q, int(n_iter)), "cspn2d_forward%s_f32" % variant)
+    return out
+
+
+def _forward2d_with_history(variant, guidance, blur_depth, sparse_depth, n_iter, norm_type):
+    g, h, s, q, d = _args2d(variant, guidance, blur_depth, sparse_depth)
+    out = torch.empty_like(h)
+    with torch.cuda.device(g.device):
+        hb = _lib.symbol("cspn2d_history_bytes" + variant)(*q, int(n_iter))
+    if hb == 0:
+        raise _lib.CspnError("cspn_amd: no history mode for B=%d C=%d H=%d W=%d, n_iter %d" % (*q, n_iter) if variant else
+                             "cspn_amd: no history mode for shape %s, n_iter %d" % (tuple(guidance.shape), n_iter))
+    hist = torch.empty(hb, dtype=torch.uint8, device=g.device)
+    _launch("cspn2d_forward_history%s_f32" % variant, g.device,
+            (_ptr(g), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, *d, int(n_iter), _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_workspace_bytes" + variant, *q, int(n_iter)))
+    return out, hist
+
+
+def _backward2d(variant, guidance, blur_depth, sparse_depth, grad_out, history, n_iter, norm_type, need_guidance, need_blur):
+    """cspn2d_backward<variant>_f32 (history None: the levels are recomputed), or cspn2d_backward_history<variant>_f32 from what a training-mode
+    forward kept"""
+    g, h, s, q, d, go = _args2d(variant, guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    if (history is None and q[0] == 0) or not (need_guidance or need_blur):
+        return gg, gh
+    kind, hist = ("backward", ()) if history is None else ("backward_history", (history.data_ptr(), history.numel()))
+    _launch("cspn2d_%s%s_f32" % (kind, variant), g.device,
+            (_ptr(g), _ptr(h), _ptr(s), _ptr(go), *hist, _ptr(gg), _ptr(gh), *d, int(n_iter), _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_%s%s_workspace_bytes" % (kind, variant), *q, int(n_iter)))
+    return gg, gh
+
+
+def cspn2d_forward(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum", algo="auto"):
+    """All n_iter steps of reference cspn_pytorch/models/cspn.py:42-83 in the HIP engine.
+
+    guidance [B,8,H,W], blur_depth [B,1,H,W], sparse_depth [B,1,H,W] or None -> [B,1,H,W]."""
+    return _forward2d("", guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
+
+
 def cspn2d_backward(guidance, blur_depth, sparse_depth, grad_out, n_iter=24, norm_type="8sum",
                     need_guidance=True, need_blur=True):
     """Gradient of cspn2d_forward w.r.t. guidance and blur_depth (what autograd computes through reference
     cspn_pytorch/models/cspn.py:42-83, back-propagated by reference train.py:196-198) in the HIP engine.
     -> (grad_guidance [B,8,H,W] or None, grad_blur [B,1,H,W] or None)"""
-    lib = _lib.load()
-    B, _, H, W = guidance.shape
-    g = _prep(guidance, "guidance", (B, 8, H, W))
-    h = _prep(blur_depth, "blur_depth", (B, 1, H, W))
-    s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W)) if sparse_depth is not None else None
-    go = _prep(grad_out, "grad_out", (B, 1, H, W))
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    if B == 0 or not (need_guidance or need_blur):
-        return gg, gh
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn2d_backward_workspace_bytes(B, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        rc = lib.cspn2d_backward_f32(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(),
-                                     gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None,
-                                     B, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, stream)
-    _lib.check(rc, "cspn2d_backward_f32")
-    return gg, gh
+    return _backward2d("", guidance, blur_depth, sparse_depth, grad_out, None, n_iter, norm_type, need_guidance, need_blur)
 
 
 def cspn2d_history_bytes(B, H, W, n_iter):
     """bytes of what the training-mode forward keeps for its backward: every fourth level + the folded coefficients (0: not available for this shape)"""
-    return int(_lib.load().cspn2d_history_bytes(int(B), int(H), int(W), int(n_iter)))
+    return int(_lib.symbol("cspn2d_history_bytes")(int(B), int(H), int(W), int(n_iter)))
 
 
 def cspn2d_forward_with_history(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum"):
@@ -214,161 +258,51 @@ def cspn2d_forward_with_history(guidance, blur_depth, sparse_depth=None, n_iter=
     the checkpoints H_4, H_8 .. H_20 (every fourth level, register order per 4-column group) followed by the 8 folded coefficient
     planes -- 13 planes of B*H*W floats (the backward recomputes the levels in between; a tensor in the round-2 format, all 23
     levels, is NOT accepted: its size differs and the size is checked).  Only where cspn2d_history_bytes(...) > 0."""
-    lib = _lib.load()
-    B, _, H, W = guidance.shape
-    g = _prep(guidance, "guidance", (B, 8, H, W))
-    h = _prep(blur_depth, "blur_depth", (B, 1, H, W))
-    s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W)) if sparse_depth is not None else None
-    out = torch.empty_like(h)
-    with torch.cuda.device(g.device):
-        hb = lib.cspn2d_history_bytes(B, H, W, int(n_iter))
-        if hb == 0:
-            raise _lib.CspnError("cspn_amd: no history mode for shape %s, n_iter %d" % (tuple(guidance.shape), n_iter))
-        hist = torch.empty(hb, dtype=torch.uint8, device=g.device)
-        ws_bytes = lib.cspn2d_workspace_bytes(B, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = lib.cspn2d_forward_history_f32(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(),
-                                            hist.data_ptr(), hb, B, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
-                                            ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_forward_history_f32")
-    return out, hist
+    return _forward2d_with_history("", guidance, blur_depth, sparse_depth, n_iter, norm_type)
 
 
 def cspn2d_backward_from_history(guidance, blur_depth, sparse_depth, grad_out, history, n_iter=24, norm_type="8sum",
                                  need_guidance=True, need_blur=True):
     """Gradients as cspn2d_backward, starting from the history a training-mode forward kept."""
-    lib = _lib.load()
-    B, _, H, W = guidance.shape
-    g = _prep(guidance, "guidance", (B, 8, H, W))
-    h = _prep(blur_depth, "blur_depth", (B, 1, H, W))
-    s = _prep(sparse_depth, "sparse_depth", (B, 1, H, W)) if sparse_depth is not None else None
-    go = _prep(grad_out, "grad_out", (B, 1, H, W))
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    if not (need_guidance or need_blur):
-        return gg, gh
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn2d_backward_history_workspace_bytes(B, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = lib.cspn2d_backward_history_f32(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(),
-                                             history.data_ptr(), history.numel(), gg.data_ptr() if gg is not None else None,
-                                             gh.data_ptr() if gh is not None else None, B, H, W, int(n_iter),
-                                             _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes,
-                                             torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_backward_history_f32")
-    return gg, gh
-
-
-# ---- C channels on shared 2D guidance (reference cspn.py:58-81 broadcasts the affinities over blur_depth's channels) ----
-def _multi_args(guidance, blur_depth, sparse_depth, extra=()):
-    if guidance.dim() != 4 or guidance.shape[1] != 8:
-        raise ValueError("guidance must be [B,8,H,W], got %s" % (tuple(guidance.shape),))
-    B, _, H, W = guidance.shape
-    if blur_depth.dim() != 4 or tuple(blur_depth.shape[:1]) + tuple(blur_depth.shape[2:]) != (B, H, W) or blur_depth.shape[1] < 1:
-        raise ValueError("blur_depth has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(blur_depth.shape), B, H, W))
-    C = blur_depth.shape[1]
-    g = _prep(guidance, "guidance")
-    h = _prep(blur_depth, "blur_depth", (B, C, H, W))
-    s, sc = None, 1
-    if sparse_depth is not None:
-        if sparse_depth.dim() != 4 or sparse_depth.shape[1] not in (1, C):
-            raise ValueError("sparse_depth has shape %s, expected (B,1,H,W) or (B,C,H,W) = (%d,%d,%d,%d)"
-                             % (tuple(sparse_depth.shape), B, C, H, W))
-        sc = sparse_depth.shape[1]
-        s = _prep(sparse_depth, "sparse_depth", (B, sc, H, W))
-    rest = [_prep(t, name, (B, C, H, W)) for t, name in extra]
-    if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
-        raise ValueError("all tensors must live on the same device")
-    return (g, h, s, sc, B, C, H, W) + tuple(rest)
+    return _backward2d("", guidance, blur_depth, sparse_depth, grad_out, history, n_iter, norm_type, need_guidance, need_blur)
 
 
 def cspn2d_multi_supported(B, C, H, W, n_iter):
     """True where C channels on shared guidance take the fast path (one ring launch per pass over the B*C image-channels)"""
-    return bool(_lib.late_symbol("cspn2d_multi_supported")(int(B), int(C), int(H), int(W), int(n_iter)))
+    return bool(_lib.symbol("cspn2d_multi_supported")(int(B), int(C), int(H), int(W), int(n_iter)))
 
 
 def cspn2d_forward_multi(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum", algo="auto"):
     """guidance [B,8,H,W], blur_depth [B,C,H,W], sparse_depth None, [B,1,H,W] (one mask for every channel) or [B,C,H,W] -> [B,C,H,W]:
     the C channels propagated on the same affinities (reference cspn.py:58-81), one engine call (cspn2d_forward_multi_f32)."""
-    g, h, s, sc, B, C, H, W = _multi_args(guidance, blur_depth, sparse_depth)
-    out = torch.empty_like(h)
-    if B == 0:
-        return out
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_workspace_bytes_multi")(B, C, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_forward_multi_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), B, C, sc, H, W, int(n_iter),
-            _lib.NORM_TYPES[norm_type], _lib.ALGOS[algo], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_forward_multi_f32")
-    return out
+    return _forward2d("_multi", guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
 
 
 def cspn2d_backward_multi(guidance, blur_depth, sparse_depth, grad_out, n_iter=24, norm_type="8sum", need_guidance=True, need_blur=True):
     """Gradient of cspn2d_forward_multi: -> (grad_guidance [B,8,H,W] summed over the C channels or None, grad_blur [B,C,H,W] or None);
     one engine call (cspn2d_backward_multi_f32)."""
-    g, h, s, sc, B, C, H, W, go = _multi_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    if B == 0 or not (need_guidance or need_blur):
-        return gg, gh
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_backward_multi_workspace_bytes")(B, C, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_backward_multi_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(), gg.data_ptr() if gg is not None else None,
-            gh.data_ptr() if gh is not None else None, B, C, sc, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes,
-            torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_backward_multi_f32")
-    return gg, gh
+    return _backward2d("_multi", guidance, blur_depth, sparse_depth, grad_out, None, n_iter, norm_type, need_guidance, need_blur)
 
 
 def cspn2d_history_bytes_multi(B, C, H, W, n_iter):
     """bytes of the training-mode history of C channels on shared guidance (0: not available for this shape)"""
-    return int(_lib.late_symbol("cspn2d_history_bytes_multi")(int(B), int(C), int(H), int(W), int(n_iter)))
+    return int(_lib.symbol("cspn2d_history_bytes_multi")(int(B), int(C), int(H), int(W), int(n_iter)))
 
 
 def cspn2d_forward_with_history_multi(guidance, blur_depth, sparse_depth=None, n_iter=24, norm_type="8sum"):
     """Training-mode cspn2d_forward_multi: (out [B,C,H,W], history) -- checkpoints and folded planes per image-channel."""
-    g, h, s, sc, B, C, H, W = _multi_args(guidance, blur_depth, sparse_depth)
-    out = torch.empty_like(h)
-    with torch.cuda.device(g.device):
-        hb = cspn2d_history_bytes_multi(B, C, H, W, n_iter)
-        if hb == 0:
-            raise _lib.CspnError("cspn_amd: no history mode for B=%d C=%d H=%d W=%d, n_iter %d" % (B, C, H, W, n_iter))
-        hist = torch.empty(hb, dtype=torch.uint8, device=g.device)
-        ws_bytes = _lib.late_symbol("cspn2d_workspace_bytes_multi")(B, C, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_forward_history_multi_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(), hist.data_ptr(), hb, B, C, sc, H, W,
-            int(n_iter), _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_forward_history_multi_f32")
-    return out, hist
+    return _forward2d_with_history("_multi", guidance, blur_depth, sparse_depth, n_iter, norm_type)
 
 
 def cspn2d_backward_from_history_multi(guidance, blur_depth, sparse_depth, grad_out, history, n_iter=24, norm_type="8sum",
                                        need_guidance=True, need_blur=True):
     """Gradients as cspn2d_backward_multi, starting from the history cspn2d_forward_with_history_multi kept."""
-    g, h, s, sc, B, C, H, W, go = _multi_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    if not (need_guidance or need_blur):
-        return gg, gh
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_backward_history_multi_workspace_bytes")(B, C, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn2d_backward_history_multi_f32")(
-            g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None, go.data_ptr(), history.data_ptr(), history.numel(),
-            gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None, B, C, sc, H, W, int(n_iter),
-            _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn2d_backward_history_multi_f32")
-    return gg, gh
+    return _backward2d("_multi", guidance, blur_depth, sparse_depth, grad_out, history, n_iter, norm_type, need_guidance, need_blur)
 
 
 def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", algo="auto", _return_ws=False):
     """gate [B,26,D,H,W], feat [B,1,D,H,W] -> [B,1,D,H,W]; n_iter 3x3x3 propagation steps.  algo: 'auto' | 'stepwise'
     (one launch per step) | 'persistent' (gates resident in registers across the steps; norm_type 'none' without a mask)."""
-    lib = _lib.load()
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
@@ -378,17 +312,13 @@ def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", alg
     out = torch.empty_like(h)
     if B == 0:
         return out
-    with torch.cuda.device(g.device):
-        if any(t.data_ptr() % 16 for t in (g, h, out)):   # misaligned views take the folding path: the full workspace
-            ws_bytes = lib.cspn3d_workspace_bytes(B, D, H, W, int(n_iter))
-        else:
-            ws_bytes = lib.cspn3d_workspace_bytes_ex(B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], int(s is not None))
-        ws = _workspace(ws_bytes, g.device)
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        rc = lib.cspn3d_forward_f32_algo(g.data_ptr(), h.data_ptr(), s.data_ptr() if s is not None else None,
-                                         out.data_ptr(), B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
-                                         _lib.ALGOS_3D[algo], ws.data_ptr(), ws_bytes, stream)
-    _lib.check(rc, "cspn3d_forward_f32")
+    if any(t.data_ptr() % 16 for t in (g, h, out)):   # misaligned views take the folding path: the full workspace
+        ws_query = ("cspn3d_workspace_bytes", B, D, H, W, int(n_iter))
+    else:
+        ws_query = ("cspn3d_workspace_bytes_ex", B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], int(s is not None))
+    ws = _launch("cspn3d_forward_f32_algo", g.device,
+                 (_ptr(g), _ptr(h), _ptr(s), _ptr(out), B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], _lib.ALGOS_3D[algo]),
+                 ws_query, "cspn3d_forward_f32")
     return (out, ws) if _return_ws else out
 
 
@@ -396,7 +326,6 @@ def cspn3d_forward_multi(gate, feat, n_iter=12):
     """gate [B,26,D,H,W] (used as given: the Paddle contract), feat [B,C,D,H,W] -> [B,C,D,H,W]: the C channels share the gates
     (reference cspn_paddle/README.md:56), which are read once per forward and stay in the registers while the n_iter steps run for
     one channel after the other.  Raises CspnError where the persistent kernel does not take the call (see cspn3d_multi_supported)."""
-    lib = _lib.load()
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
@@ -408,12 +337,8 @@ def cspn3d_forward_multi(gate, feat, n_iter=12):
     out = torch.empty_like(h)
     if B == 0:
         return out
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn3d_workspace_bytes_ex(B, D, H, W, int(n_iter), _lib.NORM_TYPES["none"], 0)
-        ws = _workspace(ws_bytes, g.device)
-        rc = lib.cspn3d_forward_multi_f32(g.data_ptr(), h.data_ptr(), out.data_ptr(), B, C, D, H, W, int(n_iter), ws.data_ptr(), ws_bytes,
-                                          torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn3d_forward_multi_f32")
+    _launch("cspn3d_forward_multi_f32", g.device, (_ptr(g), _ptr(h), _ptr(out), B, C, D, H, W, int(n_iter)),
+            ("cspn3d_workspace_bytes_ex", B, D, H, W, int(n_iter), _lib.NORM_TYPES["none"], 0))
     return out
 
 
@@ -421,48 +346,16 @@ def cspn3d_check_status(device=None):
     """Synchronises the current stream of `device` and raises CspnError if a persistent 3D launch gave up on it (its outputs are
     NaN-filled): the failure the C ABI can only report after the call has returned.  Every later cspn3d_* call raises it too
     (once) without a synchronisation; call this where a result is about to be trusted without another 3D call in between."""
-    lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    with torch.cuda.device(dev):
-        rc = lib.cspn3d_check_status(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "cspn3d_check_status")
+    _launch("cspn3d_check_status", dev, ())
 
 
-def cspn3d_backward(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
-    """Gradient of cspn3d_forward(gate, feat, None, n_iter, 'none') -- the Paddle contract, the op the reference demo's
-    optimiser differentiates (cspn_paddle/demo.py:65-75) -- w.r.t. gate and feat, in the HIP engine.
-    -> (grad_gate [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None)"""
-    lib = _lib.load()
+def _backward3d(variant, gate, feat, grad_out, n_iter, need_gate, need_feat):
+    """cspn3d_backward<variant>_f32: variant "" takes feat [B,1,D,H,W], "_multi" [B,C,D,H,W] on shared gates"""
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
-    g = _prep(gate, "gate")
-    h = _prep(feat, "feat", (B, 1, D, H, W))
-    go = _prep(grad_out, "grad_out", (B, 1, D, H, W))
-    gg = torch.empty_like(g) if need_gate else None
-    gf = torch.empty_like(h) if need_feat else None
-    if B == 0 or not (need_gate or need_feat):
-        return gg, gf
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn3d_backward_workspace_bytes(B, D, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        rc = lib.cspn3d_backward_f32(g.data_ptr(), h.data_ptr(), go.data_ptr(), gg.data_ptr() if gg is not None else None,
-                                     gf.data_ptr() if gf is not None else None, B, D, H, W, int(n_iter),
-                                     _lib.NORM_TYPES["none"], ws.data_ptr(), ws_bytes, stream)
-    _lib.check(rc, "cspn3d_backward_f32")
-    return gg, gf
-
-
-def cspn3d_backward_multi(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
-    """Gradient of the n_iter-step 3D propagation of C channels on SHARED gates (feat, grad_out [B,C,D,H,W]; reference
-    cspn_paddle/README.md:56, differentiated at demo.py:65-75) -> (grad_gate [B,26,D,H,W] summed over the channels or None,
-    grad_feat [B,C,D,H,W] or None); one call of the HIP engine (cspn3d_backward_multi_f32)."""
-    lib = _lib.load()
-    if gate.dim() != 5 or gate.shape[1] != 26:
-        raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
-    B, _, D, H, W = gate.shape
-    C = feat.shape[1]
+    C = feat.shape[1] if variant else 1
     g = _prep(gate, "gate")
     h = _prep(feat, "feat", (B, C, D, H, W))
     go = _prep(grad_out, "grad_out", (B, C, D, H, W))
@@ -472,70 +365,53 @@ def cspn3d_backward_multi(gate, feat, grad_out, n_iter=1, need_gate=True, need_f
     gf = torch.empty_like(h) if need_feat else None
     if B == 0 or not (need_gate or need_feat):
         return gg, gf
-    with torch.cuda.device(g.device):
-        ws_bytes = lib.cspn3d_backward_multi_workspace_bytes(B, C, D, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = lib.cspn3d_backward_multi_f32(g.data_ptr(), h.data_ptr(), go.data_ptr(), gg.data_ptr() if gg is not None else None,
-                                           gf.data_ptr() if gf is not None else None, B, C, D, H, W, int(n_iter),
-                                           ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn3d_backward_multi_f32")
+    dims = (B, C, D, H, W) if variant else (B, D, H, W)
+    _launch("cspn3d_backward%s_f32" % variant, g.device,
+            (_ptr(g), _ptr(h), _ptr(go), _ptr(gg), _ptr(gf), *dims, int(n_iter), *(() if variant else (_lib.NORM_TYPES["none"],))),
+            ("cspn3d_backward%s_workspace_bytes" % variant, *dims, int(n_iter)))
     return gg, gf
 
 
-class _AffinityPropagateMultiFunction(torch.autograd.Function):
-    """3D, C > 1 input channels on shared gates: forward and backward are one engine call each for all channels"""
-
-    @staticmethod
-    def forward(ctx, x, gate_weight, n_iter):
-        ctx.n_iter = int(n_iter)
-        ctx.save_for_backward(x, gate_weight)
-        if _lib.load().cspn3d_multi_supported(x.shape[0], x.shape[1], *x.shape[2:], int(n_iter)) and x.data_ptr() % 16 == 0 \
-                and gate_weight.data_ptr() % 16 == 0:
-            return cspn3d_forward_multi(gate_weight, x, n_iter)
-        return torch.cat([cspn3d_forward(gate_weight, x[:, c:c + 1].contiguous(), None, n_iter, "none") for c in range(x.shape[1])], 1)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        x, gate_weight = ctx.saved_tensors
-        gg, gx = cspn3d_backward_multi(gate_weight, x, grad_out, ctx.n_iter, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        return gx, gg, None
+def cspn3d_backward(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
+    """Gradient of cspn3d_forward(gate, feat, None, n_iter, 'none') -- the Paddle contract, the op the reference demo's
+    optimiser differentiates (cspn_paddle/demo.py:65-75) -- w.r.t. gate and feat, in the HIP engine.
+    -> (grad_gate [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None)"""
+    return _backward3d("", gate, feat, grad_out, n_iter, need_gate, need_feat)
 
 
-class _AffinityPropagate2dMultiFunction(torch.autograd.Function):
-    """2D, C > 1 input channels on shared gates: cspn2d_forward_multi / cspn2d_backward_multi (the gate gradient summed in the engine)"""
-
-    @staticmethod
-    def forward(ctx, x, gate_weight, n_iter):
-        ctx.n_iter = int(n_iter)
-        ctx.save_for_backward(x, gate_weight)
-        return cspn2d_forward_multi(gate_weight, x, None, n_iter, "none")
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        x, gate_weight = ctx.saved_tensors
-        gg, gx = cspn2d_backward_multi(gate_weight, x, None, grad_out, ctx.n_iter, "none", ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        return gx, gg, None
+def cspn3d_backward_multi(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
+    """Gradient of the n_iter-step 3D propagation of C channels on SHARED gates (feat, grad_out [B,C,D,H,W]; reference
+    cspn_paddle/README.md:56, differentiated at demo.py:65-75) -> (grad_gate [B,26,D,H,W] summed over the channels or None,
+    grad_feat [B,C,D,H,W] or None); one call of the HIP engine (cspn3d_backward_multi_f32)."""
+    return _backward3d("_multi", gate, feat, grad_out, n_iter, need_gate, need_feat)
 
 
 class _AffinityPropagateFunction(torch.autograd.Function):
-    """n_iter chained propagation steps with the same gates, one input channel; differentiable w.r.t. both arguments."""
+    """n_iter chained 3 x 3 (x 3) propagation steps of C >= 1 input channels on shared gates, differentiable w.r.t. both arguments: one engine call
+    each way for all channels (the gate gradient summed in the engine), but for the 3D forward where the persistent kernel does not take them"""
 
     @staticmethod
     def forward(ctx, x, gate_weight, n_iter):
         ctx.n_iter = int(n_iter)
         ctx.save_for_backward(x, gate_weight)
+        C = x.shape[1]
         if x.dim() == 4:
-            return cspn2d_forward(gate_weight, x, None, n_iter, "none")
-        return cspn3d_forward(gate_weight, x, None, n_iter, "none")
+            return (cspn2d_forward if C == 1 else cspn2d_forward_multi)(gate_weight, x, None, n_iter, "none")
+        if C == 1:
+            return cspn3d_forward(gate_weight, x, None, n_iter, "none")
+        if _lib.symbol("cspn3d_multi_supported")(x.shape[0], C, *x.shape[2:], int(n_iter)) and x.data_ptr() % 16 == 0 \
+                and gate_weight.data_ptr() % 16 == 0:
+            return cspn3d_forward_multi(gate_weight, x, n_iter)
+        return torch.cat([cspn3d_forward(gate_weight, x[:, c:c + 1].contiguous(), None, n_iter, "none") for c in range(C)], 1)
 
     @staticmethod
     def backward(ctx, grad_out):
         x, gate_weight = ctx.saved_tensors
         need_x, need_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if x.dim() == 4:
-            gg, gx = cspn2d_backward(gate_weight, x, None, grad_out, ctx.n_iter, "none", need_g, need_x)
+            gg, gx = (cspn2d_backward if x.shape[1] == 1 else cspn2d_backward_multi)(gate_weight, x, None, grad_out, ctx.n_iter, "none", need_g, need_x)
         else:
-            gg, gx = cspn3d_backward(gate_weight, x, grad_out, ctx.n_iter, need_g, need_x)
+            gg, gx = (cspn3d_backward if x.shape[1] == 1 else cspn3d_backward_multi)(gate_weight, x, grad_out, ctx.n_iter, need_g, need_x)
         return gx, gg, None
 
 
@@ -599,20 +475,14 @@ def _kxk_forward(gate, x, kernel_size, n_iter, return_history, contract):
     hist = None
     if out.numel() == 0:
         return (out, None) if return_history else out
-    with torch.cuda.device(g.device):
-        if return_history:
-            hb = _lib.late_symbol("cspn2d_kxk_history_bytes")(N, C, H, W, K, n)
-            hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-            ws_bytes, ws = 0, None
-        else:
-            hb = 0
-            ws_bytes = _lib.late_symbol("cspn2d_kxk_workspace_bytes")(N, C, H, W, K, n)
-            ws = _workspace(ws_bytes, g.device)
-        name = "cspn2d_forward_kxk%s_%s" % (contract, "f32" if dt is None else "g16")
-        rc = _lib.late_symbol(name)(
-            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), out.data_ptr(), hist.data_ptr() if hist is not None else None, hb,
-            N, C, H, W, K, n, ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, name)
+    hb = 0
+    if return_history:   # the levels go to the history: no workspace
+        with torch.cuda.device(g.device):
+            hb = _lib.symbol("cspn2d_kxk_history_bytes")(N, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    args = (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(out), _ptr(hist), hb, N, C, H, W, K, n)
+    _launch("cspn2d_forward_kxk%s_%s" % (contract, "f32" if dt is None else "g16"), g.device, args + ((None, 0) if return_history else ()),
+            None if return_history else ("cspn2d_kxk_workspace_bytes", N, C, H, W, K, n))
     return (out, hist) if return_history else out
 
 
@@ -638,16 +508,10 @@ def _kxk_backward(gate, x, grad_out, kernel_size, n_iter, history, need_gate, ne
         return (gg.zero_() if gg is not None else None), gx
     if need_gate and n >= 2 and history is None:
         _, history = _kxk_forward(g, h, K, n, True, contract)
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk%s_workspace_bytes" % contract)(N, C, H, W, K, n)
-        ws = _workspace(ws_bytes, g.device)
-        hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
-        name = "cspn2d_backward_kxk%s_%s" % (contract, "f32" if dt is None else "g16")
-        rc = _lib.late_symbol(name)(
-            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), hp, hb, go.data_ptr(), gg.data_ptr() if gg is not None else None,
-            gx.data_ptr() if gx is not None else None, N, C, H, W, K, n, ws.data_ptr(), ws_bytes,
-            torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, name)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    _launch("cspn2d_backward_kxk%s_%s" % (contract, "f32" if dt is None else "g16"), g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gx), N, C, H, W, K, n),
+            ("cspn2d_backward_kxk%s_workspace_bytes" % contract, N, C, H, W, K, n))
     return gg, gx
 
 
@@ -720,16 +584,16 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     needs_grad = torch.is_grad_enabled() and (input.requires_grad or gate_weight.requires_grad)
     if input.device != gate_weight.device:
         raise ValueError("all tensors must live on the same device")
-    if d == 3 and C > 1 and not needs_grad and input.is_cuda and _lib.load().cspn3d_multi_supported(N, C, *input.shape[2:], int(n_iter)) \
+    if d == 3 and C > 1 and not needs_grad and input.is_cuda and _lib.symbol("cspn3d_multi_supported")(N, C, *input.shape[2:], int(n_iter)) \
             and input.is_contiguous() and gate_weight.is_contiguous() and input.data_ptr() % 16 == 0 and gate_weight.data_ptr() % 16 == 0:
         return cspn3d_forward_multi(gate_weight, input, n_iter)   # the gates are read once for all C channels
     if d == 3 and C > 1 and needs_grad and input.is_cuda:
         # training through C channels on shared gates (demo.py:65-75): one forward and one backward call for all of them
-        return _AffinityPropagateMultiFunction.apply(input.contiguous(), gate_weight.contiguous(), n_iter)
+        return _AffinityPropagateFunction.apply(input.contiguous(), gate_weight.contiguous(), n_iter)
     if d == 2 and C > 1:
         # C channels on shared gates (README.md:56): one forward and one backward engine call for all of them
         if needs_grad:
-            return _AffinityPropagate2dMultiFunction.apply(input, gate_weight, n_iter)
+            return _AffinityPropagateFunction.apply(input, gate_weight, n_iter)
         return cspn2d_forward_multi(gate_weight, input, None, n_iter, "none")
     outs = []
     for c in range(C):  # gates shared across channels (README.md:56)
@@ -800,19 +664,15 @@ def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size
     hist = None
     if out.numel() == 0:
         return (out, None) if return_history else out
-    with torch.cuda.device(g.device):
-        hb = _lib.late_symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n) if return_history else 0
-        if return_history:
-            hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-        # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
-        ws_bytes = _lib.late_symbol("cspn2d_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, 1 if return_history else n)
-        ws = _workspace(ws_bytes, g.device)
-        name = "cspn2d_forward_kxk_norm_f32" if dt is None else "cspn2d_forward_kxk_norm_g16"
-        rc = _lib.late_symbol(name)(
-            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), s.data_ptr() if s is not None else None, out.data_ptr(),
-            hist.data_ptr() if hist is not None else None, hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes,
-            torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, name)
+    hb = 0
+    if return_history:
+        with torch.cuda.device(g.device):
+            hb = _lib.symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
+    _launch("cspn2d_forward_kxk_norm_f32" if dt is None else "cspn2d_forward_kxk_norm_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_kxk_norm_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
     return (out, hist) if return_history else out
 
 
@@ -836,16 +696,11 @@ def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kerne
         return (gg.zero_() if gg is not None else None), gh
     if need_guidance and n >= 2 and history is None:
         _, history = cspn2d_forward_kxk_norm(g, h, s, K, n, norm_type, return_history=True)
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn2d_backward_kxk_norm_workspace_bytes")(B, C, sc, H, W, K, n)
-        ws = _workspace(ws_bytes, g.device)
-        hp, hb = (history.data_ptr(), history.numel() * history.element_size()) if history is not None else (None, 0)
-        name = "cspn2d_backward_kxk_norm_f32" if dt is None else "cspn2d_backward_kxk_norm_g16"
-        rc = _lib.late_symbol(name)(
-            g.data_ptr(), *(() if dt is None else (dt,)), h.data_ptr(), s.data_ptr() if s is not None else None, hp, hb, go.data_ptr(),
-            gg.data_ptr() if gg is not None else None, gh.data_ptr() if gh is not None else None, B, C, sc, H, W, K, n,
-            _lib.NORM_TYPES[norm_type], ws.data_ptr(), ws_bytes, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, name)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    _launch("cspn2d_backward_kxk_norm_f32" if dt is None else "cspn2d_backward_kxk_norm_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), B, C, sc, H, W, K, n,
+             _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
     return gg, gh
 
 
@@ -871,9 +726,7 @@ def _gate_absnorm(guide, K):
     out = torch.empty_like(g)
     if out.numel() == 0:
         return out
-    with torch.cuda.device(g.device):
-        rc = _lib.late_symbol("cspn_gate_absnorm_f32")(g.data_ptr(), out.data_ptr(), S, K, V, torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn_gate_absnorm_f32")
+    _launch("cspn_gate_absnorm_f32", g.device, (_ptr(g), _ptr(out), S, K, V))
     return out
 
 
@@ -888,10 +741,7 @@ def gate_absnorm_backward(guide, grad_gate, K):
     out = torch.empty_like(g)
     if out.numel() == 0:
         return out
-    with torch.cuda.device(g.device):
-        rc = _lib.late_symbol("cspn_gate_absnorm_backward_f32")(g.data_ptr(), r.data_ptr(), out.data_ptr(), S, K, V,
-                                                                torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn_gate_absnorm_backward_f32")
+    _launch("cspn_gate_absnorm_backward_f32", g.device, (_ptr(g), _ptr(r), _ptr(out), S, K, V))
     return out
 
 
@@ -936,13 +786,8 @@ def cspn3d_forward_absnorm(guide, feat, n_iter=12, algo="auto"):
     out = torch.empty_like(h)
     if B == 0:
         return out
-    with torch.cuda.device(g.device):
-        ws_bytes = _lib.late_symbol("cspn3d_forward_absnorm_workspace_bytes")(B, D, H, W, int(n_iter))
-        ws = _workspace(ws_bytes, g.device)
-        rc = _lib.late_symbol("cspn3d_forward_absnorm_f32")(g.data_ptr(), h.data_ptr(), out.data_ptr(), B, D, H, W, int(n_iter),
-                                                            _lib.ALGOS_3D[algo], ws.data_ptr(), ws_bytes,
-                                                            torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn3d_forward_absnorm_f32")
+    _launch("cspn3d_forward_absnorm_f32", g.device, (_ptr(g), _ptr(h), _ptr(out), B, D, H, W, int(n_iter), _lib.ALGOS_3D[algo]),
+            ("cspn3d_forward_absnorm_workspace_bytes", B, D, H, W, int(n_iter)))
     return out
 
 

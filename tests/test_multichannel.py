@@ -290,3 +290,48 @@ def test_module_rejects_mismatched_sparse_channels():
         m(g, h, s)
     with pytest.raises(ValueError):
         m(g, h[:, :, :, :-1], None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", [1, 2])
+def test_merged_autograd_functions_are_bitwise_the_public_functional_calls(C):
+    """The one autograd Function behind Affinity_Propagate (one channel and C > 1, with and without the kept history) and the one behind the
+    3 x 3 affinity_propagate against the public functional call each path stands for: the same engine calls, so no tolerance.  The forward
+    that keeps a history is compared with cspn2d_forward_with_history[_multi], whose output differs from the plain forward's in the
+    summation order (test_training_mode_multi_is_bitwise_the_recomputing_path)."""
+    sfx = "_multi" if C > 1 else ""
+    fn = lambda name: getattr(F, name + sfx)   # noqa: E731
+    for (B, H, W), has_history in (((2, 64, 512), True), ((1, 17, 30), False)):
+        hb = F.cspn2d_history_bytes_multi(B, C, H, W, 24) if C > 1 else F.cspn2d_history_bytes(B, H, W, 24)
+        assert (hb > 0) == has_history
+        for sparse in (None, "shared"):
+            g, h, s = _dev(*_inputs(B, C, H, W, seed=91, sparse=sparse))
+            go = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(5)).cuda()
+            for keep in (True, False):
+                m = cspn_amd.Affinity_Propagate(24, 3)
+                m.keep_history = keep
+                gd, hd = g.clone().requires_grad_(True), h.clone().requires_grad_(True)
+                out = m(gd, hd, s)
+                out.backward(go)
+                if keep and has_history:
+                    ref, hist = fn("cspn2d_forward_with_history")(g, h, s, 24, "8sum")
+                    rg, rh = fn("cspn2d_backward_from_history")(g, h, s, go, hist, 24, "8sum")
+                else:
+                    ref = fn("cspn2d_forward")(g, h, s, 24, "8sum")
+                    rg, rh = fn("cspn2d_backward")(g, h, s, go, 24, "8sum")
+                assert torch.equal(out, ref) and torch.equal(gd.grad, rg) and torch.equal(hd.grad, rh)
+    if C == 1:
+        return
+    # the NONE op on C = 2 channels, 2D and 3D: the merged Function calls the multi-channel backward
+    for shape, K, backward in (((2, 2, 17, 30), 8, lambda gate, x, go, n: F.cspn2d_backward_multi(gate, x, None, go, n, "none")),
+                               ((1, 2, 4, 8, 8), 26, F.cspn3d_backward_multi)):
+        gen = torch.Generator().manual_seed(93)
+        gate = torch.rand(shape[0], K, *shape[2:], generator=gen)
+        gate = (gate / gate.sum(1, keepdim=True)).cuda()
+        x = torch.rand(*shape, generator=gen).cuda()
+        go = torch.randn(*shape, generator=gen).cuda()
+        for n in (1, 3):
+            gt, xt = gate.clone().requires_grad_(True), x.clone().requires_grad_(True)
+            cspn_amd.affinity_propagate(xt, gt, 3, n).backward(go)
+            rg, rx = backward(gate, x, go, n)
+            assert torch.equal(gt.grad, rg) and torch.equal(xt.grad, rx)
