@@ -131,6 +131,11 @@ _SYMBOLS.update({
     "cspn_guidance_head_kxk_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 7 + _WS),
     "cspn_guidance_head_kxk_backward_g16_workspace_bytes": (c_size_t, [c_int] * 5),
     "cspn_guidance_head_kxk_backward_g16": (c_int, [vp, c_int] + [vp] * 7 + [c_int] * 7 + _WS),
+    # the 8-plane head + the blur head on an fp16 / bf16 feature map, feeding the float32 rings: 16-bit x and dL/dx; float32 guidance, blur, their gradients, dL/dW
+    "cspn_guidance_head_g16_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn_guidance_head_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn_guidance_head_backward_g16_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn_guidance_head_backward_g16": (c_int, [vp, c_int] + [vp] * 7 + [c_int] * 6 + _WS),
 })
 _LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
 

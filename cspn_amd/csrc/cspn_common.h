@@ -142,6 +142,14 @@ int head_kxk_g16_forward(const void* x, int dtype, const float* wg, const float*
 size_t head_kxk_g16_backward_workspace(int B, int C, int h, int w, int K);
 int head_kxk_g16_backward(const void* x, int dtype, const float* wg, const float* wb, const void* gg, const float* gb, void* dx, float* dwg, float* dwb, int B,
                           int C, int h, int w, int H, int W, int K, void* ws, hipStream_t st);
+// the 8-plane head + the blur head on fp16 / bf16 x and dL/dx (cspn_head_g16.hip): guidance, blur and their gradients float32 (the gradients rounded once as
+// they enter the GEMMs), float32 master weights rounded once per call, float32 weight gradients
+size_t head_g16_workspace(int C);
+int head_g16_forward(const void* x, int dtype, const float* wg, const float* wb, float* gout, float* bout, int B, int C, int h, int w, int H, int W, void* ws,
+                     hipStream_t st);
+size_t head_g16_backward_workspace(int B, int C, int h, int w);
+int head_g16_backward(const void* x, int dtype, const float* wg, const float* wb, const float* gg, const float* gb, void* dx, float* dwg, float* dwb, int B, int C,
+                      int h, int w, int H, int W, void* ws, hipStream_t st);
 
 // ---- fused path (all iterations in one launch; time-skewed wave ring) ----
 bool fused2d_supported(int B, int H, int W, int n_iter);

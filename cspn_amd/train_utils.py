@@ -206,7 +206,26 @@ def _head_dtype16(x, weight_guidance, weight_blur, P):
         return None
     if P == 8:
         raise TypeError("the 3 x 3 guidance head (weight_guidance [8, C, 3, 3]) is float32 only: its ring has no 16-bit consumer; x is %s -- pass x.float(), "
-                        "or use the 24- / 48-plane heads of prop_kernel 5 / 7" % (x.dtype,))
+                        "or use the 24- / 48-plane heads of prop_kernel 5 / 7 (guidance_dtype=torch.float32, or cspn_amd.GuidanceHeads, runs the 16-bit head that emits "
+                        "float32 guidance)" % (x.dtype,))
+    for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
+        if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
+            raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
+    return x.dtype
+
+
+def _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type=None):
+    """guidance_dtype given -> the 16-bit dtype of x: the 8-plane head on a float16 / bfloat16 x that emits float32 guidance (cspn_guidance_head_g16).  Raised
+    before any device check: ValueError for every other combination, TypeError for 16-bit weights whose dtype differs from x's"""
+    if guidance_dtype is not torch.float32:
+        raise ValueError("guidance_dtype must be None or torch.float32, got %r" % (guidance_dtype,))
+    if P != 8:
+        raise ValueError("guidance_dtype=torch.float32 is the 8-plane head's (prop_kernel 3); the %d-plane head of prop_kernel %d returns its guidance in the "
+                         "dtype of x" % (P, _PLANES_TO_K[P]))
+    if x.dtype not in _GATE16:
+        raise ValueError("guidance_dtype=torch.float32 is for a float16 / bfloat16 x; x is %s (a float32 x takes the default guidance_dtype=None)" % (x.dtype,))
+    if norm_type is not None:
+        raise ValueError("the 16-bit 8-plane head returns raw guidance only (norm_type=None): Affinity_Propagate(prop_time, 3, norm_type) normalises it")
     for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
         if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
             raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
@@ -248,15 +267,69 @@ def _heads_forward(xx, wg, wb, H, W, norm):
     return g, b
 
 
-def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad_blur, need_x=True, need_w=True):
+def _heads16_forward(xx, wg, wb, H, W):
+    """cspn_guidance_head_g16: the 8-plane guidance head and the blur head, raw, on a float16 / bfloat16 xx; float32 weights (rounded once to xx's dtype in the
+    engine) -> guidance and blur in float32, the unrounded accumulators"""
+    B, C, h, w = xx.shape
+    g = torch.empty(B, 8, H, W, dtype=torch.float32, device=xx.device)
+    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.symbol("cspn_guidance_head_g16_workspace_bytes")(B, C, h, w)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.symbol("cspn_guidance_head_g16")(xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
+                                                   b.data_ptr() if b is not None else None, B, C, h, w, H, W, ws.data_ptr(), wsb,
+                                                   torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_g16")
+    return g, b
+
+
+def _heads16_backward(xx, wg, wb, gg, gb, need_x, need_w):
+    """cspn_guidance_head_backward_g16: float32 dL/dguidance and dL/dblur (rounded once to xx's dtype as they enter the GEMMs) -> dL/dx in xx's dtype, the
+    weight gradients float32"""
+    B, C, h, w = xx.shape
+    H, W = int(gg.shape[2]), int(gg.shape[3])
+    dx = torch.empty_like(xx) if need_x else None
+    dwg = torch.empty_like(wg) if need_w else None
+    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
+    with torch.cuda.device(xx.device):
+        wsb = _lib.symbol("cspn_guidance_head_backward_g16_workspace_bytes")(B, C, h, w)
+        ws = _workspace(wsb, xx.device)
+        rc = _lib.symbol("cspn_guidance_head_backward_g16")(
+            xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
+            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
+            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
+    _lib.check(rc, "cspn_guidance_head_backward_g16")
+    return dx, dwg, dwb
+
+
+def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad_blur, need_x=True, need_w=True, guidance_dtype=None):
     """cspn_guidance_head_backward_f32: (dL/dx, dL/dweight_guidance, dL/dweight_blur) of the RAW heads -- what torch autograd computes through the two reference
     layers (torch_resnet_cspn_nyu.py:187-206) -- from dL/dguidance [B,8,H,W] and dL/dblur [B,1,H,W] (None without a blur head); skipped outputs are None.
     weight_guidance [24 | 48, C, 3, 3] with dL/dguidance [B, 24 | 48, H, W]: cspn_guidance_head_kxk_backward_f32, the heads of prop_kernel 5 / 7.
     With those weights x may be float16 / bfloat16 = dt (cspn_guidance_head_kxk_backward_g16): grad_guidance is dt (what cspn2d_backward_kxk_norm returns for a
     dt guidance), grad_blur is float32 and is ROUNDED ONCE TO dt as it enters the GEMMs (what a 16-bit convolution's backward would have received); dL/dx comes
-    back in dt (rounded once), the weight gradients in float32 (the accumulators) -- or in dt, the float32 ones .to(dt), for weights that are dt themselves."""
+    back in dt (rounded once), the weight gradients in float32 (the accumulators) -- or in dt, the float32 ones .to(dt), for weights that are dt themselves.
+    guidance_dtype=torch.float32 with a dt x and the 8-plane weights (cspn_guidance_head_backward_g16): grad_guidance AND grad_blur are float32 (what
+    cspn2d_backward returns) and are both rounded once to dt as they enter the GEMMs; the outputs as above.  Any other use of guidance_dtype: ValueError."""
     lib = _lib.load()
     P = _head_planes(x, weight_guidance, weight_blur, grad_guidance, grad_blur)
+    if guidance_dtype is not None:
+        dt = _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype)
+        xx = _prep16(x, "x", dt)
+        B, C, h, w = xx.shape
+        wg = _prep_w16(weight_guidance, "weight_guidance", dt, (8, C, 3, 3))
+        wb = _prep_w16(weight_blur, "weight_blur", dt, (1, C, 3, 3)) if weight_blur is not None else None
+        if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
+            raise ValueError("grad_guidance must be [B,8,H,W]")
+        H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
+        gg = _prep(grad_guidance, "grad_guidance", (B, 8, H, W))
+        gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
+        dx, dwg, dwb = _heads16_backward(xx, wg, wb, gg, gb, need_x, need_w)
+        if dwg is not None and weight_guidance.dtype == dt:
+            dwg = dwg.to(dt)
+        if dwb is not None and weight_blur.dtype == dt:
+            dwb = dwb.to(dt)
+        return dx, dwg, dwb
     dt = _head_dtype16(x, weight_guidance, weight_blur, P)
     if dt is not None:
         xx = _prep16(x, "x", dt)
@@ -361,7 +434,30 @@ class _GuidanceHeadsKxK16Function(torch.autograd.Function):
                 dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
 
 
-def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, norm_type=None):
+class _GuidanceHeads16Function(torch.autograd.Function):
+    """the 8-plane guidance head + the blur head on a float16 / bfloat16 x, float32 guidance and blur: cspn_guidance_head_g16 and its backward.  wg / wb:
+    float32 master weights, or weights of x's dtype (widened exactly; their gradients are the float32 ones .to(dtype))"""
+
+    @staticmethod
+    def forward(ctx, x, wg, wb, H, W):
+        ctx.save_for_backward(x, wg, wb)
+        return _heads16_forward(x, wg.float(), wb.float() if wb is not None else None, H, W)
+
+    @staticmethod
+    def backward(ctx, grad_g, grad_b):
+        x, wg, wb = ctx.saved_tensors
+        if grad_g is None:
+            grad_g = torch.zeros(x.shape[0], 8, grad_b.shape[2], grad_b.shape[3], dtype=torch.float32, device=x.device)
+        if wb is not None and grad_b is None:
+            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], dtype=torch.float32, device=x.device)
+        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
+        dx, dwg, dwb = _heads16_backward(x, wg.float(), wb.float() if wb is not None else None, grad_g.float().contiguous(),
+                                         grad_b.float().contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
+        return (dx, dwg.to(wg.dtype) if ctx.needs_input_grad[1] else None,
+                dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
+
+
+def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, norm_type=None, guidance_dtype=None):
     """The producer of the propagation's inputs: what the reference computes as
         guidance = self.gud_up_proj_layer6(x); x = self.gud_up_proj_layer5(x)          (torch_resnet_cspn_nyu.py:372-373)
     with both heads Simple_Gudi_UpConv_Block_Last_Layer (:187-206: Unpool + narrow to (oheight, owidth) + bias-free 3x3 conv), in ONE kernel that never
@@ -379,8 +475,27 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     the float32 master weights (rounded once to dt in the engine) or dt weights (passed as .float(), exact; their gradients come back .to(dt)); products of two
     dt values accumulate in float32 on the matrix cores; guidance comes back in dt (the accumulator rounded once) -- what Affinity_PropagateKxK takes as it is
     --, blur in float32 (the accumulator: the engine's value tensors are float32); dL/dx comes back in dt.  A dt that differs between x and 16-bit weights
-    raises TypeError, and so does a 16-bit x with the 8-plane weights: the 3 x 3 head is float32 only."""
+    raises TypeError, and so does a 16-bit x with the 8-plane weights: the 3 x 3 head is float32 only -- by default.
+    guidance_dtype=torch.float32 with a dt x and the 8-plane weights (cspn_guidance_head_g16; what cspn_amd.GuidanceHeads calls): the same contract for the
+    weights and the sums, and guidance AND blur come back in float32, the unrounded accumulators -- what Affinity_Propagate(prop_time, 3, norm_type) takes as it
+    is, with no x.float() before the head and no widening pass behind it; dL/dx comes back in dt.  Raw only.  Any other use of guidance_dtype (24 / 48 planes, a
+    float32 x, another dtype, a norm_type) raises ValueError."""
     P = _head_planes(x, weight_guidance, weight_blur)
+    if guidance_dtype is not None:
+        dt = _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type)
+        xx = _prep16(x, "x", dt)
+        B, C, h, w = xx.shape
+        H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
+        for t, name, shape in ((weight_guidance, "weight_guidance", (8, C, 3, 3)), (weight_blur, "weight_blur", (1, C, 3, 3))):
+            if t is not None and t.dtype == dt:
+                _prep16(t, name, dt, shape)
+            elif t is not None:
+                _prep(t, name, shape)
+        wg = weight_guidance.contiguous()
+        wb = weight_blur.contiguous() if weight_blur is not None else None
+        if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
+            return _GuidanceHeads16Function.apply(xx, wg, wb, H, W)
+        return _heads16_forward(xx, wg.float(), wb.float() if wb is not None else None, H, W)
     dt = _head_dtype16(x, weight_guidance, weight_blur, P)
     if P != 8:
         if norm_type is not None:
@@ -439,3 +554,57 @@ def _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth,
     H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
     g, b = _GuidanceHeadsFunction.apply(xx, wg, wb, H, W)
     return cspn2d_normalize(g, norm_type), b
+
+
+class GuidanceHeads(nn.Module):
+    """Both Simple_Gudi_UpConv_Block_Last_Layer heads of the reference model (torch_resnet_cspn_nyu.py:187-206, :318-319: gud_up_proj_layer6 C -> K*K-1 and
+    gud_up_proj_layer5 C -> 1) as one module that owns the two bias-free 3x3 weights: forward(x) -> (guidance, blur), the inputs of
+    Affinity_Propagate(prop_time, 3, ...) / Affinity_PropagateKxK(prop_time, 5 | 7, ...).  weight_guidance [K*K-1, C, 3, 3] and weight_blur [1, C, 3, 3] (absent
+    with blur=False) are float32 parameters initialised as nn.Conv2d initialises; the path is chosen by the dtype of x and the plane count:
+        float32 x                      guidance_heads as it is                 -> float32 guidance, float32 blur
+        float16 / bfloat16 x, K 5 | 7  the 16-bit 24- / 48-plane heads         -> guidance in x's dtype, float32 blur
+        float16 / bfloat16 x, K 3      guidance_heads(guidance_dtype=float32)  -> float32 guidance, float32 blur (no x.float(), no widening pass)
+    so a backbone under torch.autocast hands its feature map over as it is.  Differentiable w.r.t. x and both weights, one autograd Function per path."""
+
+    def __init__(self, in_channels, prop_kernel=3, oheight=0, owidth=0, blur=True):
+        super(GuidanceHeads, self).__init__()
+        if prop_kernel not in (3, 5, 7):
+            raise ValueError("prop_kernel must be 3, 5 or 7, got %r" % (prop_kernel,))
+        self.in_channels, self.prop_kernel = int(in_channels), int(prop_kernel)
+        self.oheight, self.owidth = int(oheight), int(owidth)
+        # (what nn.Conv2d(C, planes, 3, bias=False).reset_parameters() does)
+        self.weight_guidance = nn.Parameter(torch.empty(prop_kernel * prop_kernel - 1, self.in_channels, 3, 3))
+        nn.init.kaiming_uniform_(self.weight_guidance, a=5 ** 0.5)
+        if blur:
+            self.weight_blur = nn.Parameter(torch.empty(1, self.in_channels, 3, 3))
+            nn.init.kaiming_uniform_(self.weight_blur, a=5 ** 0.5)
+        else:
+            self.register_parameter("weight_blur", None)
+
+    @classmethod
+    def from_reference(cls, layer_guidance, layer_blur=None):
+        """from the reference model's two layers (anything with .conv1.weight, .oheight and .owidth): copies of their weights and their output size"""
+        wg = layer_guidance.conv1.weight
+        planes, C = int(wg.shape[0]), int(wg.shape[1])
+        if planes not in _PLANES_TO_K or tuple(wg.shape[2:]) != (3, 3):
+            raise ValueError("layer_guidance.conv1.weight must be [8 | 24 | 48, C, 3, 3], got %s" % (tuple(wg.shape),))
+        if layer_blur is not None:
+            if tuple(layer_blur.conv1.weight.shape) != (1, C, 3, 3):
+                raise ValueError("layer_blur.conv1.weight must be [1, %d, 3, 3], got %s" % (C, tuple(layer_blur.conv1.weight.shape)))
+            if (int(layer_blur.oheight), int(layer_blur.owidth)) != (int(layer_guidance.oheight), int(layer_guidance.owidth)):
+                raise ValueError("the two layers narrow to different output sizes")
+        m = cls(C, _PLANES_TO_K[planes], layer_guidance.oheight, layer_guidance.owidth, blur=layer_blur is not None)
+        with torch.no_grad():
+            m.weight_guidance.copy_(wg)
+            if layer_blur is not None:
+                m.weight_blur.copy_(layer_blur.conv1.weight)
+        return m.to(wg.device)
+
+    def forward(self, x):
+        f32_guidance = isinstance(x, torch.Tensor) and x.dtype in _GATE16 and self.prop_kernel == 3
+        return guidance_heads(x, self.weight_guidance, self.weight_blur, self.oheight, self.owidth,
+                              guidance_dtype=torch.float32 if f32_guidance else None)
+
+    def extra_repr(self):
+        return "in_channels=%d, prop_kernel=%d, oheight=%d, owidth=%d, blur=%s" % (self.in_channels, self.prop_kernel, self.oheight, self.owidth,
+                                                                                   self.weight_blur is not None)

@@ -51,7 +51,8 @@ extern "C" {
                               *    (cspn2d_*_kxk*, K = 5 / 7), K = 24 / 48 on the gate normaliser and the depth-completion contract over
                               *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*),
                               *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*), the demo module's
-                              *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*) */
+                              *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*), the 8-plane heads on a 16-bit feature map with float32 guidance
+                              *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -463,7 +464,7 @@ int cspn_guidance_head_kxk_backward_f32(const float* x, const float* w_guidance,
                                         void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the same heads on a 16-bit feature map (what a backbone under autocast hands over), dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16 = DT, K = 5 or 7 only (the
- * 8-plane head of K = 3 is float32 only: its ring has no 16-bit consumer) -- the producer of what cspn2d_forward_kxk_norm_g16 consumes.
+ * 8-plane head of K = 3 has no 16-bit guidance, its ring has no 16-bit consumer: cspn_guidance_head_g16 below) -- the producer of what cspn2d_forward_kxk_norm_g16 consumes.
  *   x [B,C,h,w], guidance_out / grad_guidance [B,K*K-1,H,W] and grad_x [B,C,h,w] are DT;  w_guidance, w_blur (the master weights), blur_out / grad_blur
  *   [B,1,H,W] and grad_w_guidance / grad_w_blur are float32.
  *   The weights are rounded once to DT (to nearest even) in the per-call repack; every product is of two DT values, exact in float32; the sums accumulate in
@@ -481,6 +482,28 @@ size_t cspn_guidance_head_kxk_backward_g16_workspace_bytes(int B, int C, int h, 
 int cspn_guidance_head_kxk_backward_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, const void* grad_guidance,
                                         const float* grad_blur, void* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w,
                                         int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the 3 x 3 model's heads (8 guidance planes + the blur plane, raw) on a 16-bit feature map, dtype CSPN_DTYPE_F16 or CSPN_DTYPE_BF16 = DT, feeding the
+ * float32 rings: the producer of what cspn2d_forward_f32 / Affinity_Propagate consume, with no widening pass on either side.
+ *   x [B,C,h,w] and grad_x [B,C,h,w] are DT;  w_guidance [8,C,3,3], w_blur [1,C,3,3] (the master weights), guidance_out / grad_guidance [B,8,H,W], blur_out /
+ *   grad_blur [B,1,H,W] and grad_w_guidance / grad_w_blur are float32.
+ *   The weights are rounded once to DT (to nearest even) in the per-call repack; every product is of two DT values, exact in float32; the sums accumulate in
+ *   float32 on the matrix cores (v_mfma_f32_16x16x32_f16 / _bf16 forward, v_mfma_f32_32x32x16 backward).  guidance_out and blur_out are the accumulators,
+ *   UNROUNDED.  grad_guidance and grad_blur arrive in float32 (what cspn2d_backward_f32 returns) and are ROUNDED ONCE TO DT as they enter the GEMMs -- what a
+ *   16-bit convolution's backward would have received; grad_x is the float32 accumulator rounded once to DT at its single store; the weight gradients are the
+ *   float32 accumulators, their partial sums added in a fixed order (no atomics: deterministic, every element written once).
+ *   No loss scaling happens inside: fp16 underflow of small gradients is the caller's GradScaler, as for any 16-bit convolution.
+ *   w_blur / blur_out (grad_blur) come together or are both null; grad_x, grad_w_guidance, grad_w_blur may each be null.  An unknown dtype, a 16-bit pointer
+ *   that is not 2-byte aligned, a null required pointer or a bad shape (H > 2 h, W > 2 w): CSPN_E_BADARG.  B = 0: nothing to do, 0.
+ * workspace: the matching *_g16_workspace_bytes(B, C, h, w) bytes, 256-byte aligned; too small or misaligned: CSPN_E_WORKSPACE. */
+size_t cspn_guidance_head_g16_workspace_bytes(int B, int C, int h, int w);
+int cspn_guidance_head_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out,
+                           int B, int C, int h, int w, int H, int W,
+                           void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn_guidance_head_backward_g16_workspace_bytes(int B, int C, int h, int w);
+int cspn_guidance_head_backward_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, const float* grad_guidance,
+                                    const float* grad_blur, void* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w,
+                                    int H, int W, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 #ifdef __cplusplus
 }
