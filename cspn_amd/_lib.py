@@ -136,6 +136,17 @@ _SYMBOLS.update({
     "cspn_guidance_head_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 6 + _WS),
     "cspn_guidance_head_backward_g16_workspace_bytes": (c_size_t, [c_int] * 4),
     "cspn_guidance_head_backward_g16": (c_int, [vp, c_int] + [vp] * 7 + [c_int] * 6 + _WS),
+    # the 3D entry points of the Paddle contract on fp16 / bf16 gates or guides (gate_dtype DTYPES[...] after the gate pointer): values, levels,
+    # workspaces float32; the gate / guide gradient in the gate's type
+    "cspn3d_forward_g16_algo": (c_int, [vp, c_int] + [vp] * 3 + [c_int] * 7 + _WS),
+    "cspn3d_forward_multi_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_int] * 6 + _WS),
+    "cspn3d_forward_absnorm_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_int] * 6 + _WS),
+    "cspn3d_backward_g16_workspace_bytes": (c_size_t, [c_int] * 5),
+    "cspn3d_backward_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn3d_backward_multi_g16_workspace_bytes": (c_size_t, [c_int] * 6),
+    "cspn3d_backward_multi_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn_gate_absnorm_g16": (c_int, [vp, c_int, vp] + [c_int] * 2 + [c_size_t, vp]),
+    "cspn_gate_absnorm_backward_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_int] * 2 + [c_size_t, vp]),
 })
 _LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
 

@@ -174,7 +174,8 @@ class CSPN(nn.Module):
     [N, feat_chan*K, *S] raw (K = prop_kernel^dim_num - 1; prop_kernel 3, or 5 / 7 in 2D), feat [N, feat_chan, *S]: abs, each channel's
     slice of K gates divided by its abs-sum, prop_step chained propagations (F.absnorm_propagate: one engine call for all channels, the 3D
     normalisation inside the persistent kernel; for prop_kernel 5 / 7 inside the K x K engine's step, F.cspn2d_forward_kxk_absnorm, which
-    stores no normalised gate and takes a float16 / bfloat16 guide as it is).  The result is float32.  A port of demo.py changes its
+    stores no normalised gate).  A float16 / bfloat16 guide goes to the engine as it is in 3D (cspn3d_forward_absnorm_g16) and for
+    prop_kernel 5 / 7, and its gradient comes back in its dtype; 2D 3 x 3 widens it first.  The result is float32.  A port of demo.py changes its
     imports and tensor types, nothing else."""
 
     def __init__(self, dim_num, feat_chan, prop_kernel, prop_step):
@@ -190,10 +191,10 @@ class CSPN(nn.Module):
     def cspn(self, guide, feat):
         if feat.dim() != self.dim_num + 2:
             raise ValueError("feat must have %d dimensions for dim_num %d, got %s" % (self.dim_num + 2, self.dim_num, tuple(feat.shape)))
-        if self.dim_num == 2 and self.prop_kernel != 3:
-            feat = F.widen16(feat)   # the K x K engine widens a 16-bit guide where it uses it; values are float32
+        if self.dim_num == 3 or self.prop_kernel != 3:
+            feat = F.widen16(feat)   # the K x K engine and the 3D kernels widen a 16-bit guide where they read it; values are float32
         else:
-            guide, feat = F.widen16(guide, feat)   # the gate_absnorm tensor op has no 16-bit kernel: float32 from here on
+            guide, feat = F.widen16(guide, feat)   # 2D 3 x 3: the gate_absnorm tensor op has no 16-bit kernel, float32 from here on
         return F.absnorm_propagate(guide, feat, self.prop_step, self.prop_kernel)
 
     def forward(self, guide, feat):

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 
 namespace cspn {
 
@@ -65,38 +66,6 @@ __device__ __forceinline__ void stage(float* lds, const float* __restrict__ s, i
         const int r = i / SW, c = i - r * SW;
         const int gy = y0 - R + r, gx = xt0 - R + c;
         lds[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? s[gy * W + gx] : 0.f;
-    }
-}
-
-// ---- the gate storage type.  A 16-bit gate travels as its bit pattern (unsigned short); float gates as themselves ----
-template <class GT>
-struct Store {
-    using type = unsigned short;
-};
-template <>
-struct Store<float> {
-    using type = float;
-};
-template <class GT>
-using store_t = typename Store<GT>::type;
-
-// exact widening of a stored gate
-template <class GT>
-__device__ __forceinline__ float widen(store_t<GT> v) {
-    if constexpr (std::is_same<GT, float>::value) return v;
-    else if constexpr (std::is_same<GT, __half>::value) return (float)__builtin_bit_cast(_Float16, v);
-    else return __uint_as_float((uint32_t)v << 16);
-}
-
-// the single rounding of a float32 gradient to the storage type: to nearest even, subnormals kept, NaN stays NaN
-template <class GT>
-__device__ __forceinline__ store_t<GT> narrow(float v) {
-    if constexpr (std::is_same<GT, float>::value) return v;
-    else if constexpr (std::is_same<GT, __half>::value) return __builtin_bit_cast(unsigned short, (_Float16)v);
-    else {
-        const uint32_t u = __float_as_uint(v);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0;
-        return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
     }
 }
 
@@ -792,20 +761,7 @@ __global__ __launch_bounds__(NT) void kxk_unsite(const float* __restrict__ dg, c
     }
 }
 
-// ---- the host dispatch: a runtime value as a template argument of a generic lambda ----
-template <class T>
-struct Tag {
-    using type = T;
-};
-
-// the gate storage type of dtype: 0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16 (checked by the caller)
-template <class F>
-int with_gate_type(int dtype, F&& f) {
-    if (dtype == 0) return f(Tag<float>{});
-    if (dtype == CSPN_DTYPE_F16) return f(Tag<__half>{});
-    return f(Tag<__hip_bfloat16>{});
-}
-
+// ---- the host dispatch: a runtime value as a template argument of a generic lambda (Tag / with_gate_type: cspn_gate16.h) ----
 // K as a constant out of the contract's list (checked by the caller to be one of them)
 template <int K0, int... Ks, class F>
 int with_k(int K, F&& f) {

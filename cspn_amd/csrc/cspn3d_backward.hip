@@ -16,18 +16,13 @@
 #include <cstdlib>
 
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 
 namespace cspn {
 
 namespace {
 
 __host__ __device__ constexpr int ch3(int k) { return k < 13 ? k : k + 1; }  // skip the centre (index 13)
-
-__device__ __forceinline__ float4 ld4u(const float* p) {   // 16 bytes, 4-byte aligned
-    float4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
 
 // voxel index -> (b, z, y, x) of a thread's VEC consecutive voxels
 template <int VEC>
@@ -51,15 +46,16 @@ struct Pos {
 
 // one adjoint step: aout(q) = sum_k g_k(q - off_k) ain(q - off_k); VEC = 4 (W % 4 == 0, 16-byte aligned tensors) or 1
 // fbs: floats from one volume of ain / aout to the next (V, or C V when the call's C value channels share the gates: the caller
-// passes the channel's first volume)
-template <int VEC>
-__global__ __launch_bounds__(256) void adjoint3d_kernel(const float* __restrict__ g, const float* __restrict__ ain,
+// passes the channel's first volume).  GT: the gate storage type (cspn_gate16.h); the shifted quads of a 16-bit plane are 8-byte reads at
+// 2-byte alignment (ld4gu)
+template <int VEC, class GT>
+__global__ __launch_bounds__(256) void adjoint3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ ain,
                                                          float* __restrict__ aout, int B, int D, int H, int W, size_t fbs) {
     const Pos<VEC> p(B, D, H, W);
     if (!p.ok) return;
     const size_t HW = (size_t)H * W, V = (size_t)D * HW;
     const float* ab = ain + (size_t)p.b * fbs;
-    const float* gb = g + (size_t)p.b * 26 * V;
+    const store_t<GT>* gb = g + (size_t)p.b * 26 * V;
     float acc[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
@@ -84,16 +80,16 @@ __global__ __launch_bounds__(256) void adjoint3d_kernel(const float* __restrict_
             if (c27 == 13) continue;
             const int k = c27 < 13 ? c27 : c27 - 1;
             const int dx = 1 - t;
-            const float* gp = gb + (size_t)k * V + ro + p.x - dx;
+            const store_t<GT>* gp = gb + (size_t)k * V + ro + p.x - dx;
             float w[VEC];
             if (VEC == 4 && p.x - dx >= 0 && p.x - dx + 3 < W) {
-                const float4 q = ld4u(gp);
+                const float4 q = ld4gu<GT>(gp);
                 w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
             } else {
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
                     const int xs = p.x + i - dx;
-                    w[i] = (xs >= 0 && xs < W) ? gp[i] : 0.f;
+                    w[i] = (xs >= 0 && xs < W) ? widen<GT>(gp[i]) : 0.f;
                 }
             }
 #pragma unroll
@@ -107,11 +103,12 @@ __global__ __launch_bounds__(256) void adjoint3d_kernel(const float* __restrict_
 
 // dL/dg_k(p) = sum_c sum_t A^c_{t+1}(p) H^c_t(p + off_k) over the C value channels that share the gates (reference
 // cspn_paddle/README.md:56; C = 1: the plain op).  Every value tensor is [B][C][V]; level t of channel c: H_0 = feat,
-// H_t = hist + (t-1) total; A_n = gout, A_t = ahist + (t-1) total (t = 1 .. n-1), total = B C V
-template <int VEC>
+// H_t = hist + (t-1) total; A_n = gout, A_t = ahist + (t-1) total (t = 1 .. n-1), total = B C V.  The sums are float32 whatever the
+// type GT of gg: a 16-bit gradient is rounded once, at its store
+template <int VEC, class GT>
 __global__ __launch_bounds__(256) void gate_grad3d_kernel(const float* __restrict__ feat, const float* __restrict__ hist,
                                                            const float* __restrict__ ahist, const float* __restrict__ gout,
-                                                           float* __restrict__ gg, int B, int D, int H, int W, int n_iter, int C) {
+                                                           store_t<GT>* __restrict__ gg, int B, int D, int H, int W, int n_iter, int C) {
     const Pos<VEC> p(B, D, H, W);
     if (!p.ok) return;
     const size_t HW = (size_t)H * W, V = (size_t)D * HW, total = (size_t)B * C * V;
@@ -162,34 +159,54 @@ __global__ __launch_bounds__(256) void gate_grad3d_kernel(const float* __restric
             }
         }
     }
-    float* o = gg + (size_t)p.b * 26 * V + p.r;
+    store_t<GT>* o = gg + (size_t)p.b * 26 * V + p.r;
 #pragma unroll
     for (int k = 0; k < 26; ++k) {
-        if (VEC == 4) *reinterpret_cast<float4*>(o + (size_t)k * V) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-        else o[(size_t)k * V] = acc[k][0];
+        if (VEC == 4) st4g<GT>(o + (size_t)k * V, acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+        else o[(size_t)k * V] = narrow<GT>(acc[k][0]);
     }
 }
 
 // forward step for shapes / alignments the 16-byte kernel of cspn3d_stepwise.hip does not take
-__global__ __launch_bounds__(256) void step3d_scalar_kernel(const float* __restrict__ g, const float* __restrict__ hin,
+template <class GT>
+__global__ __launch_bounds__(256) void step3d_scalar_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ hin,
                                                              float* __restrict__ hout, int B, int D, int H, int W, size_t fbs) {
     const Pos<1> p(B, D, H, W);
     if (!p.ok) return;
     const size_t HW = (size_t)H * W, V = (size_t)D * HW;
     const float* hb = hin + (size_t)p.b * fbs;
-    const float* gb = g + (size_t)p.b * 26 * V + p.r;
+    const store_t<GT>* gb = g + (size_t)p.b * 26 * V + p.r;
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 26; ++k) {
         const int c = ch3(k);
         const int zz = p.z + 1 - c / 9, yy = p.y + 1 - (c / 3) % 3, xx = p.x + 1 - c % 3;
         if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W)
-            acc = fmaf(gb[(size_t)k * V], hb[((size_t)zz * H + yy) * W + xx], acc);
+            acc = fmaf(widen<GT>(gb[(size_t)k * V]), hb[((size_t)zz * H + yy) * W + xx], acc);
     }
     hout[(size_t)p.b * fbs + p.r] = acc;
 }
 
+// the exact widening of a 16-bit gate tensor into float32, streaming: what the transposed persistent instance (ADJ) reads, since its
+// prologue takes planes shifted by one element in x and has no 16-bit form
+template <class GT>
+__global__ __launch_bounds__(256) void widen_gates_kernel(const store_t<GT>* __restrict__ g, float* __restrict__ w, size_t n4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) *reinterpret_cast<float4*>(w + 4 * i) = ld4g<GT>(g + 4 * i);
+}
+
 }  // namespace
+
+// n floats, n % 4 == 0, g 8-byte and w 16-byte aligned
+int widen_gates(const void* g, int gdt, float* w, size_t n, hipStream_t st) {
+    with_gate_type(gdt, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        if constexpr (!std::is_same<GT, float>::value)
+            hipLaunchKernelGGL(widen_gates_kernel<GT>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, (const store_t<GT>*)g, w, n / 4);
+        return 0;
+    });
+    return check_launch("widen_gates_kernel");
+}
 
 // levels kept: H_1 .. H_{n-1} and A_1 .. A_{n-1} (A_0 goes to grad_feat, or to one more volume when the caller does not want
 // it), each level B C volumes laid out like feat ([B][C][V]); then the workspace of the persistent kernel (fused sweeps, n >= 3)
@@ -199,81 +216,101 @@ static size_t levels_bytes(int B, int D, int H, int W, int n_iter, int C) {
     return (b + 255) & ~(size_t)255;
 }
 
-size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C) {
-    return levels_bytes(B, D, H, W, n_iter, C) + persistent3d_workspace(B, D, H, W);
+// the fused sweeps' conditions on the shape (the pointers' alignment is the call's)
+static bool fused3d_shape(int B, int C, int D, int H, int W, int n_iter) {
+    return (W % 4) == 0 && n_iter >= 3 &&
+           (C == 1 ? persistent3d_supported(B, D, H, W, n_iter - 1) && persistent3d_supported(B, D, H, W, n_iter)
+                   : persistent3d_multi_supported(B, C, D, H, W, n_iter - 1) && persistent3d_multi_supported(B, C, D, H, W, n_iter));
 }
 
-int step3d_direct(const float* g, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st);   // cspn3d_stepwise.hip
+// gdt != 0 (16-bit gates): where the fused sweeps can take the call, the float32 copy of the gates the transposed sweep reads follows
+size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C, int gdt) {
+    const size_t base = levels_bytes(B, D, H, W, n_iter, C) + persistent3d_workspace(B, D, H, W);
+    return gdt && fused3d_shape(B, C, D, H, W, n_iter) ? round256(base) + round256(26 * sizeof(float) * (size_t)B * D * H * W) : base;
+}
 
 // C > 1 (round 5; reference cspn_paddle/README.md:56, trained through at demo.py:65-75): feat / gout / gf hold C value channels per
 // volume on shared gates, gg is the gate gradient summed over the channels.  Fused sweeps: ONE level-keeping forward launch and ONE
 // transposed launch of the persistent kernel for all channels (its MULTI instantiations: the gates of a chunk stay in the registers
 // while the steps run for channel after channel), then one gate-gradient pass that loops over the channels and writes the 26
 // planes once.  Otherwise one launch per step and channel.
-int backward3d(const float* g, const float* feat, const float* gout, float* gg, float* gf, int B, int D, int H, int W,
-               int n_iter, void* ws, hipStream_t st, bool stepwise_only, int C) {
+// gdt: the storage type of g and gg (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16).  16-bit gates are read as they are by every kernel but the
+// transposed persistent sweep, which reads one exact float32 copy made in the workspace; gg is the float32 sum rounded once at its store
+int backward3d(const void* g, const float* feat, const float* gout, void* gg, float* gf, int B, int D, int H, int W,
+               int n_iter, void* ws, hipStream_t st, bool stepwise_only, int C, int gdt) {
     const size_t V = (size_t)D * H * W, total = (size_t)B * C * V, fbs = (size_t)C * V;
     float* hist = (float*)ws;                                  // H_1 .. H_{n-1}
     float* ahist = hist + (size_t)(n_iter - 1) * total;        // A_1 .. A_{n-1}
     float* a0 = gf ? gf : ahist + (size_t)(n_iter - 1) * total;
-    const bool vec = (W % 4) == 0 &&
-                     ((((uintptr_t)g | (uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gg | (uintptr_t)gf | (uintptr_t)ws) & 15u) == 0);
+    const bool vec = (W % 4) == 0 && ((((uintptr_t)g | (uintptr_t)gg) & gate_quad_mask(gdt)) == 0) &&
+                     ((((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gf | (uintptr_t)ws) & 15u) == 0);
     const unsigned blocks = (unsigned)(((size_t)B * V / (vec ? 4 : 1) + 255) / 256);   // threads cover ONE channel's B volumes
+    const unsigned blocks1 = (unsigned)(((size_t)B * V + 255) / 256);
     // fused sweeps: the persistent kernel (gates read once per sweep, resident in registers across the steps) in its
     // level-keeping and transposed variants -- forward H_1 .. H_{n-1} (n - 1 steps, the last one "out" = H_{n-1}), adjoint
     // A_{n-1} .. A_0 (n steps).  One launch per step otherwise.
     void* pws = (char*)ws + levels_bytes(B, D, H, W, n_iter, C);
-    const bool fused = vec && !stepwise_only && n_iter >= 3 &&
-                       (C == 1 ? persistent3d_supported(B, D, H, W, n_iter - 1) && persistent3d_supported(B, D, H, W, n_iter)
-                               : persistent3d_multi_supported(B, C, D, H, W, n_iter - 1) && persistent3d_multi_supported(B, C, D, H, W, n_iter));
-    if (fused) {
-        if (gg)
-            if (int e = persistent3d_run(g, feat, hist + (size_t)(n_iter - 2) * total, hist, -1, 1, false, B, D, H, W, n_iter - 1, pws, st, P3Options(), C))
-                return e;
-        // step it of the adjoint run produces A_{n-it}: volume n - it - 1 of ahist; the last one (A_0) is its "out"
-        if (gf || gg)
-            if (int e = persistent3d_run(g, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st, P3Options(), C)) return e;
+    const bool fused = vec && !stepwise_only && fused3d_shape(B, C, D, H, W, n_iter);
+    return with_gate_type(gdt, [&](auto gt) -> int {
+        using GT = typename decltype(gt)::type;
+        const store_t<GT>* gs = (const store_t<GT>*)g;
+        store_t<GT>* ggs = (store_t<GT>*)gg;
+        if (fused) {
+            if (gg)
+                if (int e = persistent3d_run(g, feat, hist + (size_t)(n_iter - 2) * total, hist, -1, 1, false, B, D, H, W, n_iter - 1, pws, st, P3Options(), C, gdt))
+                    return e;
+            // step it of the adjoint run produces A_{n-it}: volume n - it - 1 of ahist; the last one (A_0) is its "out"
+            if (gf || gg) {
+                const void* ga = g;
+                if (gdt) {
+                    float* wide = (float*)((char*)ws + round256(levels_bytes(B, D, H, W, n_iter, C) + persistent3d_workspace(B, D, H, W)));
+                    if (int e = widen_gates(g, gdt, wide, 26 * (size_t)B * V, st)) return e;
+                    ga = wide;
+                }
+                if (int e = persistent3d_run(ga, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st, P3Options(), C)) return e;
+            }
+            if (gg) {
+                hipLaunchKernelGGL((gate_grad3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
+                if (int e = check_launch("gate_grad3d_kernel")) return e;
+            }
+            return 0;
+        }
+        for (int c = 0; c < C; ++c) {
+            const size_t co = (size_t)c * V;
+            if (gg) {   // the value levels the gate gradient multiplies with
+                const float* src = feat + co;
+                for (int t = 1; t < n_iter; ++t) {
+                    float* dst = hist + (size_t)(t - 1) * total + co;
+                    if (vec && C == 1) {
+                        if (int e = step3d_direct(g, gdt, src, dst, B, D, H, W, st)) return e;
+                    } else {
+                        hipLaunchKernelGGL(step3d_scalar_kernel<GT>, dim3(blocks1), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
+                    }
+                    src = dst;
+                }
+                if (int e = check_launch("3D forward levels")) return e;
+            }
+            // adjoint levels A_{n-1} .. A_1 (kept only if the gate gradient needs them: otherwise two volumes would do, but the
+            // workspace is sized for the general call) and A_0
+            const float* src = gout + co;
+            for (int t = n_iter - 1; t >= 0; --t) {
+                float* dst = (t == 0 ? a0 : ahist + (size_t)(t - 1) * total) + co;
+                if (t == 0 && !gf) break;   // A_0 is only the feature gradient
+                if (vec) hipLaunchKernelGGL((adjoint3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
+                else hipLaunchKernelGGL((adjoint3d_kernel<1, GT>), dim3(blocks), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
+                src = dst;
+            }
+            if (int e = check_launch("adjoint3d_kernel")) return e;
+        }
         if (gg) {
-            hipLaunchKernelGGL(gate_grad3d_kernel<4>, dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, gg, B, D, H, W, n_iter, C);
+            if (vec)
+                hipLaunchKernelGGL((gate_grad3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
+            else
+                hipLaunchKernelGGL((gate_grad3d_kernel<1, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
             if (int e = check_launch("gate_grad3d_kernel")) return e;
         }
         return 0;
-    }
-    for (int c = 0; c < C; ++c) {
-        const size_t co = (size_t)c * V;
-        if (gg) {   // the value levels the gate gradient multiplies with
-            const float* src = feat + co;
-            for (int t = 1; t < n_iter; ++t) {
-                float* dst = hist + (size_t)(t - 1) * total + co;
-                if (vec && C == 1) {
-                    if (int e = step3d_direct(g, src, dst, B, D, H, W, st)) return e;
-                } else {
-                    hipLaunchKernelGGL(step3d_scalar_kernel, dim3((unsigned)(((size_t)B * V + 255) / 256)), dim3(256), 0, st, g, src, dst, B, D, H, W, fbs);
-                }
-                src = dst;
-            }
-            if (int e = check_launch("3D forward levels")) return e;
-        }
-        // adjoint levels A_{n-1} .. A_1 (kept only if the gate gradient needs them: otherwise two volumes would do, but the
-        // workspace is sized for the general call) and A_0
-        const float* src = gout + co;
-        for (int t = n_iter - 1; t >= 0; --t) {
-            float* dst = (t == 0 ? a0 : ahist + (size_t)(t - 1) * total) + co;
-            if (t == 0 && !gf) break;   // A_0 is only the feature gradient
-            if (vec) hipLaunchKernelGGL(adjoint3d_kernel<4>, dim3(blocks), dim3(256), 0, st, g, src, dst, B, D, H, W, fbs);
-            else hipLaunchKernelGGL(adjoint3d_kernel<1>, dim3(blocks), dim3(256), 0, st, g, src, dst, B, D, H, W, fbs);
-            src = dst;
-        }
-        if (int e = check_launch("adjoint3d_kernel")) return e;
-    }
-    if (gg) {
-        if (vec)
-            hipLaunchKernelGGL(gate_grad3d_kernel<4>, dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, gg, B, D, H, W, n_iter, C);
-        else
-            hipLaunchKernelGGL(gate_grad3d_kernel<1>, dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, gg, B, D, H, W, n_iter, C);
-        if (int e = check_launch("gate_grad3d_kernel")) return e;
-    }
-    return 0;
+    });
 }
 
 }  // namespace cspn

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 #include "cspn_gate_norm.h"
 
 // P3_ROWS_PLAIN / P3_ROWS_CF / P3_NO_PRIO / P3_LYP: A/B builds of the round-5 row assignment (correct results, tools/r05/build_p3var.sh)
@@ -168,15 +169,23 @@ __device__ __forceinline__ void lds_dma16(unsigned byte_off, const float* base, 
 // while the n_iter steps are run for one channel after the other (only level 0 is re-read per channel, 4 B/voxel against 104)
 // NRM: `gate` holds the demo's RAW guide (reference cspn_paddle/demo.py:24,34-36,47-49): the resident gates of every voxel inside the
 // volume are divided by their abs-sum in the registers (cspn_gate_norm.h, the stand-alone normaliser's arithmetic), no HBM bytes for it
-template <bool ADJ, bool HASC, bool MUTE = false, bool MULTI = false, bool NRM = false>
+// G16 (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16): `gate` holds 16-bit gates (or, with NRM, the 16-bit raw guide).  Only the chunk
+// prologue differs: a thread's two quads of a plane are two 8-byte loads under the float32 guards, and after the wait each plane's packed
+// pair is widened exactly into the eight gate registers it was to fill (plane by plane: the pair dies as its floats are born, so the peak
+// stays at the 208 gate registers).  No parked quads (NPRE = 0: there is no 8-byte LDS-DMA), so less LDS than the float32 twin.  Forward
+// instances only: the transposed prologue (ADJ) reads planes shifted by one element and stays float32.
+template <bool ADJ, bool HASC, bool MUTE = false, bool MULTI = false, bool NRM = false, int G16 = 0>
 __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) void cspn3d_persistent_kernel(const float* __restrict__ gate, const float* __restrict__ feat,
                                                                  const float* __restrict__ cprime, float* __restrict__ out,
                                                                  float* __restrict__ levels, float* __restrict__ scratch,
                                                                  unsigned* __restrict__ sync, Geo3 g) {
     static_assert(!NRM || (!ADJ && !HASC && !MULTI), "the normalising instance is a forward on raw gates of one value channel");
+    static_assert(!G16 || (!ADJ && !HASC && !MUTE), "16-bit gates: the forward instances of the Paddle contract");
+    using GT = std::conditional_t<G16 == CSPN_DTYPE_F16, __half, std::conditional_t<G16 == CSPN_DTYPE_BF16, __hip_bfloat16, float>>;
+    constexpr unsigned GB = G16 ? 2u : 4u;   // bytes of a stored gate
     __shared__ __attribute__((aligned(16))) float lds[2 * LTILE];
     __shared__ __attribute__((aligned(16))) float4 s_c[HASC ? 2 * NTP : 1];   // c' of the thread's two quads, [quad][thread]
-    constexpr int NPRE = Pre3<ADJ, HASC>::N;
+    constexpr int NPRE = G16 ? 0 : Pre3<ADJ, HASC>::N;
     __shared__ __attribute__((aligned(16))) float4 s_pre[NPRE ? NPRE * NTP : 1];   // parked gate quads, [quad][thread] (addressed by hand)
     __shared__ int s_bail;
     unsigned* err = sync + MAX_WG + 64 * 9;  // [1] (the words in front of it belonged to the flag exchange of the first version)
@@ -345,7 +354,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int row = (z * g.H + y) * g.W;
                 // byte offsets: 1-channel tensors (feat, c') and the gate tensor (volume stride gbs floats)
                 const unsigned fo0 = in0 ? (unsigned)(b0 * FBS + row + xq0) * 4u : 0u, fo1 = in1 ? (unsigned)(b1 * FBS + row + xq1) * 4u : 0u;
-                const unsigned go0 = (unsigned)(b0 * (int)g.gbs + row + xq0) * 4u, go1 = (unsigned)(b1 * (int)g.gbs + row + xq1) * 4u;
+                const unsigned go0 = (unsigned)(b0 * (int)g.gbs + row + xq0) * GB, go1 = (unsigned)(b1 * (int)g.gbs + row + xq1) * GB;
                 const unsigned voff0 = in0 ? go0 : 0u, voff1 = in1 ? go1 : 0u;
                 auto shell_pos = [&](int i, int& pz, int& py, int& px) {
                     if (i < SH_Z) { pz = i < LY * LXU ? 0 : LZ - 1; const int r = i < LY * LXU ? i : i - LY * LXU; py = r / LXU; px = r - py * LXU; }
@@ -377,6 +386,8 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
                 // ---- the 26 gates of the thread's eight voxels: read once, kept in registers for all steps
                 v4f w[26][2];
+                typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                v2u pk[G16 ? 26 : 1][2];   // G16: the packed quads as they arrive
                 // the 26 plane bases are worked out per chunk from an opaque copy of the plane stride: computed once per kernel they
                 // were 52 scalar registers live across everything (all of them spilled to VGPR lanes, which cost the vector
                 // registers the gates need: round 3 had 50 .. 78 SGPR spills and a VGPR spill per variant)
@@ -386,8 +397,12 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (ADJ) asm volatile("" : "+s"(Hc), "+s"(Wc));
 #pragma unroll
                 for (int k = 0; k < 26; ++k) {
-                    const float* gk = gate + (size_t)k * (size_t)gps_c;
-                    if (ADJ) {
+                    const float* gk = G16 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(gate) + (size_t)k * (size_t)gps_c * GB)
+                                          : gate + (size_t)k * (size_t)gps_c;
+                    if (G16) {
+                        asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2" : "=&v"(pk[G16 ? k : 0][0]) : "v"(voff0), "s"(gk) : "memory");
+                        asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2" : "=&v"(pk[G16 ? k : 0][1]) : "v"(voff1), "s"(gk) : "memory");
+                    } else if (ADJ) {
                         const int c27 = k < 13 ? k : k + 1, dz = 1 - c27 / 9, dy = 1 - (c27 / 3) % 3, dx = 1 - c27 % 3;
                         const int ko = (26 - c27) < 13 ? (26 - c27) : (26 - c27) - 1;   // the plane of the opposite offset
                         const float* gko = gate + (size_t)ko * (size_t)gps_c;
@@ -470,10 +485,20 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
                 }
                 // the gates are back; outside the volume they are zero (such voxels keep the value 0)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0][0]), "+v"(w[0][1]) : : "memory");
+                if (G16) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(pk[0][0]), "+v"(pk[0][1]) : : "memory");
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0][0]), "+v"(w[0][1]) : : "memory");
 #pragma unroll
                 for (int k = 0; k < 26; ++k) {
-                    if (k) asm volatile("" : "+v"(w[k][0]), "+v"(w[k][1]));
+                    if (G16) {
+                        if (k) asm volatile("" : "+v"(pk[k][0]), "+v"(pk[k][1]));
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const v2u u = pk[G16 ? k : 0][q];
+                            w[k][q] = v4f{widen<GT>((unsigned short)u.x), widen<GT>((unsigned short)(u.x >> 16)), widen<GT>((unsigned short)u.y),
+                                          widen<GT>((unsigned short)(u.y >> 16))};
+                        }
+                        asm volatile("" : "+v"(w[k][0]), "+v"(w[k][1]));   // (one plane at a time)
+                    } else if (k) asm volatile("" : "+v"(w[k][0]), "+v"(w[k][1]));
                     const v4f zero = {0.f, 0.f, 0.f, 0.f};
                     if (ADJ) {
                         const int c27 = k < 13 ? k : k + 1, dz = 1 - c27 / 9, dy = 1 - (c27 / 3) % 3, dx = 1 - c27 % 3;
@@ -828,7 +853,13 @@ int resident_wgs() {
         const void* fns[] = {(const void*)cspn3d_persistent_kernel<false, false>, (const void*)cspn3d_persistent_kernel<false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false>, (const void*)cspn3d_persistent_kernel<false, false, false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false, false, true>,
-                             (const void*)cspn3d_persistent_kernel<false, false, false, false, true>};
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, true>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_F16>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_BF16>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, true, false, CSPN_DTYPE_F16>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, true, false, CSPN_DTYPE_BF16>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, true, CSPN_DTYPE_F16>,
+                             (const void*)cspn3d_persistent_kernel<false, false, false, false, true, CSPN_DTYPE_BF16>};
         for (const void* fn : fns) {
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, NTP, 0) == hipSuccess && nb < occ) occ = nb < 0 ? 0 : nb;
@@ -911,9 +942,12 @@ size_t persistent3d_workspace(int B, int D, int H, int W) {
 
 // adjoint: the transposed operator (backward); levels: volume lv0 + it * lvs receives the result of step it < n_iter;
 // cprime != nullptr: gate holds the 26 folded planes [26][B][V] and cprime the constant term (normalising / masked modes)
-static int persistent3d_launch(const float* gate, const float* feat, const float* cprime, float* out, float* levels, int lv0, int lvs,
+// gdt != 0: gate holds fp16 / bf16 gates (forward, MULTI and NRM instances; the caller never asks for another)
+static int persistent3d_launch(const void* gate_, const float* feat, const float* cprime, float* out, float* levels, int lv0, int lvs,
                                bool adjoint, int B, int D, int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C = 1,
-                               bool nrm = false) {
+                               bool nrm = false, int gdt = 0) {
+    const float* gate = (const float*)gate_;   // (the kernel argument's type; a 16-bit instance reads it as its own)
+    if (gdt && (adjoint || cprime || opt.mute >= 0)) { set_error("persistent 3D kernel: no 16-bit instance of this variant"); return CSPN_E_UNSUPPORTED; }
     Geo3 g = make_geo3(B, D, H, W, n_iter, opt.placement);
     g.C = C;
     g.wt = opt.write_through ? 1 : 0;
@@ -967,7 +1001,13 @@ static int persistent3d_launch(const float* gate, const float* feat, const float
     }
     g.status = d.status_dev;
     void* args[] = {(void*)&gate, (void*)&feat, (void*)&cprime, (void*)&out, (void*)&levels, (void*)&scratch, (void*)&sync, (void*)&g};
-    const void* fn = nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true>
+    const void* fn = gdt == CSPN_DTYPE_F16 ? (nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true, CSPN_DTYPE_F16>
+                                              : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true, false, CSPN_DTYPE_F16>
+                                                      : (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_F16>)
+                   : gdt == CSPN_DTYPE_BF16 ? (nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true, CSPN_DTYPE_BF16>
+                                               : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true, false, CSPN_DTYPE_BF16>
+                                                       : (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_BF16>)
+                   : nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true>
                    : cprime ? (const void*)cspn3d_persistent_kernel<false, true>
                    : adjoint ? (C > 1 ? (const void*)cspn3d_persistent_kernel<true, false, false, true> : (const void*)cspn3d_persistent_kernel<true, false>)
                    : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true>
@@ -1014,9 +1054,9 @@ int persistent3d_take_status() {
     return 2;
 }
 
-int persistent3d_run(const float* gate, const float* feat, float* out, float* levels, int lv0, int lvs, bool adjoint, int B, int D,
-                     int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C) {
-    return persistent3d_launch(gate, feat, nullptr, out, levels, lv0, lvs, adjoint, B, D, H, W, n_iter, ws, st, opt, C);
+int persistent3d_run(const void* gate, const float* feat, float* out, float* levels, int lv0, int lvs, bool adjoint, int B, int D,
+                     int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C, int gdt) {
+    return persistent3d_launch(gate, feat, nullptr, out, levels, lv0, lvs, adjoint, B, D, H, W, n_iter, ws, st, opt, C, false, gdt);
 }
 
 // H_{t+1} = c' + sum_k w'_k H_t(p + off_k) with the folded planes wf = [26 w'][c'] of fold3d_kernel
@@ -1034,21 +1074,21 @@ bool persistent3d_multi_supported(int B, int C, int D, int H, int W, int n_iter)
     return (long long)g.nchunk * C * (n_iter - 1) < (1LL << 31);
 }
 
-int persistent3d_forward_multi(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter, void* ws,
-                               hipStream_t st) {
-    return persistent3d_launch(gate, feat, nullptr, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), C);
+int persistent3d_forward_multi(const void* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter, void* ws,
+                               hipStream_t st, int gdt) {
+    return persistent3d_launch(gate, feat, nullptr, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), C, false, gdt);
 }
 
-int persistent3d_forward(const float* gate, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
-                         hipStream_t st) {
-    return persistent3d_run(gate, feat, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st);
+int persistent3d_forward(const void* gate, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                         hipStream_t st, int gdt) {
+    return persistent3d_run(gate, feat, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), 1, gdt);
 }
 
 // the demo's module (reference cspn_paddle/demo.py:24,34-36,47-49 then :41-43): `guide` holds the RAW gates [B][26][V], normalised per voxel
 // in the registers after the chunk's gate loads (NRM).  Takes exactly the calls persistent3d_supported takes.
-int persistent3d_forward_absnorm(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
-                                 hipStream_t st) {
-    return persistent3d_launch(guide, feat, nullptr, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), 1, true);
+int persistent3d_forward_absnorm(const void* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                                 hipStream_t st, int gdt) {
+    return persistent3d_launch(guide, feat, nullptr, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), 1, true, gdt);
 }
 
 // (test-hook library) the plan of a persistent launch: info[9] = tz, ty, cx, tiles, workgroups launched, bz, by, bx (0: plain order), chunks

@@ -4,6 +4,7 @@
 // generalisation of cspn_pytorch/models/cspn.py:42-172, see oracle/cspn_oracle.c).
 // Channel order: raster over (f,t,l) in {0,1,2}^3 without (1,1,1); offset (1-f,1-t,1-l).
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 
 namespace cspn {
 
@@ -12,8 +13,10 @@ __host__ __device__ constexpr int dz3(int k) { return 1 - ch3(k) / 9; }
 __host__ __device__ constexpr int dy3(int k) { return 1 - (ch3(k) / 3) % 3; }
 __host__ __device__ constexpr int dx3(int k) { return 1 - ch3(k) % 3; }
 
-// wf: [27][B*D*H*W] (26 folded weights + c')
-__global__ __launch_bounds__(256) void fold3d_kernel(const float* __restrict__ g, const float* __restrict__ feat,
+// wf: [27][B*D*H*W] (26 folded weights + c').  GT: the gate storage type (cspn_gate16.h); a 16-bit gate comes here only with norm NONE and
+// no mask (a misaligned gate tensor of the Paddle contract), where folding is the exact widening
+template <class GT>
+__global__ __launch_bounds__(256) void fold3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ feat,
                                                       const float* __restrict__ sparse, float* __restrict__ wf,
                                                       int B, int D, int H, int W, int norm) {
     const size_t HW = (size_t)H * W, V = (size_t)D * HW, total = (size_t)B * V;
@@ -24,18 +27,18 @@ __global__ __launch_bounds__(256) void fold3d_kernel(const float* __restrict__ g
     const int z = (int)(r / HW);
     const int r2 = (int)(r - (size_t)z * HW);
     const int y = r2 / W, x = r2 - y * W;
-    const float* gb = g + (size_t)b * 26 * V;
+    const store_t<GT>* gb = g + (size_t)b * 26 * V;
     float G[26], S = 0.f;
 #pragma unroll
     for (int k = 0; k < 26; ++k) {
         float v;
         if (norm == CSPN_NORM_NONE) {
-            v = gb[k * V + r];
+            v = widen<GT>(gb[k * V + r]);
         } else {
             const int zz = z + dz3(k), yy = y + dy3(k), xx = x + dx3(k);
             v = 0.f;
             if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W)
-                v = gb[k * V + ((size_t)zz * H + yy) * W + xx];
+                v = widen<GT>(gb[k * V + ((size_t)zz * H + yy) * W + xx]);
             if (norm == CSPN_NORM_8SUM_ABS) v = fabsf(v);
         }
         G[k] = v;
@@ -86,8 +89,10 @@ __global__ __launch_bounds__(256) void step3d_kernel(const float* __restrict__ w
 // The Paddle contract (norm_type NONE, no sparse): gates are used as given, centre-sited, no centre term
 // (reference cspn_paddle/README.md:54-56, demo.py:41-52).  One iteration then needs exactly the algorithmic traffic of a
 // single propagation step -- 26 gates + value in, value out = 112 B/voxel -- so it reads the gate tensor directly: no
-// fold pass, no coefficient planes.  4 voxels per thread along x (16-byte loads of the gate planes).
-__global__ __launch_bounds__(256) void step3d_direct_kernel(const float* __restrict__ g, const float* __restrict__ hin,
+// fold pass, no coefficient planes.  4 voxels per thread along x (16-byte loads of the gate planes; 8-byte loads of fp16 / bf16 planes,
+// widened as they arrive).
+template <class GT>
+__global__ __launch_bounds__(256) void step3d_direct_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ hin,
                                                              float* __restrict__ hout, int B, int D, int H, int W4) {
     const int W = 4 * W4;
     const size_t HW = (size_t)H * W, V = (size_t)D * HW, total4 = (size_t)B * D * H * W4;
@@ -100,7 +105,7 @@ __global__ __launch_bounds__(256) void step3d_direct_kernel(const float* __restr
     const int r2 = (int)(r - (size_t)z * HW);
     const int y = r2 / W, x = r2 - y * W;
     const float* hb = hin + (size_t)b * V;
-    const float* gb = g + (size_t)b * 26 * V + r;
+    const store_t<GT>* gb = g + (size_t)b * 26 * V + r;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int n = 0; n < 9; ++n) {  // the 9 neighbour rows (dz, dy); three x-taps each
@@ -119,7 +124,7 @@ __global__ __launch_bounds__(256) void step3d_direct_kernel(const float* __restr
             const int c27 = n * 3 + t;   // raster index (f,t,l) with f = n/3, t = n%3, l = t
             if (c27 == 13) continue;     // the centre has no gate
             const int k = c27 < 13 ? c27 : c27 - 1;
-            const float4 w = *reinterpret_cast<const float4*>(gb + (size_t)k * V);
+            const float4 w = ld4g<GT>(gb + (size_t)k * V);
             const int dx = 1 - t;
             const float h0 = dx > 0 ? hc.y : (dx < 0 ? hm : hc.x);
             const float h1 = dx > 0 ? hc.z : (dx < 0 ? hc.x : hc.y);
@@ -134,17 +139,21 @@ __global__ __launch_bounds__(256) void step3d_direct_kernel(const float* __restr
     *reinterpret_cast<float4*>(hout + idx) = acc;
 }
 
-// one step of the Paddle contract for other files (the backward keeps the value levels): W % 4 == 0, 16-byte aligned tensors
-int step3d_direct(const float* g, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st) {
+// one step of the Paddle contract for other files (the backward keeps the value levels): W % 4 == 0, 16-byte aligned tensors (a 16-bit
+// gate tensor: 8-byte aligned); gdt: the gate storage type (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16)
+int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st) {
     const size_t total = (size_t)B * D * H * W;
-    hipLaunchKernelGGL(step3d_direct_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, g, hin, hout, B, D, H, W / 4);
-    return 0;
+    return with_gate_type(gdt, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        hipLaunchKernelGGL(step3d_direct_kernel<GT>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, (const store_t<GT>*)g, hin, hout, B,
+                           D, H, W / 4);
+        return 0;
+    });
 }
 
-static bool direct3d_ok(const float* g, const float* feat, const float* sparse, const float* out, int W, int norm,
-                        const void* ws) {
-    return norm == CSPN_NORM_NONE && sparse == nullptr && (W % 4) == 0 &&
-           (((uintptr_t)g | (uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0;
+static bool direct3d_ok(const void* g, int gdt, const float* feat, const float* sparse, const float* out, int W, int norm, const void* ws) {
+    return norm == CSPN_NORM_NONE && sparse == nullptr && (W % 4) == 0 && ((uintptr_t)g & gate_quad_mask(gdt)) == 0 &&
+           (((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0;
 }
 
 size_t stepwise3d_workspace(int B, int D, int H, int W, int n_iter) {
@@ -163,31 +172,36 @@ size_t forward3d_workspace(int B, int D, int H, int W, int n_iter, int norm, boo
 }
 
 // algo: 0 auto, 1 one launch per step, 2 persistent (gates resident across steps)
-int stepwise3d_forward(const float* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
-                       int W, int n_iter, int norm, void* ws, hipStream_t st, int algo) {
+// gdt: the gate storage type; CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 with norm NONE and no mask only (checked by the caller).  The dispatch is
+// the float32 one with the gate pointer's 16-byte condition at 8 bytes
+int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                       int W, int n_iter, int norm, void* ws, hipStream_t st, int algo, int gdt) {
     const size_t total = (size_t)B * D * H * W;
     float* wf = (float*)ws;
-    const bool direct = direct3d_ok(g, feat, sparse, out, W, norm, ws);
+    const bool direct = direct3d_ok(g, gdt, feat, sparse, out, W, norm, ws);
     if (algo == 2 && direct && !persistent3d_supported(B, D, H, W, n_iter)) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;
     }
     if (direct && algo != 1 && persistent3d_supported(B, D, H, W, n_iter))
-        return persistent3d_forward(g, feat, out, B, D, H, W, n_iter, ws, st);
+        return persistent3d_forward(g, feat, out, B, D, H, W, n_iter, ws, st, gdt);
     if (direct) {
         float* pp[2] = {wf, wf + total};
-        const unsigned blocks4 = (unsigned)((total / 4 + 255) / 256);
         const float* src = feat;
         for (int it = 0; it < n_iter; ++it) {
             float* dst = (it == n_iter - 1) ? out : pp[it & 1];
-            hipLaunchKernelGGL(step3d_direct_kernel, dim3(blocks4), dim3(256), 0, st, g, src, dst, B, D, H, W / 4);
+            step3d_direct(g, gdt, src, dst, B, D, H, W, st);
             src = dst;
         }
         return check_launch("step3d_direct_kernel");
     }
     float* ping[2] = {wf + 27 * total, wf + 28 * total};
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(fold3d_kernel, dim3(blocks), dim3(256), 0, st, g, feat, sparse, wf, B, D, H, W, norm);
+    with_gate_type(gdt, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        hipLaunchKernelGGL(fold3d_kernel<GT>, dim3(blocks), dim3(256), 0, st, (const store_t<GT>*)g, feat, sparse, wf, B, D, H, W, norm);
+        return 0;
+    });
     if (int e = check_launch("fold3d_kernel")) return e;
     // the normalising / masked modes fused: H_{t+1} = c' + sum_k w'_k H_t(p + off_k) with the folded planes resident in the
     // persistent kernel's registers (c' in LDS): fold once, then one pass over the 27 planes for all steps

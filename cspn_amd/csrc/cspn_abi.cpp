@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 
 namespace cspn {
 
@@ -85,10 +86,10 @@ static int identity_copy(float* out, const float* in, size_t floats, hipStream_t
 }
 
 // n_iter == 0, backward: dL/dfeat = dL/dout, the gates are not used
-static int identity_backward(float* grad_feat, const float* grad_out, size_t floats, float* grad_gate, size_t gate_floats, hipStream_t st) {
+static int identity_backward(float* grad_feat, const float* grad_out, size_t floats, void* grad_gate, size_t gate_bytes, hipStream_t st) {
     hipError_t e = hipSuccess;
     if (grad_feat) e = hipMemcpyAsync(grad_feat, grad_out, sizeof(float) * floats, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, sizeof(float) * gate_floats, st);
+    if (e == hipSuccess && grad_gate) e = hipMemsetAsync(grad_gate, 0, gate_bytes, st);
     if (e != hipSuccess) { set_error("hipMemcpyAsync / hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }
@@ -99,7 +100,8 @@ static bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
     return x < y + bn && y < x + an;
 }
 
-static int absnorm_check(const char* what, const float* guide, const float* a, const float* out, int N, int K, size_t V) {
+// gsize: bytes of an element of guide (and, in the backward, of out = grad_guide): 4, or 2 for the *_g16 forms
+static int absnorm_check(const char* what, const void* guide, const float* a, const void* out, int N, int K, size_t V, size_t gsize = 4, bool out_is_guide_type = false) {
     if (!guide || !a || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (N <= 0 || V == 0) { set_error("%s: bad shape N=%d V=%zu", what, N, V); return CSPN_E_BADARG; }
     if (K != 8 && K != 26 && K != 24 && K != 48) {
@@ -107,8 +109,12 @@ static int absnorm_check(const char* what, const float* guide, const float* a, c
         return CSPN_E_BADARG;
     }
     if ((size_t)N * V > ((size_t)1 << 39)) { set_error("%s: N * V = %zu voxels is beyond the launch grid", what, (size_t)N * V); return CSPN_E_UNSUPPORTED; }
-    const size_t bytes = sizeof(float) * (size_t)N * K * V;
-    if (overlaps(out, bytes, guide, bytes) || overlaps(out, bytes, a, bytes)) { set_error("%s: the output must not alias an input", what); return CSPN_E_BADARG; }
+    const size_t elems = (size_t)N * K * V, gbytes = gsize * elems, obytes = (out_is_guide_type ? gsize : sizeof(float)) * elems;
+    const bool a_is_guide = (const void*)a == guide;   // (the forward passes guide twice)
+    if (overlaps(out, obytes, guide, gbytes) || overlaps(out, obytes, a, a_is_guide ? gbytes : sizeof(float) * elems)) {
+        set_error("%s: the output must not alias an input", what);
+        return CSPN_E_BADARG;
+    }
     return 0;
 }
 
@@ -531,21 +537,38 @@ int cspn3d_forward_f32(const float* gate, const float* feat, const float* sparse
     return cspn3d_forward_f32_algo(gate, feat, sparse, out, B, D, H, W, n_iter, norm_type, CSPN_ALGO3D_AUTO, ws, ws_bytes, stream);
 }
 
-int cspn3d_forward_f32_algo(const float* gate, const float* feat, const float* sparse, float* out, int B, int D, int H,
-                            int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+// the checks of cspn3d_forward_f32_algo (gdt 0) and cspn3d_forward_g16_algo, then the engine
+static int forward3d_entry(const void* gate, int gdt, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                           int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (int e = check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
     if (int e = check_index32((long long)B * D * H * W, 27)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
     if (int e = async_failure_of_earlier_call()) return e;
-    // misaligned tensors cannot take the 16-byte paths: they fold like the normalising modes (cspn3d_workspace_bytes())
-    const bool aligned = ((((uintptr_t)gate | (uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
+    // misaligned tensors cannot take the 16-byte paths: they fold like the normalising modes (cspn3d_workspace_bytes()); a 16-bit gate
+    // tensor is aligned at 8 bytes (four gates)
+    const bool aligned = ((uintptr_t)gate & gate_quad_mask(gdt)) == 0 && ((((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
     size_t need = n_iter == 0 ? 0 : (aligned ? forward3d_workspace(B, D, H, W, n_iter, norm_type, sparse != nullptr)
                                              : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(gate, feat, out, n_iter, norm_type, ws, ws_bytes, need)) return e;
     if (n_iter == 0) return identity_copy(out, feat, (size_t)B * D * H * W, st);
-    return stepwise3d_forward(gate, feat, sparse, out, B, D, H, W, n_iter, norm_type, ws, st, algo);
+    return stepwise3d_forward(gate, feat, sparse, out, B, D, H, W, n_iter, norm_type, ws, st, algo, gdt);
+}
+
+int cspn3d_forward_f32_algo(const float* gate, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                            int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return forward3d_entry(gate, 0, feat, sparse, out, B, D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
+}
+
+int cspn3d_forward_g16_algo(const void* gate, int gate_dtype, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                            int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_forward_g16_algo", gate_dtype, gate, nullptr)) return e;
+    if (norm_type != CSPN_NORM_NONE || sparse) {
+        set_error("cspn3d_forward_g16_algo: 16-bit gates cover the Paddle contract only (norm_type CSPN_NORM_NONE, sparse NULL)");
+        return CSPN_E_BADARG;
+    }
+    return forward3d_entry(gate, gate_dtype, feat, sparse, out, B, D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
 }
 
 int cspn3d_multi_supported(int B, int C, int D, int H, int W, int n_iter) {
@@ -553,21 +576,32 @@ int cspn3d_multi_supported(int B, int C, int D, int H, int W, int n_iter) {
     return persistent3d_multi_supported(B, C, D, H, W, n_iter) ? 1 : 0;
 }
 
-int cspn3d_forward_multi_f32(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
-                             void* ws, size_t ws_bytes, cspn_stream_t stream) {
+static int forward3d_multi_entry(const void* gate, int gdt, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                                 void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (int e = check_shape("BCDHW", {B, C, D, H, W})) return e;
     if (B == 0) return 0;
     if (int e = async_failure_of_earlier_call()) return e;
     if (int e = check_common(gate, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes,
                              n_iter == 0 ? 0 : forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false))) return e;
-    const bool aligned = ((((uintptr_t)gate | (uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
+    const bool aligned = ((uintptr_t)gate & gate_quad_mask(gdt)) == 0 && ((((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
     if (!aligned || !persistent3d_multi_supported(B, C, D, H, W, n_iter)) {
         set_error("cspn3d_forward_multi_f32 runs the persistent kernel only (W %% 4 == 0, 2 <= n_iter <= 60, 16-byte aligned tensors, "
                   "volume resident on the device): loop over the channels with cspn3d_forward_f32 for B=%d C=%d D=%d H=%d W=%d n_iter=%d",
                   B, C, D, H, W, n_iter);
         return CSPN_E_UNSUPPORTED;
     }
-    return persistent3d_forward_multi(gate, feat, out, B, C, D, H, W, n_iter, ws, (hipStream_t)stream);
+    return persistent3d_forward_multi(gate, feat, out, B, C, D, H, W, n_iter, ws, (hipStream_t)stream, gdt);
+}
+
+int cspn3d_forward_multi_f32(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                             void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return forward3d_multi_entry(gate, 0, feat, out, B, C, D, H, W, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn3d_forward_multi_g16(const void* gate, int gate_dtype, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                             void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_forward_multi_g16", gate_dtype, gate, nullptr)) return e;
+    return forward3d_multi_entry(gate, gate_dtype, feat, out, B, C, D, H, W, n_iter, ws, ws_bytes, stream);
 }
 
 size_t cspn3d_backward_workspace_bytes(int B, int D, int H, int W, int n_iter) {
@@ -576,7 +610,8 @@ size_t cspn3d_backward_workspace_bytes(int B, int D, int H, int W, int n_iter) {
 }
 
 // the checks of cspn3d_backward_f32 (multi false, C = 1) and cspn3d_backward_multi_f32 (norm_type NONE), then the engine
-static int backward3d_entry(bool multi, const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B, int C,
+// gdt: the type of gate and grad_gate (0: float32)
+static int backward3d_entry(bool multi, const void* gate, int gdt, const float* feat, const float* grad_out, void* grad_gate, float* grad_feat, int B, int C,
                             int D, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (int e = multi ? check_shape("BCDHW", {B, C, D, H, W}) : check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
@@ -585,15 +620,26 @@ static int backward3d_entry(bool multi, const float* gate, const float* feat, co
     if (int e = check_index32((long long)V * C, 2)) return e;
     if (norm_type != CSPN_NORM_NONE) { set_error("the 3D backward covers the Paddle contract only (norm_type NONE: gates used as given, no mask)"); return CSPN_E_UNSUPPORTED; }
     if (int e = async_failure_of_earlier_call()) return e;
-    if (int e = check_common(gate, feat, grad_out, n_iter, norm_type, ws, ws_bytes, n_iter == 0 ? 0 : backward3d_workspace(B, D, H, W, n_iter, C))) return e;
+    if (int e = check_common(gate, feat, grad_out, n_iter, norm_type, ws, ws_bytes, n_iter == 0 ? 0 : backward3d_workspace(B, D, H, W, n_iter, C, gdt))) return e;
     if (!grad_gate && !grad_feat) return 0;
-    if (n_iter == 0) return identity_backward(grad_feat, grad_out, V * C, grad_gate, 26 * V, (hipStream_t)stream);
-    return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, (hipStream_t)stream, false, C);
+    if (n_iter == 0) return identity_backward(grad_feat, grad_out, V * C, grad_gate, 26 * V * gate_bytes(gdt), (hipStream_t)stream);
+    return backward3d(gate, feat, grad_out, grad_gate, grad_feat, B, D, H, W, n_iter, ws, (hipStream_t)stream, false, C, gdt);
 }
 
 int cspn3d_backward_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B,
                         int D, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    return backward3d_entry(false, gate, feat, grad_out, grad_gate, grad_feat, B, 1, D, H, W, n_iter, norm_type, ws, ws_bytes, stream);
+    return backward3d_entry(false, gate, 0, feat, grad_out, grad_gate, grad_feat, B, 1, D, H, W, n_iter, norm_type, ws, ws_bytes, stream);
+}
+
+size_t cspn3d_backward_g16_workspace_bytes(int B, int D, int H, int W, int n_iter) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
+    return backward3d_workspace(B, D, H, W, n_iter, 1, CSPN_DTYPE_F16);
+}
+
+int cspn3d_backward_g16(const void* gate, int gate_dtype, const float* feat, const float* grad_out, void* grad_gate, float* grad_feat, int B,
+                        int D, int H, int W, int n_iter, int norm_type, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_backward_g16", gate_dtype, gate, grad_gate)) return e;
+    return backward3d_entry(false, gate, gate_dtype, feat, grad_out, grad_gate, grad_feat, B, 1, D, H, W, n_iter, norm_type, ws, ws_bytes, stream);
 }
 
 size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter) {
@@ -603,7 +649,18 @@ size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, 
 
 int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat, int B,
                               int C, int D, int H, int W, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    return backward3d_entry(true, gate, feat, grad_out, grad_gate, grad_feat, B, C, D, H, W, n_iter, CSPN_NORM_NONE, ws, ws_bytes, stream);
+    return backward3d_entry(true, gate, 0, feat, grad_out, grad_gate, grad_feat, B, C, D, H, W, n_iter, CSPN_NORM_NONE, ws, ws_bytes, stream);
+}
+
+size_t cspn3d_backward_multi_g16_workspace_bytes(int B, int C, int D, int H, int W, int n_iter) {
+    if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
+    return backward3d_workspace(B, D, H, W, n_iter, C, CSPN_DTYPE_F16);
+}
+
+int cspn3d_backward_multi_g16(const void* gate, int gate_dtype, const float* feat, const float* grad_out, void* grad_gate, float* grad_feat, int B,
+                              int C, int D, int H, int W, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_backward_multi_g16", gate_dtype, gate, grad_gate)) return e;
+    return backward3d_entry(true, gate, gate_dtype, feat, grad_out, grad_gate, grad_feat, B, C, D, H, W, n_iter, CSPN_NORM_NONE, ws, ws_bytes, stream);
 }
 
 // ---- the demo's module (reference cspn_paddle/demo.py:20-54): w = |g| / sum_k |g_k| per voxel over one slice's K gates, then the NONE op ----
@@ -618,20 +675,40 @@ int cspn_gate_absnorm_backward_f32(const float* guide, const float* grad_gate, f
     return gate_absnorm_backward(guide, grad_gate, grad_guide, N, K, V, (hipStream_t)stream);
 }
 
+// the 3D module's forms on a 16-bit guide (K = 26 only)
+static int absnorm_g16_check(const char* what, int dtype, const void* guide, const void* grad_guide, int K) {
+    if (int e = g16_check(what, dtype, guide, grad_guide)) return e;
+    if (K != 26) { set_error("%s: K must be 26 (the 3D module), got %d", what, K); return CSPN_E_BADARG; }
+    return 0;
+}
+
+int cspn_gate_absnorm_g16(const void* guide, int gate_dtype, float* gate, int N, int K, size_t V, cspn_stream_t stream) {
+    if (int e = absnorm_g16_check("cspn_gate_absnorm_g16", gate_dtype, guide, nullptr, K)) return e;
+    if (int e = absnorm_check("cspn_gate_absnorm_g16", guide, (const float*)guide, gate, N, K, V, 2)) return e;
+    return gate_absnorm_g16(guide, gate_dtype, gate, N, V, (hipStream_t)stream);
+}
+
+int cspn_gate_absnorm_backward_g16(const void* guide, int gate_dtype, const float* grad_gate, void* grad_guide, int N, int K, size_t V,
+                                   cspn_stream_t stream) {
+    if (int e = absnorm_g16_check("cspn_gate_absnorm_backward_g16", gate_dtype, guide, grad_guide, K)) return e;
+    if (int e = absnorm_check("cspn_gate_absnorm_backward_g16", guide, grad_gate, grad_guide, N, K, V, 2, true)) return e;
+    return gate_absnorm_backward_g16(guide, gate_dtype, grad_gate, grad_guide, N, V, (hipStream_t)stream);
+}
+
 size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_iter) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
     return absnorm_planes_bytes(B, D, H, W) + forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false);
 }
 
-int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
-                               void* ws, size_t ws_bytes, cspn_stream_t stream) {
+static int forward3d_absnorm_entry(const char* what, const void* guide, int gdt, const float* feat, float* out, int B, int D, int H, int W, int n_iter,
+                                   int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (int e = check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
     if (int e = check_index32((long long)B * D * H * W, 27)) return e;
     if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
     const size_t total = (size_t)B * D * H * W;
-    if (guide && feat && out && (overlaps(out, total * sizeof(float), guide, 26 * total * sizeof(float)) || overlaps(out, total * sizeof(float), feat, total * sizeof(float)))) {
-        set_error("cspn3d_forward_absnorm_f32: out must not alias an input");
+    if (guide && feat && out && (overlaps(out, total * sizeof(float), guide, 26 * total * gate_bytes(gdt)) || overlaps(out, total * sizeof(float), feat, total * sizeof(float)))) {
+        set_error("%s: out must not alias an input", what);
         return CSPN_E_BADARG;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -642,16 +719,27 @@ int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out
                                                                                             : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(guide, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes, need)) return e;
     if (n_iter == 0) return identity_copy(out, feat, total, st);
-    const bool fused = vals_aligned && ((((uintptr_t)guide | (uintptr_t)ws) & 15u) == 0) && persistent3d_supported(B, D, H, W, n_iter);
+    const bool fused = vals_aligned && ((uintptr_t)guide & gate_quad_mask(gdt)) == 0 && ((uintptr_t)ws & 15u) == 0 && persistent3d_supported(B, D, H, W, n_iter);
     if (algo == CSPN_ALGO3D_PERSISTENT && !fused) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;
     }
-    if (fused && algo != CSPN_ALGO3D_STEPWISE) return persistent3d_forward_absnorm(guide, feat, out, B, D, H, W, n_iter, ws, st);
-    // unfused: the normaliser into the workspace, then the NONE op on it
+    if (fused && algo != CSPN_ALGO3D_STEPWISE) return persistent3d_forward_absnorm(guide, feat, out, B, D, H, W, n_iter, ws, st, gdt);
+    // unfused: the normaliser into the workspace (float32 gates, whatever the guide's type), then the NONE op on it
     float* gate = (float*)ws;
-    if (int e = gate_absnorm(guide, gate, B, 26, (size_t)D * H * W, st)) return e;
+    if (int e = gdt ? gate_absnorm_g16(guide, gdt, gate, B, (size_t)D * H * W, st) : gate_absnorm((const float*)guide, gate, B, 26, (size_t)D * H * W, st)) return e;
     return stepwise3d_forward(gate, feat, nullptr, out, B, D, H, W, n_iter, CSPN_NORM_NONE, (char*)ws + absnorm_planes_bytes(B, D, H, W), st, algo);
+}
+
+int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
+                               void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return forward3d_absnorm_entry("cspn3d_forward_absnorm_f32", guide, 0, feat, out, B, D, H, W, n_iter, algo, ws, ws_bytes, stream);
+}
+
+int cspn3d_forward_absnorm_g16(const void* guide, int gate_dtype, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
+                               void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_forward_absnorm_g16", gate_dtype, guide, nullptr)) return e;
+    return forward3d_absnorm_entry("cspn3d_forward_absnorm_g16", guide, gate_dtype, feat, out, B, D, H, W, n_iter, algo, ws, ws_bytes, stream);
 }
 
 

@@ -41,15 +41,19 @@ size_t padded2d_workspace(int B, int H, int W, int n_iter);
 int padded2d_forward(const float* g, const float* blur, const float* sparse, float* out, int B, int H, int W, int n_iter, int norm, void* ws,
                      hipStream_t st);
 size_t stepwise3d_workspace(int B, int D, int H, int W, int n_iter);
-int stepwise3d_forward(const float* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
-                       int W, int n_iter, int norm, void* ws, hipStream_t st, int algo = 0);
+// gdt (here and below): the storage type of the gates, 0 float32 or CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 (Paddle contract only: norm NONE, no
+// mask); 16-bit gates are widened exactly where they are read (cspn_gate16.h), every value, level and workspace stays float32
+int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                       int W, int n_iter, int norm, void* ws, hipStream_t st, int algo = 0, int gdt = 0);
+// one step of the Paddle contract (W % 4 == 0, 16-byte aligned values, gates aligned to four elements)
+int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st);
 size_t forward3d_workspace(int B, int D, int H, int W, int n_iter, int norm, bool has_sparse);
 
 // ---- 3D, gates resident in registers for all steps (cspn3d_persistent.hip); Paddle contract only ----
 bool persistent3d_supported(int B, int D, int H, int W, int n_iter);
 size_t persistent3d_workspace(int B, int D, int H, int W);
-int persistent3d_forward(const float* gate, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
-                         hipStream_t st);
+int persistent3d_forward(const void* gate, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                         hipStream_t st, int gdt = 0);
 // the folded form of the normalising / masked modes: wf = 26 planes w' + the constant term c' ([27][B*V], fold3d_kernel)
 int persistent3d_forward_folded(const float* wf, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
                                 hipStream_t st);
@@ -59,19 +63,20 @@ struct P3Options { int mute = -1; bool coop = false; bool placement = true; /* f
                    bool write_through = false; /* true: no L2-resident stores, every published row goes write-through (A/B, tests) */ };
 // the same run for the backward: adjoint = transposed operator; levels + (lv0 + it * lvs) volumes receive step it < n_iter
 // C > 1: feat / out / the level volumes hold C value channels per volume ([B][C][V]) on shared gates (the MULTI instantiations)
-int persistent3d_run(const float* gate, const float* feat, float* out, float* levels, int lv0, int lvs, bool adjoint, int B, int D,
-                     int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt = P3Options(), int C = 1);
+// gdt != 0: the forward instances only (the transposed one reads float32 gates)
+int persistent3d_run(const void* gate, const float* feat, float* out, float* levels, int lv0, int lvs, bool adjoint, int B, int D,
+                     int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt = P3Options(), int C = 1, int gdt = 0);
 int persistent3d_error_word(const void* ws, int B, int D, int H, int W);
 void persistent3d_geo(int B, int D, int H, int W, int n_iter, int* info);   // (test-hook library)
 // C value channels per volume that share the gates ([B][C][V] value tensors, [B][26][V] gates used as given)
 bool persistent3d_multi_supported(int B, int C, int D, int H, int W, int n_iter);
-int persistent3d_forward_multi(const float* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter, void* ws,
-                               hipStream_t st);
+int persistent3d_forward_multi(const void* gate, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter, void* ws,
+                               hipStream_t st, int gdt = 0);
 
 // the demo's module on RAW gates (NRM instantiation): each voxel's 26 gates divided by their abs-sum in the registers, then the n_iter
 // steps of persistent3d_forward; same calls as persistent3d_supported
-int persistent3d_forward_absnorm(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
-                                 hipStream_t st);
+int persistent3d_forward_absnorm(const void* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
+                                 hipStream_t st, int gdt = 0);
 
 // sticky per-device status of the persistent launches: != 0 once after a launch gave up (a workgroup waited in vain for a
 // neighbour: not all workgroups resident); read without synchronisation from a pinned host word, cleared by the read
@@ -81,6 +86,10 @@ int persistent3d_take_status();
 // or 48 ----
 int gate_absnorm(const float* g, float* w, int N, int K, size_t V, hipStream_t st);
 int gate_absnorm_backward(const float* g, const float* gw, float* gg, int N, int K, size_t V, hipStream_t st);
+// the 3D module's forms on an fp16 / bf16 guide (K = 26; gdt CSPN_DTYPE_F16 or CSPN_DTYPE_BF16): the guide widened exactly as it is read, w
+// and dL/dw float32, dL/dguide the float32 value rounded once at its store -- the float32 kernels' arithmetic, statement for statement
+int gate_absnorm_g16(const void* g, int gdt, float* w, int N, size_t V, hipStream_t st);
+int gate_absnorm_backward_g16(const void* g, int gdt, const float* gw, void* gg, int N, size_t V, hipStream_t st);
 
 // ---- the 2D NONE op over a K x K neighbourhood, K = 5 or 7 (cspn2d_kxk.hip): gate [N][K*K-1][H][W], values [N][C][H][W] ----
 // gate and gg in the type of dtype: 0 (float32), CSPN_DTYPE_F16 or CSPN_DTYPE_BF16.  A 16-bit gate is widened exactly where it is used
@@ -114,9 +123,13 @@ int kxk_norm_backward(const void* guid, int dtype, const float* blur, const floa
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels
-size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C = 1);
-int backward3d(const float* g, const float* feat, const float* gout, float* gg, float* gf, int B, int D, int H, int W, int n_iter,
-               void* ws, hipStream_t st, bool stepwise_only = false /* test-hook library: one launch per step */, int C = 1);
+// gdt: the storage type of g and gg; 16-bit: where the fused sweeps can run, the workspace also holds the float32 copy of the gates the
+// transposed sweep reads
+size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C = 1, int gdt = 0);
+int backward3d(const void* g, const float* feat, const float* gout, void* gg, float* gf, int B, int D, int H, int W, int n_iter,
+               void* ws, hipStream_t st, bool stepwise_only = false /* test-hook library: one launch per step */, int C = 1, int gdt = 0);
+// n gates (n % 4 == 0, g 8-byte and w 16-byte aligned) widened exactly into float32
+int widen_gates(const void* g, int gdt, float* w, size_t n, hipStream_t st);
 
 // ---- the producer of the path's inputs (cspn_head.hip): Unpool + 3x3 conv C -> 8 (guidance) and C -> 1 (blur) as one kernel; mode 0 raw guidance,
 // 1 / 2 gate_wb of '8sum' / '8sum_abs' (the normalisation fused behind the conv) ----

@@ -24,15 +24,16 @@ _GATE16 = {torch.float16: _lib.DTYPES["float16"], torch.bfloat16: _lib.DTYPES["b
 
 
 def _prep_gate(t, name):
-    """a gate / guidance tensor of the K x K engine: float32, or float16 / bfloat16 as it is (the *_g16 entry points widen it exactly
-    where it is used) -> (tensor, gate_dtype code or None for float32)"""
+    """a gate / guidance tensor of the K x K engine or of the 3D Paddle contract: float32, or float16 / bfloat16 as it is (the *_g16 entry
+    points widen it exactly where it is used) -> (tensor, gate_dtype code or None for float32)"""
     if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in _GATE16:
         return t.contiguous(), _GATE16[t.dtype]
     return _prep(t, name), None
 
 
 def _prep_value(t, name, shape=None):
-    """a value tensor of the K x K engine (one plane per channel): float32; float16 / bfloat16 is widened with one torch cast"""
+    """a value tensor of the K x K engine or of the 3D Paddle contract (one plane per channel): float32; float16 / bfloat16 is widened with
+    one torch cast"""
     if isinstance(t, torch.Tensor) and t.dtype in _GATE16:
         t = t.float()
     return _prep(t, name, shape)
@@ -40,7 +41,9 @@ def _prep_value(t, name, shape=None):
 
 def widen16(*tensors):
     """float16 / bfloat16 tensors widened with a differentiable .float() (autograd carries the gradient back through the cast), everything
-    else as it is: what the modules and mirrors do in front of the paths that have no 16-bit kernel (3 x 3 in 2D, 3D, the gate_absnorm tensor op)"""
+    else as it is: what the modules and mirrors do with value tensors, and in front of the paths that have no 16-bit kernel (3 x 3 in 2D: the
+    ring; the normalising / masked 3D modes; the gate_absnorm tensor op).  The 3D Paddle contract and the 3D demo module take a 16-bit gate or
+    guide as it is (cspn3d_*_g16)"""
     out = tuple(t.float() if isinstance(t, torch.Tensor) and t.dtype in _GATE16 else t for t in tensors)
     return out[0] if len(out) == 1 else out
 
@@ -302,42 +305,49 @@ def cspn2d_backward_from_history_multi(guidance, blur_depth, sparse_depth, grad_
 
 def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", algo="auto", _return_ws=False):
     """gate [B,26,D,H,W], feat [B,1,D,H,W] -> [B,1,D,H,W]; n_iter 3x3x3 propagation steps.  algo: 'auto' | 'stepwise'
-    (one launch per step) | 'persistent' (gates resident in registers across the steps; norm_type 'none' without a mask)."""
+    (one launch per step) | 'persistent' (gates resident in registers across the steps; norm_type 'none' without a mask).
+    With norm_type 'none' and no mask (the Paddle contract) gate may be float16 / bfloat16 (cspn3d_forward_g16_algo: widened exactly where
+    it is read, out is float32 and bitwise the float32 call on gate.float() on the same path); a 16-bit feat is widened with one cast.  The
+    normalising and masked modes take float32 gates only."""
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
-    g = _prep(gate, "gate")
-    h = _prep(feat, "feat", (B, 1, D, H, W))
+    paddle = norm_type == "none" and sparse is None
+    g, dt = _prep_gate(gate, "gate") if paddle else (_prep(gate, "gate"), None)
+    h = _prep_value(feat, "feat", (B, 1, D, H, W)) if paddle else _prep(feat, "feat", (B, 1, D, H, W))
     s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
     out = torch.empty_like(h)
     if B == 0:
         return out
-    if any(t.data_ptr() % 16 for t in (g, h, out)):   # misaligned views take the folding path: the full workspace
+    if g.data_ptr() % (16 if dt is None else 8) or any(t.data_ptr() % 16 for t in (h, out)):   # misaligned views take the folding path: the full workspace
         ws_query = ("cspn3d_workspace_bytes", B, D, H, W, int(n_iter))
     else:
         ws_query = ("cspn3d_workspace_bytes_ex", B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], int(s is not None))
-    ws = _launch("cspn3d_forward_f32_algo", g.device,
-                 (_ptr(g), _ptr(h), _ptr(s), _ptr(out), B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], _lib.ALGOS_3D[algo]),
-                 ws_query, "cspn3d_forward_f32")
+    ws = _launch("cspn3d_forward_f32_algo" if dt is None else "cspn3d_forward_g16_algo", g.device,
+                 (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(out), B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
+                  _lib.ALGOS_3D[algo]),
+                 ws_query, "cspn3d_forward_f32" if dt is None else "cspn3d_forward_g16")
     return (out, ws) if _return_ws else out
 
 
 def cspn3d_forward_multi(gate, feat, n_iter=12):
     """gate [B,26,D,H,W] (used as given: the Paddle contract), feat [B,C,D,H,W] -> [B,C,D,H,W]: the C channels share the gates
     (reference cspn_paddle/README.md:56), which are read once per forward and stay in the registers while the n_iter steps run for
-    one channel after the other.  Raises CspnError where the persistent kernel does not take the call (see cspn3d_multi_supported)."""
+    one channel after the other.  Raises CspnError where the persistent kernel does not take the call (see cspn3d_multi_supported).
+    gate may be float16 / bfloat16 (cspn3d_forward_multi_g16; out float32, bitwise the float32 call on gate.float())."""
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
     C = feat.shape[1]
-    g = _prep(gate, "gate")
-    h = _prep(feat, "feat", (B, C, D, H, W))
+    g, dt = _prep_gate(gate, "gate")
+    h = _prep_value(feat, "feat", (B, C, D, H, W))
     if h.device != g.device:
         raise ValueError("all tensors must live on the same device")
     out = torch.empty_like(h)
     if B == 0:
         return out
-    _launch("cspn3d_forward_multi_f32", g.device, (_ptr(g), _ptr(h), _ptr(out), B, C, D, H, W, int(n_iter)),
+    _launch("cspn3d_forward_multi_f32" if dt is None else "cspn3d_forward_multi_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(out), B, C, D, H, W, int(n_iter)),
             ("cspn3d_workspace_bytes_ex", B, D, H, W, int(n_iter), _lib.NORM_TYPES["none"], 0))
     return out
 
@@ -351,14 +361,14 @@ def cspn3d_check_status(device=None):
 
 
 def _backward3d(variant, gate, feat, grad_out, n_iter, need_gate, need_feat):
-    """cspn3d_backward<variant>_f32: variant "" takes feat [B,1,D,H,W], "_multi" [B,C,D,H,W] on shared gates"""
+    """cspn3d_backward<variant>_f32 / _g16: variant "" takes feat [B,1,D,H,W], "_multi" [B,C,D,H,W] on shared gates"""
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
     C = feat.shape[1] if variant else 1
-    g = _prep(gate, "gate")
-    h = _prep(feat, "feat", (B, C, D, H, W))
-    go = _prep(grad_out, "grad_out", (B, C, D, H, W))
+    g, dt = _prep_gate(gate, "gate")
+    h = _prep_value(feat, "feat", (B, C, D, H, W))
+    go = _prep_value(grad_out, "grad_out", (B, C, D, H, W))
     if h.device != g.device or go.device != g.device:
         raise ValueError("all tensors must live on the same device")
     gg = torch.empty_like(g) if need_gate else None
@@ -366,23 +376,26 @@ def _backward3d(variant, gate, feat, grad_out, n_iter, need_gate, need_feat):
     if B == 0 or not (need_gate or need_feat):
         return gg, gf
     dims = (B, C, D, H, W) if variant else (B, D, H, W)
-    _launch("cspn3d_backward%s_f32" % variant, g.device,
-            (_ptr(g), _ptr(h), _ptr(go), _ptr(gg), _ptr(gf), *dims, int(n_iter), *(() if variant else (_lib.NORM_TYPES["none"],))),
-            ("cspn3d_backward%s_workspace_bytes" % variant, *dims, int(n_iter)))
+    _launch("cspn3d_backward%s_%s" % (variant, "f32" if dt is None else "g16"), g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(go), _ptr(gg), _ptr(gf), *dims, int(n_iter),
+             *(() if variant else (_lib.NORM_TYPES["none"],))),
+            ("cspn3d_backward%s%s_workspace_bytes" % (variant, "" if dt is None else "_g16"), *dims, int(n_iter)))
     return gg, gf
 
 
 def cspn3d_backward(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
     """Gradient of cspn3d_forward(gate, feat, None, n_iter, 'none') -- the Paddle contract, the op the reference demo's
     optimiser differentiates (cspn_paddle/demo.py:65-75) -- w.r.t. gate and feat, in the HIP engine.
-    -> (grad_gate [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None)"""
+    -> (grad_gate [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None).  A float16 / bfloat16 gate (cspn3d_backward_g16): grad_feat is
+    float32 and bitwise the float32 call's on gate.float(), grad_gate comes back in the gate's dtype, the float32 sum rounded once."""
     return _backward3d("", gate, feat, grad_out, n_iter, need_gate, need_feat)
 
 
 def cspn3d_backward_multi(gate, feat, grad_out, n_iter=1, need_gate=True, need_feat=True):
     """Gradient of the n_iter-step 3D propagation of C channels on SHARED gates (feat, grad_out [B,C,D,H,W]; reference
     cspn_paddle/README.md:56, differentiated at demo.py:65-75) -> (grad_gate [B,26,D,H,W] summed over the channels or None,
-    grad_feat [B,C,D,H,W] or None); one call of the HIP engine (cspn3d_backward_multi_f32)."""
+    grad_feat [B,C,D,H,W] or None); one call of the HIP engine (cspn3d_backward_multi_f32; cspn3d_backward_multi_g16 for a float16 /
+    bfloat16 gate, whose gradient comes back in its dtype)."""
     return _backward3d("_multi", gate, feat, grad_out, n_iter, need_gate, need_feat)
 
 
@@ -400,7 +413,7 @@ class _AffinityPropagateFunction(torch.autograd.Function):
         if C == 1:
             return cspn3d_forward(gate_weight, x, None, n_iter, "none")
         if _lib.symbol("cspn3d_multi_supported")(x.shape[0], C, *x.shape[2:], int(n_iter)) and x.data_ptr() % 16 == 0 \
-                and gate_weight.data_ptr() % 16 == 0:
+                and gate_weight.data_ptr() % (8 if gate_weight.dtype in _GATE16 else 16) == 0:
             return cspn3d_forward_multi(gate_weight, x, n_iter)
         return torch.cat([cspn3d_forward(gate_weight, x[:, c:c + 1].contiguous(), None, n_iter, "none") for c in range(C)], 1)
 
@@ -560,8 +573,9 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     d = 2 or 3; kernel_size 3, or 5 / 7 in 2D (the K x K engine, cspn2d_forward_kxk).  n_iter > 1 fuses that many chained calls
     (demo.py:39,50).  Differentiable w.r.t. input and gate_weight like the reference op (the demo trains through it, demo.py:65-75).
     float16 / bfloat16 (a head under torch.autocast): with kernel_size 5 / 7 the gates go to the engine as they are (widened exactly where
-    used; the gate gradient comes back in their dtype) and a 16-bit input is widened with one cast; with kernel_size 3 (2D and 3D, no 16-bit
-    kernel) both are widened with a differentiable .float().  The result is float32 either way."""
+    used; the gate gradient comes back in their dtype) and a 16-bit input is widened with one cast; so it is with kernel_size 3 in 3D (the
+    16-bit instances of the 3D kernels, cspn3d_*_g16); with kernel_size 3 in 2D (the ring: no 16-bit kernel) both are widened with a
+    differentiable .float().  The result is float32 either way."""
     if kernel_size != 3:
         if not isinstance(input, torch.Tensor) or not isinstance(gate_weight, torch.Tensor):
             raise TypeError("input and gate_weight must be torch.Tensor")
@@ -574,10 +588,12 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
         if torch.is_grad_enabled() and (input.requires_grad or gate_weight.requires_grad):
             return _AffinityPropagateKxKFunction.apply(input, gate_weight, K, int(n_iter))
         return cspn2d_forward_kxk(gate_weight, input, K, n_iter)
-    input, gate_weight = widen16(input, gate_weight)
+    input = widen16(input)
     d = input.dim() - 2
     if d not in (2, 3):
         raise ValueError("input must be [N,C,H,W] or [N,C,D,H,W]")
+    if d == 2:
+        gate_weight = widen16(gate_weight)
     if gate_weight.shape[1] != 3 ** d - 1:
         raise ValueError("gate_weight must have %d channels" % (3 ** d - 1))
     N, C = input.shape[:2]
@@ -585,7 +601,8 @@ def affinity_propagate(input, gate_weight, kernel_size=3, n_iter=1):
     if input.device != gate_weight.device:
         raise ValueError("all tensors must live on the same device")
     if d == 3 and C > 1 and not needs_grad and input.is_cuda and _lib.symbol("cspn3d_multi_supported")(N, C, *input.shape[2:], int(n_iter)) \
-            and input.is_contiguous() and gate_weight.is_contiguous() and input.data_ptr() % 16 == 0 and gate_weight.data_ptr() % 16 == 0:
+            and input.is_contiguous() and gate_weight.is_contiguous() and input.data_ptr() % 16 == 0 \
+            and gate_weight.data_ptr() % (8 if gate_weight.dtype in _GATE16 else 16) == 0:
         return cspn3d_forward_multi(gate_weight, input, n_iter)   # the gates are read once for all C channels
     if d == 3 and C > 1 and needs_grad and input.is_cuda:
         # training through C channels on shared gates (demo.py:65-75): one forward and one backward call for all of them
@@ -720,13 +737,29 @@ def _absnorm_flat(guide, K):
     return guide.shape[0] * (guide.shape[1] // K), V
 
 
-def _gate_absnorm(guide, K):
+def _gate_absnorm(guide, K, allow16=False):
+    """allow16 (the 3D module's backward, K = 26): a float16 / bfloat16 guide as it is -> float32 gates (cspn_gate_absnorm_g16)"""
     S, V = _absnorm_flat(guide, K)
-    g = _prep(guide, "guide")
+    g, dt = _prep_gate(guide, "guide") if allow16 and K == 26 else (_prep(guide, "guide"), None)
+    out = torch.empty_like(g, dtype=torch.float32)
+    if out.numel() == 0:
+        return out
+    _launch("cspn_gate_absnorm_f32" if dt is None else "cspn_gate_absnorm_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(out), S, K, V))
+    return out
+
+
+def _gate_absnorm_backward26(guide, grad_gate):
+    """the 3D module's chain through the normalisation: guide float32, float16 or bfloat16, grad_gate = dL/dw float32 -> dL/dguide in the
+    guide's dtype (cspn_gate_absnorm_backward_f32 / _g16: the float32 value, rounded once at its store)"""
+    S, V = _absnorm_flat(guide, 26)
+    g, dt = _prep_gate(guide, "guide")
+    r = _prep(grad_gate, "grad_gate", tuple(g.shape))
     out = torch.empty_like(g)
     if out.numel() == 0:
         return out
-    _launch("cspn_gate_absnorm_f32", g.device, (_ptr(g), _ptr(out), S, K, V))
+    _launch("cspn_gate_absnorm_backward_f32" if dt is None else "cspn_gate_absnorm_backward_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(r), _ptr(out), S, 26, V))
     return out
 
 
@@ -773,12 +806,14 @@ def gate_absnorm(guide, K):
 def cspn3d_forward_absnorm(guide, feat, n_iter=12, algo="auto"):
     """guide [B,26,D,H,W] RAW, feat [B,1,D,H,W] -> [B,1,D,H,W]: gate_absnorm(guide, 26), then cspn3d_forward(..., 'none') -- one engine call
     (cspn3d_forward_absnorm_f32).  algo 'auto' normalises the resident gates inside the persistent kernel wherever the NONE op would take
-    it; 'stepwise' normalises into the workspace and steps; 'persistent' raises CspnError where the kernel cannot take the call."""
+    it; 'stepwise' normalises into the workspace and steps; 'persistent' raises CspnError where the kernel cannot take the call.
+    guide may be float16 / bfloat16 (cspn3d_forward_absnorm_g16: widened exactly where it is read, out is float32 and bitwise the float32
+    call on guide.float()); a 16-bit feat is widened with one cast."""
     if guide.dim() != 5 or guide.shape[1] != 26:
         raise ValueError("guide must be [B,26,D,H,W], got %s" % (tuple(guide.shape),))
     B, _, D, H, W = guide.shape
-    g = _prep(guide, "guide")
-    h = _prep(feat, "feat", (B, 1, D, H, W))
+    g, dt = _prep_gate(guide, "guide")
+    h = _prep_value(feat, "feat", (B, 1, D, H, W))
     if h.device != g.device:
         raise _lib.CspnError("cspn_amd: guide is on %s, feat on %s: all tensors must live on the same device" % (g.device, h.device))
     if h.data_ptr() % 16:
@@ -786,7 +821,8 @@ def cspn3d_forward_absnorm(guide, feat, n_iter=12, algo="auto"):
     out = torch.empty_like(h)
     if B == 0:
         return out
-    _launch("cspn3d_forward_absnorm_f32", g.device, (_ptr(g), _ptr(h), _ptr(out), B, D, H, W, int(n_iter), _lib.ALGOS_3D[algo]),
+    _launch("cspn3d_forward_absnorm_f32" if dt is None else "cspn3d_forward_absnorm_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(out), B, D, H, W, int(n_iter), _lib.ALGOS_3D[algo]),
             ("cspn3d_forward_absnorm_workspace_bytes", B, D, H, W, int(n_iter)))
     return out
 
@@ -816,7 +852,8 @@ def _absnorm_forward(guide, feat, n_iter, kernel_size=3, keep_history=False):
 
 class _AbsnormPropagateFunction(torch.autograd.Function):
     """the demo's module under autograd.  3 x 3 (x 3): the backward recomputes w with the normaliser, runs the NONE op's backward on the
-    folded N*C batch and chains the gate gradient through cspn_gate_absnorm_backward_f32.  K x K: the forward keeps its levels where the
+    folded N*C batch and chains the gate gradient through cspn_gate_absnorm_backward_f32 (3D: the guide may be float16 / bfloat16 -- w is
+    recomputed in float32 from it and dL/dguide comes back in its dtype, cspn_gate_absnorm*_g16).  K x K: the forward keeps its levels where the
     guide gradient needs them, the backward is one cspn2d_backward_kxk_absnorm call on the raw guide (float32, float16 or bfloat16)"""
 
     @staticmethod
@@ -835,12 +872,13 @@ class _AbsnormPropagateFunction(torch.autograd.Function):
         if K not in (8, 26):
             gg, gx = cspn2d_backward_kxk_absnorm(g, x, go, ctx.kernel_size, ctx.n_iter, hist, need_g, need_x)
             return gg.view(guide.shape) if need_g else None, gx.view(feat.shape) if need_x else None, None, None
-        w = _gate_absnorm(g, K)
+        w = _gate_absnorm(g, K, allow16=True)
         if K == 26:
             gw, gx = cspn3d_backward(w, x, go, ctx.n_iter, need_g, need_x)
+            gg = _gate_absnorm_backward26(g, gw).view(guide.shape) if need_g else None
         else:
             gw, gx = cspn2d_backward(w, x, None, go, ctx.n_iter, "none", need_g, need_x)
-        gg = gate_absnorm_backward(g, gw, K).view(guide.shape) if need_g else None
+            gg = gate_absnorm_backward(g, gw, K).view(guide.shape) if need_g else None
         return gg, gx.view(feat.shape) if need_x else None, None, None
 
 
@@ -850,8 +888,9 @@ def absnorm_propagate(guide, feat, n_iter, kernel_size=3):
     voxel, for n_iter chained steps.  One engine call for all channels (they fold into the batch).  3D: cspn3d_forward_absnorm_f32 (the
     normalisation inside the persistent kernel where it runs); 2D: gate_absnorm, then cspn2d_forward(..., 'none'); with kernel_size
     5 / 7 (2D only) cspn2d_forward_kxk_absnorm / cspn2d_backward_kxk_absnorm on the folded views, which normalise the gates inside the
-    K x K step and store no normalised gate.  That route alone takes a float16 / bfloat16 guide as it is (dL/dguide comes back in its
-    dtype) and widens a 16-bit feat with one differentiable cast; the result is float32.  Differentiable w.r.t. guide and feat.
+    K x K step and store no normalised gate.  That route and the 3D one take a float16 / bfloat16 guide as it is (dL/dguide comes back in its
+    dtype; 3D: cspn3d_forward_absnorm_g16, and in the backward the normaliser's 16-bit forms) and widen a 16-bit feat with one differentiable
+    cast; the result is float32.  (2D 3 x 3 takes float32 only.)  Differentiable w.r.t. guide and feat.
     n_iter == 0 returns feat itself."""
     for t, name in ((guide, "guide"), (feat, "feat")):
         if not isinstance(t, torch.Tensor):
@@ -868,7 +907,7 @@ def absnorm_propagate(guide, feat, n_iter, kernel_size=3):
         raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
     if int(n_iter) == 0:
         return feat
-    if kernel_size != 3:
+    if kernel_size != 3 or feat.dim() == 5:
         g = _prep_gate(guide, "guide")[0]
         x = _prep(widen16(feat), "feat")
     else:

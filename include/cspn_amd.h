@@ -52,7 +52,8 @@ extern "C" {
                               *    K x K (cspn2d_*_kxk_norm*, K = 3 / 5 / 7), the guidance heads that feed it (cspn_guidance_head_kxk_*),
                               *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*), the demo module's
                               *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*), the 8-plane heads on a 16-bit feature map with float32 guidance
-                              *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16) */
+                              *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16), fp16 / bf16 gates and guides on the 3D entry points of the
+                              *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -254,6 +255,47 @@ int cspn_gate_absnorm_backward_f32(const float* guide, const float* grad_gate, f
 size_t cspn3d_forward_absnorm_workspace_bytes(int B, int D, int H, int W, int n_iter);
 int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the 3D entry points of the Paddle contract on 16-bit gates (what a stereo head under autocast emits), gate_dtype CSPN_DTYPE_F16 or
+ * CSPN_DTYPE_BF16 right after the gate pointer.  gate / guide and grad_gate / grad_guide are of that type; feat, out, grad_out, grad_feat,
+ * every level and the workspace stay float32.  A gate is widened to float32 exactly where it is read (fp16 subnormals kept, bf16 = its
+ * bits shifted left by 16) and every multiply-add, sum and division is the float32 kernel's in the same order: out and grad_feat are
+ * BITWISE what the _f32 twin gives on the widened gates for the same shape, pointer alignments and path (persistent kernel or the same
+ * per-step kernels; the same algo).  grad_gate / grad_guide is the float32 value rounded once, to nearest even, at its single store
+ * (no atomics, every element written once): bitwise the _f32 twin's result converted to the type.
+ * Dispatch: the _f32 twin's with the gate pointer's 16-byte condition at 8 bytes (four gates); W % 4 == 0 stays the condition of the
+ * vector and persistent paths.  The persistent kernel reads a thread's quads with 8-byte loads and widens them into the gate registers
+ * it already has (forward, level-keeping forward, multi-channel and raw-guide instances).  Its transposed instance has no 16-bit form:
+ * the fused backward sweeps (n_iter >= 3 where the persistent kernel takes the call) widen the gates once into the workspace with an
+ * exact streaming pass and run the float32 instance on that copy, which the *_g16_workspace_bytes queries account for.
+ * All checks and return codes of the _f32 twins apply, gate ranges counted in 2-byte elements; any other gate_dtype or an odd address
+ * of a 16-bit tensor: CSPN_E_BADARG.
+ * cspn3d_forward_g16_algo: cspn3d_forward_f32_algo with norm_type CSPN_NORM_NONE and sparse NULL -- anything else CSPN_E_BADARG (the
+ *   normalising and masked modes take float32 gates only).  Workspace: cspn3d_workspace_bytes_ex / cspn3d_workspace_bytes as the twin.
+ * cspn3d_forward_multi_g16, cspn3d_backward_g16, cspn3d_backward_multi_g16: as their twins; workspaces of the backward:
+ *   cspn3d_backward_g16_workspace_bytes / cspn3d_backward_multi_g16_workspace_bytes (the same for both 16-bit types).
+ * cspn3d_forward_absnorm_g16: guide RAW in 16 bits; the unfused route normalises into float32 gates in the workspace
+ *   (cspn3d_forward_absnorm_workspace_bytes as the twin).
+ * cspn_gate_absnorm_g16 / cspn_gate_absnorm_backward_g16: the normaliser of the 3D module (K = 26 only, else CSPN_E_BADARG) on a 16-bit
+ *   guide: gate and grad_gate float32, grad_guide in the guide's type. */
+int cspn3d_forward_g16_algo(const void* gate, int gate_dtype, const float* feat, const float* sparse, float* out,
+                            int B, int D, int H, int W, int n_iter, int norm_type, int algo,
+                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn3d_forward_multi_g16(const void* gate, int gate_dtype, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                             void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn3d_forward_absnorm_g16(const void* guide, int gate_dtype, const float* feat, float* out, int B, int D, int H, int W, int n_iter, int algo,
+                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn3d_backward_g16_workspace_bytes(int B, int D, int H, int W, int n_iter);
+int cspn3d_backward_g16(const void* gate, int gate_dtype, const float* feat, const float* grad_out, void* grad_gate, float* grad_feat,
+                        int B, int D, int H, int W, int n_iter, int norm_type,
+                        void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn3d_backward_multi_g16_workspace_bytes(int B, int C, int D, int H, int W, int n_iter);
+int cspn3d_backward_multi_g16(const void* gate, int gate_dtype, const float* feat, const float* grad_out, void* grad_gate, float* grad_feat,
+                              int B, int C, int D, int H, int W, int n_iter,
+                              void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn_gate_absnorm_g16(const void* guide, int gate_dtype, float* gate, int N, int K, size_t V, cspn_stream_t stream);
+int cspn_gate_absnorm_backward_g16(const void* guide, int gate_dtype, const float* grad_gate, void* grad_guide, int N, int K, size_t V,
+                                   cspn_stream_t stream);
 
 /* ---- 2D over a K x K neighbourhood, K = 2R+1 in {5, 7}: fluid.layers.affinity_propagate(input, gate_weight, kernel_size) with
  * kernel_size 5 or 7, the NONE contract (gates used as given, centre-sited, no centre term, any sign; reference cspn_paddle/README.md:54-56).
