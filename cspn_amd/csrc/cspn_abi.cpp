@@ -1006,6 +1006,50 @@ static bool head_kxk_too_large(int B, int C, int h, int w, int H, int W, int K) 
     return (long long)B * (K * K - 1) * H * W >= (1ll << 40) || (long long)C * h * w >= (1ll << 31) || (long long)(K * K - 1) * H * W >= (1ll << 31);
 }
 
+// ---- one set of checks for the six head entry points below.  t16: how many of the call's tensors are 16-bit -- 0: none (the float32 heads, dtype unused);
+// 1: x and dL/dx (the 8-plane head on fp16 / bf16 feature maps, float32 guidance: cspn_head_g16.hip; K = 3 stands for it); 2: the guidance and its gradient too
+// (K = 5 or 7: cspn_head_kxk_g16.hip) ----
+static int head_check_16(const char* what, int t16, int dtype, std::initializer_list<const void*> tensors16) {
+    if (!t16) return 0;
+    if (dtype != CSPN_DTYPE_F16 && dtype != CSPN_DTYPE_BF16) {
+        set_error("%s: dtype must be CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dtype);
+        return CSPN_E_BADARG;
+    }
+    for (const void* p : tensors16)
+        if ((uintptr_t)p & 1u) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
+    return 0;
+}
+
+// the forward's checks -> an error, 0 to launch, 1 when there is nothing to do (an empty batch), 2 for the float32 heads at K = 3: the 8-plane head's own entry
+// point takes over from here (ahead of the size test, which is stricter than its own)
+static int head_forward_check(const char* what, const void* x, int t16, int dtype, const float* w_guidance, const float* w_blur, const void* guidance_out,
+                              const float* blur_out, int B, int C, int h, int w, int H, int W, int K, const void* ws, size_t ws_bytes, size_t need) {
+    if (!x || !w_guidance || !guidance_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = head_check_16(what, t16, dtype, {x, t16 == 2 ? guidance_out : nullptr})) return e;
+    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
+    if ((w_blur != nullptr) != (blur_out != nullptr)) { set_error("%s: w_blur and blur_out come together", what); return CSPN_E_BADARG; }
+    if (int e = head_kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    if (!t16 && K == 3) return 2;
+    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
+    return B == 0 ? 1 : 0;
+}
+
+// the backward's checks -> as the forward's; nothing to do: an empty batch, no output asked for
+static int head_backward_check(const char* what, const void* x, int t16, int dtype, const float* w_guidance, const float* w_blur, const void* grad_guidance,
+                               const float* grad_blur, const void* grad_x, const float* grad_w_guidance, const float* grad_w_blur, int B, int C, int h, int w,
+                               int H, int W, int K, const void* ws, size_t ws_bytes, size_t need) {
+    if (!x || !w_guidance || !grad_guidance) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = head_check_16(what, t16, dtype, {x, t16 == 2 ? grad_guidance : nullptr, grad_x})) return e;
+    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
+    if ((w_blur != nullptr) != (grad_blur != nullptr)) { set_error("%s: w_blur and grad_blur come together", what); return CSPN_E_BADARG; }
+    if (grad_w_blur && !w_blur) { set_error("%s: grad_w_blur without a blur head", what); return CSPN_E_BADARG; }
+    if (B == 0 || (!grad_x && !grad_w_guidance && !grad_w_blur)) return 1;
+    if (int e = head_kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    if (!t16 && K == 3) return 2;
+    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
 size_t cspn_guidance_head_kxk_workspace_bytes(int B, int C, int h, int w, int K) {
     (void)B; (void)h; (void)w;
     if (C <= 0) return 0;
@@ -1015,13 +1059,10 @@ size_t cspn_guidance_head_kxk_workspace_bytes(int B, int C, int h, int w, int K)
 int cspn_guidance_head_kxk_f32(const float* x, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out, int B, int C, int h, int w,
                                int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_kxk_f32";
-    if (!x || !w_guidance || !guidance_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
-    if ((w_blur != nullptr) != (blur_out != nullptr)) { set_error("%s: w_blur and blur_out come together", what); return CSPN_E_BADARG; }
-    if (int e = head_kxk_check_ws(what, workspace, workspace_bytes, cspn_guidance_head_kxk_workspace_bytes(B, C, h, w, K))) return e;
-    if (K == 3) return cspn_guidance_head_f32(x, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, CSPN_NORM_NONE, workspace, workspace_bytes, stream);
-    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
-    if (B == 0) return 0;
+    int e = head_forward_check(what, x, 0, 0, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, K, workspace, workspace_bytes,
+                               cspn_guidance_head_kxk_workspace_bytes(B, C, h, w, K));
+    if (e == 2) return cspn_guidance_head_f32(x, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, CSPN_NORM_NONE, workspace, workspace_bytes, stream);
+    if (e) return e < 0 ? e : 0;
     return head_kxk_forward(x, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, K, workspace, (hipStream_t)stream);
 }
 
@@ -1034,62 +1075,19 @@ int cspn_guidance_head_kxk_backward_f32(const float* x, const float* w_guidance,
                                         float* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W, int K,
                                         void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_kxk_backward_f32";
-    if (!x || !w_guidance || !grad_guidance) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
-    if ((w_blur != nullptr) != (grad_blur != nullptr)) { set_error("%s: w_blur and grad_blur come together", what); return CSPN_E_BADARG; }
-    if (grad_w_blur && !w_blur) { set_error("%s: grad_w_blur without a blur head", what); return CSPN_E_BADARG; }
-    if (B == 0 || (!grad_x && !grad_w_guidance && !grad_w_blur)) return 0;
-    if (int e = head_kxk_check_ws(what, workspace, workspace_bytes, cspn_guidance_head_kxk_backward_workspace_bytes(B, C, h, w, K))) return e;
-    if (K == 3)
+    int e = head_backward_check(what, x, 0, 0, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, K, workspace,
+                                workspace_bytes, cspn_guidance_head_kxk_backward_workspace_bytes(B, C, h, w, K));
+    if (e == 2)
         return cspn_guidance_head_backward_f32(x, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, workspace,
                                                workspace_bytes, stream);
-    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
+    if (e) return e < 0 ? e : 0;
     return head_kxk_backward(x, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, K, workspace,
                              (hipStream_t)stream);
 }
 
-// ---- the heads on fp16 / bf16 feature maps: K = 5 or 7 with 16-bit guidance (cspn_head_kxk_g16.hip), the 8-plane head with float32 guidance
-// (cspn_head_g16.hip).  One set of checks for the four entry points; K = 3 below stands for the 8-plane head ----
+// ---- the heads on fp16 / bf16 feature maps with 16-bit guidance, K = 5 or 7 (cspn_head_kxk_g16.hip) ----
 static int head_kxk_g16_check_K(const char* what, int K) {
     if (K != 5 && K != 7) { set_error("%s: K must be 5 or 7 (the 8-plane head of K = 3 is float32 only), got %d", what, K); return CSPN_E_BADARG; }
-    return 0;
-}
-
-static int head_g16_check(const char* what, int dtype, std::initializer_list<const void*> tensors16) {
-    if (dtype != CSPN_DTYPE_F16 && dtype != CSPN_DTYPE_BF16) {
-        set_error("%s: dtype must be CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dtype);
-        return CSPN_E_BADARG;
-    }
-    for (const void* p : tensors16)
-        if ((uintptr_t)p & 1u) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
-    return 0;
-}
-
-// the forward's checks; guidance16: guidance_out is a 16-bit tensor.  -> an error, 0 to launch, 1 when there is nothing to do (an empty batch)
-static int head_g16_forward_check(const char* what, const void* x, int dtype, const float* w_guidance, const float* w_blur, const void* guidance_out,
-                                  bool guidance16, const float* blur_out, int B, int C, int h, int w, int H, int W, int K, const void* ws, size_t ws_bytes,
-                                  size_t need) {
-    if (!x || !w_guidance || !guidance_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = head_g16_check(what, dtype, {x, guidance16 ? guidance_out : nullptr})) return e;
-    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
-    if ((w_blur != nullptr) != (blur_out != nullptr)) { set_error("%s: w_blur and blur_out come together", what); return CSPN_E_BADARG; }
-    if (int e = head_kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
-    return B == 0 ? 1 : 0;
-}
-
-// the backward's checks; guidance16: grad_guidance is a 16-bit tensor.  -> an error, 0 to launch, 1 when there is nothing to do (an empty batch, no output asked for)
-static int head_g16_backward_check(const char* what, const void* x, int dtype, const float* w_guidance, const float* w_blur, const void* grad_guidance,
-                                   bool guidance16, const float* grad_blur, const void* grad_x, const float* grad_w_guidance, const float* grad_w_blur, int B,
-                                   int C, int h, int w, int H, int W, int K, const void* ws, size_t ws_bytes, size_t need) {
-    if (!x || !w_guidance || !grad_guidance) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = head_g16_check(what, dtype, {x, guidance16 ? grad_guidance : nullptr, grad_x})) return e;
-    if (int e = head_kxk_check(what, B, C, h, w, H, W, K)) return e;
-    if ((w_blur != nullptr) != (grad_blur != nullptr)) { set_error("%s: w_blur and grad_blur come together", what); return CSPN_E_BADARG; }
-    if (grad_w_blur && !w_blur) { set_error("%s: grad_w_blur without a blur head", what); return CSPN_E_BADARG; }
-    if (B == 0 || (!grad_x && !grad_w_guidance && !grad_w_blur)) return 1;
-    if (int e = head_kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    if (head_kxk_too_large(B, C, h, w, H, W, K)) { set_error("%s: tensor too large", what); return CSPN_E_UNSUPPORTED; }
     return 0;
 }
 
@@ -1102,8 +1100,8 @@ int cspn_guidance_head_kxk_g16(const void* x, int dtype, const float* w_guidance
                                int w, int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_kxk_g16";
     if (int e = head_kxk_g16_check_K(what, K)) return e;
-    if (int e = head_g16_forward_check(what, x, dtype, w_guidance, w_blur, guidance_out, true, blur_out, B, C, h, w, H, W, K, workspace, workspace_bytes,
-                                       cspn_guidance_head_kxk_g16_workspace_bytes(B, C, h, w, K)))
+    if (int e = head_forward_check(what, x, 2, dtype, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, K, workspace, workspace_bytes,
+                                   cspn_guidance_head_kxk_g16_workspace_bytes(B, C, h, w, K)))
         return e < 0 ? e : 0;
     return head_kxk_g16_forward(x, dtype, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, K, workspace, (hipStream_t)stream);
 }
@@ -1118,8 +1116,8 @@ int cspn_guidance_head_kxk_backward_g16(const void* x, int dtype, const float* w
                                         int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_kxk_backward_g16";
     if (int e = head_kxk_g16_check_K(what, K)) return e;
-    if (int e = head_g16_backward_check(what, x, dtype, w_guidance, w_blur, grad_guidance, true, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H,
-                                        W, K, workspace, workspace_bytes, cspn_guidance_head_kxk_backward_g16_workspace_bytes(B, C, h, w, K)))
+    if (int e = head_backward_check(what, x, 2, dtype, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H,
+                                    W, K, workspace, workspace_bytes, cspn_guidance_head_kxk_backward_g16_workspace_bytes(B, C, h, w, K)))
         return e < 0 ? e : 0;
     return head_kxk_g16_backward(x, dtype, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, K, workspace,
                                  (hipStream_t)stream);
@@ -1134,8 +1132,8 @@ size_t cspn_guidance_head_g16_workspace_bytes(int B, int C, int h, int w) {
 int cspn_guidance_head_g16(const void* x, int dtype, const float* w_guidance, const float* w_blur, float* guidance_out, float* blur_out, int B, int C, int h,
                            int w, int H, int W, void* workspace, size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_g16";
-    if (int e = head_g16_forward_check(what, x, dtype, w_guidance, w_blur, guidance_out, false, blur_out, B, C, h, w, H, W, 3, workspace, workspace_bytes,
-                                       cspn_guidance_head_g16_workspace_bytes(B, C, h, w)))
+    if (int e = head_forward_check(what, x, 1, dtype, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, 3, workspace, workspace_bytes,
+                                   cspn_guidance_head_g16_workspace_bytes(B, C, h, w)))
         return e < 0 ? e : 0;
     return head_g16_forward(x, dtype, w_guidance, w_blur, guidance_out, blur_out, B, C, h, w, H, W, workspace, (hipStream_t)stream);
 }
@@ -1149,8 +1147,8 @@ int cspn_guidance_head_backward_g16(const void* x, int dtype, const float* w_gui
                                     void* grad_x, float* grad_w_guidance, float* grad_w_blur, int B, int C, int h, int w, int H, int W, void* workspace,
                                     size_t workspace_bytes, cspn_stream_t stream) {
     static const char* what = "cspn_guidance_head_backward_g16";
-    if (int e = head_g16_backward_check(what, x, dtype, w_guidance, w_blur, grad_guidance, false, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H,
-                                        W, 3, workspace, workspace_bytes, cspn_guidance_head_backward_g16_workspace_bytes(B, C, h, w)))
+    if (int e = head_backward_check(what, x, 1, dtype, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H,
+                                    W, 3, workspace, workspace_bytes, cspn_guidance_head_backward_g16_workspace_bytes(B, C, h, w)))
         return e < 0 ? e : 0;
     return head_g16_backward(x, dtype, w_guidance, w_blur, grad_guidance, grad_blur, grad_x, grad_w_guidance, grad_w_blur, B, C, h, w, H, W, workspace,
                              (hipStream_t)stream);

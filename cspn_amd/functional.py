@@ -6,15 +6,16 @@ import torch
 from . import _lib
 
 
-def _prep(t, name, shape=None):
+def _prep(t, name, shape=None, dtype=torch.float32):
+    """a tensor of the engine: on the GPU, of `dtype` (another than float32: the 16-bit dtype of the heads' x), of `shape` if given -> contiguous"""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
         raise _lib.CspnError(
             "cspn_amd: %s is on %s; the engine is GPU-only (hand-written HIP for gfx950) and has no CPU path"
             % (name, t.device))
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s (got %s)" % (name, "float32" if dtype == torch.float32 else "%s as x" % dtype, t.dtype))
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     return t.contiguous()

@@ -14,11 +14,13 @@
                                                                   ONE kernel; with norm_type the guidance comes back as gate_wb; differentiable
 
 The reference moves every prediction to the host before reducing it (train.py:204-206, eval.py:146-150)."""
+import collections
+
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .functional import _GATE16, _prep, _workspace, cspn2d_normalize
+from .functional import _GATE16, _launch, _prep, _ptr, cspn2d_normalize
 
 _KEYS = ['MSE', 'RMSE', 'ABS_REL', 'LG10', 'MAE', 'DELTA1.02', 'DELTA1.05', 'DELTA1.10', 'DELTA1.25', 'DELTA1.25^2',
          'DELTA1.25^3']
@@ -26,17 +28,11 @@ _KEYS = ['MSE', 'RMSE', 'ABS_REL', 'LG10', 'MAE', 'DELTA1.02', 'DELTA1.05', 'DEL
 
 def _metrics(gt, pred):
     """-> device float32[12]: n_valid, then the 11 values of _KEYS"""
-    lib = _lib.load()
     g = _prep(gt, "gt_depth")
     p = _prep(pred, "pred_depth", tuple(g.shape))
     out = torch.empty(12, dtype=torch.float32, device=g.device)
     n = g.numel()
-    with torch.cuda.device(g.device):
-        wsb = lib.cspn_metrics_workspace_bytes(n)
-        ws = _workspace(wsb, g.device)
-        rc = lib.cspn_metrics_f32(g.data_ptr(), p.data_ptr(), n, out.data_ptr(), ws.data_ptr(), wsb,
-                                  torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(rc, "cspn_metrics_f32")
+    _launch("cspn_metrics_f32", g.device, (_ptr(g), _ptr(p), n, _ptr(out)), ("cspn_metrics_workspace_bytes", n))
     return out
 
 
@@ -57,14 +53,10 @@ class _L1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         pred, label, stats = ctx.saved_tensors
-        lib = _lib.load()
         p, l = pred.contiguous(), label.contiguous()
         gp = torch.empty_like(p)
         gs = grad.reshape(1).to(torch.float32).contiguous()
-        with torch.cuda.device(p.device):
-            rc = lib.cspn_l1_backward_f32(p.data_ptr(), l.data_ptr(), stats.data_ptr(), gs.data_ptr(), gp.data_ptr(), p.numel(),
-                                          torch.cuda.current_stream(p.device).cuda_stream)
-        _lib.check(rc, "cspn_l1_backward_f32")
+        _launch("cspn_l1_backward_f32", p.device, (_ptr(p), _ptr(l), _ptr(stats), _ptr(gs), _ptr(gp), p.numel()))
         return gp.view_as(pred), None
 
 
@@ -78,27 +70,19 @@ class Wighted_L1_Loss(nn.Module):
 class _Unpool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, stride):
-        lib = _lib.load()
         xc = _prep(x, "x")
         N, C, H, W = xc.shape
         out = torch.empty(N, C, H * stride, W * stride, dtype=torch.float32, device=xc.device)
         ctx.shape, ctx.stride = (N, C, H, W), stride
-        with torch.cuda.device(xc.device):
-            rc = lib.cspn_unpool_f32(xc.data_ptr(), out.data_ptr(), N * C, H, W, stride,
-                                     torch.cuda.current_stream(xc.device).cuda_stream)
-        _lib.check(rc, "cspn_unpool_f32")
+        _launch("cspn_unpool_f32", xc.device, (_ptr(xc), _ptr(out), N * C, H, W, stride))
         return out
 
     @staticmethod
     def backward(ctx, go):
-        lib = _lib.load()
         N, C, H, W = ctx.shape
         g = go.contiguous()
         gx = torch.empty(N, C, H, W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            rc = lib.cspn_unpool_backward_f32(g.data_ptr(), gx.data_ptr(), N * C, H, W, ctx.stride,
-                                              torch.cuda.current_stream(g.device).cuda_stream)
-        _lib.check(rc, "cspn_unpool_backward_f32")
+        _launch("cspn_unpool_backward_f32", g.device, (_ptr(g), _ptr(gx), N * C, H, W, ctx.stride))
         return gx, None
 
 
@@ -122,7 +106,6 @@ def createSparseDepthImage(depth_image, n_sample, mode="nyu", seed=0):
     sparse_depth = depth_image * bernoulli(p), independently per pixel.  depth_image [..., H, W] on the device (any number
     of leading dims; every [H, W] slice is one image).  `seed` keys a counter-based generator (a fixed seed reproduces the
     mask; the reference draws from torch's global CPU generator)."""
-    lib = _lib.load()
     d = _prep(depth_image, "depth_image")
     if d.dim() < 2:
         raise ValueError("depth_image must be [..., H, W]")
@@ -132,16 +115,28 @@ def createSparseDepthImage(depth_image, n_sample, mode="nyu", seed=0):
     if d.numel() == 0:
         return out
     m = {"nyu": 0, "kitti": 1}[mode]
-    with torch.cuda.device(d.device):
-        wsb = lib.cspn_sparse_sample_workspace_bytes(n_images)
-        ws = _workspace(wsb, d.device)
-        rc = lib.cspn_sparse_sample_f32(d.data_ptr(), out.data_ptr(), n_images, hw, int(n_sample), m, int(seed) & (2 ** 64 - 1),
-                                        ws.data_ptr(), wsb, torch.cuda.current_stream(d.device).cuda_stream)
-    _lib.check(rc, "cspn_sparse_sample_f32")
+    _launch("cspn_sparse_sample_f32", d.device, (_ptr(d), _ptr(out), n_images, hw, int(n_sample), m, int(seed) & (2 ** 64 - 1)),
+            ("cspn_sparse_sample_workspace_bytes", n_images))
     return out
 
 
 _PLANES_TO_K = {8: 3, 24: 5, 48: 7}
+
+# What differs between the four host paths of the heads.  fwd / bwd: the entry points (_lib.check reports under these names); *_ws: their workspace queries;
+# *_ws_args: the queries' arguments, letters of B C h w K.  x16: x and dL/dx are float16 / bfloat16 and a dtype code follows x in both calls; guidance16: the
+# guidance and its gradient are in x's dtype too (float32 otherwise; blur, its gradient and the weights are float32 on every path).  K: both calls end in K;
+# norm: the forward call ends in a norm_type
+_HeadPath = collections.namedtuple("_HeadPath", "fwd fwd_ws fwd_ws_args bwd bwd_ws bwd_ws_args x16 guidance16 K norm")
+_HEAD_PATHS = {
+    "f32": _HeadPath("cspn_guidance_head_f32", "cspn_guidance_head_workspace_bytes", "C",
+                     "cspn_guidance_head_backward_f32", "cspn_guidance_head_backward_workspace_bytes", "BChw", False, False, False, True),
+    "kxk_f32": _HeadPath("cspn_guidance_head_kxk_f32", "cspn_guidance_head_kxk_workspace_bytes", "BChwK",
+                         "cspn_guidance_head_kxk_backward_f32", "cspn_guidance_head_kxk_backward_workspace_bytes", "BChwK", False, False, True, False),
+    "kxk_g16": _HeadPath("cspn_guidance_head_kxk_g16", "cspn_guidance_head_kxk_g16_workspace_bytes", "BChwK",
+                         "cspn_guidance_head_kxk_backward_g16", "cspn_guidance_head_kxk_backward_g16_workspace_bytes", "BChwK", True, True, True, False),
+    "g16": _HeadPath("cspn_guidance_head_g16", "cspn_guidance_head_g16_workspace_bytes", "BChw",
+                     "cspn_guidance_head_backward_g16", "cspn_guidance_head_backward_g16_workspace_bytes", "BChw", True, False, False, False),
+}
 
 
 def _head_planes(x, weight_guidance, *others):
@@ -157,149 +152,91 @@ def _head_planes(x, weight_guidance, *others):
     return int(weight_guidance.shape[0])
 
 
-def _heads_kxk_forward(xx, wg, wb, H, W):
-    """cspn_guidance_head_kxk_f32: the 24- / 48-plane guidance head and the blur head, raw, on the matrix cores.  xx float16 / bfloat16:
-    cspn_guidance_head_kxk_g16, float32 weights (rounded once to xx's dtype in the engine) -> guidance in xx's dtype, blur float32"""
-    B, C, h, w = xx.shape
-    P = int(wg.shape[0])
-    K = _PLANES_TO_K[P]
-    dt = _GATE16.get(xx.dtype)
-    g = torch.empty(B, P, H, W, dtype=xx.dtype, device=xx.device)
-    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
-    name = "cspn_guidance_head_kxk_f32" if dt is None else "cspn_guidance_head_kxk_g16"
-    with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk%s_workspace_bytes" % ("" if dt is None else "_g16"))(B, C, h, w, K)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol(name)(xx.data_ptr(), *(() if dt is None else (dt,)), wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
-                                    b.data_ptr() if b is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb,
-                                    torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, name)
-    return g, b
-
-
-def _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w):
-    """cspn_guidance_head_kxk_backward_f32.  xx float16 / bfloat16: cspn_guidance_head_kxk_backward_g16, dL/dguidance in xx's dtype, dL/dblur float32
-    (rounded once to xx's dtype as it enters the GEMMs) -> dL/dx in xx's dtype, the weight gradients float32"""
-    B, C, h, w = xx.shape
-    K = _PLANES_TO_K[int(wg.shape[0])]
-    H, W = int(gg.shape[2]), int(gg.shape[3])
-    dt = _GATE16.get(xx.dtype)
-    dx = torch.empty_like(xx) if need_x else None
-    dwg = torch.empty_like(wg) if need_w else None
-    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
-    name = "cspn_guidance_head_kxk_backward_%s" % ("f32" if dt is None else "g16")
-    with torch.cuda.device(xx.device):
-        wsb = _lib.late_symbol("cspn_guidance_head_kxk_backward%s_workspace_bytes" % ("" if dt is None else "_g16"))(B, C, h, w, K)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.late_symbol(name)(
-            xx.data_ptr(), *(() if dt is None else (dt,)), wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
-            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
-            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, K, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, name)
-    return dx, dwg, dwb
-
-
-def _head_dtype16(x, weight_guidance, weight_blur, P):
-    """-> the 16-bit dtype of x (float16 / bfloat16: the heads of cspn_guidance_head_kxk_g16), or None for every other x.  Raised before any device check:
-    TypeError for a 16-bit x with 8-plane weights, and for 16-bit weights whose dtype differs from x's"""
-    if x.dtype not in _GATE16:
-        return None
-    if P == 8:
+def _head_path(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type=None):
+    """-> the path of _HEAD_PATHS that the dtype of x, the plane count P and guidance_dtype select.  Raised before any device check: ValueError for a misused
+    guidance_dtype and for a norm_type on any head but the float32 8-plane one, TypeError for a 16-bit x with 8-plane weights by default, and for 16-bit weights
+    whose dtype differs from x's"""
+    x16 = x.dtype in _GATE16
+    if guidance_dtype is not None:
+        if guidance_dtype is not torch.float32:
+            raise ValueError("guidance_dtype must be None or torch.float32, got %r" % (guidance_dtype,))
+        if P != 8:
+            raise ValueError("guidance_dtype=torch.float32 is the 8-plane head's (prop_kernel 3); the %d-plane head of prop_kernel %d returns its guidance in the "
+                             "dtype of x" % (P, _PLANES_TO_K[P]))
+        if not x16:
+            raise ValueError("guidance_dtype=torch.float32 is for a float16 / bfloat16 x; x is %s (a float32 x takes the default guidance_dtype=None)" % (x.dtype,))
+        if norm_type is not None:
+            raise ValueError("the 16-bit 8-plane head returns raw guidance only (norm_type=None): Affinity_Propagate(prop_time, 3, norm_type) normalises it")
+    elif x16 and P == 8:
         raise TypeError("the 3 x 3 guidance head (weight_guidance [8, C, 3, 3]) is float32 only: its ring has no 16-bit consumer; x is %s -- pass x.float(), "
                         "or use the 24- / 48-plane heads of prop_kernel 5 / 7 (guidance_dtype=torch.float32, or cspn_amd.GuidanceHeads, runs the 16-bit head that emits "
                         "float32 guidance)" % (x.dtype,))
-    for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
-        if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
-            raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
-    return x.dtype
+    if x16:
+        for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
+            if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
+                raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
+    if P != 8 and norm_type is not None:
+        raise ValueError("the %d-plane guidance head returns raw guidance only (norm_type=None): Affinity_PropagateKxK(prop_time, %d, norm_type) "
+                         "normalises it" % (P, _PLANES_TO_K[P]))
+    return _HEAD_PATHS[("g16" if P == 8 else "kxk_g16") if x16 else ("f32" if P == 8 else "kxk_f32")]
 
 
-def _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type=None):
-    """guidance_dtype given -> the 16-bit dtype of x: the 8-plane head on a float16 / bfloat16 x that emits float32 guidance (cspn_guidance_head_g16).  Raised
-    before any device check: ValueError for every other combination, TypeError for 16-bit weights whose dtype differs from x's"""
-    if guidance_dtype is not torch.float32:
-        raise ValueError("guidance_dtype must be None or torch.float32, got %r" % (guidance_dtype,))
-    if P != 8:
-        raise ValueError("guidance_dtype=torch.float32 is the 8-plane head's (prop_kernel 3); the %d-plane head of prop_kernel %d returns its guidance in the "
-                         "dtype of x" % (P, _PLANES_TO_K[P]))
-    if x.dtype not in _GATE16:
-        raise ValueError("guidance_dtype=torch.float32 is for a float16 / bfloat16 x; x is %s (a float32 x takes the default guidance_dtype=None)" % (x.dtype,))
-    if norm_type is not None:
-        raise ValueError("the 16-bit 8-plane head returns raw guidance only (norm_type=None): Affinity_Propagate(prop_time, 3, norm_type) normalises it")
-    for t, name in ((weight_guidance, "weight_guidance"), (weight_blur, "weight_blur")):
-        if isinstance(t, torch.Tensor) and t.dtype in _GATE16 and t.dtype != x.dtype:
-            raise TypeError("x is %s but %s is %s: 16-bit weights must have the dtype of x (or be the float32 master weights)" % (x.dtype, name, t.dtype))
-    return x.dtype
+def _head_prep(path, x, weight_guidance, weight_blur, P):
+    """-> x and the two weights (weight_blur may be None), checked and contiguous.  x: float32, or its own 16-bit dtype dt on the x16 paths; there a weight is
+    the float32 master or a dt tensor, which stays dt here (the autograd Function saves it as given) and is widened with .float(), exactly, at the call"""
+    dt = x.dtype if path.x16 else torch.float32
+    xx = _prep(x, "x", None, dt)
+    C = xx.shape[1]
+    wg, wb = (_prep(t, name, (planes, C, 3, 3), dt if getattr(t, "dtype", None) == dt else torch.float32) if t is not None else None
+              for t, name, planes in ((weight_guidance, "weight_guidance", P), (weight_blur, "weight_blur", 1)))
+    return xx, wg, wb
 
 
-def _prep16(t, name, dt, shape=None):
-    """a 16-bit tensor of the heads (x, dL/dguidance): on the GPU, of dtype dt, contiguous"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not t.is_cuda:
-        raise _lib.CspnError("cspn_amd: %s is on %s; the engine is GPU-only (hand-written HIP for gfx950) and has no CPU path" % (name, t.device))
-    if t.dtype != dt:
-        raise TypeError("%s must be %s as x (got %s)" % (name, dt, t.dtype))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    return t.contiguous()
+def _head_prep_grads(path, xx, wb, P, grad_guidance, grad_blur):
+    """-> dL/dguidance [B,P,H,W] in the path's guidance dtype and dL/dblur [B,1,H,W] float32 (None without a blur head), checked and contiguous"""
+    if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
+        raise ValueError("grad_guidance must be [B,%d,H,W]" % P)
+    B, H, W = xx.shape[0], int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
+    gg = _prep(grad_guidance, "grad_guidance", (B, P, H, W), xx.dtype if path.guidance16 else torch.float32)
+    return gg, _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
 
 
-def _prep_w16(t, name, dt, shape):
-    """a weight of the 16-bit heads: the float32 master weights, or dt weights widened with .float() (exact) -> float32"""
-    if isinstance(t, torch.Tensor) and t.dtype == dt:
-        t = t.float()
-    return _prep(t, name, shape)
+def _head_out_size(xx, oheight, owidth):
+    return (int(oheight), int(owidth)) if (oheight and owidth) else (2 * xx.shape[2], 2 * xx.shape[3])
 
 
-def _heads_forward(xx, wg, wb, H, W, norm):
-    lib = _lib.load()
+def _head_call(path, backward, xx, wg, tensors, H, W, norm=()):
+    """one head entry point of `path` on prepared tensors (float32 weights): x [, dtype code], the other tensors, the sizes [, K | norm_type], the workspace"""
     B, C, h, w = xx.shape
-    g = torch.empty(B, 8, H, W, dtype=torch.float32, device=xx.device)
+    dims = dict(B=B, C=C, h=h, w=w, K=_PLANES_TO_K[int(wg.shape[0])])
+    name, ws, ws_args = (path.bwd, path.bwd_ws, path.bwd_ws_args) if backward else (path.fwd, path.fwd_ws, path.fwd_ws_args)
+    _launch(name, xx.device, (_ptr(xx), *((_GATE16[xx.dtype],) if path.x16 else ()), _ptr(wg), *map(_ptr, tensors), B, C, h, w, H, W,
+                              *((dims["K"],) if path.K else ()), *norm), (ws, *(dims[k] for k in ws_args)))
+
+
+def _heads_forward(path, xx, wg, wb, H, W, norm_type=None):
+    """path.fwd: both heads on xx, raw -- or, on the float32 8-plane path, normalised by norm_type behind the conv -> guidance (float32, or xx's dtype on the
+    guidance16 path: the accumulator rounded once), blur float32 (None without a blur head).  On the x16 paths the engine rounds the float32 weights once to
+    xx's dtype"""
+    B, P = xx.shape[0], int(wg.shape[0])
+    g = torch.empty(B, P, H, W, dtype=xx.dtype if path.guidance16 else torch.float32, device=xx.device)
     b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
-    with torch.cuda.device(xx.device):
-        wsb = lib.cspn_guidance_head_workspace_bytes(C)
-        ws = _workspace(wsb, xx.device)
-        rc = lib.cspn_guidance_head_f32(xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
-                                        b.data_ptr() if b is not None else None, B, C, h, w, H, W, norm, ws.data_ptr(), wsb,
-                                        torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_f32")
+    _head_call(path, False, xx, wg, (wb, g, b), H, W, (_lib.NORM_TYPES[norm_type or "none"],) if path.norm else ())
     return g, b
 
 
-def _heads16_forward(xx, wg, wb, H, W):
-    """cspn_guidance_head_g16: the 8-plane guidance head and the blur head, raw, on a float16 / bfloat16 xx; float32 weights (rounded once to xx's dtype in the
-    engine) -> guidance and blur in float32, the unrounded accumulators"""
-    B, C, h, w = xx.shape
-    g = torch.empty(B, 8, H, W, dtype=torch.float32, device=xx.device)
-    b = torch.empty(B, 1, H, W, dtype=torch.float32, device=xx.device) if wb is not None else None
-    with torch.cuda.device(xx.device):
-        wsb = _lib.symbol("cspn_guidance_head_g16_workspace_bytes")(B, C, h, w)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.symbol("cspn_guidance_head_g16")(xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, g.data_ptr(),
-                                                   b.data_ptr() if b is not None else None, B, C, h, w, H, W, ws.data_ptr(), wsb,
-                                                   torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_g16")
-    return g, b
-
-
-def _heads16_backward(xx, wg, wb, gg, gb, need_x, need_w):
-    """cspn_guidance_head_backward_g16: float32 dL/dguidance and dL/dblur (rounded once to xx's dtype as they enter the GEMMs) -> dL/dx in xx's dtype, the
-    weight gradients float32"""
-    B, C, h, w = xx.shape
-    H, W = int(gg.shape[2]), int(gg.shape[3])
+def _heads_backward(path, xx, wg, wb, gg, gb, need_x, need_w):
+    """path.bwd -> dL/dx in xx's dtype (rounded once on the x16 paths, where the float32 gradients are rounded once to xx's dtype as they enter the GEMMs), the
+    weight gradients float32; skipped outputs are None"""
     dx = torch.empty_like(xx) if need_x else None
     dwg = torch.empty_like(wg) if need_w else None
     dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
-    with torch.cuda.device(xx.device):
-        wsb = _lib.symbol("cspn_guidance_head_backward_g16_workspace_bytes")(B, C, h, w)
-        ws = _workspace(wsb, xx.device)
-        rc = _lib.symbol("cspn_guidance_head_backward_g16")(
-            xx.data_ptr(), _GATE16[xx.dtype], wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
-            gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None, dwg.data_ptr() if dwg is not None else None,
-            dwb.data_ptr() if dwb is not None else None, B, C, h, w, H, W, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_backward_g16")
+    _head_call(path, True, xx, wg, (wb, gg, gb, dx, dwg, dwb), int(gg.shape[2]), int(gg.shape[3]))
     return dx, dwg, dwb
+
+
+def _f32(t):
+    return t.float() if t is not None else None
 
 
 def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad_blur, need_x=True, need_w=True, guidance_dtype=None):
@@ -311,150 +248,41 @@ def guidance_heads_backward(x, weight_guidance, weight_blur, grad_guidance, grad
     back in dt (rounded once), the weight gradients in float32 (the accumulators) -- or in dt, the float32 ones .to(dt), for weights that are dt themselves.
     guidance_dtype=torch.float32 with a dt x and the 8-plane weights (cspn_guidance_head_backward_g16): grad_guidance AND grad_blur are float32 (what
     cspn2d_backward returns) and are both rounded once to dt as they enter the GEMMs; the outputs as above.  Any other use of guidance_dtype: ValueError."""
-    lib = _lib.load()
     P = _head_planes(x, weight_guidance, weight_blur, grad_guidance, grad_blur)
-    if guidance_dtype is not None:
-        dt = _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype)
-        xx = _prep16(x, "x", dt)
-        B, C, h, w = xx.shape
-        wg = _prep_w16(weight_guidance, "weight_guidance", dt, (8, C, 3, 3))
-        wb = _prep_w16(weight_blur, "weight_blur", dt, (1, C, 3, 3)) if weight_blur is not None else None
-        if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
-            raise ValueError("grad_guidance must be [B,8,H,W]")
-        H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
-        gg = _prep(grad_guidance, "grad_guidance", (B, 8, H, W))
-        gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
-        dx, dwg, dwb = _heads16_backward(xx, wg, wb, gg, gb, need_x, need_w)
-        if dwg is not None and weight_guidance.dtype == dt:
-            dwg = dwg.to(dt)
-        if dwb is not None and weight_blur.dtype == dt:
-            dwb = dwb.to(dt)
-        return dx, dwg, dwb
-    dt = _head_dtype16(x, weight_guidance, weight_blur, P)
-    if dt is not None:
-        xx = _prep16(x, "x", dt)
-        B, C, h, w = xx.shape
-        wg = _prep_w16(weight_guidance, "weight_guidance", dt, (P, C, 3, 3))
-        wb = _prep_w16(weight_blur, "weight_blur", dt, (1, C, 3, 3)) if weight_blur is not None else None
-        if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
-            raise ValueError("grad_guidance must be [B,%d,H,W]" % P)
-        H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
-        gg = _prep16(grad_guidance, "grad_guidance", dt, (B, P, H, W))
-        gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
-        dx, dwg, dwb = _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w)
-        if dwg is not None and weight_guidance.dtype == dt:
-            dwg = dwg.to(dt)
-        if dwb is not None and weight_blur.dtype == dt:
-            dwb = dwb.to(dt)
-        return dx, dwg, dwb
-    xx = _prep(x, "x")
-    B, C, h, w = xx.shape
-    wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
-    wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
-    if not isinstance(grad_guidance, torch.Tensor) or grad_guidance.dim() != 4:
-        raise ValueError("grad_guidance must be [B,%d,H,W]" % P)
-    H, W = int(grad_guidance.shape[2]), int(grad_guidance.shape[3])
-    gg = _prep(grad_guidance, "grad_guidance", (B, P, H, W))
-    gb = _prep(grad_blur, "grad_blur", (B, 1, H, W)) if wb is not None else None
-    if P != 8:
-        return _heads_kxk_backward(xx, wg, wb, gg, gb, need_x, need_w)
-    dx = torch.empty_like(xx) if need_x else None
-    dwg = torch.empty_like(wg) if need_w else None
-    dwb = torch.empty_like(wb) if (need_w and wb is not None) else None
-    with torch.cuda.device(xx.device):
-        wsb = lib.cspn_guidance_head_backward_workspace_bytes(B, C, h, w)
-        ws = _workspace(wsb, xx.device)
-        rc = lib.cspn_guidance_head_backward_f32(xx.data_ptr(), wg.data_ptr(), wb.data_ptr() if wb is not None else None, gg.data_ptr(),
-                                                 gb.data_ptr() if gb is not None else None, dx.data_ptr() if dx is not None else None,
-                                                 dwg.data_ptr() if dwg is not None else None, dwb.data_ptr() if dwb is not None else None,
-                                                 B, C, h, w, H, W, ws.data_ptr(), wsb, torch.cuda.current_stream(xx.device).cuda_stream)
-    _lib.check(rc, "cspn_guidance_head_backward_f32")
-    return dx, dwg, dwb
+    path = _head_path(x, weight_guidance, weight_blur, P, guidance_dtype)
+    xx, wg, wb = _head_prep(path, x, weight_guidance, weight_blur, P)
+    gg, gb = _head_prep_grads(path, xx, wb, P, grad_guidance, grad_blur)
+    dx, dwg, dwb = _heads_backward(path, xx, _f32(wg), _f32(wb), gg, gb, need_x, need_w)
+    return dx, dwg.to(wg.dtype) if dwg is not None else None, dwb.to(wb.dtype) if dwb is not None else None
 
 
 class _GuidanceHeadsFunction(torch.autograd.Function):
+    """both heads of one path of _HEAD_PATHS (ctx.path) and their backward.  wg / wb: float32 master weights, or on the x16 paths weights of x's dtype (widened
+    exactly; their gradients are the float32 ones .to(dtype))"""
+
     @staticmethod
-    def forward(ctx, x, wg, wb, H, W):
+    def forward(ctx, path, x, wg, wb, H, W):
+        ctx.path = path
         ctx.save_for_backward(x, wg, wb)
-        g, b = _heads_forward(x, wg, wb, H, W, _lib.NORM_TYPES["none"])
-        return g, b
+        return _heads_forward(path, x, _f32(wg), _f32(wb), H, W)
 
     @staticmethod
     def backward(ctx, grad_g, grad_b):
+        path = ctx.path
         x, wg, wb = ctx.saved_tensors
-        if grad_g is None:
-            grad_g = torch.zeros(x.shape[0], 8, *((grad_b.shape[2:]) if grad_b is not None else (2 * x.shape[2], 2 * x.shape[3])), device=x.device)
-        if wb is not None and grad_b is None:
-            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], device=x.device)
-        dx, dwg, dwb = guidance_heads_backward(x, wg, wb, grad_g.contiguous(), grad_b.contiguous() if grad_b is not None else None,
-                                               need_x=ctx.needs_input_grad[0], need_w=ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2]))
-        return dx, dwg if ctx.needs_input_grad[1] else None, dwb if (wb is not None and ctx.needs_input_grad[2]) else None, None, None
-
-
-class _GuidanceHeadsKxKFunction(torch.autograd.Function):
-    """the 24- / 48-plane guidance head + the blur head: cspn_guidance_head_kxk_f32 and its backward"""
-
-    @staticmethod
-    def forward(ctx, x, wg, wb, H, W):
-        ctx.save_for_backward(x, wg, wb)
-        return _heads_kxk_forward(x, wg, wb, H, W)
-
-    @staticmethod
-    def backward(ctx, grad_g, grad_b):
-        x, wg, wb = ctx.saved_tensors
-        if grad_g is None:
-            grad_g = torch.zeros(x.shape[0], wg.shape[0], grad_b.shape[2], grad_b.shape[3], device=x.device)
-        if wb is not None and grad_b is None:
-            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], device=x.device)
-        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
-        dx, dwg, dwb = _heads_kxk_backward(x, wg, wb, grad_g.contiguous(), grad_b.contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
-        return dx, dwg if ctx.needs_input_grad[1] else None, dwb if (wb is not None and ctx.needs_input_grad[2]) else None, None, None
-
-
-class _GuidanceHeadsKxK16Function(torch.autograd.Function):
-    """the 24- / 48-plane guidance head + the blur head on a float16 / bfloat16 x: cspn_guidance_head_kxk_g16 and its backward.  wg / wb: float32 master
-    weights, or weights of x's dtype (widened exactly; their gradients are the float32 ones .to(dtype))"""
-
-    @staticmethod
-    def forward(ctx, x, wg, wb, H, W):
-        ctx.save_for_backward(x, wg, wb)
-        return _heads_kxk_forward(x, wg.float(), wb.float() if wb is not None else None, H, W)
-
-    @staticmethod
-    def backward(ctx, grad_g, grad_b):
-        x, wg, wb = ctx.saved_tensors
-        if grad_g is None:
-            grad_g = torch.zeros(x.shape[0], wg.shape[0], grad_b.shape[2], grad_b.shape[3], dtype=x.dtype, device=x.device)
+        need_x, need_wg, need_wb = ctx.needs_input_grad[1], ctx.needs_input_grad[2], wb is not None and ctx.needs_input_grad[3]
+        if grad_g is None:   # an output the loss does not use: zeros in the dtype the entry point takes
+            grad_g = torch.zeros(x.shape[0], wg.shape[0], *(grad_b.shape[2:] if grad_b is not None else (2 * x.shape[2], 2 * x.shape[3])),
+                                 dtype=x.dtype if path.guidance16 else torch.float32, device=x.device)
         if wb is not None and grad_b is None:
             grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], dtype=torch.float32, device=x.device)
-        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
-        dx, dwg, dwb = _heads_kxk_backward(x, wg.float(), wb.float() if wb is not None else None, grad_g.contiguous(),
-                                             grad_b.float().contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
-        return (dx, dwg.to(wg.dtype) if ctx.needs_input_grad[1] else None,
-                dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
+        dx, dwg, dwb = _heads_backward(path, x, _f32(wg), _f32(wb), (grad_g if path.guidance16 else grad_g.float()).contiguous(),
+                                       grad_b.float().contiguous() if wb is not None else None, need_x, need_wg or need_wb)
+        return None, dx, dwg.to(wg.dtype) if need_wg else None, dwb.to(wb.dtype) if need_wb else None, None, None
 
 
-class _GuidanceHeads16Function(torch.autograd.Function):
-    """the 8-plane guidance head + the blur head on a float16 / bfloat16 x, float32 guidance and blur: cspn_guidance_head_g16 and its backward.  wg / wb:
-    float32 master weights, or weights of x's dtype (widened exactly; their gradients are the float32 ones .to(dtype))"""
-
-    @staticmethod
-    def forward(ctx, x, wg, wb, H, W):
-        ctx.save_for_backward(x, wg, wb)
-        return _heads16_forward(x, wg.float(), wb.float() if wb is not None else None, H, W)
-
-    @staticmethod
-    def backward(ctx, grad_g, grad_b):
-        x, wg, wb = ctx.saved_tensors
-        if grad_g is None:
-            grad_g = torch.zeros(x.shape[0], 8, grad_b.shape[2], grad_b.shape[3], dtype=torch.float32, device=x.device)
-        if wb is not None and grad_b is None:
-            grad_b = torch.zeros(x.shape[0], 1, grad_g.shape[2], grad_g.shape[3], dtype=torch.float32, device=x.device)
-        need_w = ctx.needs_input_grad[1] or (wb is not None and ctx.needs_input_grad[2])
-        dx, dwg, dwb = _heads16_backward(x, wg.float(), wb.float() if wb is not None else None, grad_g.float().contiguous(),
-                                         grad_b.float().contiguous() if wb is not None else None, ctx.needs_input_grad[0], need_w)
-        return (dx, dwg.to(wg.dtype) if ctx.needs_input_grad[1] else None,
-                dwb.to(wb.dtype) if (wb is not None and ctx.needs_input_grad[2]) else None, None, None)
+def _requires_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
 def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, norm_type=None, guidance_dtype=None):
@@ -481,78 +309,26 @@ def guidance_heads(x, weight_guidance, weight_blur=None, oheight=0, owidth=0, no
     is, with no x.float() before the head and no widening pass behind it; dL/dx comes back in dt.  Raw only.  Any other use of guidance_dtype (24 / 48 planes, a
     float32 x, another dtype, a norm_type) raises ValueError."""
     P = _head_planes(x, weight_guidance, weight_blur)
-    if guidance_dtype is not None:
-        dt = _head_dtype16_f32(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type)
-        xx = _prep16(x, "x", dt)
-        B, C, h, w = xx.shape
-        H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
-        for t, name, shape in ((weight_guidance, "weight_guidance", (8, C, 3, 3)), (weight_blur, "weight_blur", (1, C, 3, 3))):
-            if t is not None and t.dtype == dt:
-                _prep16(t, name, dt, shape)
-            elif t is not None:
-                _prep(t, name, shape)
-        wg = weight_guidance.contiguous()
-        wb = weight_blur.contiguous() if weight_blur is not None else None
-        if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
-            return _GuidanceHeads16Function.apply(xx, wg, wb, H, W)
-        return _heads16_forward(xx, wg.float(), wb.float() if wb is not None else None, H, W)
-    dt = _head_dtype16(x, weight_guidance, weight_blur, P)
-    if P != 8:
-        if norm_type is not None:
-            raise ValueError("the %d-plane guidance head returns raw guidance only (norm_type=None): Affinity_PropagateKxK(prop_time, %d, norm_type) "
-                             "normalises it" % (P, _PLANES_TO_K[P]))
-        if dt is not None:
-            xx = _prep16(x, "x", dt)
-            B, C, h, w = xx.shape
-            H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
-            for t, name, shape in ((weight_guidance, "weight_guidance", (P, C, 3, 3)), (weight_blur, "weight_blur", (1, C, 3, 3))):
-                if t is not None and t.dtype == dt:
-                    _prep16(t, name, dt, shape)
-                elif t is not None:
-                    _prep(t, name, shape)
-            wg = weight_guidance.contiguous()
-            wb = weight_blur.contiguous() if weight_blur is not None else None
-            if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
-                return _GuidanceHeadsKxK16Function.apply(xx, wg, wb, H, W)
-            return _heads_kxk_forward(xx, wg.float(), wb.float() if wb is not None else None, H, W)
-        xx = _prep(x, "x")
-        B, C, h, w = xx.shape
-        wg = _prep(weight_guidance, "weight_guidance", (P, C, 3, 3))
-        wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
-        H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
-        if torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
-            return _GuidanceHeadsKxKFunction.apply(xx, wg, wb, H, W)
-        return _heads_kxk_forward(xx, wg, wb, H, W)
-    if norm_type is not None and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, weight_guidance, weight_blur)):
+    path = _head_path(x, weight_guidance, weight_blur, P, guidance_dtype, norm_type)
+    if norm_type is not None and _requires_grad(x, weight_guidance, weight_blur):
         return _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth, norm_type)
-    xx = _prep(x, "x")
-    B, C, h, w = xx.shape
-    wg = _prep(weight_guidance, "weight_guidance", (8, C, 3, 3))
-    wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
-    H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
+    xx, wg, wb = _head_prep(path, x, weight_guidance, weight_blur, P)
+    H, W = _head_out_size(xx, oheight, owidth)
     if norm_type not in (None, "8sum", "8sum_abs"):
         raise ValueError("norm_type must be None (raw guidance), '8sum' or '8sum_abs' (gate_wb)")
-    if norm_type is None and torch.is_grad_enabled() and (xx.requires_grad or wg.requires_grad or (wb is not None and wb.requires_grad)):
-        return _GuidanceHeadsFunction.apply(xx, wg, wb, H, W)
-    return _heads_forward(xx, wg, wb, H, W, _lib.NORM_TYPES["none" if norm_type is None else norm_type])
+    if norm_type is None and _requires_grad(xx, wg, wb):
+        return _GuidanceHeadsFunction.apply(path, xx, wg, wb, H, W)
+    return _heads_forward(path, xx, _f32(wg), _f32(wb), H, W, norm_type)
 
 
 def _guidance_heads_normalised(x, weight_guidance, weight_blur, oheight, owidth, norm_type):
-    """guidance_heads with norm_type under autograd: the raw heads, then cspn2d_normalize (both differentiable).  Forward traffic: the raw guidance
-    written (32 B/pixel) and normalised (36 B read + 32 B written) -- the fused mode writes 32 B and normalises in place in the same 32 + 32 B."""
+    """guidance_heads with norm_type under autograd (the float32 8-plane path): the raw heads, then cspn2d_normalize (both differentiable).  Forward traffic: the
+    raw guidance written (32 B/pixel) and normalised (36 B read + 32 B written) -- the fused mode writes 32 B and normalises in place in the same 32 + 32 B."""
     if norm_type not in ("8sum", "8sum_abs"):
         raise ValueError("norm_type must be None (raw guidance), '8sum' or '8sum_abs' (gate_wb)")
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError("x must be [B,C,h,w], got %s" % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__,))
-    for t in (weight_guidance, weight_blur):
-        if isinstance(t, torch.Tensor) and t.device != x.device:
-            raise ValueError("all tensors must live on the same device")
-    xx = _prep(x, "x")
-    B, C, h, w = xx.shape
-    wg = _prep(weight_guidance, "weight_guidance", (8, C, 3, 3))
-    wb = _prep(weight_blur, "weight_blur", (1, C, 3, 3)) if weight_blur is not None else None
-    H, W = (int(oheight), int(owidth)) if (oheight and owidth) else (2 * h, 2 * w)
-    g, b = _GuidanceHeadsFunction.apply(xx, wg, wb, H, W)
+    path = _HEAD_PATHS["f32"]
+    xx, wg, wb = _head_prep(path, x, weight_guidance, weight_blur, 8)
+    g, b = _GuidanceHeadsFunction.apply(path, xx, wg, wb, *_head_out_size(xx, oheight, owidth))
     return cspn2d_normalize(g, norm_type), b
 
 

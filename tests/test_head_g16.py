@@ -242,7 +242,8 @@ def test_module_train_step_is_the_manual_composition(dtn):
     xa = x.clone().requires_grad_(True)
     g, b = heads(xa)
     assert g.dtype == F32 and b.dtype == F32 and g.grad_fn is b.grad_fn
-    assert type(g.grad_fn).__name__ == "_GuidanceHeads16FunctionBackward"          # the head's own node: nothing (no .float()) between it and the ring
+    # the head's own node: nothing (no .float()) between it and the ring
+    assert type(g.grad_fn).__name__ == "_GuidanceHeadsFunctionBackward" and g.grad_fn.path.fwd == "cspn_guidance_head_g16"
     out = prop(g, b, sp)
     loss = loss_fn(out, label)
     loss.backward()
@@ -276,13 +277,14 @@ def test_the_other_paths_of_the_module_are_todays_functions():
         g, b = m(x)
         rg, rb = guidance_heads(x, m.weight_guidance, m.weight_blur, 9, 73)
         assert g.dtype == F32 and torch.equal(g, rg) and torch.equal(b, rb)
-        assert type(g.grad_fn).__name__ == ("_GuidanceHeadsFunctionBackward" if K == 3 else "_GuidanceHeadsKxKFunctionBackward")
+        assert type(g.grad_fn).__name__ == "_GuidanceHeadsFunctionBackward"
+        assert g.grad_fn.path.fwd == ("cspn_guidance_head_f32" if K == 3 else "cspn_guidance_head_kxk_f32")
     for dt in (torch.float16, torch.bfloat16):
         m = cspn_amd.GuidanceHeads(33, 5, 9, 73).cuda()
         g, b = m(x.to(dt))
         rg, rb = guidance_heads(x.to(dt), m.weight_guidance, m.weight_blur, 9, 73)
         assert g.dtype == dt and b.dtype == F32 and torch.equal(g, rg) and torch.equal(b, rb)
-        assert type(g.grad_fn).__name__ == "_GuidanceHeadsKxK16FunctionBackward"
+        assert type(g.grad_fn).__name__ == "_GuidanceHeadsFunctionBackward" and g.grad_fn.path.fwd == "cspn_guidance_head_kxk_g16"
 
 
 @pytest.mark.gpu
