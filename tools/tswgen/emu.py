@@ -61,6 +61,9 @@ class Emu(object):
         self.nsteps = 0
         self.check_races = True
         self.sched_rng = None
+        # windows = [(virtual address, bytes, offset in mem)]: global addresses are then VIRTUAL, and only these ranges of them exist
+        # (a slice of a tensor too large to hold: run_emu.py `window`); None: an address is an offset in mem
+        self.windows = None
 
     # ---- operand access -----------------------------------------------------------------------------
     def _chk(self, w, reg):
@@ -181,6 +184,16 @@ class Emu(object):
         a = base + voff.astype(np.int64) + int(ins.mods.get("offset", 0))
         if np.any(a[lanes] % 4):
             raise EmuError("misaligned global access")
+        if self.windows is not None:
+            phys = np.full(64, -1, np.int64)
+            for va, nbytes, pa in self.windows:
+                inside = (a >= va) & (a + 4 * ndw <= va + nbytes)
+                phys = np.where(inside, a - va + pa, phys)
+            if np.any(phys[lanes] < 0):
+                bad = a[lanes][phys[lanes] < 0]
+                raise EmuError("wave %d pc %d: global access outside every window (0x%x..0x%x): %s" % (
+                    w.wid, w.pc, bad.min(), bad.max(), ins.text()))
+            a = phys
         if np.any(a[lanes] < 4096) or np.any(a[lanes] + 4 * ndw > self.mem.size):
             raise EmuError("wave %d pc %d: global access out of range (%d..%d): %s" % (
                 w.wid, w.pc, a[lanes].min(), a[lanes].max(), ins.text()))

@@ -231,3 +231,32 @@ def build_plan(B, H, W, n_iter, n_wg, xcd=None):
         p0b, lob, hib = bands[wg_group(g, len(bands), n_wg, xcd)[1]]
         fill_plan_rows(hdr, tab, g, segs, bands, H, W, n_iter, (lob - p0b) | ((hib - p0b) << 16))   # owned columns of the workgroup's band
     return hdr, tab
+
+
+def build_plan_window(B, H, W, n_iter, n_wg, b0, nimg, xcd=None):
+    """the band groups of build_plan(B, ..) whose rows lie wholly in the images b0 .. b0 + nimg - 1, for a batch too large to build (or
+    to hold) whole -> (workgroup ids, header, table, rows [nimg][H] bool: the rows those groups own); header and table have one entry
+    per workgroup id returned, with the descriptors (byte offsets into the tensors of all B images) that build_plan gives them"""
+    bands = plan_bands(W, n_iter)
+    nb = len(bands)
+    ng = wg_group(0, nb, n_wg, xcd)[2]
+    stride = stride_of(-(-(B * H) // ng), H, n_iter)
+    assert stride <= TAB_MAX_ROWS
+    wgs = []
+    for g in range(n_wg):
+        G, bi, _ = wg_group(g, nb, n_wg, xcd)
+        if G is None:
+            continue
+        r0, r1 = G * (B * H) // ng, (G + 1) * (B * H) // ng
+        if r1 > r0 and r0 >= b0 * H and r1 <= (b0 + nimg) * H:
+            wgs.append(g)
+    hdr = np.zeros((len(wgs), 4), np.int32)
+    tab = np.zeros((len(wgs), stride, 4), np.uint32)
+    rows = np.zeros((nimg, H), bool)
+    for i, g in enumerate(wgs):
+        segs = share_segments(B, H, W, n_iter, bands, g, n_wg, xcd)
+        p0b, lob, hib = bands[wg_group(g, nb, n_wg, xcd)[1]]
+        fill_plan_rows(hdr, tab, i, segs, bands, H, W, n_iter, (lob - p0b) | ((hib - p0b) << 16))
+        for b, _, _, _, y0, y1 in segs:
+            rows[b - b0, y0:y1] = True
+    return wgs, hdr, tab, rows

@@ -34,3 +34,10 @@ def build_plan_linear(B, H, W, n_iter, ncu, xcd=True):
     with _consts():
         lp, hdr, tab = P2.build_plan_linear(B, H, W, n_iter, ncu, xcd)
     return lp, _fix(hdr), tab
+
+
+def build_plan_window(B, H, W, n_iter, n_wg, b0, nimg, xcd=None):
+    with _consts():
+        wgs, hdr, tab, rows = P2.build_plan_window(B, H, W, n_iter, n_wg, b0, nimg, xcd)
+    hdr[:, 2] = -1
+    return wgs, _fix(hdr), tab, rows

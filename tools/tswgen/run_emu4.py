@@ -9,10 +9,12 @@ from . import kernel4 as K
 from .emu import Emu, EmuError
 from .plan import plan_bands
 from .plan4 import build_plan, build_plan_linear
-from .run_emu import normalized_planes
+from .run_emu import memory_image, normalized_planes
 
 
-def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verbose=True, sched=True, linear=None, cfg=None, neg_sparse=True):
+def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verbose=True, sched=True, linear=None, cfg=None, neg_sparse=True, window=None):
+    """window = (B_total, b0): as in run_emu.run_case -- the B images are images b0 .. of a batch too large to hold, the band
+    groups that lie wholly in them run at the large batch's descriptors and virtual addresses -> err, NaN mismatches, out, ref, rows compared"""
     sys.path.insert(0, ".")
     from oracle import oracle as O
     rng = np.random.default_rng(seed)
@@ -33,27 +35,21 @@ def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verb
     prog = K.build(dict(norm=norm, sparse=sparse, **(cfg or {})), sched=sched)
     g_dev = normalized_planes(g, 0) if norm == 3 else g
     nb = len(plan_bands(W, n_iter))
-    if linear:
+    rows = np.ones((B, H), bool)   # the rows whose owners run
+    if window:
+        from .plan4 import build_plan_window
+        assert not linear
+        n_wg = -(-n_wg // nb) * nb
+        wgs, hdr, tab, rows = build_plan_window(window[0], H, W, n_iter, n_wg, window[1], B)
+        assert len(wgs), "no band group lies wholly in the window"
+        n_wg = len(wgs)
+    elif linear:
         lp, hdr, tab = build_plan_linear(B, H, W, n_iter, linear, xcd=False)
         n_wg = lp.n_wg
     else:
         n_wg = -(-n_wg // nb) * nb   # whole groups of nb workgroups
         hdr, tab = build_plan(B, H, W, n_iter, n_wg)
-
-    def al(n):
-        return (n + 4095) // 4096 * 4096
-    off, cur = {}, 8192
-    for name, arr in (("gd", g_dev), ("blur", blur), ("sp", sp), ("out", np.zeros_like(blur))):
-        if arr is None:
-            off[name] = 4096
-            continue
-        off[name] = cur
-        cur += al(arr.nbytes) + 4096
-    mem = np.zeros(cur + 4096, np.uint8)
-    mem.view(np.float32)[:] = np.nan
-    for name, arr in (("gd", g_dev), ("blur", blur), ("sp", sp)):
-        if arr is not None:
-            mem[off[name]:off[name] + arr.nbytes] = arr.view(np.uint8).ravel()
+    mem, off, base, windows, _ = memory_image((("gd", g_dev), ("blur", blur), ("sp", sp), ("out", np.zeros_like(blur))), B, window)
     t0 = time.time()
     tot = 0
     icount = {}
@@ -61,6 +57,7 @@ def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verb
         if hdr[wg, 0] == 0:
             continue
         emu = Emu(prog, mem, K.LDS_BYTES, nwaves=K.NW)
+        emu.windows = windows
         flat = np.ascontiguousarray(tab[wg], np.uint32).ravel()
         emu.lds[K.LDS_TAB // 4:K.LDS_TAB // 4 + flat.size] = flat
         for w in emu.waves:
@@ -69,11 +66,11 @@ def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verb
             def set64(r, val):
                 w.s[r.i] = val & 0xffffffff
                 w.s[r.i + 1] = val >> 32
-            set64(K.S_GD, off["gd"])
-            set64(K.S_BLUR, off["blur"])
-            set64(K.S_HIN, off["blur"])
-            set64(K.S_SP, off["sp"])
-            set64(K.S_OUT, off["out"])
+            set64(K.S_GD, base["gd"])
+            set64(K.S_BLUR, base["blur"])
+            set64(K.S_HIN, base["blur"])
+            set64(K.S_SP, base["sp"])
+            set64(K.S_OUT, base["out"])
             w.s[K.S_W4.i] = 4 * W
             w.s[K.S_HW4.i] = 4 * H * W
             w.s[K.S_LAST.i] = int(hdr[wg, 1])
@@ -86,9 +83,11 @@ def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verb
                 icount[k] = icount.get(k, 0) + v
     out = mem[off["out"]:off["out"] + blur.nbytes].view(np.float32).reshape(blur.shape)
     ref = O.cspn2d_oracle(g, blur, sp, n_iter, ["8sum", "8sum_abs", "none", "8sum"][norm])
-    nanmis = np.isnan(out) != np.isnan(ref)
+    if window:   # nothing was stored outside the rows that ran
+        assert np.isnan(out[:, 0][~rows]).all(), "a store outside the rows of the workgroups that ran"
+    nanmis = (np.isnan(out) != np.isnan(ref))[:, 0][rows]
     den = np.nanmax(np.abs(ref))
-    err = np.nanmax(np.abs(out - ref)) / den if not nanmis.any() else np.inf
+    err = np.nanmax(np.abs(out - ref)[:, 0][rows]) / den if not nanmis.any() else np.inf
     if verbose:
         steps = int(hdr[:, 1].max()) + 1 + K.LEAD
         print("B%d H%d W%d wg%d norm%d sp%d: rel err %.3g  nan mismatch %d  (%d instr, %.1fs, %d NaNs in ref)" % (
@@ -99,6 +98,8 @@ def run_case(B, H, W, n_wg, norm=0, sparse=False, seed=0, zero_patch=False, verb
         nm = sum(v for k, v in icount.items() if k.startswith("ds_") or k.startswith("global_"))
         print("   per wave-step: VALU %.1f SALU %.1f nop %.1f mem %.1f (steps %d)" % (
             nv / K.NW / steps / n_wg, ns / K.NW / steps / n_wg, nn / K.NW / steps / n_wg, nm / K.NW / steps / n_wg, steps))
+    if window:   # a fifth value with a window only: the rows compared (without one every row is, and the callers unpack four values)
+        return err, nanmis.sum(), out, ref, rows
     return err, nanmis.sum(), out, ref
 
 
