@@ -147,6 +147,9 @@ _SYMBOLS.update({
     "cspn3d_backward_multi_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 6 + _WS),
     "cspn_gate_absnorm_g16": (c_int, [vp, c_int, vp] + [c_int] * 2 + [c_size_t, vp]),
     "cspn_gate_absnorm_backward_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_int] * 2 + [c_size_t, vp]),
+    # the backward of the 3D normalising / masked modes (raw guidance, optional mask)
+    "cspn3d_backward_norm_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn3d_backward_norm_f32": (c_int, [vp] * 6 + [c_int] * 7 + _WS),
 })
 _LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
 

@@ -113,6 +113,50 @@ class Affinity_Propagate(nn.Module):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
 
 
+class _CSPN3dNormFunction(torch.autograd.Function):
+    """F.cspn3d_forward in a normalising mode; the backward is one cspn3d_backward_norm_f32 call (the fold and the levels are recomputed there)"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo):
+        ctx.n_iter, ctx.norm_type, ctx.algo = n_iter, norm_type, algo
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth)
+        return F.cspn3d_forward(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth = ctx.saved_tensors
+        gg, gh = F.cspn3d_backward_norm(guidance, blur_depth, sparse_depth, grad_out, ctx.n_iter, ctx.norm_type,
+                                        "stepwise" if ctx.algo == "stepwise" else "auto",   # ('persistent' is a wish about the forward)
+                                        need_guidance=ctx.needs_input_grad[0], need_feat=ctx.needs_input_grad[1])
+        return gg, gh, None, None, None, None
+
+
+class Affinity_Propagate3d(nn.Module):
+    """The 3D twin of Affinity_Propagate (same constructor, same forward): guidance [B,26,D,H,W] raw, blur_depth and sparse_depth
+    [B,1,D,H,W] -- neighbour-sited gates divided by the abs-sum of the in-range ones, the (1 - sigma) H_0 centre term and the sparse pin over
+    the 26-neighbourhood (F.cspn3d_forward with '8sum' / '8sum_abs'), differentiable w.r.t. guidance and blur_depth
+    (F.cspn3d_backward_norm); sparse_depth gets no gradient.  float16 / bfloat16 inputs are widened first; the result is float32."""
+
+    def __init__(self, prop_time, prop_kernel=3, norm_type='8sum_abs'):
+        super(Affinity_Propagate3d, self).__init__()
+        self.prop_time = prop_time
+        self.prop_kernel = prop_kernel
+        assert prop_kernel == 3, 'this version only support 26 (3x3x3 - 1) neighborhood'
+        self.norm_type = norm_type
+        assert norm_type in ['8sum', '8sum_abs']
+        self.algo = "auto"   # 'stepwise': one launch per step, forward and backward
+
+    def forward(self, guidance, blur_depth, sparse_depth=None, n_iter=None):
+        n = self.prop_time if n_iter is None else int(n_iter)
+        if n == 0:
+            return blur_depth
+        guidance, blur_depth, sparse_depth = F.widen16(guidance, blur_depth, sparse_depth)
+        return _CSPN3dNormFunction.apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo)
+
+    def extra_repr(self):
+        return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
+
+
 class _CSPN2dKxKNormFunction(torch.autograd.Function):
     """Affinity_PropagateKxK with prop_kernel 5 / 7: the forward keeps H_1 .. H_{n-1} where the guidance gradient needs them, the
     backward is one cspn2d_backward_kxk_norm_f32 call (the fold is recomputed there)"""

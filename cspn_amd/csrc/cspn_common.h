@@ -131,6 +131,15 @@ int backward3d(const void* g, const float* feat, const float* gout, void* gg, fl
 // n gates (n % 4 == 0, g 8-byte and w 16-byte aligned) widened exactly into float32
 int widen_gates(const void* g, int gdt, float* w, size_t n, hipStream_t st);
 
+// ---- backward of the 3D op in its normalising / masked modes (cspn3d_norm_backward.hip): norm 8SUM / 8SUM_ABS, or NONE with a mask; g raw
+// guidance [B][26][V], sparse NULL or [B][V]; gg and gf may each be NULL.  The adjoint sweep runs through the persistent kernel's transposed
+// instance where backward3d_norm_fused() holds and stepwise_only is false, every other launch is per step ----
+size_t backward3d_norm_workspace(int B, int D, int H, int W, int n_iter);
+bool backward3d_norm_fused(const float* g, const float* feat, const float* sparse, const float* gout, const float* gg, const float* gf, int B, int D,
+                           int H, int W, int n_iter, const void* ws);
+int backward3d_norm(const float* g, const float* feat, const float* sparse, const float* gout, float* gg, float* gf, int B, int D, int H, int W,
+                    int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only);
+
 // ---- the producer of the path's inputs (cspn_head.hip): Unpool + 3x3 conv C -> 8 (guidance) and C -> 1 (blur) as one kernel; mode 0 raw guidance,
 // 1 / 2 gate_wb of '8sum' / '8sum_abs' (the normalisation fused behind the conv) ----
 size_t head_workspace(int C);

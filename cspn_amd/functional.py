@@ -400,6 +400,31 @@ def cspn3d_backward_multi(gate, feat, grad_out, n_iter=1, need_gate=True, need_f
     return _backward3d("_multi", gate, feat, grad_out, n_iter, need_gate, need_feat)
 
 
+def cspn3d_backward_norm(guidance, feat, sparse, grad_out, n_iter=12, norm_type="8sum_abs", algo="auto", need_guidance=True, need_feat=True):
+    """Gradient of cspn3d_forward(guidance, feat, sparse, n_iter, norm_type) in its normalising / masked modes ('8sum', '8sum_abs', or
+    'none' with a mask; 'none' without one is cspn3d_backward) w.r.t. the raw guidance and feat, in the HIP engine
+    (cspn3d_backward_norm_f32: the fold is recomputed, one launch per step).  sparse gets no gradient (only its sign is used).
+    -> (grad_guidance [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None).  float32 only."""
+    if guidance.dim() != 5 or guidance.shape[1] != 26:
+        raise ValueError("guidance must be [B,26,D,H,W], got %s" % (tuple(guidance.shape),))
+    B, _, D, H, W = guidance.shape
+    g = _prep(guidance, "guidance")
+    h = _prep(feat, "feat", (B, 1, D, H, W))
+    s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
+    go = _prep(grad_out, "grad_out", (B, 1, D, H, W))
+    if any(t is not None and t.device != g.device for t in (h, s, go)):
+        raise ValueError("all tensors must live on the same device")
+    gg = torch.empty_like(g) if need_guidance else None
+    gf = torch.empty_like(h) if need_feat else None
+    if B == 0 or not (need_guidance or need_feat):
+        return gg, gf
+    norm = _lib.NORM_TYPES[norm_type]
+    _launch("cspn3d_backward_norm_f32", g.device,
+            (_ptr(g), _ptr(h), _ptr(s), _ptr(go), _ptr(gg), _ptr(gf), B, D, H, W, int(n_iter), norm, _lib.ALGOS_3D[algo]),
+            ("cspn3d_backward_norm_workspace_bytes", B, D, H, W, int(n_iter), norm, int(s is not None)))
+    return gg, gf
+
+
 class _AffinityPropagateFunction(torch.autograd.Function):
     """n_iter chained 3 x 3 (x 3) propagation steps of C >= 1 input channels on shared gates, differentiable w.r.t. both arguments: one engine call
     each way for all channels (the gate gradient summed in the engine), but for the 3D forward where the persistent kernel does not take them"""

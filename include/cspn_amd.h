@@ -53,7 +53,8 @@ extern "C" {
                               *    fp16 / bf16 gates and guidance on the K x K entry points (cspn2d_*_kxk*_g16, CSPN_DTYPE_*), the demo module's
                               *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*), the 8-plane heads on a 16-bit feature map with float32 guidance
                               *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16), fp16 / bf16 gates and guides on the 3D entry points of the
-                              *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16) */
+                              *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16), the backward of the 3D normalising / masked modes
+                              *    (cspn3d_backward_norm_f32) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -228,6 +229,33 @@ size_t cspn3d_backward_multi_workspace_bytes(int B, int C, int D, int H, int W, 
 int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float* grad_out, float* grad_gate, float* grad_feat,
                               int B, int C, int D, int H, int W, int n_iter,
                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* Backward of the 3D op in its normalising and masked modes -- what cspn3d_forward_f32 computes with CSPN_NORM_8SUM / CSPN_NORM_8SUM_ABS
+ * (its default: the 3D form of Affinity_Propagate's contract) or with a mask: guidance [B,26,D,H,W] RAW, feat / grad_out [B,1,D,H,W], sparse
+ * [B,1,D,H,W] or NULL (only its sign is used; it gets no gradient); grad_guidance [B,26,D,H,W] and grad_feat [B,1,D,H,W] are outputs, either may
+ * be NULL (both: returns 0, launches nothing).  Per voxel p, off_k the offset of channel k, everything outside the volume zero:
+ *   forward   G_k(p) = g~_k(p + off_k), g~ = |g| (8SUM_ABS) or g;  S = sum_j |G_j|, wb_k = G_k / S, sigma = sum_k wb_k
+ *             (NONE: G_k(p) = g_k(p), S = 1, no centre term);  m = sign(sparse) (0 without), u = 1 - m
+ *             w'_k = u wb_k,  c' = (u (1 - sigma) + m) H_0  (NONE: m H_0),  H_0 = feat,  H_{t+1}(p) = c'(p) + sum_k w'_k(p) H_t(p + off_k)
+ *   backward  A_n = grad_out, A_t(q) = sum_k w'_k(q - off_k) A_{t+1}(q - off_k);  dW'_k(p) = sum_t A_{t+1}(p) H_t(p + off_k), dC = sum_t A_{t+1}
+ *             grad_feat = A_0 + dC (u (1 - sigma) + m);  dwb_k = u (dW'_k - dC H_0)   (NONE: grad_guidance_k = u dW'_k)
+ *             T = sum_j dwb_j G_j,  dG_k = dwb_k / S - sign(G_k) T / S^2,  grad_guidance_k(q) = dG_k(q - off_k) [x sign(g_k(q)) for 8SUM_ABS]
+ *   sign(0) = 0 (torch's abs backward); S = 0 gives NaN as in the forward.  Every output element is written once, no atomics: two calls
+ *   with the same algo are bitwise equal.  The fold is recomputed into the workspace; the forward levels run one launch per step, and only
+ *   where grad_guidance is wanted.
+ * norm_type CSPN_NORM_NONE with sparse NULL is cspn3d_backward_f32 (bitwise; algo STEPWISE: its per-step kernels); CSPN_NORM_PRENORM or an
+ *   unknown value: CSPN_E_BADARG.  algo: CSPN_ALGO3D_STEPWISE runs one launch per adjoint step, for every shape and alignment;
+ *   CSPN_ALGO3D_AUTO runs the n adjoint steps as ONE launch of the persistent kernel's transposed instance on w' where that instance takes
+ *   the call (W % 4 == 0, every pointer 16-byte aligned, 3 <= n_iter <= 60, the volume fits the device: the fused sweep of
+ *   cspn3d_backward_f32, failures reported the same way: CSPN_E_ASYNC, cspn3d_check_status) and per step elsewhere; CSPN_ALGO3D_PERSISTENT
+ *   returns CSPN_E_UNSUPPORTED where AUTO would not use that instance.  Any B, D, H, W >= 1 and 4-byte aligned pointers; 16-byte loads and
+ *   stores where W % 4 == 0 and every pointer is 16-byte aligned.  n_iter = 0: grad_feat = grad_out, grad_guidance = 0.  An output that overlaps an input,
+ *   the other output or the workspace: CSPN_E_BADARG; a workspace smaller than cspn3d_backward_norm_workspace_bytes() or not 256-byte
+ *   aligned: CSPN_E_WORKSPACE; the query returns 0 for an invalid shape or norm_type.  Float32 and one channel only. */
+size_t cspn3d_backward_norm_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
+int cspn3d_backward_norm_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out,
+                             float* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter,
+                             int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the demo's module (reference cspn_paddle/demo.py:20-54, CSPN.cspn): guide = abs(guide) (:24), each slice of K = 3^d - 1 gate
  * channels divided by its own channel sum at the voxel (:34-36,47-49), then the chained propagation (:40-43,50-52) -- what a port of the
