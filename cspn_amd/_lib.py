@@ -150,6 +150,11 @@ _SYMBOLS.update({
     # the backward of the 3D normalising / masked modes (raw guidance, optional mask)
     "cspn3d_backward_norm_workspace_bytes": (c_size_t, [c_int] * 7),
     "cspn3d_backward_norm_f32": (c_int, [vp] * 6 + [c_int] * 7 + _WS),
+    # the 3D normalising / masked modes on fp16 / bf16 guidance (gate_dtype after the guidance pointer): read where it is used, its gradient in
+    # its type; everything else float32
+    "cspn3d_forward_norm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_int] * 7 + _WS),
+    "cspn3d_backward_norm_g16_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn3d_backward_norm_g16": (c_int, [vp, c_int] + [vp] * 5 + [c_int] * 7 + _WS),
 })
 _LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
 

@@ -20,9 +20,9 @@ Differences a caller can observe, all deliberate:
     sparse_depth None, [B,1,H,W] or [B,C,H,W]: one engine call each way (cspn2d_forward_multi_f32 / cspn2d_backward_multi_f32),
     dL/dguidance summed over the channels;
   * float16 / bfloat16 inputs (heads under torch.autocast) are taken and the result is float32: Affinity_PropagateKxK with prop_kernel
-    5 / 7 and CSPN in 2D with prop_kernel 5 / 7 hand a 16-bit guidance / guide to the engine as it is (widened exactly where used, its
-    gradient in its dtype); everything without a 16-bit kernel (Affinity_Propagate, prop_kernel 3, propagate_prenorm, CSPN in 3D) widens
-    with a differentiable .float() first."""
+    5 / 7, CSPN in 2D with prop_kernel 5 / 7, CSPN in 3D and Affinity_Propagate3d hand a 16-bit guidance / guide to the engine as it is
+    (widened exactly where used, its gradient in its dtype); everything without a 16-bit kernel (Affinity_Propagate, prop_kernel 3 in 2D,
+    propagate_prenorm) widens with a differentiable .float() first, and so does every module with its value tensors."""
 import torch
 import torch.nn as nn
 
@@ -114,13 +114,14 @@ class Affinity_Propagate(nn.Module):
 
 
 class _CSPN3dNormFunction(torch.autograd.Function):
-    """F.cspn3d_forward in a normalising mode; the backward is one cspn3d_backward_norm_f32 call (the fold and the levels are recomputed there)"""
+    """F.cspn3d_forward_norm in a normalising mode; the backward is one cspn3d_backward_norm_f32 / _g16 call (the fold and the levels are
+    recomputed there).  A float16 / bfloat16 guidance is saved as it is and gets its gradient in its dtype"""
 
     @staticmethod
     def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo):
         ctx.n_iter, ctx.norm_type, ctx.algo = n_iter, norm_type, algo
         ctx.save_for_backward(guidance, blur_depth, sparse_depth)
-        return F.cspn3d_forward(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
+        return F.cspn3d_forward_norm(guidance, blur_depth, sparse_depth, n_iter, norm_type, algo)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -135,7 +136,9 @@ class Affinity_Propagate3d(nn.Module):
     """The 3D twin of Affinity_Propagate (same constructor, same forward): guidance [B,26,D,H,W] raw, blur_depth and sparse_depth
     [B,1,D,H,W] -- neighbour-sited gates divided by the abs-sum of the in-range ones, the (1 - sigma) H_0 centre term and the sparse pin over
     the 26-neighbourhood (F.cspn3d_forward with '8sum' / '8sum_abs'), differentiable w.r.t. guidance and blur_depth
-    (F.cspn3d_backward_norm); sparse_depth gets no gradient.  float16 / bfloat16 inputs are widened first; the result is float32."""
+    (F.cspn3d_backward_norm); sparse_depth gets no gradient.  A float16 / bfloat16 guidance (a head under torch.autocast) goes to the engine
+    as it is -- widened exactly where a kernel reads it, no float32 copy, its gradient in its dtype (cspn3d_forward_norm_g16 /
+    cspn3d_backward_norm_g16); a 16-bit blur_depth or sparse_depth is widened with a differentiable .float().  The result is float32."""
 
     def __init__(self, prop_time, prop_kernel=3, norm_type='8sum_abs'):
         super(Affinity_Propagate3d, self).__init__()
@@ -150,7 +153,7 @@ class Affinity_Propagate3d(nn.Module):
         n = self.prop_time if n_iter is None else int(n_iter)
         if n == 0:
             return blur_depth
-        guidance, blur_depth, sparse_depth = F.widen16(guidance, blur_depth, sparse_depth)
+        blur_depth, sparse_depth = F.widen16(blur_depth, sparse_depth)   # the guidance stays as it is: the 3D kernels read it in 16 bits
         return _CSPN3dNormFunction.apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo)
 
     def extra_repr(self):

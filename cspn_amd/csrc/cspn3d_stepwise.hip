@@ -13,8 +13,9 @@ __host__ __device__ constexpr int dz3(int k) { return 1 - ch3(k) / 9; }
 __host__ __device__ constexpr int dy3(int k) { return 1 - (ch3(k) / 3) % 3; }
 __host__ __device__ constexpr int dx3(int k) { return 1 - ch3(k) % 3; }
 
-// wf: [27][B*D*H*W] (26 folded weights + c').  GT: the gate storage type (cspn_gate16.h); a 16-bit gate comes here only with norm NONE and
-// no mask (a misaligned gate tensor of the Paddle contract), where folding is the exact widening
+// wf: [27][B*D*H*W] (26 folded weights + c').  GT: the gate storage type (cspn_gate16.h).  A 16-bit gate comes here in every mode: with
+// norm NONE and no mask (a misaligned gate tensor of the Paddle contract) folding is the exact widening; in the normalising and masked modes
+// (cspn3d_forward_norm_g16) each gate is widened where it is read and the sums, divisions and products are the float32 ones in the same order
 template <class GT>
 __global__ __launch_bounds__(256) void fold3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ feat,
                                                       const float* __restrict__ sparse, float* __restrict__ wf,
@@ -172,8 +173,9 @@ size_t forward3d_workspace(int B, int D, int H, int W, int n_iter, int norm, boo
 }
 
 // algo: 0 auto, 1 one launch per step, 2 persistent (gates resident across steps)
-// gdt: the gate storage type; CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 with norm NONE and no mask only (checked by the caller).  The dispatch is
-// the float32 one with the gate pointer's 16-byte condition at 8 bytes
+// gdt: the gate storage type (which modes take CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 is the entry point's decision: cspn3d_forward_g16_algo the
+// Paddle contract only, cspn3d_forward_norm_g16 every mode).  The dispatch is the float32 one with the gate pointer's 16-byte condition at 8
+// bytes; the folding path reads the gates element by element, so their alignment plays no part in it
 int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
                        int W, int n_iter, int norm, void* ws, hipStream_t st, int algo, int gdt) {
     const size_t total = (size_t)B * D * H * W;

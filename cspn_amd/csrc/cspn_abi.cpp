@@ -571,6 +571,13 @@ int cspn3d_forward_g16_algo(const void* gate, int gate_dtype, const float* feat,
     return forward3d_entry(gate, gate_dtype, feat, sparse, out, B, D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
 }
 
+// every mode on 16-bit guidance: the normalising and masked ones fold through fold3d_kernel<GT> (cspn3d_forward_g16_algo keeps its refusal)
+int cspn3d_forward_norm_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, float* out, int B, int D, int H,
+                            int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_forward_norm_g16", gate_dtype, guidance, nullptr)) return e;
+    return forward3d_entry(guidance, gate_dtype, feat, sparse, out, B, D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
+}
+
 int cspn3d_multi_supported(int B, int C, int D, int H, int W, int n_iter) {
     if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
     return persistent3d_multi_supported(B, C, D, H, W, n_iter) ? 1 : 0;
@@ -631,47 +638,73 @@ int cspn3d_backward_f32(const float* gate, const float* feat, const float* grad_
     return backward3d_entry(false, gate, 0, feat, grad_out, grad_gate, grad_feat, B, 1, D, H, W, n_iter, norm_type, ws, ws_bytes, stream);
 }
 
-// the normalising / masked modes (cspn3d_norm_backward.hip); NONE without a mask is cspn3d_backward_f32
-size_t cspn3d_backward_norm_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse) {
+// the normalising / masked modes (cspn3d_norm_backward.hip); NONE without a mask is cspn3d_backward_f32 / cspn3d_backward_g16.  gdt: the type
+// of guidance and grad_guidance (0: float32).  Everything in the workspace is float32, so the normalising and masked modes need the same
+// bytes for every type; the Paddle contract on 16-bit gates keeps backward3d()'s widened copy for the transposed sweep
+static size_t backward3d_norm_need(int B, int D, int H, int W, int n_iter, int norm_type, bool has_sparse, int gdt) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
     if (norm_type < CSPN_NORM_8SUM || norm_type > CSPN_NORM_NONE) return 0;
-    if (norm_type == CSPN_NORM_NONE && !has_sparse) return backward3d_workspace(B, D, H, W, n_iter);
+    if (norm_type == CSPN_NORM_NONE && !has_sparse) return backward3d_workspace(B, D, H, W, n_iter, 1, gdt);
     return backward3d_norm_workspace(B, D, H, W, n_iter);
 }
 
-int cspn3d_backward_norm_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out, float* grad_guidance,
-                             float* grad_feat, int B, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes,
-                             cspn_stream_t stream) {
+size_t cspn3d_backward_norm_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse) {
+    return backward3d_norm_need(B, D, H, W, n_iter, norm_type, has_sparse != 0, 0);
+}
+
+// the checks of cspn3d_backward_norm_f32 (gdt 0) and cspn3d_backward_norm_g16, then the engine
+static int backward3d_norm_entry(const char* what, const void* guidance, int gdt, const float* feat, const float* sparse, const float* grad_out,
+                                 void* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws,
+                                 size_t ws_bytes, cspn_stream_t stream) {
     if (int e = check_shape("BDHW", {B, D, H, W})) return e;
     if (B == 0) return 0;
     const size_t V = (size_t)B * D * H * W;
     if (int e = check_index32((long long)V, 27)) return e;
     if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
     if (norm_type < CSPN_NORM_8SUM || norm_type > CSPN_NORM_NONE) {
-        set_error("cspn3d_backward_norm_f32: norm_type must be CSPN_NORM_8SUM, CSPN_NORM_8SUM_ABS or CSPN_NORM_NONE (got %d)", norm_type);
+        set_error("%s: norm_type must be CSPN_NORM_8SUM, CSPN_NORM_8SUM_ABS or CSPN_NORM_NONE (got %d)", what, norm_type);
         return CSPN_E_BADARG;
     }
     if (int e = async_failure_of_earlier_call()) return e;
-    const size_t need = cspn3d_backward_norm_workspace_bytes(B, D, H, W, n_iter, norm_type, sparse != nullptr);
+    const size_t need = backward3d_norm_need(B, D, H, W, n_iter, norm_type, sparse != nullptr, gdt);
     if (int e = check_common(guidance, feat, grad_out, n_iter, norm_type, ws, ws_bytes, need)) return e;
-    const size_t vb = sizeof(float) * V, gb = 26 * vb;
+    const size_t vb = sizeof(float) * V, gb = 26 * V * gate_bytes(gdt);   // (the guidance and its gradient: in elements of their type)
     if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {feat, vb}, {sparse, vb}, {grad_out, vb}, {grad_feat, vb}, {ws, need}}) ||
         kxk_overlaps(grad_feat, vb, {{guidance, gb}, {feat, vb}, {sparse, vb}, {grad_out, vb}, {ws, need}})) {
-        set_error("cspn3d_backward_norm_f32: an output must not overlap an input, the other output or the workspace");
+        set_error("%s: an output must not overlap an input, the other output or the workspace", what);
         return CSPN_E_BADARG;
     }
     if (!grad_guidance && !grad_feat) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (n_iter == 0) return identity_backward(grad_feat, grad_out, V, grad_guidance, gb, st);
     if (algo == CSPN_ALGO3D_PERSISTENT &&
-        !backward3d_norm_fused(guidance, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, ws)) {
+        !backward3d_norm_fused(guidance, gdt, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, ws)) {
         set_error("persistent 3D kernel does not take this backward (needs W %% 4 == 0, 16-byte aligned tensors, 3 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;
     }
     const bool stepwise_only = algo == CSPN_ALGO3D_STEPWISE;
-    if (norm_type == CSPN_NORM_NONE && !sparse)   // the Paddle contract: AUTO is cspn3d_backward_f32
-        return backward3d(guidance, feat, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, ws, st, stepwise_only);
-    return backward3d_norm(guidance, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, norm_type, ws, st, stepwise_only);
+    if (norm_type == CSPN_NORM_NONE && !sparse)   // the Paddle contract: AUTO is cspn3d_backward_f32 / cspn3d_backward_g16
+        return backward3d(guidance, feat, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, ws, st, stepwise_only, 1, gdt);
+    return backward3d_norm(guidance, gdt, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, norm_type, ws, st, stepwise_only);
+}
+
+int cspn3d_backward_norm_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out, float* grad_guidance,
+                             float* grad_feat, int B, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes,
+                             cspn_stream_t stream) {
+    return backward3d_norm_entry("cspn3d_backward_norm_f32", guidance, 0, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter,
+                                 norm_type, algo, ws, ws_bytes, stream);
+}
+
+size_t cspn3d_backward_norm_g16_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse) {
+    return backward3d_norm_need(B, D, H, W, n_iter, norm_type, has_sparse != 0, CSPN_DTYPE_F16);
+}
+
+int cspn3d_backward_norm_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, const float* grad_out,
+                             void* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws,
+                             size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_backward_norm_g16", gate_dtype, guidance, grad_guidance)) return e;
+    return backward3d_norm_entry("cspn3d_backward_norm_g16", guidance, gate_dtype, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W,
+                                 n_iter, norm_type, algo, ws, ws_bytes, stream);
 }
 
 size_t cspn3d_backward_g16_workspace_bytes(int B, int D, int H, int W, int n_iter) {

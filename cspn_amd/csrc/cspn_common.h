@@ -41,8 +41,9 @@ size_t padded2d_workspace(int B, int H, int W, int n_iter);
 int padded2d_forward(const float* g, const float* blur, const float* sparse, float* out, int B, int H, int W, int n_iter, int norm, void* ws,
                      hipStream_t st);
 size_t stepwise3d_workspace(int B, int D, int H, int W, int n_iter);
-// gdt (here and below): the storage type of the gates, 0 float32 or CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 (Paddle contract only: norm NONE, no
-// mask); 16-bit gates are widened exactly where they are read (cspn_gate16.h), every value, level and workspace stays float32
+// gdt (here and below): the storage type of the gates, 0 float32 or CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 (stepwise3d_forward: every mode, the
+// normalising and masked ones through fold3d_kernel; the persistent entry points: the Paddle contract only, norm NONE and no mask); 16-bit
+// gates are widened exactly where they are read (cspn_gate16.h), every value, level and workspace stays float32
 int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
                        int W, int n_iter, int norm, void* ws, hipStream_t st, int algo = 0, int gdt = 0);
 // one step of the Paddle contract (W % 4 == 0, 16-byte aligned values, gates aligned to four elements)
@@ -133,12 +134,13 @@ int widen_gates(const void* g, int gdt, float* w, size_t n, hipStream_t st);
 
 // ---- backward of the 3D op in its normalising / masked modes (cspn3d_norm_backward.hip): norm 8SUM / 8SUM_ABS, or NONE with a mask; g raw
 // guidance [B][26][V], sparse NULL or [B][V]; gg and gf may each be NULL.  The adjoint sweep runs through the persistent kernel's transposed
-// instance where backward3d_norm_fused() holds and stepwise_only is false, every other launch is per step ----
+// instance where backward3d_norm_fused() holds and stepwise_only is false, every other launch is per step.  gdt: the storage type of g and gg
+// (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16; read where used, gg rounded once at its store); the workspace is float32 for every type ----
 size_t backward3d_norm_workspace(int B, int D, int H, int W, int n_iter);
-bool backward3d_norm_fused(const float* g, const float* feat, const float* sparse, const float* gout, const float* gg, const float* gf, int B, int D,
-                           int H, int W, int n_iter, const void* ws);
-int backward3d_norm(const float* g, const float* feat, const float* sparse, const float* gout, float* gg, float* gf, int B, int D, int H, int W,
-                    int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only);
+bool backward3d_norm_fused(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, const void* gg, const float* gf,
+                           int B, int D, int H, int W, int n_iter, const void* ws);
+int backward3d_norm(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, void* gg, float* gf, int B, int D, int H,
+                    int W, int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only);
 
 // ---- the producer of the path's inputs (cspn_head.hip): Unpool + 3x3 conv C -> 8 (guidance) and C -> 1 (blur) as one kernel; mode 0 raw guidance,
 // 1 / 2 gate_wb of '8sum' / '8sum_abs' (the normalisation fused behind the conv) ----

@@ -43,8 +43,8 @@ def _prep_value(t, name, shape=None):
 def widen16(*tensors):
     """float16 / bfloat16 tensors widened with a differentiable .float() (autograd carries the gradient back through the cast), everything
     else as it is: what the modules and mirrors do with value tensors, and in front of the paths that have no 16-bit kernel (3 x 3 in 2D: the
-    ring; the normalising / masked 3D modes; the gate_absnorm tensor op).  The 3D Paddle contract and the 3D demo module take a 16-bit gate or
-    guide as it is (cspn3d_*_g16)"""
+    ring; the gate_absnorm tensor op).  Every 3D path takes a 16-bit gate, guide or guidance as it is (cspn3d_*_g16): the Paddle contract, the
+    demo module, and the normalising / masked modes (cspn3d_forward_norm, cspn3d_backward_norm, Affinity_Propagate3d)"""
     out = tuple(t.float() if isinstance(t, torch.Tensor) and t.dtype in _GATE16 else t for t in tensors)
     return out[0] if len(out) == 1 else out
 
@@ -309,7 +309,7 @@ def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", alg
     (one launch per step) | 'persistent' (gates resident in registers across the steps; norm_type 'none' without a mask).
     With norm_type 'none' and no mask (the Paddle contract) gate may be float16 / bfloat16 (cspn3d_forward_g16_algo: widened exactly where
     it is read, out is float32 and bitwise the float32 call on gate.float() on the same path); a 16-bit feat is widened with one cast.  The
-    normalising and masked modes take float32 gates only."""
+    normalising and masked modes take float32 gates only here: cspn3d_forward_norm takes them in 16 bits."""
     if gate.dim() != 5 or gate.shape[1] != 26:
         raise ValueError("gate must be [B,26,D,H,W], got %s" % (tuple(gate.shape),))
     B, _, D, H, W = gate.shape
@@ -317,18 +317,42 @@ def cspn3d_forward(gate, feat, sparse=None, n_iter=12, norm_type="8sum_abs", alg
     g, dt = _prep_gate(gate, "gate") if paddle else (_prep(gate, "gate"), None)
     h = _prep_value(feat, "feat", (B, 1, D, H, W)) if paddle else _prep(feat, "feat", (B, 1, D, H, W))
     s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
+    out, ws = _forward3d("cspn3d_forward_f32_algo" if dt is None else "cspn3d_forward_g16_algo", "cspn3d_forward_f32" if dt is None else "cspn3d_forward_g16",
+                         g, dt, h, s, n_iter, norm_type, algo)
+    return (out, ws) if _return_ws and B else out
+
+
+def _forward3d(name, what, g, dt, h, s, n_iter, norm_type, algo):
+    """one 3D forward call on prepared tensors (g of gate_dtype dt, None: float32) -> (out, the workspace)"""
+    B, _, D, H, W = g.shape
     out = torch.empty_like(h)
     if B == 0:
-        return out
+        return out, None
     if g.data_ptr() % (16 if dt is None else 8) or any(t.data_ptr() % 16 for t in (h, out)):   # misaligned views take the folding path: the full workspace
         ws_query = ("cspn3d_workspace_bytes", B, D, H, W, int(n_iter))
     else:
         ws_query = ("cspn3d_workspace_bytes_ex", B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type], int(s is not None))
-    ws = _launch("cspn3d_forward_f32_algo" if dt is None else "cspn3d_forward_g16_algo", g.device,
+    ws = _launch(name, g.device,
                  (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(out), B, D, H, W, int(n_iter), _lib.NORM_TYPES[norm_type],
                   _lib.ALGOS_3D[algo]),
-                 ws_query, "cspn3d_forward_f32" if dt is None else "cspn3d_forward_g16")
-    return (out, ws) if _return_ws else out
+                 ws_query, what)
+    return out, ws
+
+
+def cspn3d_forward_norm(guidance, feat, sparse=None, n_iter=12, norm_type="8sum_abs", algo="auto"):
+    """cspn3d_forward on a guidance that may be float16 / bfloat16 in EVERY mode ('8sum', '8sum_abs', 'none' with or without a mask): what a
+    head under torch.autocast emits goes to the engine as it is (cspn3d_forward_norm_g16: each gate is widened exactly where the fold reads
+    it, no float32 copy is made); out is float32 and bitwise cspn3d_forward(guidance.float(), ...) with the same algo.  feat and sparse are
+    float32.  A float32 guidance is exactly cspn3d_forward."""
+    if guidance.dim() != 5 or guidance.shape[1] != 26:
+        raise ValueError("guidance must be [B,26,D,H,W], got %s" % (tuple(guidance.shape),))
+    B, _, D, H, W = guidance.shape
+    g, dt = _prep_gate(guidance, "guidance")
+    if dt is None:
+        return cspn3d_forward(guidance, feat, sparse, n_iter, norm_type, algo)
+    h = _prep(feat, "feat", (B, 1, D, H, W))
+    s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
+    return _forward3d("cspn3d_forward_norm_g16", "cspn3d_forward_norm_g16", g, dt, h, s, n_iter, norm_type, algo)[0]
 
 
 def cspn3d_forward_multi(gate, feat, n_iter=12):
@@ -404,11 +428,13 @@ def cspn3d_backward_norm(guidance, feat, sparse, grad_out, n_iter=12, norm_type=
     """Gradient of cspn3d_forward(guidance, feat, sparse, n_iter, norm_type) in its normalising / masked modes ('8sum', '8sum_abs', or
     'none' with a mask; 'none' without one is cspn3d_backward) w.r.t. the raw guidance and feat, in the HIP engine
     (cspn3d_backward_norm_f32: the fold is recomputed, one launch per step).  sparse gets no gradient (only its sign is used).
-    -> (grad_guidance [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None).  float32 only."""
+    -> (grad_guidance [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None).  A float16 / bfloat16 guidance goes to the engine as it is
+    (cspn3d_backward_norm_g16: read where it is used, no float32 copy of it or of its gradient): grad_feat is float32 and bitwise the float32
+    call's on guidance.float(), grad_guidance comes back in the guidance's dtype, the float32 value rounded once.  The other tensors are float32."""
     if guidance.dim() != 5 or guidance.shape[1] != 26:
         raise ValueError("guidance must be [B,26,D,H,W], got %s" % (tuple(guidance.shape),))
     B, _, D, H, W = guidance.shape
-    g = _prep(guidance, "guidance")
+    g, dt = _prep_gate(guidance, "guidance")
     h = _prep(feat, "feat", (B, 1, D, H, W))
     s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
     go = _prep(grad_out, "grad_out", (B, 1, D, H, W))
@@ -419,9 +445,9 @@ def cspn3d_backward_norm(guidance, feat, sparse, grad_out, n_iter=12, norm_type=
     if B == 0 or not (need_guidance or need_feat):
         return gg, gf
     norm = _lib.NORM_TYPES[norm_type]
-    _launch("cspn3d_backward_norm_f32", g.device,
-            (_ptr(g), _ptr(h), _ptr(s), _ptr(go), _ptr(gg), _ptr(gf), B, D, H, W, int(n_iter), norm, _lib.ALGOS_3D[algo]),
-            ("cspn3d_backward_norm_workspace_bytes", B, D, H, W, int(n_iter), norm, int(s is not None)))
+    _launch("cspn3d_backward_norm_f32" if dt is None else "cspn3d_backward_norm_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(go), _ptr(gg), _ptr(gf), B, D, H, W, int(n_iter), norm, _lib.ALGOS_3D[algo]),
+            ("cspn3d_backward_norm%s_workspace_bytes" % ("" if dt is None else "_g16"), B, D, H, W, int(n_iter), norm, int(s is not None)))
     return gg, gf
 
 

@@ -251,7 +251,8 @@ int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float*
  *   returns CSPN_E_UNSUPPORTED where AUTO would not use that instance.  Any B, D, H, W >= 1 and 4-byte aligned pointers; 16-byte loads and
  *   stores where W % 4 == 0 and every pointer is 16-byte aligned.  n_iter = 0: grad_feat = grad_out, grad_guidance = 0.  An output that overlaps an input,
  *   the other output or the workspace: CSPN_E_BADARG; a workspace smaller than cspn3d_backward_norm_workspace_bytes() or not 256-byte
- *   aligned: CSPN_E_WORKSPACE; the query returns 0 for an invalid shape or norm_type.  Float32 and one channel only. */
+ *   aligned: CSPN_E_WORKSPACE; the query returns 0 for an invalid shape or norm_type.  One channel only; float16 / bfloat16 guidance:
+ *   cspn3d_backward_norm_g16 below. */
 size_t cspn3d_backward_norm_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
 int cspn3d_backward_norm_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out,
                              float* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter,
@@ -299,7 +300,7 @@ int cspn3d_forward_absnorm_f32(const float* guide, const float* feat, float* out
  * All checks and return codes of the _f32 twins apply, gate ranges counted in 2-byte elements; any other gate_dtype or an odd address
  * of a 16-bit tensor: CSPN_E_BADARG.
  * cspn3d_forward_g16_algo: cspn3d_forward_f32_algo with norm_type CSPN_NORM_NONE and sparse NULL -- anything else CSPN_E_BADARG (the
- *   normalising and masked modes take float32 gates only).  Workspace: cspn3d_workspace_bytes_ex / cspn3d_workspace_bytes as the twin.
+ *   normalising and masked modes on 16-bit guidance have their own entry point, cspn3d_forward_norm_g16 below).  Workspace: cspn3d_workspace_bytes_ex / cspn3d_workspace_bytes as the twin.
  * cspn3d_forward_multi_g16, cspn3d_backward_g16, cspn3d_backward_multi_g16: as their twins; workspaces of the backward:
  *   cspn3d_backward_g16_workspace_bytes / cspn3d_backward_multi_g16_workspace_bytes (the same for both 16-bit types).
  * cspn3d_forward_absnorm_g16: guide RAW in 16 bits; the unfused route normalises into float32 gates in the workspace
@@ -324,6 +325,31 @@ int cspn3d_backward_multi_g16(const void* gate, int gate_dtype, const float* fea
 int cspn_gate_absnorm_g16(const void* guide, int gate_dtype, float* gate, int N, int K, size_t V, cspn_stream_t stream);
 int cspn_gate_absnorm_backward_g16(const void* guide, int gate_dtype, const float* grad_gate, void* grad_guide, int N, int K, size_t V,
                                    cspn_stream_t stream);
+
+/* ---- the 3D depth-completion contract (normalising and masked modes) on 16-bit guidance: the same exact-widening contract as above.
+ * guidance and grad_guidance are of gate_dtype; feat, sparse, out, grad_out, grad_feat, w', c', coef, dG, every level and the workspace
+ * stay float32.  No float32 copy of the guidance or of its gradient is made.
+ * cspn3d_forward_norm_g16: cspn3d_forward_f32_algo in EVERY mode (CSPN_NORM_8SUM, CSPN_NORM_8SUM_ABS, CSPN_NORM_NONE with or without a
+ *   mask) on 16-bit guidance; out is bitwise the twin's on the widened guidance.  The fold reads each gate where it uses it; the steps are
+ *   the twin's (persistent kernel on the folded planes, or per step).  CSPN_NORM_NONE with sparse NULL is cspn3d_forward_g16_algo.
+ *   Workspace: cspn3d_workspace_bytes_ex / cspn3d_workspace_bytes as the twin (guidance aligned to 8 bytes where the twin wants 16).
+ * cspn3d_backward_norm_g16: cspn3d_backward_norm_f32's checks in its order, the guidance's and grad_guidance's ranges counted in 2-byte
+ *   elements.  grad_feat is bitwise the twin's on the widened guidance; grad_guidance is the twin's float32 value rounded once, to nearest
+ *   even, at its single store (NaN where the twin has NaN, zero where no voxel reads the gate), no atomics.  The fold, the gate-gradient
+ *   epilogue and the gather read the 16-bit guidance directly (8-byte loads of four gates, at 2-byte alignment for the neighbour-sited
+ *   reads); the vector kernels need W % 4 == 0, guidance and grad_guidance 8-byte aligned and every float32 tensor 16-byte aligned, the
+ *   same condition decides CSPN_ALGO3D_PERSISTENT.  The adjoint sweep runs on the float32 w' as in the twin.
+ *   CSPN_NORM_NONE with sparse NULL is cspn3d_backward_g16 (bitwise; algo STEPWISE: its per-step kernels).
+ * cspn3d_backward_norm_g16_workspace_bytes: in the normalising and masked modes exactly cspn3d_backward_norm_workspace_bytes (everything
+ *   in the workspace is float32); for CSPN_NORM_NONE with has_sparse 0 it is cspn3d_backward_g16_workspace_bytes, which keeps the
+ *   widened copy the transposed sweep of the Paddle contract reads.  The same for both 16-bit types. */
+int cspn3d_forward_norm_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, float* out,
+                            int B, int D, int H, int W, int n_iter, int norm_type, int algo,
+                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn3d_backward_norm_g16_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
+int cspn3d_backward_norm_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, const float* grad_out,
+                             void* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter,
+                             int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- 2D over a K x K neighbourhood, K = 2R+1 in {5, 7}: fluid.layers.affinity_propagate(input, gate_weight, kernel_size) with
  * kernel_size 5 or 7, the NONE contract (gates used as given, centre-sited, no centre term, any sign; reference cspn_paddle/README.md:54-56).
