@@ -13,36 +13,11 @@
 // each, like a forward step), and ONE gate-gradient pass that reads the 2n value volumes and writes the 26 planes once
 // (26 x 4 accumulators per thread).  A single chained call (n = 1, how the Paddle graph uses the op) therefore moves
 // 28 + 28 planes: the adjoint step and the gate-gradient pass, nothing else.
-#include <cstdlib>
-
-#include "cspn_common.h"
-#include "cspn_gate16.h"
+#include "cspn3d_voxel.h"
 
 namespace cspn {
 
 namespace {
-
-__host__ __device__ constexpr int ch3(int k) { return k < 13 ? k : k + 1; }  // skip the centre (index 13)
-
-// voxel index -> (b, z, y, x) of a thread's VEC consecutive voxels
-template <int VEC>
-struct Pos {
-    int b, z, y, x;
-    size_t r;   // offset inside the volume
-    bool ok;
-    __device__ Pos(int B, int D, int H, int W) {
-        const size_t HW = (size_t)H * W, V = (size_t)D * HW, n = (size_t)B * V / VEC;
-        const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-        ok = i < n;
-        const size_t idx = (ok ? i : 0) * VEC;
-        b = (int)(idx / V);
-        r = idx - (size_t)b * V;
-        z = (int)(r / HW);
-        const int r2 = (int)(r - (size_t)z * HW);
-        y = r2 / W;
-        x = r2 - y * W;
-    }
-};
 
 // one adjoint step: aout(q) = sum_k g_k(q - off_k) ain(q - off_k); VEC = 4 (W % 4 == 0, 16-byte aligned tensors) or 1
 // fbs: floats from one volume of ain / aout to the next (V, or C V when the call's C value channels share the gates: the caller
@@ -61,25 +36,11 @@ __global__ __launch_bounds__(256) void adjoint3d_kernel(const store_t<GT>* __res
     for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
 #pragma unroll
     for (int n = 0; n < 9; ++n) {   // source rows (z - dz, y - dy)
-        const int dz = 1 - n / 3, dy = 1 - n % 3;
-        const int zz = p.z - dz, yy = p.y - dy;
-        if (zz < 0 || zz >= D || yy < 0 || yy >= H) continue;
-        const size_t ro = ((size_t)zz * H + yy) * W;
+        const int dz = row_dz3(n), dy = row_dy3(n);
         float a[VEC + 2];   // ain at columns x-1 .. x+VEC of the source row
-        if (VEC == 4) {
-            const float4 c = *reinterpret_cast<const float4*>(ab + ro + p.x);
-            a[1] = c.x; a[2] = c.y; a[3] = c.z; a[4] = c.w;
-        } else {
-            a[1] = ab[ro + p.x];
-        }
-        a[0] = p.x > 0 ? ab[ro + p.x - 1] : 0.f;
-        a[VEC + 1] = p.x + VEC < W ? ab[ro + p.x + VEC] : 0.f;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {   // dx = 1 - t: the source voxel of column x + i is x + i - dx
-            const int c27 = n * 3 + t;
-            if (c27 == 13) continue;
-            const int k = c27 < 13 ? c27 : c27 - 1;
-            const int dx = 1 - t;
+        if (!load_row3<VEC>(ab, p, -dz, -dy, D, H, W, a)) continue;   // (a row outside the volume has no gates to read either)
+        const size_t ro = ((size_t)(p.z - dz) * H + (p.y - dy)) * W;
+        for_taps3(n, [&](int k, int dx) {   // the source voxel of column x + i is x + i - dx
             const store_t<GT>* gp = gb + (size_t)k * V + ro + p.x - dx;
             float w[VEC];
             if (VEC == 4 && p.x - dx >= 0 && p.x - dx + 3 < W) {
@@ -94,11 +55,9 @@ __global__ __launch_bounds__(256) void adjoint3d_kernel(const store_t<GT>* __res
             }
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w[i], a[1 + i - dx], acc[i]);
-        }
+        });
     }
-    float* o = aout + (size_t)p.b * fbs + p.r;
-    if (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    else o[0] = acc[0];
+    store_vec<VEC>(aout + (size_t)p.b * fbs + p.r, acc);
 }
 
 // dL/dg_k(p) = sum_c sum_t A^c_{t+1}(p) H^c_t(p + off_k) over the C value channels that share the gates (reference
@@ -124,40 +83,8 @@ __global__ __launch_bounds__(256) void gate_grad3d_kernel(const float* __restric
         const float* ht = (t == 0 ? feat : hist + (size_t)(t - 1) * total) + vol;
         const float* at = t == n_iter - 1 ? gout : ahist + (size_t)t * total;   // A_{t+1}
         float a[VEC];
-        if (VEC == 4) {
-            const float4 q = *reinterpret_cast<const float4*>(at + vox);
-            a[0] = q.x; a[1] = q.y; a[2] = q.z; a[3] = q.w;
-        } else {
-            a[0] = at[vox];
-        }
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {   // neighbour rows (z + dz, y + dy)
-            const int dz = 1 - n / 3, dy = 1 - n % 3;
-            const int zz = p.z + dz, yy = p.y + dy;
-            float h[VEC + 2];
-#pragma unroll
-            for (int i = 0; i < VEC + 2; ++i) h[i] = 0.f;
-            if (zz >= 0 && zz < D && yy >= 0 && yy < H) {
-                const float* row = ht + ((size_t)zz * H + yy) * W;
-                if (VEC == 4) {
-                    const float4 c = *reinterpret_cast<const float4*>(row + p.x);
-                    h[1] = c.x; h[2] = c.y; h[3] = c.z; h[4] = c.w;
-                } else {
-                    h[1] = row[p.x];
-                }
-                if (p.x > 0) h[0] = row[p.x - 1];
-                if (p.x + VEC < W) h[VEC + 1] = row[p.x + VEC];
-            }
-#pragma unroll
-            for (int t3 = 0; t3 < 3; ++t3) {
-                const int c27 = n * 3 + t3;
-                if (c27 == 13) continue;
-                const int k = c27 < 13 ? c27 : c27 - 1;
-                const int dx = 1 - t3;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc[k][i] = fmaf(a[i], h[1 + i + dx], acc[k][i]);
-            }
-        }
+        load_vec<VEC>(at + vox, a);
+        gate_grad_level3<VEC>(acc, a, ht, p, D, H, W);
     }
     store_t<GT>* o = gg + (size_t)p.b * 26 * V + p.r;
 #pragma unroll
@@ -165,26 +92,6 @@ __global__ __launch_bounds__(256) void gate_grad3d_kernel(const float* __restric
         if (VEC == 4) st4g<GT>(o + (size_t)k * V, acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
         else o[(size_t)k * V] = narrow<GT>(acc[k][0]);
     }
-}
-
-// forward step for shapes / alignments the 16-byte kernel of cspn3d_stepwise.hip does not take
-template <class GT>
-__global__ __launch_bounds__(256) void step3d_scalar_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ hin,
-                                                             float* __restrict__ hout, int B, int D, int H, int W, size_t fbs) {
-    const Pos<1> p(B, D, H, W);
-    if (!p.ok) return;
-    const size_t HW = (size_t)H * W, V = (size_t)D * HW;
-    const float* hb = hin + (size_t)p.b * fbs;
-    const store_t<GT>* gb = g + (size_t)p.b * 26 * V + p.r;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 26; ++k) {
-        const int c = ch3(k);
-        const int zz = p.z + 1 - c / 9, yy = p.y + 1 - (c / 3) % 3, xx = p.x + 1 - c % 3;
-        if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W)
-            acc = fmaf(widen<GT>(gb[(size_t)k * V]), hb[((size_t)zz * H + yy) * W + xx], acc);
-    }
-    hout[(size_t)p.b * fbs + p.r] = acc;
 }
 
 // the exact widening of a 16-bit gate tensor into float32, streaming: what the transposed persistent instance (ADJ) reads, since its
@@ -208,14 +115,6 @@ int widen_gates(const void* g, int gdt, float* w, size_t n, hipStream_t st) {
     return check_launch("widen_gates_kernel");
 }
 
-// levels kept: H_1 .. H_{n-1} and A_1 .. A_{n-1} (A_0 goes to grad_feat, or to one more volume when the caller does not want
-// it), each level B C volumes laid out like feat ([B][C][V]); then the workspace of the persistent kernel (fused sweeps, n >= 3)
-static size_t levels_bytes(int B, int D, int H, int W, int n_iter, int C) {
-    const size_t total = (size_t)B * C * D * H * W;
-    const size_t b = (2 * (size_t)(n_iter > 0 ? n_iter - 1 : 0) + 1) * total * sizeof(float);
-    return (b + 255) & ~(size_t)255;
-}
-
 // the fused sweeps' conditions on the shape (the pointers' alignment is the call's)
 static bool fused3d_shape(int B, int C, int D, int H, int W, int n_iter) {
     return (W % 4) == 0 && n_iter >= 3 &&
@@ -223,11 +122,24 @@ static bool fused3d_shape(int B, int C, int D, int H, int W, int n_iter) {
                    : persistent3d_multi_supported(B, C, D, H, W, n_iter - 1) && persistent3d_multi_supported(B, C, D, H, W, n_iter));
 }
 
-// gdt != 0 (16-bit gates): where the fused sweeps can take the call, the float32 copy of the gates the transposed sweep reads follows
-size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C, int gdt) {
-    const size_t base = levels_bytes(B, D, H, W, n_iter, C) + persistent3d_workspace(B, D, H, W);
-    return gdt && fused3d_shape(B, C, D, H, W, n_iter) ? round256(base) + round256(26 * sizeof(float) * (size_t)B * D * H * W) : base;
+// levels kept: H_1 .. H_{n-1} and A_1 .. A_{n-1} (A_0 goes to grad_feat, or to one more volume when the caller does not want it); then the
+// workspace of the persistent kernel (fused sweeps, n >= 3); gdt != 0 (16-bit gates): where the fused sweeps can take the call, the float32
+// copy of the gates the transposed sweep reads follows
+Backward3dLayout::Backward3dLayout(int B, int C, int D, int H, int W, int n_iter, int gdt) {
+    const size_t level = sizeof(float) * (size_t)B * C * D * H * W, kept = n_iter > 0 ? n_iter - 1 : 0;
+    hist = 0;
+    ahist = kept * level;
+    a0 = 2 * kept * level;
+    pers = round256(a0 + level);
+    bytes = pers + persistent3d_workspace(B, D, H, W);
+    wide = 0;
+    if (gdt && fused3d_shape(B, C, D, H, W, n_iter)) {
+        wide = round256(bytes);
+        bytes = wide + round256(26 * sizeof(float) * (size_t)B * D * H * W);
+    }
 }
+
+size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C, int gdt) { return Backward3dLayout(B, C, D, H, W, n_iter, gdt).bytes; }
 
 // C > 1 (round 5; reference cspn_paddle/README.md:56, trained through at demo.py:65-75): feat / gout / gf hold C value channels per
 // volume on shared gates, gg is the gate gradient summed over the channels.  Fused sweeps: ONE level-keeping forward launch and ONE
@@ -239,77 +151,67 @@ size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C, int g
 int backward3d(const void* g, const float* feat, const float* gout, void* gg, float* gf, int B, int D, int H, int W,
                int n_iter, void* ws, hipStream_t st, bool stepwise_only, int C, int gdt) {
     const size_t V = (size_t)D * H * W, total = (size_t)B * C * V, fbs = (size_t)C * V;
-    float* hist = (float*)ws;                                  // H_1 .. H_{n-1}
-    float* ahist = hist + (size_t)(n_iter - 1) * total;        // A_1 .. A_{n-1}
-    float* a0 = gf ? gf : ahist + (size_t)(n_iter - 1) * total;
-    const bool vec = (W % 4) == 0 && ((((uintptr_t)g | (uintptr_t)gg) & gate_quad_mask(gdt)) == 0) &&
-                     ((((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gf | (uintptr_t)ws) & 15u) == 0);
-    const unsigned blocks = (unsigned)(((size_t)B * V / (vec ? 4 : 1) + 255) / 256);   // threads cover ONE channel's B volumes
-    const unsigned blocks1 = (unsigned)(((size_t)B * V + 255) / 256);
+    const Backward3dLayout L(B, C, D, H, W, n_iter, gdt);
+    float* hist = (float*)((char*)ws + L.hist);     // H_1 .. H_{n-1}
+    float* ahist = (float*)((char*)ws + L.ahist);   // A_1 .. A_{n-1}
+    float* a0 = gf ? gf : (float*)((char*)ws + L.a0);
+    void* pws = (char*)ws + L.pers;
+    const bool vec = quads_ok(W, gdt, {g, gg}, {feat, gout, gf, ws});
+    const dim3 grid((unsigned)(((size_t)B * V / (vec ? 4 : 1) + 255) / 256)), block(256);   // threads cover ONE channel's B volumes
     // fused sweeps: the persistent kernel (gates read once per sweep, resident in registers across the steps) in its
     // level-keeping and transposed variants -- forward H_1 .. H_{n-1} (n - 1 steps, the last one "out" = H_{n-1}), adjoint
     // A_{n-1} .. A_0 (n steps).  One launch per step otherwise.
-    void* pws = (char*)ws + levels_bytes(B, D, H, W, n_iter, C);
-    const bool fused = vec && !stepwise_only && fused3d_shape(B, C, D, H, W, n_iter);
+    const bool fused = vec && !stepwise_only && (gdt ? L.wide != 0 : fused3d_shape(B, C, D, H, W, n_iter));   // (the layout has asked already)
+    if (fused) {
+        if (gg)
+            if (int e = persistent3d_run(g, feat, hist + (size_t)(n_iter - 2) * total, hist, -1, 1, false, B, D, H, W, n_iter - 1, pws, st, P3Options(), C, gdt))
+                return e;
+        // step it of the adjoint run produces A_{n-it}: volume n - it - 1 of ahist; the last one (A_0) is its "out"
+        if (gf || gg) {
+            const void* ga = g;
+            if (gdt) {
+                float* wide = (float*)((char*)ws + L.wide);
+                if (int e = widen_gates(g, gdt, wide, 26 * (size_t)B * V, st)) return e;
+                ga = wide;
+            }
+            if (int e = persistent3d_run(ga, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st, P3Options(), C)) return e;
+        }
+    }
     return with_gate_type(gdt, [&](auto gt) -> int {
         using GT = typename decltype(gt)::type;
-        const store_t<GT>* gs = (const store_t<GT>*)g;
-        store_t<GT>* ggs = (store_t<GT>*)gg;
-        if (fused) {
-            if (gg)
-                if (int e = persistent3d_run(g, feat, hist + (size_t)(n_iter - 2) * total, hist, -1, 1, false, B, D, H, W, n_iter - 1, pws, st, P3Options(), C, gdt))
-                    return e;
-            // step it of the adjoint run produces A_{n-it}: volume n - it - 1 of ahist; the last one (A_0) is its "out"
-            if (gf || gg) {
-                const void* ga = g;
-                if (gdt) {
-                    float* wide = (float*)((char*)ws + round256(levels_bytes(B, D, H, W, n_iter, C) + persistent3d_workspace(B, D, H, W)));
-                    if (int e = widen_gates(g, gdt, wide, 26 * (size_t)B * V, st)) return e;
-                    ga = wide;
+        return with_vec(vec, [&](auto v) -> int {
+            constexpr int VEC = decltype(v)::value;
+            const store_t<GT>* gs = (const store_t<GT>*)g;
+            if (!fused)   // one launch per step and channel where the sweeps above did not run
+                for (int c = 0; c < C; ++c) {
+                    const size_t co = (size_t)c * V;
+                    if (gg) {   // the value levels the gate gradient multiplies with
+                        const float* src = feat + co;
+                        for (int t = 1; t < n_iter; ++t) {
+                            float* dst = hist + (size_t)(t - 1) * total + co;
+                            if (int e = vec && C == 1 ? step3d_direct(g, gdt, src, dst, B, D, H, W, st) : step3d_scalar(g, gdt, src, dst, B, D, H, W, fbs, st))
+                                return e;
+                            src = dst;
+                        }
+                        if (int e = check_launch("3D forward levels")) return e;
+                    }
+                    // adjoint levels A_{n-1} .. A_1 (kept only if the gate gradient needs them: otherwise two volumes would do, but the
+                    // workspace is sized for the general call) and A_0
+                    const float* src = gout + co;
+                    for (int t = n_iter - 1; t >= 0; --t) {
+                        float* dst = (t == 0 ? a0 : ahist + (size_t)(t - 1) * total) + co;
+                        if (t == 0 && !gf) break;   // A_0 is only the feature gradient
+                        hipLaunchKernelGGL((adjoint3d_kernel<VEC, GT>), grid, block, 0, st, gs, src, dst, B, D, H, W, fbs);
+                        src = dst;
+                    }
+                    if (int e = check_launch("adjoint3d_kernel")) return e;
                 }
-                if (int e = persistent3d_run(ga, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st, P3Options(), C)) return e;
-            }
             if (gg) {
-                hipLaunchKernelGGL((gate_grad3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
+                hipLaunchKernelGGL((gate_grad3d_kernel<VEC, GT>), grid, block, 0, st, feat, hist, ahist, gout, (store_t<GT>*)gg, B, D, H, W, n_iter, C);
                 if (int e = check_launch("gate_grad3d_kernel")) return e;
             }
             return 0;
-        }
-        for (int c = 0; c < C; ++c) {
-            const size_t co = (size_t)c * V;
-            if (gg) {   // the value levels the gate gradient multiplies with
-                const float* src = feat + co;
-                for (int t = 1; t < n_iter; ++t) {
-                    float* dst = hist + (size_t)(t - 1) * total + co;
-                    if (vec && C == 1) {
-                        if (int e = step3d_direct(g, gdt, src, dst, B, D, H, W, st)) return e;
-                    } else {
-                        hipLaunchKernelGGL(step3d_scalar_kernel<GT>, dim3(blocks1), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
-                    }
-                    src = dst;
-                }
-                if (int e = check_launch("3D forward levels")) return e;
-            }
-            // adjoint levels A_{n-1} .. A_1 (kept only if the gate gradient needs them: otherwise two volumes would do, but the
-            // workspace is sized for the general call) and A_0
-            const float* src = gout + co;
-            for (int t = n_iter - 1; t >= 0; --t) {
-                float* dst = (t == 0 ? a0 : ahist + (size_t)(t - 1) * total) + co;
-                if (t == 0 && !gf) break;   // A_0 is only the feature gradient
-                if (vec) hipLaunchKernelGGL((adjoint3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
-                else hipLaunchKernelGGL((adjoint3d_kernel<1, GT>), dim3(blocks), dim3(256), 0, st, gs, src, dst, B, D, H, W, fbs);
-                src = dst;
-            }
-            if (int e = check_launch("adjoint3d_kernel")) return e;
-        }
-        if (gg) {
-            if (vec)
-                hipLaunchKernelGGL((gate_grad3d_kernel<4, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
-            else
-                hipLaunchKernelGGL((gate_grad3d_kernel<1, GT>), dim3(blocks), dim3(256), 0, st, feat, hist, ahist, gout, ggs, B, D, H, W, n_iter, C);
-            if (int e = check_launch("gate_grad3d_kernel")) return e;
-        }
-        return 0;
+        });
     });
 }
 

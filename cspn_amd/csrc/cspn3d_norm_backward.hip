@@ -1,5 +1,6 @@
 // cspn3d_norm_backward.hip -- backward of the 3x3x3 propagation in its normalising / masked modes: the 3D form of the
-// depth-completion contract (the forward is fold3d_kernel + step3d_kernel of cspn3d_stepwise.hip).
+// depth-completion contract (the forward is fold3d_kernel + step3d_kernel of cspn3d_stepwise.hip).  The voxel helpers
+// (Pos, the vector loads and stores, load_G, gate_grad_level3, quads_ok, with_vec): cspn3d_voxel.h.
 //
 //   forward   off_k = (dz3, dy3, dx3)(k),  g~ = |g| (8SUM_ABS) or g,  zero outside the volume
 //             G_k(p) = g~_k(p + off_k)                 (NONE: G_k(p) = g_k(p), S = 1, no centre term)
@@ -15,7 +16,8 @@
 //
 // Launches, all HBM-bound streaming, no atomics, every output element written once:
 //   1. fold_norm3d_kernel: w' as a gate tensor [B][26][V] + the planes c' and coef, into the workspace
-//   2. step_const3d_kernel x (n - 1): H_1 .. H_{n-1} (27 planes + H in, H out), only when grad_guidance is wanted
+//   2. the forward step with the constant term x (n - 1): H_1 .. H_{n-1} (27 planes + H in, H out), only when grad_guidance is wanted; the
+//      kernels are cspn3d_stepwise.hip's: step3d_direct_kernel<float, true> on w' (four voxels a thread), else step3d_kernel
 //   3. the n adjoint steps on w', read as the gates of the Paddle contract, keeping A_1 .. A_{n-1}, A_0 in the workspace: ONE launch of
 //      the persistent kernel's transposed instance where it takes the call (W % 4 == 0, 16-byte aligned tensors, 3 <= n_iter <= 60, the
 //      volume resident on the device: as backward3d()'s fused sweeps), else backward3d() of cspn3d_backward.hip, one launch per step
@@ -26,128 +28,12 @@
 // GT is the storage type of guidance and grad_guidance (cspn_gate16.h): float, or __half / __hip_bfloat16 (cspn3d_backward_norm_g16).  The three
 // kernels that touch the guidance read a 16-bit gate where they use it, widened exactly, and grad_guidance is the float32 value rounded once at
 // its single store; w', c', coef, dG, every level and every sum stay float32, so grad_feat is bitwise the float32 call's on the widened guidance
-// and grad_guidance that call's converted to the type.  step_const3d_kernel and the adjoint sweep never see the guidance.
-#include <initializer_list>
-
-#include "cspn_common.h"
-#include "cspn_gate16.h"
+// and grad_guidance that call's converted to the type.  The forward steps on w' and the adjoint sweep never see the guidance.
+#include "cspn3d_voxel.h"
 
 namespace cspn {
 
 namespace {
-
-__host__ __device__ constexpr int ch3(int k) { return k < 13 ? k : k + 1; }  // skip the centre (index 13)
-__host__ __device__ constexpr int dz3(int k) { return 1 - ch3(k) / 9; }
-__host__ __device__ constexpr int dy3(int k) { return 1 - (ch3(k) / 3) % 3; }
-__host__ __device__ constexpr int dx3(int k) { return 1 - ch3(k) % 3; }
-
-// voxel index -> (b, z, y, x) of a thread's VEC consecutive voxels (VEC = 4: W % 4 == 0, so they share a row)
-template <int VEC>
-struct Pos {
-    int b, z, y, x;
-    size_t r;   // offset inside the volume
-    bool ok;
-    __device__ Pos(int B, int D, int H, int W) {
-        const size_t HW = (size_t)H * W, V = (size_t)D * HW, n = (size_t)B * V / VEC;
-        const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-        ok = i < n;
-        const size_t idx = (ok ? i : 0) * VEC;
-        b = (int)(idx / V);
-        r = idx - (size_t)b * V;
-        z = (int)(r / HW);
-        const int r2 = (int)(r - (size_t)z * HW);
-        y = r2 / W;
-        x = r2 - y * W;
-    }
-};
-
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float* p, float* v) {
-    if (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_vec(float* p, const float* v) {
-    if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-
-// the thread's VEC consecutive elements of a guidance-typed plane, widened / narrowed: one 16-byte (float) or 8-byte (16-bit) access
-template <int VEC, class GT>
-__device__ __forceinline__ void load_gvec(const store_t<GT>* p, float* v) {
-    if (VEC == 4) {
-        const float4 q = ld4g<GT>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = widen<GT>(p[0]);
-    }
-}
-
-// narrow<GT>() of a value that a float multiply has just produced.  Left to itself the compiler folds that multiply into the float16
-// conversion behind it (v_fma_mixlo_f16 a, b, +0), and (-0) + (+0) = +0: a product of -0 -- a negative dW' of a pinned voxel, a dG of zero
-// times sign(g) = -1 -- would lose the sign the float32 engine stores.  The conversion as an instruction of its own keeps it; bfloat16 is
-// rounded with integer operations, which nothing folds
-template <class GT>
-__device__ __forceinline__ store_t<GT> narrow_product(float v) {
-    if constexpr (std::is_same<GT, __half>::value) {
-        uint32_t h;
-        asm("v_cvt_f16_f32 %0, %1" : "=v"(h) : "v"(v));
-        return (unsigned short)h;
-    } else {
-        return narrow<GT>(v);
-    }
-}
-
-template <int VEC, class GT>
-__device__ __forceinline__ void store_gvec(store_t<GT>* p, const float* v) {
-    if constexpr (std::is_same<GT, float>::value) {
-        if (VEC == 4) st4g<GT>(p, v[0], v[1], v[2], v[3]);
-        else p[0] = v[0];
-    } else if (VEC == 4) {
-        *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)narrow_product<GT>(v[0]) | ((uint32_t)narrow_product<GT>(v[1]) << 16),
-                                                  (uint32_t)narrow_product<GT>(v[2]) | ((uint32_t)narrow_product<GT>(v[3]) << 16));
-    } else {
-        p[0] = narrow_product<GT>(v[0]);
-    }
-}
-
-// v[i] = plane(z + dz, y + dy, x + i + dx) of one volume, zero outside it: a 16-byte load at 4-byte alignment (16-bit planes: an 8-byte
-// load at 2-byte alignment) where the quad lies inside the row
-template <int VEC, class GT>
-__device__ __forceinline__ void load_shifted(const store_t<GT>* plane, const Pos<VEC>& p, int dz, int dy, int dx, int D, int H, int W, float* v) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = 0.f;
-    const int zz = p.z + dz, yy = p.y + dy, xs = p.x + dx;
-    if (zz < 0 || zz >= D || yy < 0 || yy >= H) return;
-    const store_t<GT>* row = plane + ((size_t)zz * H + yy) * W;
-    if (VEC == 4 && xs >= 0 && xs + 3 < W) {
-        const float4 q = ld4gu<GT>(row + xs);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i)
-            if (xs + i >= 0 && xs + i < W) v[i] = widen<GT>(row[xs + i]);
-    }
-}
-
-// G_k at the thread's voxels: the raw gate of plane k where the norm uses it (at the neighbour; NONE: at the voxel itself)
-template <int VEC, class GT>
-__device__ __forceinline__ void load_G(const store_t<GT>* gb, size_t V, int k, const Pos<VEC>& p, int D, int H, int W, int norm, float* G) {
-    if (norm == CSPN_NORM_NONE) {
-        load_gvec<VEC, GT>(gb + (size_t)k * V + p.r, G);
-        return;
-    }
-    load_shifted<VEC, GT>(gb + (size_t)k * V, p, dz3(k), dy3(k), dx3(k), D, H, W, G);
-    if (norm == CSPN_NORM_8SUM_ABS) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) G[i] = fabsf(G[i]);
-    }
-}
 
 // the fold of fold3d_kernel with w' laid out as a gate tensor: wp [B][26][V], cp = c' and kp = coef [B][V]
 template <int VEC, class GT>
@@ -184,6 +70,8 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
 #pragma unroll
         for (int i = 0; i < VEC; ++i) m[i] = signf(m[i]);
     }
+    // c' in this file's rounding, ((1 - m) (1 - sigma) + m) h0: fold3d_kernel forms (1 - m) ((1 - sigma) h0) + m h0, and each output stays
+    // bitwise what it has always been
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
         const float om = 1.f - m[i];
@@ -199,46 +87,6 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
     for (int k = 0; k < 26; ++k) store_vec<VEC>(o + (size_t)k * V, G[k]);
     store_vec<VEC>(cp + vox, c);
     store_vec<VEC>(kp + vox, coef);
-}
-
-// one forward step with the constant term: hout(p) = c'(p) + sum_k w'_k(p) hin(p + off_k)
-template <int VEC>
-__global__ __launch_bounds__(256) void step_const3d_kernel(const float* __restrict__ wp, const float* __restrict__ cp,
-                                                            const float* __restrict__ hin, float* __restrict__ hout, int B, int D,
-                                                            int H, int W) {
-    const Pos<VEC> p(B, D, H, W);
-    if (!p.ok) return;
-    const size_t V = (size_t)D * H * W, vox = (size_t)p.b * V + p.r;
-    const float* hb = hin + (size_t)p.b * V;
-    const float* wb = wp + (size_t)p.b * 26 * V + p.r;
-    float acc[VEC];
-    load_vec<VEC>(cp + vox, acc);
-#pragma unroll
-    for (int n = 0; n < 9; ++n) {   // neighbour rows (z + dz, y + dy); three x-taps each
-        const int dz = 1 - n / 3, dy = 1 - n % 3;
-        const int zz = p.z + dz, yy = p.y + dy;
-        float h[VEC + 2];   // hin at columns x-1 .. x+VEC of the row, zero outside the volume
-#pragma unroll
-        for (int i = 0; i < VEC + 2; ++i) h[i] = 0.f;
-        if (zz >= 0 && zz < D && yy >= 0 && yy < H) {
-            const float* row = hb + ((size_t)zz * H + yy) * W;
-            load_vec<VEC>(row + p.x, h + 1);
-            if (p.x > 0) h[0] = row[p.x - 1];
-            if (p.x + VEC < W) h[VEC + 1] = row[p.x + VEC];
-        }
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int c27 = n * 3 + t;
-            if (c27 == 13) continue;
-            const int k = c27 < 13 ? c27 : c27 - 1;
-            const int dx = 1 - t;
-            float w[VEC];
-            load_vec<VEC>(wb + (size_t)k * V, w);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w[i], h[1 + i + dx], acc[i]);
-        }
-    }
-    store_vec<VEC>(hout + vox, acc);
 }
 
 // dW'_k(p) = sum_t A_{t+1}(p) H_t(p + off_k) and dC(p) = sum_t A_{t+1}(p) in registers (H_0 = feat, H_t = hist + (t-1) total;
@@ -270,30 +118,7 @@ __global__ __launch_bounds__(256) void gate_grad_norm3d_kernel(const store_t<GT>
 #pragma unroll
         for (int i = 0; i < VEC; ++i) dC[i] += a[i];
         if (!planes) continue;
-        const float* ht = (t == 0 ? feat : hist + (size_t)(t - 1) * total) + vol;
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {   // neighbour rows (z + dz, y + dy)
-            const int dz = 1 - n / 3, dy = 1 - n % 3;
-            const int zz = p.z + dz, yy = p.y + dy;
-            float h[VEC + 2];
-#pragma unroll
-            for (int i = 0; i < VEC + 2; ++i) h[i] = 0.f;
-            if (zz >= 0 && zz < D && yy >= 0 && yy < H) {
-                const float* row = ht + ((size_t)zz * H + yy) * W;
-                load_vec<VEC>(row + p.x, h + 1);
-                if (p.x > 0) h[0] = row[p.x - 1];
-                if (p.x + VEC < W) h[VEC + 1] = row[p.x + VEC];
-            }
-#pragma unroll
-            for (int t3 = 0; t3 < 3; ++t3) {
-                const int c27 = n * 3 + t3;
-                if (c27 == 13) continue;
-                const int k = c27 < 13 ? c27 : c27 - 1;
-                const int dx = 1 - t3;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc[k][i] = fmaf(a[i], h[1 + i + dx], acc[k][i]);
-            }
-        }
+        gate_grad_level3<VEC>(acc, a, (t == 0 ? feat : hist + (size_t)(t - 1) * total) + vol, p, D, H, W);
     }
     if (gf) {
         float a[VEC], coef[VEC];
@@ -376,15 +201,6 @@ __global__ __launch_bounds__(256) void gather_guidance3d_kernel(const float* __r
 
 size_t planes_bytes(size_t total, int planes) { return round256(sizeof(float) * total * (size_t)planes); }
 
-// the vector kernels' condition: four voxels of a thread share a row, every float32 tensor of the call is 16-byte aligned and the two
-// guidance-typed ones to four of their elements (16 bytes, or 8 for a 16-bit type); NULL: absent
-bool quads_ok(int W, int gdt, std::initializer_list<const void*> gates, std::initializer_list<const void*> tensors) {
-    uintptr_t gbits = 0, bits = 0;
-    for (const void* t : gates) gbits |= (uintptr_t)t;
-    for (const void* t : tensors) bits |= (uintptr_t)t;
-    return (W % 4) == 0 && (gbits & gate_quad_mask(gdt)) == 0 && (bits & 15u) == 0;
-}
-
 }  // namespace
 
 // w' / dG (26 planes), c', coef, then the workspace of backward3d(): the levels H_1 .. H_{n-1}, A_1 .. A_{n-1}, A_0 and what the persistent
@@ -410,57 +226,51 @@ int backward3d_norm(const void* g, int gdt, const float* feat, const float* spar
     float* wp = (float*)ws;
     float* cp = (float*)((char*)ws + planes_bytes(total, 26));
     float* kp = (float*)((char*)cp + planes_bytes(total, 1));
-    float* levels = (float*)((char*)kp + planes_bytes(total, 1));   // the layout of backward3d()
-    float* hist = levels;                                          // H_1 .. H_{n-1}
-    float* ahist = hist + (size_t)(n_iter - 1) * total;            // A_1 .. A_{n-1}
-    float* a0 = ahist + (size_t)(n_iter - 1) * total;
-    void* pws = (char*)levels + (backward3d_workspace(B, D, H, W, n_iter) - persistent3d_workspace(B, D, H, W));
+    char* levels = (char*)kp + planes_bytes(total, 1);   // the workspace of backward3d()
+    const Backward3dLayout L(B, 1, D, H, W, n_iter, 0);
+    float* hist = (float*)(levels + L.hist);     // H_1 .. H_{n-1}
+    float* ahist = (float*)(levels + L.ahist);   // A_1 .. A_{n-1}
+    float* a0 = (float*)(levels + L.a0);
+    void* pws = levels + L.pers;
     const bool vec = quads_ok(W, gdt, {g, gg}, {feat, sparse, gout, gf, ws});
     const bool fused = !stepwise_only && backward3d_norm_fused(g, gdt, feat, sparse, gout, gg, gf, B, D, H, W, n_iter, ws);
     const dim3 grid((unsigned)((total / (vec ? 4 : 1) + 255) / 256)), block(256);
-#define CSPN_LAUNCH_VEC(kernel, ...)                                                 \
-    do {                                                                              \
-        if (vec) hipLaunchKernelGGL(kernel<4>, grid, block, 0, st, __VA_ARGS__);      \
-        else hipLaunchKernelGGL(kernel<1>, grid, block, 0, st, __VA_ARGS__);          \
-    } while (0)
-#define CSPN_LAUNCH_VEC_GT(kernel, ...)                                                  \
-    do {                                                                                  \
-        if (vec) hipLaunchKernelGGL((kernel<4, GT>), grid, block, 0, st, __VA_ARGS__);    \
-        else hipLaunchKernelGGL((kernel<1, GT>), grid, block, 0, st, __VA_ARGS__);        \
-    } while (0)
     return with_gate_type(gdt, [&](auto gt) -> int {
         using GT = typename decltype(gt)::type;
-        const store_t<GT>* gs = (const store_t<GT>*)g;
-        CSPN_LAUNCH_VEC_GT(fold_norm3d_kernel, gs, feat, sparse, wp, cp, kp, B, D, H, W, norm);
-        if (int e = check_launch("fold_norm3d_kernel")) return e;
-        if (gg) {
-            const float* src = feat;
-            for (int t = 1; t < n_iter; ++t) {
-                float* dst = hist + (size_t)(t - 1) * total;
-                CSPN_LAUNCH_VEC(step_const3d_kernel, wp, cp, src, dst, B, D, H, W);
-                src = dst;
+        return with_vec(vec, [&](auto v) -> int {
+            constexpr int VEC = decltype(v)::value;
+            const store_t<GT>* gs = (const store_t<GT>*)g;
+            hipLaunchKernelGGL((fold_norm3d_kernel<VEC, GT>), grid, block, 0, st, gs, feat, sparse, wp, cp, kp, B, D, H, W, norm);
+            if (int e = check_launch("fold_norm3d_kernel")) return e;
+            if (gg) {   // H_1 .. H_{n-1}: the forward step with the constant term, on w' as the gate tensor it is laid out as
+                const float* src = feat;
+                for (int t = 1; t < n_iter; ++t) {
+                    float* dst = hist + (size_t)(t - 1) * total;
+                    if (vec) step3d_direct(wp, 0, src, dst, B, D, H, W, st, cp);
+                    else step3d_folded(wp, cp, 26 * V, V, src, dst, B, D, H, W, st);
+                    src = dst;
+                }
+                if (int e = check_launch("step_const3d_kernel")) return e;   // (the text from before the two steps moved to cspn3d_stepwise.hip)
             }
-            if (int e = check_launch("step_const3d_kernel")) return e;
-        }
-        // the adjoint levels have no constant term: the Paddle contract's on w' (float32 whatever the guidance is).  Fused: step it = 1 .. n
-        // of the transposed run produces A_{n-it}, volume n - it - 1 of ahist, the last one (A_0) its "out"; else backward3d()'s per-step
-        // launches (A_0 only where grad_feat wants it)
-        if (fused) {
-            if (int e = persistent3d_run(wp, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st)) return e;
-        } else if (int e = backward3d(wp, feat, gout, nullptr, gf ? a0 : nullptr, B, D, H, W, n_iter, levels, st, true)) {
-            return e;
-        }
-        void* planes = !gg ? nullptr : (norm == CSPN_NORM_NONE ? gg : (void*)wp);
-        CSPN_LAUNCH_VEC_GT(gate_grad_norm3d_kernel, gs, feat, sparse, kp, hist, ahist, gout, a0, planes, gf, B, D, H, W, n_iter, norm);
-        if (int e = check_launch("gate_grad_norm3d_kernel")) return e;
-        if (gg && norm != CSPN_NORM_NONE) {
-            CSPN_LAUNCH_VEC_GT(gather_guidance3d_kernel, wp, gs, (store_t<GT>*)gg, B, D, H, W, norm);
-            if (int e = check_launch("gather_guidance3d_kernel")) return e;
-        }
-        return 0;
+            // the adjoint levels have no constant term: the Paddle contract's on w' (float32 whatever the guidance is).  Fused: step it = 1 .. n
+            // of the transposed run produces A_{n-it}, volume n - it - 1 of ahist, the last one (A_0) its "out"; else backward3d()'s per-step
+            // launches (A_0 only where grad_feat wants it)
+            if (fused) {
+                if (int e = persistent3d_run(wp, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st)) return e;
+            } else if (int e = backward3d(wp, feat, gout, nullptr, gf ? a0 : nullptr, B, D, H, W, n_iter, levels, st, true)) {
+                return e;
+            }
+            void* planes = !gg ? nullptr : (norm == CSPN_NORM_NONE ? gg : (void*)wp);
+            hipLaunchKernelGGL((gate_grad_norm3d_kernel<VEC, GT>), grid, block, 0, st, gs, feat, sparse, kp, hist, ahist, gout, a0, planes, gf, B, D, H, W,
+                               n_iter, norm);
+            if (int e = check_launch("gate_grad_norm3d_kernel")) return e;
+            if (gg && norm != CSPN_NORM_NONE) {
+                hipLaunchKernelGGL((gather_guidance3d_kernel<VEC, GT>), grid, block, 0, st, wp, gs, (store_t<GT>*)gg, B, D, H, W, norm);
+                if (int e = check_launch("gather_guidance3d_kernel")) return e;
+            }
+            return 0;
+        });
     });
-#undef CSPN_LAUNCH_VEC
-#undef CSPN_LAUNCH_VEC_GT
 }
 
 }  // namespace cspn

@@ -1,42 +1,37 @@
-// cspn3d_stepwise.hip -- 3x3x3 propagation (26 neighbours), one launch per iteration.
+// cspn3d_stepwise.hip -- 3x3x3 propagation (26 neighbours), one launch per iteration: the fold, and the three forward steps every 3D file
+// launches (step3d_kernel on folded planes, step3d_direct_kernel on a gate tensor four voxels a thread, step3d_scalar_kernel on a gate
+// tensor of any shape and alignment).
 // API surface: reference cspn_paddle/demo.py:41-43,50-52 (fluid.layers.affinity_propagate,
 // kernel source NOT in the reference tree -> parity unpinned; semantics = the 3D
 // generalisation of cspn_pytorch/models/cspn.py:42-172, see oracle/cspn_oracle.c).
-// Channel order: raster over (f,t,l) in {0,1,2}^3 without (1,1,1); offset (1-f,1-t,1-l).
-#include "cspn_common.h"
-#include "cspn_gate16.h"
+// Channel order and the neighbourhood helpers: cspn3d_voxel.h.
+#include "cspn3d_voxel.h"
 
 namespace cspn {
 
-__host__ __device__ constexpr int ch3(int k) { return k < 13 ? k : k + 1; }  // skip the centre (index 13)
-__host__ __device__ constexpr int dz3(int k) { return 1 - ch3(k) / 9; }
-__host__ __device__ constexpr int dy3(int k) { return 1 - (ch3(k) / 3) % 3; }
-__host__ __device__ constexpr int dx3(int k) { return 1 - ch3(k) % 3; }
-
 // wf: [27][B*D*H*W] (26 folded weights + c').  GT: the gate storage type (cspn_gate16.h).  A 16-bit gate comes here in every mode: with
 // norm NONE and no mask (a misaligned gate tensor of the Paddle contract) folding is the exact widening; in the normalising and masked modes
-// (cspn3d_forward_norm_g16) each gate is widened where it is read and the sums, divisions and products are the float32 ones in the same order
+// (cspn3d_forward_norm_g16) each gate is widened where it is read and the sums, divisions and products are the float32 ones in the same order.
+// fold_norm3d_kernel (cspn3d_norm_backward.hip) is the same fold, VEC voxels a thread, into another layout.  The two stay two: this one keeps
+// its single bounds test per gate and its scalar registers -- written over the shared load_G it ran 2 % slower at config 5's volume
+// (profiles/3d_stepwise_refactor.md) -- and they form c' differently, here (1 - m) ((1 - sigma) h0) + m h0, there ((1 - m) (1 - sigma) + m) h0:
+// the two round differently and each output stays bitwise what it has always been
 template <class GT>
 __global__ __launch_bounds__(256) void fold3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ feat,
                                                       const float* __restrict__ sparse, float* __restrict__ wf,
                                                       int B, int D, int H, int W, int norm) {
-    const size_t HW = (size_t)H * W, V = (size_t)D * HW, total = (size_t)B * V;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / V);
-    const size_t r = idx - (size_t)b * V;
-    const int z = (int)(r / HW);
-    const int r2 = (int)(r - (size_t)z * HW);
-    const int y = r2 / W, x = r2 - y * W;
-    const store_t<GT>* gb = g + (size_t)b * 26 * V;
+    const Pos<1> p(B, D, H, W);
+    if (!p.ok) return;
+    const size_t V = (size_t)D * H * W, total = (size_t)B * V, idx = (size_t)p.b * V + p.r;
+    const store_t<GT>* gb = g + (size_t)p.b * 26 * V;
     float G[26], S = 0.f;
 #pragma unroll
     for (int k = 0; k < 26; ++k) {
         float v;
         if (norm == CSPN_NORM_NONE) {
-            v = widen<GT>(gb[k * V + r]);
+            v = widen<GT>(gb[k * V + p.r]);
         } else {
-            const int zz = z + dz3(k), yy = y + dy3(k), xx = x + dx3(k);
+            const int zz = p.z + dz3(k), yy = p.y + dy3(k), xx = p.x + dx3(k);
             v = 0.f;
             if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W)
                 v = widen<GT>(gb[k * V + ((size_t)zz * H + yy) * W + xx]);
@@ -65,26 +60,23 @@ __global__ __launch_bounds__(256) void fold3d_kernel(const store_t<GT>* __restri
     wf[26 * total + idx] = c;
 }
 
-__global__ __launch_bounds__(256) void step3d_kernel(const float* __restrict__ wf, const float* __restrict__ hin,
-                                                      float* __restrict__ hout, int B, int D, int H, int W) {
-    const size_t HW = (size_t)H * W, V = (size_t)D * HW, total = (size_t)B * V;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / V);
-    const size_t r = idx - (size_t)b * V;
-    const int z = (int)(r / HW);
-    const int r2 = (int)(r - (size_t)z * HW);
-    const int y = r2 / W, x = r2 - y * W;
-    const float* hb = hin + (size_t)b * V;
-    float acc = wf[26 * total + idx];
+// one step on folded planes: hout(p) = c(p) + sum_k w_k(p) hin(p + off_k), one voxel a thread.  w_k(p) of batch b at w + b bs + k ps + r,
+// c [B][V]: (bs, ps) = (V, B V) for the forward's [27][B V] planes (c = plane 26), (26 V, V) for the backward's gate-tensor layout [B][26][V]
+__global__ __launch_bounds__(256) void step3d_kernel(const float* __restrict__ w, const float* __restrict__ c, const float* __restrict__ hin,
+                                                      float* __restrict__ hout, int B, int D, int H, int W, size_t bs, size_t ps) {
+    const Pos<1> p(B, D, H, W);
+    if (!p.ok) return;
+    const size_t V = (size_t)D * H * W, vox = (size_t)p.b * V + p.r;
+    const float* hb = hin + (size_t)p.b * V;
+    const float* wb = w + (size_t)p.b * bs + p.r;
+    float acc = c[vox];
 #pragma unroll
-    for (int k = 0; k < 26; ++k) {
-        const int zz = z + dz3(k), yy = y + dy3(k), xx = x + dx3(k);
-        float hv = 0.f;
-        if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W) hv = hb[((size_t)zz * H + yy) * W + xx];
-        acc = fmaf(wf[k * total + idx], hv, acc);
+    for (int n = 0; n < 9; ++n) {   // neighbour rows (z + dz, y + dy); three x-taps each
+        float h[3];                 // hin at columns x-1 .. x+1 of the row, zero outside the volume
+        load_row3<1>(hb, p, row_dz3(n), row_dy3(n), D, H, W, h);
+        for_taps3(n, [&](int k, int dx) { acc = fmaf(wb[(size_t)k * ps], h[1 + dx], acc); });
     }
-    hout[idx] = acc;
+    hout[vox] = acc;
 }
 
 // The Paddle contract (norm_type NONE, no sparse): gates are used as given, centre-sited, no centre term
@@ -92,69 +84,90 @@ __global__ __launch_bounds__(256) void step3d_kernel(const float* __restrict__ w
 // single propagation step -- 26 gates + value in, value out = 112 B/voxel -- so it reads the gate tensor directly: no
 // fold pass, no coefficient planes.  4 voxels per thread along x (16-byte loads of the gate planes; 8-byte loads of fp16 / bf16 planes,
 // widened as they arrive).
-template <class GT>
+// CONST: the accumulator starts at cp(p) instead of 0 -- the step of the normalising / masked backward on its folded planes
+// (g = w' [B][26][V] float32, cp = c' [B][V]): hout(p) = c'(p) + sum_k w'_k(p) hin(p + off_k)
+template <class GT, bool CONST>
 __global__ __launch_bounds__(256) void step3d_direct_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ hin,
-                                                             float* __restrict__ hout, int B, int D, int H, int W4) {
+                                                             float* __restrict__ hout, int B, int D, int H, int W4,
+                                                             const float* __restrict__ cp) {
     const int W = 4 * W4;
-    const size_t HW = (size_t)H * W, V = (size_t)D * HW, total4 = (size_t)B * D * H * W4;
-    const size_t i4 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i4 >= total4) return;
-    const size_t idx = 4 * i4;
-    const int b = (int)(idx / V);
-    const size_t r = idx - (size_t)b * V;
-    const int z = (int)(r / HW);
-    const int r2 = (int)(r - (size_t)z * HW);
-    const int y = r2 / W, x = r2 - y * W;
-    const float* hb = hin + (size_t)b * V;
-    const store_t<GT>* gb = g + (size_t)b * 26 * V + r;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const Pos<4> p(B, D, H, W);
+    if (!p.ok) return;
+    const size_t V = (size_t)D * H * W, vox = (size_t)p.b * V + p.r;
+    const float* hb = hin + (size_t)p.b * V;
+    const store_t<GT>* gb = g + (size_t)p.b * 26 * V + p.r;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (CONST) load_vec<4>(cp + vox, acc);
 #pragma unroll
-    for (int n = 0; n < 9; ++n) {  // the 9 neighbour rows (dz, dy); three x-taps each
-        const int dz = 1 - n / 3, dy = 1 - n % 3;
-        const int zz = z + dz, yy = y + dy;
-        float hm = 0.f, hp = 0.f;
-        float4 hc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (zz >= 0 && zz < D && yy >= 0 && yy < H) {
-            const float* row = hb + ((size_t)zz * H + yy) * W;
-            hc = *reinterpret_cast<const float4*>(row + x);
-            if (x > 0) hm = row[x - 1];
-            if (x + 4 < W) hp = row[x + 4];
-        }
+    for (int n = 0; n < 9; ++n) {   // the 9 neighbour rows (dz, dy); three x-taps each
+        float h[6];
+        load_row3<4>(hb, p, row_dz3(n), row_dy3(n), D, H, W, h);
+        for_taps3(n, [&](int k, int dx) {
+            float w[4];
+            load_gvec<4, GT>(gb + (size_t)k * V, w);
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {  // dx = 1 - t
-            const int c27 = n * 3 + t;   // raster index (f,t,l) with f = n/3, t = n%3, l = t
-            if (c27 == 13) continue;     // the centre has no gate
-            const int k = c27 < 13 ? c27 : c27 - 1;
-            const float4 w = ld4g<GT>(gb + (size_t)k * V);
-            const int dx = 1 - t;
-            const float h0 = dx > 0 ? hc.y : (dx < 0 ? hm : hc.x);
-            const float h1 = dx > 0 ? hc.z : (dx < 0 ? hc.x : hc.y);
-            const float h2 = dx > 0 ? hc.w : (dx < 0 ? hc.y : hc.z);
-            const float h3 = dx > 0 ? hp : (dx < 0 ? hc.z : hc.w);
-            acc.x = fmaf(w.x, h0, acc.x);
-            acc.y = fmaf(w.y, h1, acc.y);
-            acc.z = fmaf(w.z, h2, acc.z);
-            acc.w = fmaf(w.w, h3, acc.w);
-        }
+            for (int i = 0; i < 4; ++i) acc[i] = fmaf(w[i], h[1 + i + dx], acc[i]);
+        });
     }
-    *reinterpret_cast<float4*>(hout + idx) = acc;
+    store_vec<4>(hout + vox, acc);
 }
 
+// forward step on a gate tensor for the shapes / alignments step3d_direct_kernel does not take.  fbs: floats from one volume of hin / hout
+// to the next (V, or C V when C value channels share the gates).
+// It SKIPS a tap whose neighbour lies outside the volume; the other step kernels multiply the gate by a zero.  The two differ where a gate
+// at a face of the volume is NaN or infinite (0 x NaN = NaN): that is the behaviour the scalar path has always had, and it is kept
+namespace {
+template <class GT>
+__global__ __launch_bounds__(256) void step3d_scalar_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ hin,
+                                                             float* __restrict__ hout, int B, int D, int H, int W, size_t fbs) {
+    const Pos<1> p(B, D, H, W);
+    if (!p.ok) return;
+    const size_t HW = (size_t)H * W, V = (size_t)D * HW;
+    const float* hb = hin + (size_t)p.b * fbs;
+    const store_t<GT>* gb = g + (size_t)p.b * 26 * V + p.r;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 26; ++k) {
+        const int c = ch3(k);   // (p.z + 1 - c / 9, not p.z + dz3(k): the other association moves this kernel's blocks)
+        const int zz = p.z + 1 - c / 9, yy = p.y + 1 - (c / 3) % 3, xx = p.x + 1 - c % 3;
+        if (zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W)
+            acc = fmaf(widen<GT>(gb[(size_t)k * V]), hb[((size_t)zz * H + yy) * W + xx], acc);
+    }
+    hout[(size_t)p.b * fbs + p.r] = acc;
+}
+}  // namespace
+
 // one step of the Paddle contract for other files (the backward keeps the value levels): W % 4 == 0, 16-byte aligned tensors (a 16-bit
-// gate tensor: 8-byte aligned); gdt: the gate storage type (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16)
-int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st) {
+// gate tensor: 8-byte aligned); gdt: the gate storage type (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16).  cp != NULL (float32 gates
+// only): the step with the constant term cp
+int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st, const float* cp) {
     const size_t total = (size_t)B * D * H * W;
+    const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
+    if (cp) {
+        hipLaunchKernelGGL((step3d_direct_kernel<float, true>), grid, block, 0, st, (const float*)g, hin, hout, B, D, H, W / 4, cp);
+        return 0;
+    }
     return with_gate_type(gdt, [&](auto gt) {
         using GT = typename decltype(gt)::type;
-        hipLaunchKernelGGL(step3d_direct_kernel<GT>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, (const store_t<GT>*)g, hin, hout, B,
-                           D, H, W / 4);
+        hipLaunchKernelGGL((step3d_direct_kernel<GT, false>), grid, block, 0, st, (const store_t<GT>*)g, hin, hout, B, D, H, W / 4, cp);
         return 0;
     });
 }
 
-static bool direct3d_ok(const void* g, int gdt, const float* feat, const float* sparse, const float* out, int W, int norm, const void* ws) {
-    return norm == CSPN_NORM_NONE && sparse == nullptr && (W % 4) == 0 && ((uintptr_t)g & gate_quad_mask(gdt)) == 0 &&
-           (((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0;
+int step3d_folded(const float* w, const float* c, size_t bs, size_t ps, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st) {
+    const size_t total = (size_t)B * D * H * W;
+    hipLaunchKernelGGL(step3d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, c, hin, hout, B, D, H, W, bs, ps);
+    return 0;
+}
+
+int step3d_scalar(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, size_t fbs, hipStream_t st) {
+    const size_t total = (size_t)B * D * H * W;
+    return with_gate_type(gdt, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        hipLaunchKernelGGL(step3d_scalar_kernel<GT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const store_t<GT>*)g, hin, hout, B, D,
+                           H, W, fbs);
+        return 0;
+    });
 }
 
 size_t stepwise3d_workspace(int B, int D, int H, int W, int n_iter) {
@@ -178,9 +191,9 @@ size_t forward3d_workspace(int B, int D, int H, int W, int n_iter, int norm, boo
 // bytes; the folding path reads the gates element by element, so their alignment plays no part in it
 int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
                        int W, int n_iter, int norm, void* ws, hipStream_t st, int algo, int gdt) {
-    const size_t total = (size_t)B * D * H * W;
+    const size_t V = (size_t)D * H * W, total = (size_t)B * V;
     float* wf = (float*)ws;
-    const bool direct = direct3d_ok(g, gdt, feat, sparse, out, W, norm, ws);
+    const bool direct = norm == CSPN_NORM_NONE && sparse == nullptr && quads_ok(W, gdt, {g}, {feat, out, ws});
     if (algo == 2 && direct && !persistent3d_supported(B, D, H, W, n_iter)) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;
@@ -198,16 +211,16 @@ int stepwise3d_forward(const void* g, const float* feat, const float* sparse, fl
         return check_launch("step3d_direct_kernel");
     }
     float* ping[2] = {wf + 27 * total, wf + 28 * total};
-    const unsigned blocks = (unsigned)((total + 255) / 256);
     with_gate_type(gdt, [&](auto gt) {
         using GT = typename decltype(gt)::type;
-        hipLaunchKernelGGL(fold3d_kernel<GT>, dim3(blocks), dim3(256), 0, st, (const store_t<GT>*)g, feat, sparse, wf, B, D, H, W, norm);
+        hipLaunchKernelGGL(fold3d_kernel<GT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const store_t<GT>*)g, feat, sparse, wf, B, D,
+                           H, W, norm);
         return 0;
     });
     if (int e = check_launch("fold3d_kernel")) return e;
     // the normalising / masked modes fused: H_{t+1} = c' + sum_k w'_k H_t(p + off_k) with the folded planes resident in the
     // persistent kernel's registers (c' in LDS): fold once, then one pass over the 27 planes for all steps
-    const bool aligned = ((((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0) && (W % 4) == 0 && (total % 4) == 0;
+    const bool aligned = quads_ok(W, 0, {}, {feat, out, ws});
     if (algo == 2 && !(aligned && persistent3d_supported(B, D, H, W, n_iter))) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;
@@ -217,7 +230,7 @@ int stepwise3d_forward(const void* g, const float* feat, const float* sparse, fl
     const float* src = feat;
     for (int it = 0; it < n_iter; ++it) {
         float* dst = (it == n_iter - 1) ? out : ping[it & 1];
-        hipLaunchKernelGGL(step3d_kernel, dim3(blocks), dim3(256), 0, st, wf, src, dst, B, D, H, W);
+        step3d_folded(wf, wf + 26 * total, V, total, src, dst, B, D, H, W, st);
         src = dst;
     }
     return check_launch("step3d_kernel");

@@ -548,7 +548,7 @@ static int forward3d_entry(const void* gate, int gdt, const float* feat, const f
     if (int e = async_failure_of_earlier_call()) return e;
     // misaligned tensors cannot take the 16-byte paths: they fold like the normalising modes (cspn3d_workspace_bytes()); a 16-bit gate
     // tensor is aligned at 8 bytes (four gates)
-    const bool aligned = ((uintptr_t)gate & gate_quad_mask(gdt)) == 0 && ((((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
+    const bool aligned = quads_ok(W, gdt, {gate}, {feat, out, ws});   // (W % 4 != 0 takes the folding path's size from either query)
     size_t need = n_iter == 0 ? 0 : (aligned ? forward3d_workspace(B, D, H, W, n_iter, norm_type, sparse != nullptr)
                                              : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(gate, feat, out, n_iter, norm_type, ws, ws_bytes, need)) return e;
@@ -590,7 +590,7 @@ static int forward3d_multi_entry(const void* gate, int gdt, const float* feat, f
     if (int e = async_failure_of_earlier_call()) return e;
     if (int e = check_common(gate, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes,
                              n_iter == 0 ? 0 : forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false))) return e;
-    const bool aligned = ((uintptr_t)gate & gate_quad_mask(gdt)) == 0 && ((((uintptr_t)feat | (uintptr_t)out | (uintptr_t)ws) & 15u) == 0);
+    const bool aligned = quads_ok(W, gdt, {gate}, {feat, out, ws});
     if (!aligned || !persistent3d_multi_supported(B, C, D, H, W, n_iter)) {
         set_error("cspn3d_forward_multi_f32 runs the persistent kernel only (W %% 4 == 0, 2 <= n_iter <= 60, 16-byte aligned tensors, "
                   "volume resident on the device): loop over the channels with cspn3d_forward_f32 for B=%d C=%d D=%d H=%d W=%d n_iter=%d",
@@ -790,12 +790,12 @@ static int forward3d_absnorm_entry(const char* what, const void* guide, int gdt,
     hipStream_t st = (hipStream_t)stream;
     if (int e = async_failure_of_earlier_call()) return e;
     // misaligned feat / out take the folding path after the normaliser: its 27 planes more (as cspn3d_forward_f32 with such tensors)
-    const bool vals_aligned = ((((uintptr_t)feat | (uintptr_t)out) & 15u) == 0);
+    const bool vals_aligned = quads_ok(W, gdt, {}, {feat, out});   // (W % 4 != 0 takes the folding path's size from either query)
     const size_t need = n_iter == 0 ? 0 : absnorm_planes_bytes(B, D, H, W) + (vals_aligned ? forward3d_workspace(B, D, H, W, n_iter, CSPN_NORM_NONE, false)
                                                                                             : stepwise3d_workspace(B, D, H, W, n_iter));
     if (int e = check_common(guide, feat, out, n_iter, CSPN_NORM_NONE, ws, ws_bytes, need)) return e;
     if (n_iter == 0) return identity_copy(out, feat, total, st);
-    const bool fused = vals_aligned && ((uintptr_t)guide & gate_quad_mask(gdt)) == 0 && ((uintptr_t)ws & 15u) == 0 && persistent3d_supported(B, D, H, W, n_iter);
+    const bool fused = quads_ok(W, gdt, {guide}, {feat, out, ws}) && persistent3d_supported(B, D, H, W, n_iter);
     if (algo == CSPN_ALGO3D_PERSISTENT && !fused) {
         set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
         return CSPN_E_UNSUPPORTED;

@@ -46,8 +46,14 @@ size_t stepwise3d_workspace(int B, int D, int H, int W, int n_iter);
 // gates are widened exactly where they are read (cspn_gate16.h), every value, level and workspace stays float32
 int stepwise3d_forward(const void* g, const float* feat, const float* sparse, float* out, int B, int D, int H,
                        int W, int n_iter, int norm, void* ws, hipStream_t st, int algo = 0, int gdt = 0);
-// one step of the Paddle contract (W % 4 == 0, 16-byte aligned values, gates aligned to four elements)
-int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st);
+// one step of the Paddle contract (W % 4 == 0, 16-byte aligned values, gates aligned to four elements); cp != NULL (float32 gates only):
+// hout = cp + that step, the step of the normalising / masked backward on its folded planes (g = w' [B][26][V], cp = c' [B][V])
+int step3d_direct(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st, const float* cp = nullptr);
+// the same step on a gate tensor of any shape and alignment, one voxel a thread (no constant term); fbs: floats from one volume of hin /
+// hout to the next.  It skips the taps outside the volume where the others multiply by zero (cspn3d_stepwise.hip)
+int step3d_scalar(const void* g, int gdt, const float* hin, float* hout, int B, int D, int H, int W, size_t fbs, hipStream_t st);
+// one step on folded planes, one voxel a thread: hout = c + sum_k w_k hin(p + off_k), w_k(p) of batch b at w + b bs + k ps + r, c [B][V]
+int step3d_folded(const float* w, const float* c, size_t bs, size_t ps, const float* hin, float* hout, int B, int D, int H, int W, hipStream_t st);
 size_t forward3d_workspace(int B, int D, int H, int W, int n_iter, int norm, bool has_sparse);
 
 // ---- 3D, gates resident in registers for all steps (cspn3d_persistent.hip); Paddle contract only ----
@@ -127,6 +133,13 @@ int kxk_norm_backward(const void* guid, int dtype, const float* blur, const floa
 // gdt: the storage type of g and gg; 16-bit: where the fused sweeps can run, the workspace also holds the float32 copy of the gates the
 // transposed sweep reads
 size_t backward3d_workspace(int B, int D, int H, int W, int n_iter, int C = 1, int gdt = 0);
+// that workspace's parts, in bytes from its start: the levels H_1 .. H_{n-1} (hist) and A_1 .. A_{n-1} (ahist), each level B C volumes laid
+// out like feat ([B][C][V]), the spare volume A_0 goes to when the caller does not want grad_feat, what the persistent kernel wants (pers),
+// and -- 16-bit gates on a shape the fused sweeps take, else 0 -- the float32 copy of the gates (wide)
+struct Backward3dLayout {
+    size_t hist, ahist, a0, pers, wide, bytes;
+    Backward3dLayout(int B, int C, int D, int H, int W, int n_iter, int gdt);
+};
 int backward3d(const void* g, const float* feat, const float* gout, void* gg, float* gf, int B, int D, int H, int W, int n_iter,
                void* ws, hipStream_t st, bool stepwise_only = false /* test-hook library: one launch per step */, int C = 1, int gdt = 0);
 // n gates (n % 4 == 0, g 8-byte and w 16-byte aligned) widened exactly into float32

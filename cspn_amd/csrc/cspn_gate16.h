@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/cspn_amd.h"
@@ -96,5 +97,14 @@ auto with_gate_type(int dtype, F f) {
 // bytes of a stored gate, and the alignment mask of four of them (the vector paths' condition on a gate pointer)
 inline size_t gate_bytes(int dtype) { return dtype == 0 ? 4 : 2; }
 inline uintptr_t gate_quad_mask(int dtype) { return dtype == 0 ? 15u : 7u; }
+
+// the vector kernels' condition: four voxels of a thread share a row, every float32 tensor of the call is 16-byte aligned and the
+// gate-typed ones to four of their elements (16 bytes, or 8 for a 16-bit type); NULL: absent.  Each caller lists its own tensors
+inline bool quads_ok(int W, int gdt, std::initializer_list<const void*> gates, std::initializer_list<const void*> tensors) {
+    uintptr_t gbits = 0, bits = 0;
+    for (const void* t : gates) gbits |= (uintptr_t)t;
+    for (const void* t : tensors) bits |= (uintptr_t)t;
+    return (W % 4) == 0 && (gbits & gate_quad_mask(gdt)) == 0 && (bits & 15u) == 0;
+}
 
 }  // namespace cspn

@@ -33,6 +33,10 @@ CASES = [((2, 4, 5, 7), 1),      # odd W: scalar kernels; B = 2: the batch strid
 # where algo 'auto' runs the adjoint sweep through the persistent kernel's transposed instance (the fused shapes of tests/test_backward3d.py)
 FUSED_CASES = [((1, 8, 8, 64), 3),    # one tile
                ((1, 9, 17, 72), 5)]   # partial tiles
+# the smallest shapes at which a wrong stride or edge test of the shared voxel helpers shows (listed last: the ids of the cases above stay)
+EDGE_CASES = [((1, 1, 1, 4), 3),    # one quad is the volume: no neighbour row inside it
+              ((2, 1, 2, 3), 3),    # the one-voxel kernels at B = 2, every z-neighbour out of range
+              ((2, 4, 5, 7), 3)]    # the one-voxel step with the constant term on [B][26][V] planes: batch and plane strides both differ from V
 
 
 def _shift(a, off, dims):
@@ -223,7 +227,7 @@ def _takes_persistent(args, n_iter, norm):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mask", MASKS)
 @pytest.mark.parametrize("norm", NORMS)
-@pytest.mark.parametrize("shape,n_iter", CASES + FUSED_CASES)
+@pytest.mark.parametrize("shape,n_iter", CASES + FUSED_CASES + EDGE_CASES)
 def test_hip_gradients_vs_float64_autograd(shape, n_iter, norm, mask):
     """element-wise |got - ref| <= GFLOOR max|ref| + GTOL |ref| and max-norm <= GTOL (helpers.assert_close).  GFLOOR = 1.24e-5 is twice the
     6.19e-6 a float32 CPU restatement of the same formulas needs against this reference at (2,6,10,36), n = 12, no mask (see GFLOOR)"""

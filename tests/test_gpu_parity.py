@@ -244,7 +244,10 @@ def test_benchmarked_shape_b64(sparse):
                                                (1, 3, 8, 64, 3, "none", False), (1, 1, 1, 1, 2, "8sum", False),
                                                (2, 5, 7, 12, 12, "none", False),   # direct kernel, ping-pong over 12 launches
                                                (1, 2, 5, 10, 2, "none", False),    # W % 4 != 0: general path
-                                               (1, 4, 6, 16, 3, "none", True)])    # sparse pins: general path
+                                               (1, 4, 6, 16, 3, "none", True),     # sparse pins: general path
+                                               (1, 1, 1, 4, 3, "none", False),     # one quad is the volume: no neighbour row inside it
+                                               (2, 1, 2, 3, 3, "none", False),     # the one-voxel kernels at B = 2, every z-neighbour outside
+                                               (2, 4, 5, 7, 3, "8sum", True)])     # folded step: batch and plane strides both differ from V
 def test_3d_parity_vs_oracle(B, D, H, W, N, norm, sp):
     gen = torch.Generator().manual_seed(D * 100 + H)
     g = torch.randn(B, 26, D, H, W, generator=gen) if norm == "8sum" else torch.rand(B, 26, D, H, W, generator=gen)
