@@ -155,6 +155,14 @@ _SYMBOLS.update({
     "cspn3d_forward_norm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_int] * 7 + _WS),
     "cspn3d_backward_norm_g16_workspace_bytes": (c_size_t, [c_int] * 7),
     "cspn3d_backward_norm_g16": (c_int, [vp, c_int] + [vp] * 5 + [c_int] * 7 + _WS),
+    # the same modes for C value channels on shared guidance (feat / grad_out [B,C,D,H,W], sparse None or [B,1,D,H,W]); one backward workspace
+    # query for both guidance types
+    "cspn3d_forward_norm_multi_workspace_bytes": (c_size_t, [c_int] * 8),
+    "cspn3d_forward_norm_multi_f32": (c_int, [vp] * 4 + [c_int] * 8 + _WS),
+    "cspn3d_forward_norm_multi_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_int] * 8 + _WS),
+    "cspn3d_backward_norm_multi_workspace_bytes": (c_size_t, [c_int] * 8),
+    "cspn3d_backward_norm_multi_f32": (c_int, [vp] * 6 + [c_int] * 8 + _WS),
+    "cspn3d_backward_norm_multi_g16": (c_int, [vp, c_int] + [vp] * 5 + [c_int] * 8 + _WS),
 })
 _LATE_SYMBOLS = _SYMBOLS   # (the table's name while it held the later exports only)
 

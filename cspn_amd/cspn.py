@@ -115,7 +115,8 @@ class Affinity_Propagate(nn.Module):
 
 class _CSPN3dNormFunction(torch.autograd.Function):
     """F.cspn3d_forward_norm in a normalising mode; the backward is one cspn3d_backward_norm_f32 / _g16 call (the fold and the levels are
-    recomputed there).  A float16 / bfloat16 guidance is saved as it is and gets its gradient in its dtype"""
+    recomputed there).  A float16 / bfloat16 guidance is saved as it is and gets its gradient in its dtype.  blur_depth [B,C,D,H,W] with
+    C > 1 and a shared mask: the multi-channel entry points, one call each way"""
 
     @staticmethod
     def forward(ctx, guidance, blur_depth, sparse_depth, n_iter, norm_type, algo):
@@ -138,7 +139,12 @@ class Affinity_Propagate3d(nn.Module):
     the 26-neighbourhood (F.cspn3d_forward with '8sum' / '8sum_abs'), differentiable w.r.t. guidance and blur_depth
     (F.cspn3d_backward_norm); sparse_depth gets no gradient.  A float16 / bfloat16 guidance (a head under torch.autocast) goes to the engine
     as it is -- widened exactly where a kernel reads it, no float32 copy, its gradient in its dtype (cspn3d_forward_norm_g16 /
-    cspn3d_backward_norm_g16); a 16-bit blur_depth or sparse_depth is widened with a differentiable .float().  The result is float32."""
+    cspn3d_backward_norm_g16); a 16-bit blur_depth or sparse_depth is widened with a differentiable .float().  The result is float32.
+    blur_depth [B,C,D,H,W] with C > 1 (the feature channels of a cost volume) is propagated on the shared affinities, as the 2D module
+    broadcasts its own (reference cspn.py:58-81), with sparse_depth None or [B,1,D,H,W]: one engine call each way
+    (cspn3d_forward_norm_multi_f32 / cspn3d_backward_norm_multi_f32 and their _g16 forms), dL/dguidance summed over the channels inside the
+    engine.  A per-channel mask [B,C,D,H,W] has no shared folded weights: it takes the SLOW route, one single-channel call per channel, and
+    autograd sums the C guidance gradients."""
 
     def __init__(self, prop_time, prop_kernel=3, norm_type='8sum_abs'):
         super(Affinity_Propagate3d, self).__init__()
@@ -154,6 +160,10 @@ class Affinity_Propagate3d(nn.Module):
         if n == 0:
             return blur_depth
         blur_depth, sparse_depth = F.widen16(blur_depth, sparse_depth)   # the guidance stays as it is: the 3D kernels read it in 16 bits
+        C = blur_depth.shape[1] if blur_depth.dim() == 5 else 1
+        if C > 1 and sparse_depth is not None and sparse_depth.dim() == 5 and sparse_depth.shape[1] == C:   # a mask per channel: the slow route
+            return torch.cat([_CSPN3dNormFunction.apply(guidance, blur_depth[:, c:c + 1].contiguous(), sparse_depth[:, c:c + 1].contiguous(), n,
+                                                        self.norm_type, self.algo) for c in range(C)], 1)
         return _CSPN3dNormFunction.apply(guidance, blur_depth, sparse_depth, n, self.norm_type, self.algo)
 
     def extra_repr(self):

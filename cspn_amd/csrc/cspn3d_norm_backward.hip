@@ -29,14 +29,20 @@
 // kernels that touch the guidance read a 16-bit gate where they use it, widened exactly, and grad_guidance is the float32 value rounded once at
 // its single store; w', c', coef, dG, every level and every sum stay float32, so grad_feat is bitwise the float32 call's on the widened guidance
 // and grad_guidance that call's converted to the type.  The forward steps on w' and the adjoint sweep never see the guidance.
+//
+// C value channels on SHARED guidance (backward3d_norm_multi; feat / gout / gf [B][C][V], sparse [B][V]): launch 1 without c' (each channel's
+// constant term is coef H_{0,c}), launch 2 is step3d_shared_kernel (w' and coef read once for the C channels), launch 3 the transposed
+// multi-channel instance or backward3d()'s per-step launches channel by channel, launch 4 the MULTI instance of gate_grad_norm3d_kernel
+// (dW' summed over c then t, D = sum_c dC_c H_{0,c}), launch 5 unchanged.
 #include "cspn3d_voxel.h"
 
 namespace cspn {
 
 namespace {
 
-// the fold of fold3d_kernel with w' laid out as a gate tensor: wp [B][26][V], cp = c' and kp = coef [B][V]
-template <int VEC, class GT>
+// the fold of fold3d_kernel with w' laid out as a gate tensor: wp [B][26][V], cp = c' and kp = coef [B][V].  CP = false: no c' (feat and cp
+// are not touched): what C value channels share, each forming its own coef H_0
+template <int VEC, class GT, bool CP = true>
 __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ feat,
                                                            const float* __restrict__ sparse, float* __restrict__ wp,
                                                            float* __restrict__ cp, float* __restrict__ kp, int B, int D, int H, int W,
@@ -64,7 +70,7 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
             if (norm != CSPN_NORM_NONE) G[k][i] = G[k][i] / S[i];
             sigma[i] += G[k][i];
         }
-    load_vec<VEC>(feat + vox, h0);
+    if constexpr (CP) load_vec<VEC>(feat + vox, h0);
     if (sparse) {
         load_vec<VEC>(sparse + vox, m);
 #pragma unroll
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
     for (int i = 0; i < VEC; ++i) {
         const float om = 1.f - m[i];
         coef[i] = (norm == CSPN_NORM_NONE) ? m[i] : om * (1.f - sigma[i]) + m[i];
-        c[i] = coef[i] * h0[i];
+        if constexpr (CP) c[i] = coef[i] * h0[i];
         if (sparse) {
 #pragma unroll
             for (int k = 0; k < 26; ++k) G[k][i] *= om;
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
     float* o = wp + (size_t)p.b * 26 * V + p.r;
 #pragma unroll
     for (int k = 0; k < 26; ++k) store_vec<VEC>(o + (size_t)k * V, G[k]);
-    store_vec<VEC>(cp + vox, c);
+    if constexpr (CP) store_vec<VEC>(cp + vox, c);
     store_vec<VEC>(kp + vox, coef);
 }
 
@@ -93,40 +99,56 @@ __global__ __launch_bounds__(256) void fold_norm3d_kernel(const store_t<GT>* __r
 // A_n = gout, A_t = ahist + (t-1) total), then the fold's adjoint at the voxel:
 //   gf (may be NULL) = A_0 + dC coef;  planes (may be NULL: then hist is not read) = the consumer-sited dG_k [B][26][V] in float32, or with
 //   NONE the guidance gradient u dW'_k itself, in the guidance's type
-template <int VEC, class GT>
+// MULTI: C value channels share the gates (feat, gout, gf and every level [B][C][V]; kp, sparse and the planes stay [B][V]): dW' is summed
+// over the channels in the same registers, channel by channel and level by level inside one (a fixed order: bitwise reproducible), dC_c
+// and grad_feat_c are each channel's own, and the fold's adjoint takes D = sum_c dC_c H_{0,c} where one channel has dC H_0
+template <int VEC, class GT, bool MULTI = false>
 __global__ __launch_bounds__(256) void gate_grad_norm3d_kernel(const store_t<GT>* __restrict__ g, const float* __restrict__ feat,
                                                                 const float* __restrict__ sparse, const float* __restrict__ kp,
                                                                 const float* __restrict__ hist, const float* __restrict__ ahist,
                                                                 const float* __restrict__ gout, const float* __restrict__ a0,
                                                                 void* __restrict__ planes, float* __restrict__ gf, int B, int D,
-                                                                int H, int W, int n_iter, int norm) {
+                                                                int H, int W, int n_iter, int norm, int C = 1) {
     const Pos<VEC> p(B, D, H, W);
     if (!p.ok) return;
-    const size_t V = (size_t)D * H * W, total = (size_t)B * V, vol = (size_t)p.b * V, vox = vol + p.r;
-    float acc[26][VEC], dC[VEC];
+    const int nch = MULTI ? C : 1;
+    const size_t V = (size_t)D * H * W, total = (size_t)B * nch * V, vox = (size_t)p.b * V + p.r;   // vox: the voxel in the shared planes
+    float acc[26][VEC], dC[VEC], Dh[VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) dC[i] = 0.f;
+    for (int i = 0; i < VEC; ++i) Dh[i] = 0.f;
 #pragma unroll
     for (int k = 0; k < 26; ++k)
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[k][i] = 0.f;
 #pragma unroll 1
-    for (int t = 0; t < n_iter; ++t) {
-        const float* at = t == n_iter - 1 ? gout : ahist + (size_t)t * total;   // A_{t+1}
-        float a[VEC];
-        load_vec<VEC>(at + vox, a);
+    for (int c = 0; c < nch; ++c) {
+        const size_t vol = ((size_t)p.b * nch + c) * V, cvox = vol + p.r;   // the channel's volume, the voxel in it
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) dC[i] += a[i];
-        if (!planes) continue;
-        gate_grad_level3<VEC>(acc, a, (t == 0 ? feat : hist + (size_t)(t - 1) * total) + vol, p, D, H, W);
-    }
-    if (gf) {
-        float a[VEC], coef[VEC];
-        load_vec<VEC>(a0 + vox, a);
-        load_vec<VEC>(kp + vox, coef);
+        for (int i = 0; i < VEC; ++i) dC[i] = 0.f;
+#pragma unroll 1
+        for (int t = 0; t < n_iter; ++t) {
+            const float* at = t == n_iter - 1 ? gout : ahist + (size_t)t * total;   // A_{t+1}
+            float a[VEC];
+            load_vec<VEC>(at + cvox, a);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) a[i] = fmaf(dC[i], coef[i], a[i]);
-        store_vec<VEC>(gf + vox, a);
+            for (int i = 0; i < VEC; ++i) dC[i] += a[i];
+            if (!planes) continue;
+            gate_grad_level3<VEC>(acc, a, (t == 0 ? feat : hist + (size_t)(t - 1) * total) + vol, p, D, H, W);
+        }
+        if (gf) {
+            float a[VEC], coef[VEC];
+            load_vec<VEC>(a0 + cvox, a);
+            load_vec<VEC>(kp + vox, coef);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) a[i] = fmaf(dC[i], coef[i], a[i]);
+            store_vec<VEC>(gf + cvox, a);
+        }
+        if (MULTI && planes && norm != CSPN_NORM_NONE) {
+            float h0[VEC];
+            load_vec<VEC>(feat + cvox, h0);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) Dh[i] = fmaf(dC[i], h0[i], Dh[i]);
+        }
     }
     if (!planes) return;
     float u[VEC], h0[VEC];
@@ -146,7 +168,7 @@ __global__ __launch_bounds__(256) void gate_grad_norm3d_kernel(const store_t<GT>
         }
         return;
     }
-    load_vec<VEC>(feat + vox, h0);
+    if constexpr (!MULTI) load_vec<VEC>(feat + vox, h0);
     const store_t<GT>* gb = g + (size_t)p.b * 26 * V;
     float S[VEC], T[VEC];
     unsigned pos[VEC], neg[VEC];   // bit k: G_k > 0 / G_k < 0 (a NaN gate sets neither: its dG is NaN through S)
@@ -158,7 +180,8 @@ __global__ __launch_bounds__(256) void gate_grad_norm3d_kernel(const store_t<GT>
         load_G<VEC, GT>(gb, V, k, p, D, H, W, norm, G);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-            acc[k][i] = u[i] * (acc[k][i] - dC[i] * h0[i]);   // dwb_k
+            if constexpr (MULTI) acc[k][i] = u[i] * (acc[k][i] - Dh[i]);   // dwb_k
+            else acc[k][i] = u[i] * (acc[k][i] - dC[i] * h0[i]);
             S[i] += fabsf(G[i]);
             T[i] = fmaf(acc[k][i], G[i], T[i]);
             pos[i] |= (G[i] > 0.f ? 1u : 0u) << k;
@@ -262,7 +285,88 @@ int backward3d_norm(const void* g, int gdt, const float* feat, const float* spar
             }
             void* planes = !gg ? nullptr : (norm == CSPN_NORM_NONE ? gg : (void*)wp);
             hipLaunchKernelGGL((gate_grad_norm3d_kernel<VEC, GT>), grid, block, 0, st, gs, feat, sparse, kp, hist, ahist, gout, a0, planes, gf, B, D, H, W,
-                               n_iter, norm);
+                               n_iter, norm, 1);
+            if (int e = check_launch("gate_grad_norm3d_kernel")) return e;
+            if (gg && norm != CSPN_NORM_NONE) {
+                hipLaunchKernelGGL((gather_guidance3d_kernel<VEC, GT>), grid, block, 0, st, wp, gs, (store_t<GT>*)gg, B, D, H, W, norm);
+                if (int e = check_launch("gather_guidance3d_kernel")) return e;
+            }
+            return 0;
+        });
+    });
+}
+
+// ---- C value channels on shared guidance (feat / gout / gf [B][C][V], sparse NULL or [B][V]) ----
+
+// the fold the channels share, once per call: w' [B][26][V] and coef [B][V]; each channel forms its own constant term coef H_{0,c}
+int fold3d_shared(const void* g, int gdt, const float* sparse, float* wp, float* kp, int B, int D, int H, int W, int norm, bool vec, hipStream_t st) {
+    const size_t total = (size_t)B * D * H * W;
+    const dim3 grid((unsigned)((total / (vec ? 4 : 1) + 255) / 256)), block(256);
+    with_gate_type(gdt, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_vec(vec, [&](auto v) {
+            constexpr int VEC = decltype(v)::value;
+            hipLaunchKernelGGL((fold_norm3d_kernel<VEC, GT, false>), grid, block, 0, st, (const store_t<GT>*)g, (const float*)nullptr, sparse, wp,
+                               (float*)nullptr, kp, B, D, H, W, norm);
+            return 0;
+        });
+    });
+    return check_launch("fold_norm3d_kernel");
+}
+
+// w' / dG (26 planes) and coef, then the workspace of backward3d() on C channels: the levels H_1 .. H_{n-1}, A_1 .. A_{n-1}, each [B][C][V],
+// A_0 and what the persistent kernel wants
+size_t backward3d_norm_multi_workspace(int B, int C, int D, int H, int W, int n_iter) {
+    const size_t total = (size_t)B * D * H * W;
+    return planes_bytes(total, 26) + planes_bytes(total, 1) + backward3d_workspace(B, D, H, W, n_iter, C);
+}
+
+// where the adjoint sweep of all channels is ONE launch of the transposed multi-channel instance: backward3d()'s fused multi sweep
+bool backward3d_norm_multi_fused(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, const void* gg, const float* gf,
+                                 int B, int C, int D, int H, int W, int n_iter, const void* ws) {
+    return quads_ok(W, gdt, {g, gg}, {feat, sparse, gout, gf, ws}) && n_iter >= 3 && persistent3d_multi_supported(B, C, D, H, W, n_iter - 1) &&
+           persistent3d_multi_supported(B, C, D, H, W, n_iter);
+}
+
+// backward3d_norm() for C > 1 channels: gg is the sum over the channels, written once per element
+int backward3d_norm_multi(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, void* gg, float* gf, int B, int C,
+                          int D, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only) {
+    const size_t V = (size_t)D * H * W, total = (size_t)B * V, level = total * C;
+    float* wp = (float*)ws;
+    float* kp = (float*)((char*)ws + planes_bytes(total, 26));
+    char* levels = (char*)kp + planes_bytes(total, 1);   // the workspace of backward3d()
+    const Backward3dLayout L(B, C, D, H, W, n_iter, 0);
+    float* hist = (float*)(levels + L.hist);     // H_1 .. H_{n-1}
+    float* ahist = (float*)(levels + L.ahist);   // A_1 .. A_{n-1}
+    float* a0 = (float*)(levels + L.a0);
+    void* pws = levels + L.pers;
+    const bool vec = quads_ok(W, gdt, {g, gg}, {feat, sparse, gout, gf, ws});
+    const bool fused = !stepwise_only && backward3d_norm_multi_fused(g, gdt, feat, sparse, gout, gg, gf, B, C, D, H, W, n_iter, ws);
+    const dim3 grid((unsigned)((total / (vec ? 4 : 1) + 255) / 256)), block(256);
+    if (int e = fold3d_shared(g, gdt, sparse, wp, kp, B, D, H, W, norm, vec, st)) return e;
+    if (gg) {   // H_1 .. H_{n-1} of every channel: one launch per level, w' and coef read once for the C channels
+        const float* src = feat;
+        for (int t = 1; t < n_iter; ++t) {
+            float* dst = hist + (size_t)(t - 1) * level;
+            if (int e = step3d_shared(wp, kp, feat, src, dst, B, C, D, H, W, vec, st)) return e;
+            src = dst;
+        }
+    }
+    // the adjoint levels on w' as the gates of the Paddle contract: the transposed multi-channel instance (w' resident across the steps and
+    // the channels), else backward3d()'s per-step launches, channel by channel
+    if (fused) {
+        if (int e = persistent3d_run(wp, gout, a0, ahist, n_iter - 1, -1, true, B, D, H, W, n_iter, pws, st, P3Options(), C)) return e;
+    } else if (int e = backward3d(wp, feat, gout, nullptr, gf ? a0 : nullptr, B, D, H, W, n_iter, levels, st, true, C)) {
+        return e;
+    }
+    return with_gate_type(gdt, [&](auto gt) -> int {
+        using GT = typename decltype(gt)::type;
+        return with_vec(vec, [&](auto v) -> int {
+            constexpr int VEC = decltype(v)::value;
+            const store_t<GT>* gs = (const store_t<GT>*)g;
+            void* planes = !gg ? nullptr : (norm == CSPN_NORM_NONE ? gg : (void*)wp);
+            hipLaunchKernelGGL((gate_grad_norm3d_kernel<VEC, GT, true>), grid, block, 0, st, gs, feat, sparse, kp, hist, ahist, gout, a0, planes, gf, B, D, H,
+                               W, n_iter, norm, C);
             if (int e = check_launch("gate_grad_norm3d_kernel")) return e;
             if (gg && norm != CSPN_NORM_NONE) {
                 hipLaunchKernelGGL((gather_guidance3d_kernel<VEC, GT>), grid, block, 0, st, wp, gs, (store_t<GT>*)gg, B, D, H, W, norm);

@@ -154,8 +154,9 @@ __device__ __forceinline__ v4f ldq_sc1(const float4* base, unsigned byte_off) { 
 // profiles/r03_ubench_dma.txt), while HBM is otherwise idle; the next prologue reads them back with ds_read_b128 and requests
 // 52 - NPRE quads from memory instead of 52.  A wave reads only what it requested itself (its vmcnt wait makes the data visible
 // to it: no barrier), laid out [quad][wave][lane] so that one request fills 1 KiB.
-template <bool ADJ, bool HASC>
-struct Pre3 { static constexpr int N = ADJ ? 0 : (XG == 8 ? (HASC ? 10 : 12) : 12); };
+// (HASC && MULTI keeps coef beside c' in LDS, 16 KB more: two parked quads fewer)
+template <bool ADJ, bool HASC, bool MULTI = false>
+struct Pre3 { static constexpr int N = ADJ ? 0 : (XG == 8 ? (HASC ? (MULTI ? 8 : 10) : 12) : 12); };
 
 __device__ __forceinline__ void lds_dma16(unsigned byte_off, const float* base, unsigned lds_dst) {   // lds_dst: wave-uniform
     unsigned keep;
@@ -169,6 +170,10 @@ __device__ __forceinline__ void lds_dma16(unsigned byte_off, const float* base, 
 // while the n_iter steps are run for one channel after the other (only level 0 is re-read per channel, 4 B/voxel against 104)
 // NRM: `gate` holds the demo's RAW guide (reference cspn_paddle/demo.py:24,34-36,47-49): the resident gates of every voxel inside the
 // volume are divided by their abs-sum in the registers (cspn_gate_norm.h, the stand-alone normaliser's arithmetic), no HBM bytes for it
+// HASC && MULTI: the normalising / masked modes for C channels on shared guidance (fold3d_shared of cspn3d_norm_backward.hip writes w' as a
+// gate tensor [B][26][V] and coef [B][V]): `cprime` holds coef, which waits in LDS (s_k) for the whole chunk beside the resident w'; the
+// constant term of a channel, coef x its level 0, is formed from the level-0 quads the thread loads anyway -- at the top of the chunk for
+// channel 0, at the channel switch for the others -- and waits in s_c as c' does for one channel: the step itself is the HASC instance's
 // G16 (0 float32, CSPN_DTYPE_F16, CSPN_DTYPE_BF16): `gate` holds 16-bit gates (or, with NRM, the 16-bit raw guide).  Only the chunk
 // prologue differs: a thread's two quads of a plane are two 8-byte loads under the float32 guards, and after the wait each plane's packed
 // pair is widened exactly into the eight gate registers it was to fill (plane by plane: the pair dies as its floats are born, so the peak
@@ -185,7 +190,8 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr unsigned GB = G16 ? 2u : 4u;   // bytes of a stored gate
     __shared__ __attribute__((aligned(16))) float lds[2 * LTILE];
     __shared__ __attribute__((aligned(16))) float4 s_c[HASC ? 2 * NTP : 1];   // c' of the thread's two quads, [quad][thread]
-    constexpr int NPRE = G16 ? 0 : Pre3<ADJ, HASC>::N;
+    __shared__ __attribute__((aligned(16))) float4 s_k[HASC && MULTI ? 2 * NTP : 1];   // coef of the thread's two quads, [quad][thread]
+    constexpr int NPRE = G16 ? 0 : Pre3<ADJ, HASC, MULTI>::N;
     __shared__ __attribute__((aligned(16))) float4 s_pre[NPRE ? NPRE * NTP : 1];   // parked gate quads, [quad][thread] (addressed by hand)
     __shared__ int s_bail;
     unsigned* err = sync + MAX_WG + 64 * 9;  // [1] (the words in front of it belonged to the flag exchange of the first version)
@@ -381,8 +387,11 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 v4f cq0, cq1;
                 if (HASC) {
                     const float* cb = cprime;
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(cq0) : "v"(fo0), "s"(cb) : "memory");
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(cq1) : "v"(fo1), "s"(cb) : "memory");
+                    // (MULTI: coef is one plane per volume, [B][V], where the value tensors are [B][C][V])
+                    const unsigned ko0 = MULTI ? (in0 ? (unsigned)(b0 * (int)V + row + xq0) * 4u : 0u) : fo0;
+                    const unsigned ko1 = MULTI ? (in1 ? (unsigned)(b1 * (int)V + row + xq1) * 4u : 0u) : fo1;
+                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(cq0) : "v"(ko0), "s"(cb) : "memory");
+                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(cq1) : "v"(ko1), "s"(cb) : "memory");
                 }
                 // ---- the 26 gates of the thread's eight voxels: read once, kept in registers for all steps
                 v4f w[26][2];
@@ -442,11 +451,25 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     if (HASC) {   // (outside the volume c' = 0: such voxels keep the value 0)
                         asm volatile("" : "+v"(cq0), "+v"(cq1));
                         const v4f zero = {0.f, 0.f, 0.f, 0.f};
-                        const v4f c0 = in0 ? cq0 : zero, c1 = in1 ? cq1 : zero;
                         // (explicit 32-bit LDS addresses: with more than 64 KB of LDS the compiler's base + immediate-offset
                         // addressing went wrong, profiles/r02_perf_notes.md)
                         const unsigned ca = lds_addr(s_c) + (unsigned)tc * 16u;
-                        asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:%3" : : "v"(ca), "v"(c0), "v"(c1), "n"(NTP * 16) : "memory");
+                        if (MULTI) {
+                            // coef stays for the chunk; channel 0's constant term from the level-0 quads just loaded.  One quad at a time,
+                            // the product in the registers coef came in: nothing more is live here than in the one-channel instance
+                            const unsigned ka = lds_addr(s_k) + (unsigned)tc * 16u;
+                            cq0 = in0 ? cq0 : zero;
+                            asm volatile("ds_write_b128 %0, %1" : : "v"(ka), "v"(cq0) : "memory");
+                            cq0 = in0 ? cq0 * f0 : zero;
+                            asm volatile("ds_write_b128 %0, %1" : : "v"(ca), "v"(cq0) : "memory");
+                            cq1 = in1 ? cq1 : zero;
+                            asm volatile("ds_write_b128 %0, %1 offset:%2" : : "v"(ka), "v"(cq1), "n"(NTP * 16) : "memory");
+                            cq1 = in1 ? cq1 * f1 : zero;
+                            asm volatile("ds_write_b128 %0, %1 offset:%2" : : "v"(ca), "v"(cq1), "n"(NTP * 16) : "memory");
+                        } else {
+                            const v4f c0 = in0 ? cq0 : zero, c1 = in1 ? cq1 : zero;
+                            asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:%3" : : "v"(ca), "v"(c0), "v"(c1), "n"(NTP * 16) : "memory");
+                        }
                     }
 #pragma unroll
                     for (int j = 0; j < NSHT; ++j) asm volatile("" : "+v"(fs[j]));
@@ -563,6 +586,16 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     for (int i = 0; i < 8; ++i) {
                         lds[o + i] = own8[i];
                         lds[LTILE + o + i] = own8[i];
+                    }
+                    if (HASC) {   // this channel's constant term: coef x its level 0 (both zero outside the volume), one quad at a time
+                        const unsigned ka = lds_addr(s_k) + (unsigned)tid_ * 16u, ca = lds_addr(s_c) + (unsigned)tid_ * 16u;
+                        v4f kq;
+                        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(kq) : "v"(ka) : "memory");
+                        kq = kq * v4f{q0.x, q0.y, q0.z, q0.w};
+                        asm volatile("ds_write_b128 %0, %1" : : "v"(ca), "v"(kq) : "memory");
+                        asm volatile("ds_read_b128 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(kq) : "v"(ka), "n"(NTP * 16) : "memory");
+                        kq = kq * v4f{q1.x, q1.y, q1.z, q1.w};
+                        asm volatile("ds_write_b128 %0, %1 offset:%2" : : "v"(ca), "v"(kq), "n"(NTP * 16) : "memory");
                     }
 #pragma unroll 1
                     for (int i = tid_; i < NSH; i += NTP) {
@@ -852,7 +885,7 @@ int resident_wgs() {
         int occ = WG_PER_CU;
         const void* fns[] = {(const void*)cspn3d_persistent_kernel<false, false>, (const void*)cspn3d_persistent_kernel<false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false>, (const void*)cspn3d_persistent_kernel<false, false, false, true>,
-                             (const void*)cspn3d_persistent_kernel<true, false, false, true>,
+                             (const void*)cspn3d_persistent_kernel<true, false, false, true>, (const void*)cspn3d_persistent_kernel<false, true, false, true>,
                              (const void*)cspn3d_persistent_kernel<false, false, false, false, true>,
                              (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_F16>,
                              (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_BF16>,
@@ -941,11 +974,12 @@ size_t persistent3d_workspace(int B, int D, int H, int W) {
 }
 
 // adjoint: the transposed operator (backward); levels: volume lv0 + it * lvs receives the result of step it < n_iter;
-// cprime != nullptr: gate holds the 26 folded planes [26][B][V] and cprime the constant term (normalising / masked modes)
+// cprime != nullptr: gate holds the 26 folded planes [26][B][V] and cprime the constant term (normalising / masked modes); with shared
+// (C channels on shared guidance) gate holds w' as a gate tensor [B][26][V] and cprime coef [B][V]
 // gdt != 0: gate holds fp16 / bf16 gates (forward, MULTI and NRM instances; the caller never asks for another)
 static int persistent3d_launch(const void* gate_, const float* feat, const float* cprime, float* out, float* levels, int lv0, int lvs,
                                bool adjoint, int B, int D, int H, int W, int n_iter, void* ws, hipStream_t st, const P3Options& opt, int C = 1,
-                               bool nrm = false, int gdt = 0) {
+                               bool nrm = false, int gdt = 0, bool shared = false) {
     const float* gate = (const float*)gate_;   // (the kernel argument's type; a 16-bit instance reads it as its own)
     if (gdt && (adjoint || cprime || opt.mute >= 0)) { set_error("persistent 3D kernel: no 16-bit instance of this variant"); return CSPN_E_UNSUPPORTED; }
     Geo3 g = make_geo3(B, D, H, W, n_iter, opt.placement);
@@ -954,8 +988,9 @@ static int persistent3d_launch(const void* gate_, const float* feat, const float
     g.lv0 = lv0;
     g.lvs = lvs;
     const size_t total = (size_t)B * D * H * W;
-    g.gps = cprime ? (long long)total : (long long)(total / B);
-    g.gbs = cprime ? (long long)(total / B) : 26LL * (long long)(total / B);
+    const bool planes_first = cprime && !shared;   // [26][B][V]
+    g.gps = planes_first ? (long long)total : (long long)(total / B);
+    g.gbs = planes_first ? (long long)(total / B) : 26LL * (long long)(total / B);
     float* scratch = (float*)ws;
     unsigned* sync = (unsigned*)((char*)(scratch + 2 * total) + XBYTES);
     // tags of an earlier call in this workspace must not validate: clear the published boundaries this launch indexes
@@ -1008,6 +1043,7 @@ static int persistent3d_launch(const void* gate_, const float* feat, const float
                                                : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true, false, CSPN_DTYPE_BF16>
                                                        : (const void*)cspn3d_persistent_kernel<false, false, false, false, false, CSPN_DTYPE_BF16>)
                    : nrm ? (const void*)cspn3d_persistent_kernel<false, false, false, false, true>
+                   : shared ? (const void*)cspn3d_persistent_kernel<false, true, false, true>
                    : cprime ? (const void*)cspn3d_persistent_kernel<false, true>
                    : adjoint ? (C > 1 ? (const void*)cspn3d_persistent_kernel<true, false, false, true> : (const void*)cspn3d_persistent_kernel<true, false>)
                    : C > 1 ? (const void*)cspn3d_persistent_kernel<false, false, false, true>
@@ -1063,6 +1099,12 @@ int persistent3d_run(const void* gate, const float* feat, float* out, float* lev
 int persistent3d_forward_folded(const float* wf, const float* feat, float* out, int B, int D, int H, int W, int n_iter, void* ws,
                                 hipStream_t st) {
     return persistent3d_launch(wf, feat, wf + 26 * (size_t)B * D * H * W, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options());
+}
+
+// the normalising / masked modes for C channels on shared guidance: wp = w' [B][26][V], kp = coef [B][V] (fold3d_shared)
+int persistent3d_forward_shared(const float* wp, const float* kp, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                                void* ws, hipStream_t st) {
+    return persistent3d_launch(wp, feat, kp, out, nullptr, 0, 0, false, B, D, H, W, n_iter, ws, st, P3Options(), C, false, 0, true);
 }
 
 // C value channels per volume on shared gates (feat, out: [B][C][V]; the Paddle contract): one gate load per chunk for all of them

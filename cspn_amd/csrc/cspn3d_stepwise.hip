@@ -5,6 +5,7 @@
 // kernel source NOT in the reference tree -> parity unpinned; semantics = the 3D
 // generalisation of cspn_pytorch/models/cspn.py:42-172, see oracle/cspn_oracle.c).
 // Channel order and the neighbourhood helpers: cspn3d_voxel.h.
+// At the end: the normalising / masked modes for C value channels on shared guidance (step3d_shared_kernel, forward3d_norm_multi).
 #include "cspn3d_voxel.h"
 
 namespace cspn {
@@ -234,6 +235,98 @@ int stepwise3d_forward(const void* g, const float* feat, const float* sparse, fl
         src = dst;
     }
     return check_launch("step3d_kernel");
+}
+
+// ---- C value channels on shared guidance in the normalising / masked modes (feat / out [B][C][V], sparse NULL or [B][V]) ----
+
+// one step of all C channels on the shared folded planes wp = w' [B][26][V] and kp = coef [B][V] (fold3d_shared):
+// hout_c(p) = coef(p) h0_c(p) + sum_k w'_k(p) hin_c(p + off_k).  The 26 x VEC weights and coef of the thread's voxels are loaded once and
+// stay in registers while the channels go by: 108 + 12 C bytes a voxel where C single-channel steps move 116 C
+namespace {
+template <int VEC>
+__global__ __launch_bounds__(256) void step3d_shared_kernel(const float* __restrict__ wp, const float* __restrict__ kp, const float* __restrict__ h0,
+                                                             const float* __restrict__ hin, float* __restrict__ hout, int B, int C, int D, int H,
+                                                             int W) {
+    const Pos<VEC> p(B, D, H, W);
+    if (!p.ok) return;
+    const size_t V = (size_t)D * H * W;
+    const float* wb = wp + (size_t)p.b * 26 * V + p.r;
+    float w[26][VEC], coef[VEC];
+#pragma unroll
+    for (int k = 0; k < 26; ++k) load_vec<VEC>(wb + (size_t)k * V, w[k]);
+    load_vec<VEC>(kp + (size_t)p.b * V + p.r, coef);
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        const size_t vol = ((size_t)p.b * C + c) * V;
+        float acc[VEC];
+        load_vec<VEC>(h0 + vol + p.r, acc);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] *= coef[i];
+#pragma unroll
+        for (int n = 0; n < 9; ++n) {
+            float h[VEC + 2];
+            load_row3<VEC>(hin + vol, p, row_dz3(n), row_dy3(n), D, H, W, h);
+            for_taps3(n, [&](int k, int dx) {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc[i] = fmaf(w[k][i], h[1 + i + dx], acc[i]);
+            });
+        }
+        store_vec<VEC>(hout + vol + p.r, acc);
+    }
+}
+}  // namespace
+
+// vec: W % 4 == 0 and 16-byte aligned tensors (four voxels a thread), else one voxel a thread
+int step3d_shared(const float* wp, const float* kp, const float* h0, const float* hin, float* hout, int B, int C, int D, int H, int W, bool vec,
+                  hipStream_t st) {
+    const size_t total = (size_t)B * D * H * W;
+    const dim3 grid((unsigned)((total / (vec ? 4 : 1) + 255) / 256)), block(256);
+    with_vec(vec, [&](auto v) {
+        hipLaunchKernelGGL(step3d_shared_kernel<decltype(v)::value>, grid, block, 0, st, wp, kp, h0, hin, hout, B, C, D, H, W);
+        return 0;
+    });
+    return check_launch("step3d_shared_kernel");
+}
+
+// w' (26 planes), coef, two levels [B][C][V] (the ping-pong of the per-step route), what the persistent kernel wants
+static size_t level_bytes(int B, int C, int D, int H, int W) { return round256(sizeof(float) * (size_t)B * C * D * H * W); }
+
+size_t forward3d_norm_multi_workspace(int B, int C, int D, int H, int W, int n_iter) {
+    (void)n_iter;
+    const size_t total = (size_t)B * D * H * W;
+    return round256(26 * sizeof(float) * total) + round256(sizeof(float) * total) + 2 * level_bytes(B, C, D, H, W) + persistent3d_workspace(B, D, H, W);
+}
+
+// where the steps of all channels are ONE launch of the persistent kernel on the resident w' and coef
+bool forward3d_norm_multi_fused(const void* g, int gdt, const float* feat, const float* sparse, const float* out, int B, int C, int D, int H, int W,
+                                int n_iter, const void* ws) {
+    return quads_ok(W, gdt, {g}, {feat, sparse, out, ws}) && persistent3d_multi_supported(B, C, D, H, W, n_iter);
+}
+
+// every mode (NONE without a mask: coef = 0); algo as stepwise3d_forward
+int forward3d_norm_multi(const void* g, int gdt, const float* feat, const float* sparse, float* out, int B, int C, int D, int H, int W, int n_iter,
+                         int norm, void* ws, hipStream_t st, int algo) {
+    const size_t total = (size_t)B * D * H * W;
+    float* wp = (float*)ws;
+    float* kp = (float*)((char*)ws + round256(26 * sizeof(float) * total));
+    char* lev = (char*)kp + round256(sizeof(float) * total);
+    float* pp[2] = {(float*)lev, (float*)(lev + level_bytes(B, C, D, H, W))};
+    void* pws = lev + 2 * level_bytes(B, C, D, H, W);
+    const bool vec = quads_ok(W, gdt, {g}, {feat, sparse, out, ws});
+    const bool fused = forward3d_norm_multi_fused(g, gdt, feat, sparse, out, B, C, D, H, W, n_iter, ws);
+    if (algo == 2 && !fused) {
+        set_error("persistent 3D kernel does not take this call (needs W %% 4 == 0, 16-byte aligned tensors, 2 <= n_iter <= 60, a chunk per device)");
+        return CSPN_E_UNSUPPORTED;
+    }
+    if (int e = fold3d_shared(g, gdt, sparse, wp, kp, B, D, H, W, norm, vec, st)) return e;
+    if (algo != 1 && fused) return persistent3d_forward_shared(wp, kp, feat, out, B, C, D, H, W, n_iter, pws, st);
+    const float* src = feat;
+    for (int it = 0; it < n_iter; ++it) {
+        float* dst = (it == n_iter - 1) ? out : pp[it & 1];
+        if (int e = step3d_shared(wp, kp, feat, src, dst, B, C, D, H, W, vec, st)) return e;
+        src = dst;
+    }
+    return 0;
 }
 
 }  // namespace cspn

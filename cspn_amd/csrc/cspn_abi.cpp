@@ -707,6 +707,126 @@ int cspn3d_backward_norm_g16(const void* guidance, int gate_dtype, const float* 
                                  n_iter, norm_type, algo, ws, ws_bytes, stream);
 }
 
+// ---- the same modes for C channels on shared guidance (feat / out / grad_out / grad_feat [B,C,D,H,W], sparse NULL or [B,1,D,H,W]) ----
+static bool norm_multi_query_ok(int B, int C, int D, int H, int W, int n_iter, int norm_type) {
+    return B > 0 && C > 0 && D > 0 && H > 0 && W > 0 && n_iter > 0 && norm_type >= CSPN_NORM_8SUM && norm_type <= CSPN_NORM_NONE;
+}
+
+size_t cspn3d_forward_norm_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter, int norm_type, int has_sparse) {
+    if (!norm_multi_query_ok(B, C, D, H, W, n_iter, norm_type)) return 0;
+    if (C == 1) return forward3d_workspace(B, D, H, W, n_iter, norm_type, has_sparse != 0);
+    return forward3d_norm_multi_workspace(B, C, D, H, W, n_iter);   // (covers the Paddle contract's persistent3d_workspace too)
+}
+
+// one query for both gate types: C = 1 is cspn3d_backward_norm_g16_workspace_bytes (the float32 twin's, and for NONE without a mask the
+// widened copy of the Paddle contract's transposed sweep more); NONE without a mask is cspn3d_backward_multi_g16_workspace_bytes
+size_t cspn3d_backward_norm_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter, int norm_type, int has_sparse) {
+    if (!norm_multi_query_ok(B, C, D, H, W, n_iter, norm_type)) return 0;
+    if (C == 1) return backward3d_norm_need(B, D, H, W, n_iter, norm_type, has_sparse != 0, CSPN_DTYPE_F16);
+    if (norm_type == CSPN_NORM_NONE && !has_sparse) return backward3d_workspace(B, D, H, W, n_iter, C, CSPN_DTYPE_F16);
+    return backward3d_norm_multi_workspace(B, C, D, H, W, n_iter);
+}
+
+// the checks of cspn3d_forward_norm_multi_f32 (gdt 0) and cspn3d_forward_norm_multi_g16, then the engine
+static int forward3d_norm_multi_entry(const char* what, const void* guidance, int gdt, const float* feat, const float* sparse, float* out, int B,
+                                      int C, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes,
+                                      cspn_stream_t stream) {
+    if (int e = check_shape("BCDHW", {B, C, D, H, W})) return e;
+    if (B == 0) return 0;
+    if (C == 1) return forward3d_entry(guidance, gdt, feat, sparse, out, B, D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
+    const size_t V = (size_t)B * D * H * W;
+    if (int e = check_index32((long long)V, 27)) return e;
+    if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
+    if (norm_type < CSPN_NORM_8SUM || norm_type > CSPN_NORM_NONE) {
+        set_error("%s: norm_type must be CSPN_NORM_8SUM, CSPN_NORM_8SUM_ABS or CSPN_NORM_NONE (got %d)", what, norm_type);
+        return CSPN_E_BADARG;
+    }
+    if (int e = async_failure_of_earlier_call()) return e;
+    const size_t need = n_iter <= 0 ? 0 : forward3d_norm_multi_workspace(B, C, D, H, W, n_iter);
+    if (int e = check_common(guidance, feat, out, n_iter, norm_type, ws, ws_bytes, need)) return e;
+    const size_t vb = sizeof(float) * V * C, sb = sizeof(float) * V, gb = 26 * V * gate_bytes(gdt);
+    if (kxk_overlaps(out, vb, {{guidance, gb}, {feat, vb}, {sparse, sb}, {ws, need}})) {
+        set_error("%s: the output must not overlap an input or the workspace", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) return identity_copy(out, feat, V * C, st);
+    // the Paddle contract: cspn3d_forward_multi_f32 / _g16 where it runs (the persistent kernel on the gates as given), bitwise
+    if (norm_type == CSPN_NORM_NONE && !sparse && algo != CSPN_ALGO3D_STEPWISE && quads_ok(W, gdt, {guidance}, {feat, out, ws}) &&
+        persistent3d_multi_supported(B, C, D, H, W, n_iter))
+        return persistent3d_forward_multi(guidance, feat, out, B, C, D, H, W, n_iter, ws, st, gdt);
+    return forward3d_norm_multi(guidance, gdt, feat, sparse, out, B, C, D, H, W, n_iter, norm_type, ws, st, algo);
+}
+
+int cspn3d_forward_norm_multi_f32(const float* guidance, const float* feat, const float* sparse, float* out, int B, int C, int D, int H, int W,
+                                  int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return forward3d_norm_multi_entry("cspn3d_forward_norm_multi_f32", guidance, 0, feat, sparse, out, B, C, D, H, W, n_iter, norm_type, algo, ws,
+                                      ws_bytes, stream);
+}
+
+int cspn3d_forward_norm_multi_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, float* out, int B, int C, int D,
+                                  int H, int W, int n_iter, int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_forward_norm_multi_g16", gate_dtype, guidance, nullptr)) return e;
+    return forward3d_norm_multi_entry("cspn3d_forward_norm_multi_g16", guidance, gate_dtype, feat, sparse, out, B, C, D, H, W, n_iter, norm_type,
+                                      algo, ws, ws_bytes, stream);
+}
+
+// the checks of cspn3d_backward_norm_multi_f32 (gdt 0) and cspn3d_backward_norm_multi_g16, in backward3d_norm_entry's order, then the engine
+static int backward3d_norm_multi_entry(const char* what, const void* guidance, int gdt, const float* feat, const float* sparse,
+                                       const float* grad_out, void* grad_guidance, float* grad_feat, int B, int C, int D, int H, int W, int n_iter,
+                                       int norm_type, int algo, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = check_shape("BCDHW", {B, C, D, H, W})) return e;
+    if (B == 0) return 0;
+    if (C == 1)
+        return backward3d_norm_entry(what, guidance, gdt, feat, sparse, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, norm_type, algo, ws,
+                                     ws_bytes, stream);
+    const size_t V = (size_t)B * D * H * W;
+    if (int e = check_index32((long long)V, 27)) return e;
+    if (algo < CSPN_ALGO3D_AUTO || algo > CSPN_ALGO3D_PERSISTENT) { set_error("unknown 3D algo %d", algo); return CSPN_E_BADARG; }
+    if (norm_type < CSPN_NORM_8SUM || norm_type > CSPN_NORM_NONE) {
+        set_error("%s: norm_type must be CSPN_NORM_8SUM, CSPN_NORM_8SUM_ABS or CSPN_NORM_NONE (got %d)", what, norm_type);
+        return CSPN_E_BADARG;
+    }
+    if (int e = async_failure_of_earlier_call()) return e;
+    const bool paddle = norm_type == CSPN_NORM_NONE && !sparse;
+    const size_t need = n_iter <= 0 ? 0 : paddle ? backward3d_workspace(B, D, H, W, n_iter, C, gdt) : backward3d_norm_multi_workspace(B, C, D, H, W, n_iter);
+    if (int e = check_common(guidance, feat, grad_out, n_iter, norm_type, ws, ws_bytes, need)) return e;
+    const size_t vb = sizeof(float) * V * C, sb = sizeof(float) * V, gb = 26 * V * gate_bytes(gdt);
+    if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {feat, vb}, {sparse, sb}, {grad_out, vb}, {grad_feat, vb}, {ws, need}}) ||
+        kxk_overlaps(grad_feat, vb, {{guidance, gb}, {feat, vb}, {sparse, sb}, {grad_out, vb}, {ws, need}})) {
+        set_error("%s: an output must not overlap an input, the other output or the workspace", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_guidance && !grad_feat) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) return identity_backward(grad_feat, grad_out, V * C, grad_guidance, gb, st);
+    if (algo == CSPN_ALGO3D_PERSISTENT &&
+        !backward3d_norm_multi_fused(guidance, gdt, feat, sparse, grad_out, grad_guidance, grad_feat, B, C, D, H, W, n_iter, ws)) {
+        set_error("persistent 3D kernel does not take this backward (needs W %% 4 == 0, 16-byte aligned tensors, 3 <= n_iter <= 60, a chunk per device)");
+        return CSPN_E_UNSUPPORTED;
+    }
+    const bool stepwise_only = algo == CSPN_ALGO3D_STEPWISE;
+    if (paddle)   // the Paddle contract: cspn3d_backward_multi_f32 / _g16 (for every shape: its per-step kernels take what the sweeps decline)
+        return backward3d(guidance, feat, grad_out, grad_guidance, grad_feat, B, D, H, W, n_iter, ws, st, stepwise_only, C, gdt);
+    return backward3d_norm_multi(guidance, gdt, feat, sparse, grad_out, grad_guidance, grad_feat, B, C, D, H, W, n_iter, norm_type, ws, st,
+                                 stepwise_only);
+}
+
+int cspn3d_backward_norm_multi_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out, float* grad_guidance,
+                                   float* grad_feat, int B, int C, int D, int H, int W, int n_iter, int norm_type, int algo, void* ws,
+                                   size_t ws_bytes, cspn_stream_t stream) {
+    return backward3d_norm_multi_entry("cspn3d_backward_norm_multi_f32", guidance, 0, feat, sparse, grad_out, grad_guidance, grad_feat, B, C, D, H, W,
+                                       n_iter, norm_type, algo, ws, ws_bytes, stream);
+}
+
+int cspn3d_backward_norm_multi_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, const float* grad_out,
+                                   void* grad_guidance, float* grad_feat, int B, int C, int D, int H, int W, int n_iter, int norm_type, int algo,
+                                   void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = g16_check("cspn3d_backward_norm_multi_g16", gate_dtype, guidance, grad_guidance)) return e;
+    return backward3d_norm_multi_entry("cspn3d_backward_norm_multi_g16", guidance, gate_dtype, feat, sparse, grad_out, grad_guidance, grad_feat, B, C,
+                                       D, H, W, n_iter, norm_type, algo, ws, ws_bytes, stream);
+}
+
 size_t cspn3d_backward_g16_workspace_bytes(int B, int D, int H, int W, int n_iter) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || n_iter <= 0) return 0;
     return backward3d_workspace(B, D, H, W, n_iter, 1, CSPN_DTYPE_F16);

@@ -155,6 +155,27 @@ bool backward3d_norm_fused(const void* g, int gdt, const float* feat, const floa
 int backward3d_norm(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, void* gg, float* gf, int B, int D, int H,
                     int W, int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only);
 
+// ---- the same modes for C value channels on SHARED guidance (feat / out / gout / gf [B][C][V], sparse NULL or [B][V]): the fold runs once
+// per call into w' [B][26][V] and coef [B][V], each channel's constant term is coef H_{0,c}; gg is the sum over the channels ----
+// (cspn3d_norm_backward.hip) vec here and below: four voxels a thread (the caller's quads_ok), else one
+int fold3d_shared(const void* g, int gdt, const float* sparse, float* wp, float* kp, int B, int D, int H, int W, int norm, bool vec, hipStream_t st);
+// (cspn3d_stepwise.hip) one step of all channels: hout_c = kp h0_c + sum_k wp_k hin_c(p + off_k)
+int step3d_shared(const float* wp, const float* kp, const float* h0, const float* hin, float* hout, int B, int C, int D, int H, int W, bool vec,
+                  hipStream_t st);
+size_t forward3d_norm_multi_workspace(int B, int C, int D, int H, int W, int n_iter);
+bool forward3d_norm_multi_fused(const void* g, int gdt, const float* feat, const float* sparse, const float* out, int B, int C, int D, int H, int W,
+                                int n_iter, const void* ws);
+int forward3d_norm_multi(const void* g, int gdt, const float* feat, const float* sparse, float* out, int B, int C, int D, int H, int W, int n_iter,
+                         int norm, void* ws, hipStream_t st, int algo);
+// (cspn3d_persistent.hip) all steps of all channels in one launch, wp and kp resident: the <HASC, MULTI> instance
+int persistent3d_forward_shared(const float* wp, const float* kp, const float* feat, float* out, int B, int C, int D, int H, int W, int n_iter,
+                                void* ws, hipStream_t st);
+size_t backward3d_norm_multi_workspace(int B, int C, int D, int H, int W, int n_iter);
+bool backward3d_norm_multi_fused(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, const void* gg, const float* gf,
+                                 int B, int C, int D, int H, int W, int n_iter, const void* ws);
+int backward3d_norm_multi(const void* g, int gdt, const float* feat, const float* sparse, const float* gout, void* gg, float* gf, int B, int C,
+                          int D, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, bool stepwise_only);
+
 // ---- the producer of the path's inputs (cspn_head.hip): Unpool + 3x3 conv C -> 8 (guidance) and C -> 1 (blur) as one kernel; mode 0 raw guidance,
 // 1 / 2 gate_wb of '8sum' / '8sum_abs' (the normalisation fused behind the conv) ----
 size_t head_workspace(int C);

@@ -343,11 +343,29 @@ def cspn3d_forward_norm(guidance, feat, sparse=None, n_iter=12, norm_type="8sum_
     """cspn3d_forward on a guidance that may be float16 / bfloat16 in EVERY mode ('8sum', '8sum_abs', 'none' with or without a mask): what a
     head under torch.autocast emits goes to the engine as it is (cspn3d_forward_norm_g16: each gate is widened exactly where the fold reads
     it, no float32 copy is made); out is float32 and bitwise cspn3d_forward(guidance.float(), ...) with the same algo.  feat and sparse are
-    float32.  A float32 guidance is exactly cspn3d_forward."""
+    float32.  A float32 guidance is exactly cspn3d_forward.
+    feat may be [B,C,D,H,W] with C > 1: the channels share the guidance and the mask (sparse None or [B,1,D,H,W]) -> [B,C,D,H,W], one engine
+    call (cspn3d_forward_norm_multi_f32 / _g16: the fold runs once, w' and coef are read once per step for all channels, and stay resident
+    across steps and channels where the persistent kernel takes the call).  Its channels are close to, not bitwise, the single-channel
+    calls': the constant term is formed as coef H_0."""
     if guidance.dim() != 5 or guidance.shape[1] != 26:
         raise ValueError("guidance must be [B,26,D,H,W], got %s" % (tuple(guidance.shape),))
     B, _, D, H, W = guidance.shape
     g, dt = _prep_gate(guidance, "guidance")
+    if isinstance(feat, torch.Tensor) and feat.dim() == 5 and feat.shape[1] > 1:
+        C = feat.shape[1]
+        h = _prep(feat, "feat", (B, C, D, H, W))
+        s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
+        if any(t is not None and t.device != g.device for t in (h, s)):
+            raise ValueError("all tensors must live on the same device")
+        out = torch.empty_like(h)
+        if B == 0:
+            return out
+        norm = _lib.NORM_TYPES[norm_type]
+        _launch("cspn3d_forward_norm_multi_f32" if dt is None else "cspn3d_forward_norm_multi_g16", g.device,
+                (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(out), B, C, D, H, W, int(n_iter), norm, _lib.ALGOS_3D[algo]),
+                ("cspn3d_forward_norm_multi_workspace_bytes", B, C, D, H, W, int(n_iter), norm, int(s is not None)))
+        return out
     if dt is None:
         return cspn3d_forward(guidance, feat, sparse, n_iter, norm_type, algo)
     h = _prep(feat, "feat", (B, 1, D, H, W))
@@ -430,14 +448,18 @@ def cspn3d_backward_norm(guidance, feat, sparse, grad_out, n_iter=12, norm_type=
     (cspn3d_backward_norm_f32: the fold is recomputed, one launch per step).  sparse gets no gradient (only its sign is used).
     -> (grad_guidance [B,26,D,H,W] or None, grad_feat [B,1,D,H,W] or None).  A float16 / bfloat16 guidance goes to the engine as it is
     (cspn3d_backward_norm_g16: read where it is used, no float32 copy of it or of its gradient): grad_feat is float32 and bitwise the float32
-    call's on guidance.float(), grad_guidance comes back in the guidance's dtype, the float32 value rounded once.  The other tensors are float32."""
+    call's on guidance.float(), grad_guidance comes back in the guidance's dtype, the float32 value rounded once.  The other tensors are float32.
+    feat and grad_out may be [B,C,D,H,W] with C > 1 on the shared guidance and mask (sparse None or [B,1,D,H,W]; 'none' without a mask
+    included): one engine call (cspn3d_backward_norm_multi_f32 / _g16), grad_feat [B,C,D,H,W], grad_guidance summed over the channels inside
+    the engine -- written once per element, no atomics, bitwise reproducible."""
     if guidance.dim() != 5 or guidance.shape[1] != 26:
         raise ValueError("guidance must be [B,26,D,H,W], got %s" % (tuple(guidance.shape),))
     B, _, D, H, W = guidance.shape
+    C = feat.shape[1] if isinstance(feat, torch.Tensor) and feat.dim() == 5 and feat.shape[1] > 1 else 1
     g, dt = _prep_gate(guidance, "guidance")
-    h = _prep(feat, "feat", (B, 1, D, H, W))
+    h = _prep(feat, "feat", (B, C, D, H, W))
     s = _prep(sparse, "sparse", (B, 1, D, H, W)) if sparse is not None else None
-    go = _prep(grad_out, "grad_out", (B, 1, D, H, W))
+    go = _prep(grad_out, "grad_out", (B, C, D, H, W))
     if any(t is not None and t.device != g.device for t in (h, s, go)):
         raise ValueError("all tensors must live on the same device")
     gg = torch.empty_like(g) if need_guidance else None
@@ -445,6 +467,12 @@ def cspn3d_backward_norm(guidance, feat, sparse, grad_out, n_iter=12, norm_type=
     if B == 0 or not (need_guidance or need_feat):
         return gg, gf
     norm = _lib.NORM_TYPES[norm_type]
+    if C > 1:
+        _launch("cspn3d_backward_norm_multi_f32" if dt is None else "cspn3d_backward_norm_multi_g16", g.device,
+                (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(go), _ptr(gg), _ptr(gf), B, C, D, H, W, int(n_iter), norm,
+                 _lib.ALGOS_3D[algo]),
+                ("cspn3d_backward_norm_multi_workspace_bytes", B, C, D, H, W, int(n_iter), norm, int(s is not None)))
+        return gg, gf
     _launch("cspn3d_backward_norm_f32" if dt is None else "cspn3d_backward_norm_g16", g.device,
             (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(go), _ptr(gg), _ptr(gf), B, D, H, W, int(n_iter), norm, _lib.ALGOS_3D[algo]),
             ("cspn3d_backward_norm%s_workspace_bytes" % ("" if dt is None else "_g16"), B, D, H, W, int(n_iter), norm, int(s is not None)))

@@ -251,8 +251,8 @@ int cspn3d_backward_multi_f32(const float* gate, const float* feat, const float*
  *   returns CSPN_E_UNSUPPORTED where AUTO would not use that instance.  Any B, D, H, W >= 1 and 4-byte aligned pointers; 16-byte loads and
  *   stores where W % 4 == 0 and every pointer is 16-byte aligned.  n_iter = 0: grad_feat = grad_out, grad_guidance = 0.  An output that overlaps an input,
  *   the other output or the workspace: CSPN_E_BADARG; a workspace smaller than cspn3d_backward_norm_workspace_bytes() or not 256-byte
- *   aligned: CSPN_E_WORKSPACE; the query returns 0 for an invalid shape or norm_type.  One channel only; float16 / bfloat16 guidance:
- *   cspn3d_backward_norm_g16 below. */
+ *   aligned: CSPN_E_WORKSPACE; the query returns 0 for an invalid shape or norm_type.  One channel; C channels on shared guidance:
+ *   cspn3d_forward_norm_multi_f32 / cspn3d_backward_norm_multi_f32 below; float16 / bfloat16 guidance: cspn3d_backward_norm_g16 below. */
 size_t cspn3d_backward_norm_workspace_bytes(int B, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
 int cspn3d_backward_norm_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out,
                              float* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter,
@@ -350,6 +350,49 @@ size_t cspn3d_backward_norm_g16_workspace_bytes(int B, int D, int H, int W, int 
 int cspn3d_backward_norm_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, const float* grad_out,
                              void* grad_guidance, float* grad_feat, int B, int D, int H, int W, int n_iter,
                              int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- the 3D depth-completion contract for C value channels on SHARED guidance: feat / out / grad_out / grad_feat [B,C,D,H,W], guidance
+ * [B,26,D,H,W] raw (float32, or of gate_dtype in the _g16 forms), sparse NULL or [B,1,D,H,W] shared by the channels -- the 3D form of the
+ * broadcast of reference cspn_pytorch/models/cspn.py:58-81 and of "gate_weight would be shared in the channel dimension for input when C>1"
+ * (cspn_paddle/README.md:56).  With the shared quantities of cspn3d_backward_norm_f32 above (w'_k, coef = u (1 - sigma) + m; NONE: m):
+ *   forward   H_{0,c} = feat_c,  H_{t+1,c}(p) = coef(p) H_{0,c}(p) + sum_k w'_k(p) H_{t,c}(p + off_k),  out_c = H_{n,c}
+ *   backward  A_{n,c} = grad_out_c,  A_{t,c}(q) = sum_k w'_k(q - off_k) A_{t+1,c}(q - off_k),  dC_c = sum_t A_{t+1,c}
+ *             grad_feat_c = A_{0,c} + dC_c coef;  dW'_k = sum_c sum_t A_{t+1,c}(p) H_{t,c}(p + off_k) (c outer, t inner: a fixed order)
+ *             dwb_k = u (dW'_k - sum_c dC_c H_{0,c}), then the fold's adjoint and the gather of cspn3d_backward_norm_f32
+ *   grad_guidance is the sum over the channels, every element written once, no atomics: two calls with the same algo are bitwise equal.
+ *   The constant term is formed as coef H_0, so for C > 1 a channel of out is close to, not bitwise, the single-channel call's (which forms
+ *   (1 - m) ((1 - sigma) H_0) + m H_0).  The fold runs ONCE per call (w' and coef into the workspace); a step of all C channels reads them
+ *   once (108 + 12 C bytes a voxel where C single-channel steps move 116 C), and where the persistent kernel takes the call (W % 4 == 0,
+ *   every pointer 16-byte aligned, guidance of a 16-bit type 8-byte, 2 <= n_iter <= 60, cspn3d_multi_supported) they stay resident in
+ *   registers / LDS across the steps and the channels.  The backward's adjoint sweep of all channels is one launch of the transposed
+ *   multi-channel instance where 3 <= n_iter <= 60 and the same conditions hold for n_iter - 1 and n_iter, per step and channel elsewhere.
+ * C = 1 IS the single-channel entry point (cspn3d_forward_f32_algo / cspn3d_forward_norm_g16 / cspn3d_backward_norm_f32 / _g16), bitwise.
+ * CSPN_NORM_NONE with sparse NULL is the Paddle contract: the backward is cspn3d_backward_multi_f32 / _g16 (bitwise); the forward is
+ *   cspn3d_forward_multi_f32 / _g16 (bitwise) where that runs (algo AUTO or PERSISTENT, aligned, cspn3d_multi_supported) and the per-step
+ *   kernels with coef = 0 elsewhere.
+ * Checks and return codes as cspn3d_backward_norm_f32: CSPN_NORM_PRENORM or an unknown norm_type: CSPN_E_BADARG; an output that overlaps
+ *   an input, the other output or the workspace: CSPN_E_BADARG; workspace too small or not 256-byte aligned: CSPN_E_WORKSPACE; n_iter = 0:
+ *   out = feat, grad_feat = grad_out, grad_guidance = 0; either output of the backward may be NULL; CSPN_ALGO3D_PERSISTENT returns
+ *   CSPN_E_UNSUPPORTED where AUTO would not fuse; failures of a persistent launch: CSPN_E_ASYNC and cspn3d_check_status.
+ * The _g16 forms follow the contract above: out and grad_feat bitwise the _f32 twin's on the widened guidance on the same path,
+ *   grad_guidance that twin's float32 value rounded once at its single store.
+ * The workspace queries return 0 for an invalid shape or norm_type; one backward query serves both guidance types.  At C = 1 they are
+ *   cspn3d_workspace_bytes_ex and cspn3d_backward_norm_g16_workspace_bytes (= cspn3d_backward_norm_workspace_bytes in every mode but NONE
+ *   without a mask). */
+size_t cspn3d_forward_norm_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
+int cspn3d_forward_norm_multi_f32(const float* guidance, const float* feat, const float* sparse, float* out,
+                                  int B, int C, int D, int H, int W, int n_iter, int norm_type, int algo,
+                                  void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn3d_forward_norm_multi_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, float* out,
+                                  int B, int C, int D, int H, int W, int n_iter, int norm_type, int algo,
+                                  void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn3d_backward_norm_multi_workspace_bytes(int B, int C, int D, int H, int W, int n_iter, int norm_type, int has_sparse);
+int cspn3d_backward_norm_multi_f32(const float* guidance, const float* feat, const float* sparse, const float* grad_out,
+                                   float* grad_guidance, float* grad_feat, int B, int C, int D, int H, int W, int n_iter,
+                                   int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn3d_backward_norm_multi_g16(const void* guidance, int gate_dtype, const float* feat, const float* sparse, const float* grad_out,
+                                   void* grad_guidance, float* grad_feat, int B, int C, int D, int H, int W, int n_iter,
+                                   int norm_type, int algo, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- 2D over a K x K neighbourhood, K = 2R+1 in {5, 7}: fluid.layers.affinity_propagate(input, gate_weight, kernel_size) with
  * kernel_size 5 or 7, the NONE contract (gates used as given, centre-sited, no centre term, any sign; reference cspn_paddle/README.md:54-56).
