@@ -4,7 +4,7 @@
 // restated as
 //     H_{t+1}(p) = c'(p) + sum_k w'_k(p) * H_t(p + off_k)
 // with w'_k = (1-m) w_k, c' = (1-m)(1-sigma) H_0 + m H_0, m = sign(sparse).
-#include "cspn_common.h"
+#include "cspn2d_pixel.h"
 
 namespace cspn {
 
@@ -15,26 +15,16 @@ __global__ __launch_bounds__(256) void fold2d_kernel(const float* __restrict__ g
                                                       const float* __restrict__ sparse, float* __restrict__ wf,
                                                       int B, int H, int W, int norm) {
     const size_t HW = (size_t)H * W, total = (size_t)B * HW;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / HW);
-    const int r = (int)(idx - (size_t)b * HW);
-    const int y = r / W, x = r - y * W;
-    const float* gb = g + (size_t)b * 8 * HW;
+    const Pixel p(B, H, W);
+    if (!p.ok) return;
+    const size_t idx = p.idx;
+    const float* gb = g + (size_t)p.b * 8 * HW;
     float G[8], S = 0.f;
+    if (norm == CSPN_NORM_NONE || norm == CSPN_NORM_PRENORM) {   // used as given, centre-sited
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float v;
-        if (norm == CSPN_NORM_NONE || norm == CSPN_NORM_PRENORM) {   // used as given, centre-sited
-            v = gb[k * HW + r];
-        } else {
-            const int yy = y + dy2(k), xx = x + dx2(k);
-            v = 0.f;
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = gb[k * HW + (size_t)yy * W + xx];
-            if (norm == CSPN_NORM_8SUM_ABS) v = fabsf(v);
-        }
-        G[k] = v;
-        S += fabsf(v);
+        for (int k = 0; k < 8; ++k) G[k] = gb[k * HW + p.r];
+    } else {
+        S = gather_gates2(gb, HW, Nbrs(p.y, p.x, p.r, H, W), norm, G);
     }
     float sigma = 0.f;
 #pragma unroll
@@ -56,19 +46,19 @@ __global__ __launch_bounds__(256) void fold2d_kernel(const float* __restrict__ g
     wf[8 * total + idx] = c;
 }
 
+// (its own tap loop, not for_taps2 over load_tap2: that spelling was 40 instructions shorter and 6 % slower at 64 x 304 x 1216,
+// profiles/2d_pixel_refactor.md; bwd_step_kernel likewise)
 __global__ __launch_bounds__(256) void step2d_kernel(const float* __restrict__ wf, const float* __restrict__ hin,
                                                       float* __restrict__ hout, int B, int H, int W) {
     const size_t HW = (size_t)H * W, total = (size_t)B * HW;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / HW);
-    const int r = (int)(idx - (size_t)b * HW);
-    const int y = r / W, x = r - y * W;
-    const float* hb = hin + (size_t)b * HW;
+    const Pixel p(B, H, W);
+    if (!p.ok) return;
+    const size_t idx = p.idx;
+    const float* hb = hin + (size_t)p.b * HW;
     float acc = wf[8 * total + idx];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int yy = y + dy2(k), xx = x + dx2(k);
+        const int yy = p.y + dy2(k), xx = p.x + dx2(k);
         float hv = 0.f;  // ZeroPad2d (cspn.py:149-167)
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) hv = hb[(size_t)yy * W + xx];
         acc = fmaf(wf[k * total + idx], hv, acc);
@@ -82,25 +72,13 @@ __global__ __launch_bounds__(256) void step2d_kernel(const float* __restrict__ w
 // 32 B written per pixel.
 __global__ __launch_bounds__(256) void normalize2d_kernel(const float* __restrict__ g, float* __restrict__ wb, int B, int H, int W,
                                                            int norm) {
-    const size_t HW = (size_t)H * W, total = (size_t)B * HW;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / HW);
-    const int r = (int)(idx - (size_t)b * HW);
-    const int y = r / W, x = r - y * W;
-    const float* gb = g + (size_t)b * 8 * HW;
-    float G[8], S = 0.f;
+    const size_t HW = (size_t)H * W;
+    const Pixel p(B, H, W);
+    if (!p.ok) return;
+    float G[8];
+    const float S = gather_gates2(g + (size_t)p.b * 8 * HW, HW, Nbrs(p.y, p.x, p.r, H, W), norm, G);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int yy = y + dy2(k), xx = x + dx2(k);
-        float v = 0.f;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = gb[k * HW + (size_t)yy * W + xx];
-        if (norm == CSPN_NORM_8SUM_ABS) v = fabsf(v);
-        G[k] = v;
-        S += fabsf(v);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) wb[((size_t)b * 8 + k) * HW + r] = G[k] / S;   // IEEE division: 0/0 = NaN (cspn.py:138)
+    for (int k = 0; k < 8; ++k) wb[((size_t)p.b * 8 + k) * HW + p.r] = G[k] / S;   // IEEE division: 0/0 = NaN (cspn.py:138)
 }
 
 int normalize2d(const float* g, float* wb, int B, int H, int W, int norm, hipStream_t st) {
@@ -122,27 +100,13 @@ int normalize2d(const float* g, float* wb, int B, int H, int W, int norm, hipStr
 //     weight towards it multiplies that 0 -- what the reference's zero-padded depth gives.
 __global__ __launch_bounds__(256) void normalize2d_pitch_kernel(const float* __restrict__ g, float* __restrict__ wb, int B, int H, int W, int Wp,
                                                                  int norm) {
-    const size_t HWp = (size_t)H * Wp, HW = (size_t)H * W, total = (size_t)B * HWp;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / HWp);
-    const int r = (int)(idx - (size_t)b * HWp);
-    const int y = r / Wp, x = r - y * Wp;
+    const size_t HWp = (size_t)H * Wp, HW = (size_t)H * W;
+    const Pixel p(B, H, Wp);   // (r: inside the padded image)
+    if (!p.ok) return;
     float G[8], S = 0.f;
-    if (x < W) {
-        const float* gb = g + (size_t)b * 8 * HW;
+    if (p.x < W) S = gather_gates2(g + (size_t)p.b * 8 * HW, HW, Nbrs(p.y, p.x, p.y * W + p.x, H, W), norm, G);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int yy = y + dy2(k), xx = x + dx2(k);
-            float v = 0.f;
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = gb[k * HW + (size_t)yy * W + xx];
-            if (norm == CSPN_NORM_8SUM_ABS) v = fabsf(v);
-            G[k] = v;
-            S += fabsf(v);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) wb[((size_t)b * 8 + k) * HWp + r] = x < W ? G[k] / S : 0.f;   // IEEE division: 0/0 = NaN (cspn.py:138)
+    for (int k = 0; k < 8; ++k) wb[((size_t)p.b * 8 + k) * HWp + p.r] = p.x < W ? G[k] / S : 0.f;   // IEEE division: 0/0 = NaN (cspn.py:138)
 }
 
 // rows of W floats <-> rows of Wp >= W floats (pad columns zero)

@@ -249,6 +249,19 @@ int add_inplace(float* dst, const float* src, size_t n, hipStream_t st);        
 
 // ---- backward of the 2D op (cspn2d_backward.hip) ----
 size_t backward2d_workspace(int B, int H, int W, int n_iter);
+// that workspace's parts, in bytes from its start.  Where the ring's sweeps take the call (ckpt): the forward's checkpoints (hh), the folded
+// coefficients (wf), the adjoint's checkpoints (ah), A_0 (a0) and a scratch output; `history` bytes of it are what a training forward keeps
+// (forward2d_history), and `adjoint` bytes from `ah` what backward2d_history wants as its workspace.  Else one launch per step: the folded
+// coefficients (wf), their transposes (wt), H_1 .. H_{N-1} (hh) and A_0 .. A_{N-1} (ah)
+struct Backward2dLayout {
+    bool ckpt;
+    size_t hh, wf, wt, ah, a0, scratch, history, adjoint, bytes;
+    Backward2dLayout(int B, int H, int W, int n_iter);
+    static Backward2dLayout checkpointed(int B, int H, int W);
+
+private:
+    Backward2dLayout() = default;
+};
 // C > 1 (cspn2d_backward_multi_f32; the assembly sweeps only, backward2d_multi_supported): B counts image-channels [B][H][W], C of them share
 // each of the B / C guidance images; gg [B / C][8][H][W] is the sum over the channels
 int backward2d(const float* g, const float* blur, const float* sparse, const float* gout, float* gg, float* gb, int B, int H,

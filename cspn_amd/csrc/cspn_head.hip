@@ -18,7 +18,7 @@
 // KITTI x 64 against 0.81 + 0.3 ms for these two (profiles/r06_head.md).
 #include <cstdint>
 
-#include "cspn_common.h"
+#include "cspn2d_pixel.h"
 
 namespace cspn {
 namespace {
@@ -169,24 +169,14 @@ __global__ __launch_bounds__(256, HEAD_OCC) void head_raw_kernel(const float* __
 // affinity_normalization (cspn.py:85-144) in place on consumer-sited planes: wb_k(p) = G_k(p) / sum_j |G_j(p)| (G = |G| first for '8sum_abs'), IEEE division
 // (0 / 0 = NaN as torch.div, cspn.py:138); G_k(p) = 0 where p + off_k lies outside the image (nothing was stored there)
 __global__ __launch_bounds__(256) void head_norm_sited_kernel(float* __restrict__ g, int B, int H, int W, int norm) {
-    const size_t HW = (size_t)H * W, total = (size_t)B * HW;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int b = (int)(idx / HW);
-    const int r = (int)(idx - (size_t)b * HW);
-    const int y = r / W, x = r - y * W;
-    float* gb = g + (size_t)b * 8 * HW + r;
-    float G[8], S = 0.f;
+    const size_t HW = (size_t)H * W;
+    const Pixel p(B, H, W);
+    if (!p.ok) return;
+    float* gb = g + (size_t)p.b * 8 * HW;
+    float G[8];
+    const float S = gather_gates2(gb, HW, Nbrs(p.y, p.x, p.r, H, W, true), norm, G);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int yy = y + dy2(k), xx = x + dx2(k);
-        float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? gb[k * HW] : 0.f;
-        if (norm == CSPN_NORM_8SUM_ABS) v = fabsf(v);
-        G[k] = v;
-        S += fabsf(v);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) gb[k * HW] = G[k] / S;
+    for (int k = 0; k < 8; ++k) gb[k * HW + p.r] = G[k] / S;
 }
 
 }  // namespace

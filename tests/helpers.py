@@ -20,6 +20,20 @@ def make_inputs(B, H, W, seed=0, sparse=True, p_sparse=0.05, depth_scale=10.0, n
     return g, h, s
 
 
+def hand_mask(h, neg=False):
+    """a sparse-depth plane for images of a few pixels, where make_inputs' 5 % draw is mostly empty: in image b pixel (b + 1) % HW is
+    pinned to a positive depth and, with neg, pixel (b + 3) % HW to a negative one (sign(s) = -1); every other pixel is free.  Each image
+    of four or more pixels has a pinned and a free pixel, and the images differ (batch stride)"""
+    B, HW = h.shape[0], h.shape[2] * h.shape[3]
+    assert HW >= 4
+    s = torch.zeros_like(h)
+    for b in range(B):
+        s.view(B, HW)[b, (b + 1) % HW] = h.view(B, HW)[b, (b + 1) % HW] + 0.1
+        if neg:
+            s.view(B, HW)[b, (b + 3) % HW] = -2.5
+    return s
+
+
 def config_inputs(B, H, W, scale, sparse, seed0=1000, first=0):
     """BASELINE configs 2-4 with per-image seeding: image i (global index) comes from
     torch.Generator().manual_seed(seed0 + i) on the CPU, so any sharding of the batch sees identical data."""

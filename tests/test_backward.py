@@ -9,12 +9,22 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import live_reference, make_inputs
+from helpers import hand_mask, live_reference, make_inputs
 from oracle.backward import cspn2d_backward_oracle
 
 GFLOOR = 5e-6
 GTOL = 2e-4  # relative to max|grad|: 1e-4 forward tolerance with headroom for the longer accumulation chains
 NORMS = {0: "8sum", 1: "8sum_abs"}
+# the smallest images a per-pixel kernel can get wrong, two of them each (batch stride): one row, one column, non-square.  B, H, W, N, mask;
+# a mask there is helpers.hand_mask (make_inputs' 5 % draw is mostly empty at these sizes)
+SMALL = [(2, 1, 5, 3, False), (2, 4, 1, 3, True), (2, 3, 2, 3, True)]
+
+
+def _inputs(B, H, W, N, sp):
+    g, h, s = make_inputs(B, H, W, seed=B + H + W + N, sparse=sp, neg=sp)
+    if sp and (B, H, W, N, sp) in SMALL:
+        s = hand_mask(h, neg=True)
+    return g, h, s
 
 
 def _golden():
@@ -74,10 +84,11 @@ def test_hip_backward_vs_reference_autograd_goldens():
                                              # round 5: n_iter = 4, 8 .. 20 on the checkpointed ring path too (the sweeps run their 24 levels,
                                              # H_n / A_0 are checkpoint planes, the final pass runs n_iter / 4 segments)
                                              (2, 41, 260, 4, "8sum", True), (1, 70, 304, 8, "8sum_abs", False), (2, 33, 516, 16, "8sum", True),
-                                             (1, 50, 256, 20, "8sum_abs", True)])
+                                             (1, 50, 256, 20, "8sum_abs", True)]
+                                            + [(B, H, W, N, norm, sp) for (B, H, W, N, sp) in SMALL for norm in ("8sum", "8sum_abs")])
 def test_hip_backward_vs_oracle_and_through_autograd(B, H, W, N, norm, sp):
     import cspn_amd
-    g, h, s = make_inputs(B, H, W, seed=B + H + W + N, sparse=sp, neg=sp)
+    g, h, s = _inputs(B, H, W, N, sp)
     go = torch.randn(B, 1, H, W, generator=torch.Generator().manual_seed(5))
     _, rgg, rgh = cspn2d_backward_oracle(g.numpy(), h.numpy(), None if s is None else s.numpy(), go.numpy(), N, norm)
     gd, hd = g.cuda().requires_grad_(True), h.cuda().requires_grad_(True)
@@ -174,23 +185,13 @@ def test_forward_and_backward_vs_stock_torch_autograd_at_full_width():
     assert _check(h1.grad.cpu().numpy(), h0.grad.cpu().numpy())
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("sp", [False, True])
-def test_backward_norm_none_on_the_checkpointed_path_vs_torch_autograd(sp):
-    """norm NONE (gates used as given, centre-sited: the Paddle-style 2D contract; c' = m H_0 in the recomputing final pass) at a
-    size the assembly sweeps take, against torch autograd through the same recurrence"""
+def _none_backward_vs_torch_autograd(g, h, s, go, N):
+    """norm NONE against torch autograd through the same recurrence, in the dtype and on the device the inputs come in"""
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tools.torch_path import _gather8
     import cspn_amd
-    B, H, W, N = 2, 50, 272, 24
-    gen = torch.Generator().manual_seed(17)
-    g = torch.rand(B, 8, H, W, generator=gen)
-    g = (g / g.sum(1, keepdim=True)).cuda()
-    h = (torch.rand(B, 1, H, W, generator=gen) * 10).cuda()
-    s = ((torch.rand(B, 1, H, W, generator=gen) < 0.02).float() * 3.0).cuda() if sp else None
-    go = torch.randn(B, 1, H, W, generator=gen).cuda()
     g0, h0 = g.clone().requires_grad_(True), h.clone().requires_grad_(True)
     cur = h0
     for _ in range(N):
@@ -199,9 +200,40 @@ def test_backward_norm_none_on_the_checkpointed_path_vs_torch_autograd(sp):
             m = s.sign()
             cur = (1 - m) * cur + m * h0
     cur.backward(go)
-    gg, gh = cspn_amd.cspn2d_backward(g, h, s, go, N, "none")
+    gg, gh = cspn_amd.cspn2d_backward(g.float().cuda(), h.float().cuda(), None if s is None else s.float().cuda(), go.float().cuda(), N, "none")
     assert _check(gg.cpu().numpy(), g0.grad.cpu().numpy())
     assert _check(gh.cpu().numpy(), h0.grad.cpu().numpy())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sp", [False, True])
+def test_backward_norm_none_on_the_checkpointed_path_vs_torch_autograd(sp):
+    """norm NONE (gates used as given, centre-sited: the Paddle-style 2D contract; c' = m H_0 in the recomputing final pass) at a
+    size the assembly sweeps take, against torch autograd through the same recurrence"""
+    B, H, W, N = 2, 50, 272, 24
+    gen = torch.Generator().manual_seed(17)
+    g = torch.rand(B, 8, H, W, generator=gen)
+    g = (g / g.sum(1, keepdim=True)).cuda()
+    h = (torch.rand(B, 1, H, W, generator=gen) * 10).cuda()
+    s = ((torch.rand(B, 1, H, W, generator=gen) < 0.02).float() * 3.0).cuda() if sp else None
+    go = torch.randn(B, 1, H, W, generator=gen).cuda()
+    _none_backward_vs_torch_autograd(g, h, s, go, N)
+
+
+@pytest.mark.gpu
+def test_backward_norm_none_on_the_stepwise_path_vs_torch_autograd():
+    """the same contract one launch per step (bwd_final_kernel's NONE branch), on two images of 3 x 2 pixels under a hand-made mask, against torch
+    autograd in float64"""
+    import cspn_amd
+    B, H, W, N = 2, 3, 2, 3
+    assert cspn_amd.cspn2d_history_bytes(B, H, W, N) == 0   # not a shape the sweeps take
+    gen = torch.Generator().manual_seed(18)
+    g = torch.rand(B, 8, H, W, generator=gen, dtype=torch.float64)
+    g = g / g.sum(1, keepdim=True)
+    h = torch.rand(B, 1, H, W, generator=gen, dtype=torch.float64) * 10
+    s = hand_mask(h)
+    go = torch.randn(B, 1, H, W, generator=gen, dtype=torch.float64)
+    _none_backward_vs_torch_autograd(g, h, s, go, N)
 
 
 # ---- the pre-normalised input contract (CSPN_NORM_PRENORM, round 6): gradient w.r.t. the reference's gate_wb ------------------------------
@@ -251,13 +283,13 @@ def test_hip_prenorm_backward_vs_reference_autograd_goldens():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,H,W,N,sp", [(2, 37, 53, 24, True), (3, 20, 256, 12, False), (2, 41, 260, 24, True), (1, 89, 300, 24, False),
-                                        (1, 3, 256, 24, False), (2, 33, 516, 16, True), (1, 30, 40, 30, True), (2, 70, 512, 24, True)])
+                                        (1, 3, 256, 24, False), (2, 33, 516, 16, True), (1, 30, 40, 30, True), (2, 70, 512, 24, True)] + SMALL)
 def test_hip_prenorm_backward_vs_oracle_and_through_autograd(B, H, W, N, sp):
     """every backward path (one launch per step; the two ring sweeps + recomputing final pass, n_iter = 4 .. 24; training mode with kept
     checkpoints) with the reference's gate_wb as the input, against the numpy restatement -- and the chain rule closed: the gradient of the
     raw contract = this gradient pushed through the stand-alone normalisation by torch autograd"""
     import cspn_amd
-    g, h, s = make_inputs(B, H, W, seed=B + H + W + N, sparse=sp, neg=sp)
+    g, h, s = _inputs(B, H, W, N, sp)
     go = torch.randn(B, 1, H, W, generator=torch.Generator().manual_seed(5))
     wb = cspn_amd.cspn2d_normalize(g.cuda(), "8sum")
     sd = None if s is None else s.cuda()

@@ -7,7 +7,7 @@ import torch
 
 import cspn_amd
 from cspn_amd import _lib
-from helpers import RTOL, assert_close, assert_close_tight, config_inputs, make_inputs, rel_err
+from helpers import RTOL, assert_close, assert_close_tight, config_inputs, hand_mask, make_inputs, rel_err
 from oracle import cspn2d_oracle, cspn3d_oracle
 
 pytestmark = pytest.mark.gpu
@@ -83,12 +83,19 @@ SHAPES = [
     (2, 2, 2, 2, "8sum_abs", True),
     (1, 40, 1216, 1, "8sum", True),
     (5, 48, 128, 24, "8sum", True),
+    # the smallest images a per-pixel kernel can get wrong, two of them each (batch stride): one row, one column, non-square
+    (2, 1, 5, 3, "8sum", False),
+    (2, 4, 1, 3, "8sum_abs", True),
+    (2, 3, 2, 3, "8sum", True),
 ]
+HAND_MASKED = {(2, 4, 1), (2, 3, 2)}   # too small for make_inputs' 5 % mask (mostly empty there): helpers.hand_mask
 
 
 @pytest.mark.parametrize("B,H,W,N,norm,sp", SHAPES)
 def test_parity_vs_oracle(B, H, W, N, norm, sp):
     g, h, s = make_inputs(B, H, W, seed=B * 1000 + H + W + N, sparse=sp, neg=sp, depth_scale=80.0)
+    if sp and (B, H, W) in HAND_MASKED:
+        s = hand_mask(h, neg=True)
     ref = cspn2d_oracle(g, h, s, N, norm)
     for algo in _algos(B, H, W, N):
         assert_close_tight(_run(g, h, s, N, norm, algo), ref, algo)
