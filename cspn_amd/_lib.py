@@ -115,6 +115,15 @@ _SYMBOLS.update({
     "cspn2d_backward_kxk_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_norm_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_size_t] + [c_int] * 8 + _WS),
     "cspn2d_backward_kxk_norm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 8 + _WS),
+    # assembling K x K levels per pixel (out = sum_j conf_j H_{s_j}): the kxk_norm arguments with conf, steps (host ints) and T behind sparse; the
+    # backward also takes grad_conf behind grad_blur
+    "cspn2d_kxk_assemble_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_kxk_assemble_history_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_backward_kxk_assemble_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_forward_kxk_assemble_f32": (c_int, [vp] * 5 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 8 + _WS),
+    "cspn2d_forward_kxk_assemble_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 8 + _WS),
+    "cspn2d_backward_kxk_assemble_f32": (c_int, [vp] * 5 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 8 + _WS),
+    "cspn2d_backward_kxk_assemble_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 8 + _WS),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

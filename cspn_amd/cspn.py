@@ -226,6 +226,79 @@ class Affinity_PropagateKxK(nn.Module):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
 
 
+class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
+    """one kernel size of Affinity_PropagateAssemble: one cspn2d_forward_kxk_assemble call that keeps H_1 .. H_n where dL/dguidance or dL/dconf
+    will need them, one cspn2d_backward_kxk_assemble call"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type):
+        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type = steps, kernel_size, n_iter, norm_type
+        hist = None
+        if (ctx.needs_input_grad[0] and n_iter >= 2) or ctx.needs_input_grad[3]:
+            out, hist = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, return_history=True)
+        else:
+            out = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, conf, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, conf, hist = ctx.saved_tensors
+        gg, gh, gc = F.cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, ctx.steps, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type,
+                                                    hist, need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1],
+                                                    need_conf=ctx.needs_input_grad[3])
+        return gg, gh, None, gc, None, None, None, None
+
+
+class Affinity_PropagateAssemble(nn.Module):
+    """The propagation of CSPN++ ("context-aware" CSPN; PENet's refinement): Affinity_PropagateKxK over several kernel sizes at once, the result a
+    per-pixel weighted sum over collected iterations and over kernel sizes,
+        out = sum_k kernel_conf[:, k] * sum_j iter_conf[k][:, j] * H^{K_k}_{steps[j]},      H^K_0 = blur_depth.
+    prop_kernels: kernel sizes out of 3, 5, 7 (3 runs the K x K engine's own K = 3 instance, not the 3 x 3 ring); steps: the collected
+    iterations, strictly increasing, ending at prop_time (None: (prop_time,), the last level only).
+    forward(guidances, blur_depth, sparse_depth=None, iter_conf=None, kernel_conf=None, n_iter=None): guidances and iter_conf are sequences with
+    one entry per kernel size, [B,K*K-1,H,W] raw (the channel order of Affinity_PropagateKxK) and [B,len(steps),H,W]; kernel_conf
+    [B,len(prop_kernels),H,W].  iter_conf None means ones, kernel_conf None no such factor.  No softmax is applied: normalising the
+    confidences is the caller's job.  kernel_conf[:, k:k+1] is multiplied into iter_conf[k] with one torch op, then each kernel size is one
+    engine call each way (F.cspn2d_forward_kxk_assemble / F.cspn2d_backward_kxk_assemble) and the results are summed.  Differentiable w.r.t. the
+    guidances, blur_depth, iter_conf and kernel_conf.  float16 / bfloat16 guidance goes to the engine as it is; the result is float32.  n_iter
+    overrides prop_time and needs steps that end at it; n_iter == 0 returns blur_depth itself, as the other modules do.  No parameters or buffers."""
+
+    def __init__(self, prop_time, prop_kernels=(3, 5, 7), steps=None, norm_type='8sum'):
+        super(Affinity_PropagateAssemble, self).__init__()
+        prop_kernels = tuple(prop_kernels)
+        assert len(prop_kernels) >= 1 and all(k in (3, 5, 7) for k in prop_kernels), 'the neighbourhoods are 3 x 3, 5 x 5 or 7 x 7'
+        assert norm_type in ['8sum', '8sum_abs']
+        steps = (prop_time,) if steps is None else tuple(steps)
+        assert len(steps) >= 1 and all(isinstance(s, int) and not isinstance(s, bool) for s in steps), 'steps are ints'
+        assert steps[0] >= 0 and all(b > a for a, b in zip(steps, steps[1:])) and steps[-1] == prop_time, \
+            'steps must be strictly increasing, start at >= 0 and end at prop_time'
+        self.prop_time = prop_time
+        self.prop_kernels = prop_kernels
+        self.steps = steps
+        self.norm_type = norm_type
+
+    def forward(self, guidances, blur_depth, sparse_depth=None, iter_conf=None, kernel_conf=None, n_iter=None):
+        n = self.prop_time if n_iter is None else int(n_iter)
+        if n == 0:
+            return blur_depth
+        nk, T = len(self.prop_kernels), len(self.steps)
+        if len(guidances) != nk or (iter_conf is not None and len(iter_conf) != nk):
+            raise ValueError("guidances and iter_conf need one entry per kernel size %s" % (self.prop_kernels,))
+        if kernel_conf is not None and (kernel_conf.dim() != 4 or kernel_conf.shape[1] != nk):
+            raise ValueError("kernel_conf must be [B,%d,H,W], got %s" % (nk, tuple(kernel_conf.shape)))
+        blur_depth, sparse_depth, kernel_conf = F.widen16(blur_depth, sparse_depth, kernel_conf)
+        out = None
+        for k, K in enumerate(self.prop_kernels):
+            conf = F.assemble_conf(None if iter_conf is None else F.widen16(iter_conf[k]), kernel_conf, k, T, blur_depth)
+            y = _CSPN2dKxKAssembleFunction.apply(guidances[k], blur_depth, sparse_depth, conf, self.steps, K, n, self.norm_type)
+            out = y if out is None else out + y
+        return out
+
+    def extra_repr(self):
+        return "prop_time=%d, prop_kernels=%r, steps=%r, norm_type=%r" % (self.prop_time, self.prop_kernels, self.steps, self.norm_type)
+
+
 class CSPN(nn.Module):
     """reference cspn_paddle/demo.py:10-54 (the demo's module): same constructor, same cspn(guide, feat) -- also the forward.  guide
     [N, feat_chan*K, *S] raw (K = prop_kernel^dim_num - 1; prop_kernel 3, or 5 / 7 in 2D), feat [N, feat_chan, *S]: abs, each channel's

@@ -17,6 +17,9 @@
 // S(p) = sum_k a_k(p) in channel order, after it.  The gates are centre-sited, so the thread that steps a pixel holds all of its gates
 // and forms S from them; the adjoint step holds the gates of shifted pixels and reads 1 / S from a plane (kxk_rsum) while it stages
 // A; the gate gradient's epilogue re-reads the guide a channel at a time: no normalised gate and no dL/dw is ever stored.
+// The assembling contract (CSPN++: a per-pixel weighted sum of collected levels, out = sum_j conf_j H_{s_j}) is the folded contract with an
+// epilogue: the collecting forward step also updates out from the level it has in registers, the injecting adjoint step adds
+// conf_j grad_out to the adjoint level it stores, and kxk_conf_grad reduces grad_out H_{s_j} over the channels.
 // Gate storage type GT: float, or __half / __hip_bfloat16 (the *_g16 entry points).  A 16-bit gate is widened to float32 exactly where
 // it is used, every multiply-add and sum is the float32 one in the same order, so the results are bitwise those of the float instance
 // on the widened gates; a gradient with respect to a 16-bit tensor is accumulated in float32 and rounded once (to nearest even,
@@ -204,12 +207,27 @@ __device__ __forceinline__ void store4(store_t<T>* __restrict__ p, const float (
 template <int K>
 __host__ __device__ constexpr int chan(int t, int l) { return t * K + l - (t * K + l > (K / 2) * (K + 1) ? 1 : 0); }
 
+// what a collecting forward step and an injecting adjoint step take besides the step's own arguments (the assembling contract at the
+// end of this file); the confidences conf [B][T][H][W] are shared by the C channels and, with a mask per channel, by the cpg images
+// of a guidance image
+struct Collect {
+    const float* cj;   // the conf plane of the level this step produces, of guidance image 0; forward: NULL where that level is not collected
+    const float* c0;   // forward, first step: the conf plane of a collected level 0 (conf_0 src joins the sum from the staged pixel), else NULL
+    float* out;        // forward: the assembled output [N][C][H][W]; written, not read, unless accumulate
+    const float* g;    // adjoint: grad_out [N][C][H][W]
+    size_t stride;     // floats between the conf planes of two guidance images: T H W
+    int cpg;           // images per guidance image (NormGeo)
+    int accumulate;    // forward: out holds the levels collected so far
+};
+
 // one forward step for all C channels: dst = step(src).  VEC: W % 4 == 0, dst 16-byte aligned, gate aligned to four elements
 // BIAS: the accumulator starts from bias [N][C][H][W] (the folded normalising contract, kxk_fold), 16-byte aligned where VEC
 // ABS: gate is the raw guide; |gate| in the multiply-add, the sum times 1 / S before the store (0 * inf = NaN where a pixel's gates are all zero)
-template <int K, bool VEC, bool BIAS = false, class GT = float, bool ABS = false>
-__global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
-                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias) {
+// COLLECT: after the stencil sum the thread also updates the assembled output of its four pixels, out (+)= conf_j acc (and conf_0 src in
+// the first step); dst NULL: the level itself is not kept (the last one without a history); VEC: also out and conf 16-byte aligned
+template <int K, bool VEC, bool BIAS, class GT, bool ABS, bool COLLECT>
+__device__ __forceinline__ void forward_step_body(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst, int C, int H,
+                                                  int W, int tiles_x, int tiles_y, const float* __restrict__ bias, const Collect& col) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -230,10 +248,33 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
             for (int j = 0; j < 4; ++j) S[j] += g[k].mag(j);
         rsl[threadIdx.x] = make_float4(1.f / S[0], 1.f / S[1], 1.f / S[2], 1.f / S[3]);   // read back by this thread alone
     }
+    // COLLECT: the epilogue's operands wait in LDS as well: conf_j, conf_0 and, per channel, what out holds.  Their loads are issued with
+    // the gates' and the staged plane's and ride on those waits; loaded behind the stencil they are a dependent round trip to memory
+    // per tile, loaded in front of it into registers they cost the step an occupancy (K = 7: 294 registers, one wave)
+    __shared__ float4 park[COLLECT ? 3 * NT : 1];
+    if constexpr (COLLECT) {
+        const size_t cb = (size_t)(T.n / col.cpg) * col.stride + pix;
+        float w[4];
+        if (col.cj) {
+            load4<VEC>(w, col.cj + cb, row_in, T.x0, W);
+            park[threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
+        }
+        if (col.c0) {
+            load4<VEC>(w, col.c0 + cb, row_in, T.x0, W);
+            park[NT + threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
+        }
+    }
     for (int c = 0; c < C; ++c) {
         const size_t plane = ((size_t)T.n * C + c) * HW;
         __syncthreads();   // the previous channel's reads of lds are done
         stage<R>(lds, src + plane, T.y0, T.xt0, H, W);
+        if constexpr (COLLECT) {
+            if (col.accumulate) {
+                float a[4];
+                load4<VEC>(a, col.out + plane + pix, row_in, T.x0, W);
+                park[2 * NT + threadIdx.x] = make_float4(a[0], a[1], a[2], a[3]);
+            }
+        }
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < KK; ++k) g[k].pin();
@@ -260,16 +301,57 @@ __global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __rest
             const float4 q = rsl[threadIdx.x];
             acc[0] *= q.x; acc[1] *= q.y; acc[2] *= q.z; acc[3] *= q.w;
         }
-        store4<VEC>(dst + plane + pix, acc, row_in, T.x0, W);
+        if constexpr (COLLECT) {
+            // the epilogue starts here, behind the stencil (the sums are operands, so this cannot move above it, and memory is clobbered,
+            // so the parked values are read back, not kept): hoisted, it costs the step registers it does not have
+            int px = pix;
+            asm volatile("" : "+v"(px), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]) : : "memory");
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+            if (col.accumulate) {
+                const float4 q = park[2 * NT + threadIdx.x];
+                a[0] = q.x; a[1] = q.y; a[2] = q.z; a[3] = q.w;
+            }
+            if (col.c0) {   // level 0: the thread's own pixels of src, still staged
+                const float4 q = park[NT + threadIdx.x];
+                const float w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = w[j] * lds[(T.ly + R) * SW + 4 * T.lq + R + j];
+            }
+            if (col.cj) {
+                const float4 q = park[threadIdx.x];
+                const float w[4] = {q.x, q.y, q.z, q.w};
+                const bool first = !col.accumulate && !col.c0;   // conf * acc as it is: with conf = 1 the bits of the level
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = first ? w[j] * acc[j] : fmaf(w[j], acc[j], a[j]);
+            }
+            store4<VEC>(col.out + plane + px, a, row_in, T.x0, W);
+            if (dst) store4<VEC>(dst + plane + px, acc, row_in, T.x0, W);
+        } else {
+            store4<VEC>(dst + plane + pix, acc, row_in, T.x0, W);
+        }
     }
+}
+
+template <int K, bool VEC, bool BIAS = false, class GT = float, bool ABS = false>
+__global__ __launch_bounds__(NT) void kxk_forward_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
+                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias) {
+    forward_step_body<K, VEC, BIAS, GT, ABS, false>(gate, src, dst, C, H, W, tiles_x, tiles_y, bias, Collect{});
+}
+
+// the collecting form of the folded contract's step (float32 w' and b)
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void kxk_forward_step_collect(const float* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst, int C,
+                                                               int H, int W, int tiles_x, int tiles_y, const float* __restrict__ bias, Collect col) {
+    forward_step_body<K, VEC, true, float, false, true>(gate, src, dst, C, H, W, tiles_x, tiles_y, bias, col);
 }
 
 // one adjoint step for all C channels: dst = step^T(src).  The gate of pixel q and channel k is read at q - off_k (zero outside the
 // image); VEC: W % 4 == 0 and dst 16-byte aligned, 16-bit gates 8-byte aligned
 // ABS: gate is the raw guide; src is staged times 1 / S (rs [N][H][W], or NULL: stage_scaled) and the stencil runs on |gate|
-template <int K, bool VEC, class GT = float, bool ABS = false>
-__global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
-                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ rs) {
+// INJECT: dst = step^T(src) + conf_j grad_out, added in the store epilogue (col.cj, col.g); VEC: also grad_out and conf 16-byte aligned
+template <int K, bool VEC, class GT, bool ABS, bool INJECT>
+__device__ __forceinline__ void adjoint_step_body(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst, int C, int H,
+                                                  int W, int tiles_x, int tiles_y, const float* __restrict__ rs, const Collect& col) {
     constexpr int R = K / 2, KK = K * K - 1, SW = TW + 2 * R;
     __shared__ float lds[(TH + 2 * R) * SW];
     const Tile T = tile_of(tiles_x, tiles_y);
@@ -352,8 +434,61 @@ __global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __rest
                 for (int j = 0; j < 4; ++j) acc[j] = fmaf(ABS ? g[k].mag(j) : g[k].get(j), row[j + l], acc[j]);
             }
         }
+        if constexpr (INJECT) {
+            int pix = T.y * W + T.x0;
+            asm volatile("" : "+v"(pix), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]) : : "memory");   // behind the stencil, as the collecting step's
+            float w[4], go[4];
+            load4<VEC>(w, col.cj + (size_t)(T.n / col.cpg) * col.stride + pix, row_in, T.x0, W);
+            load4<VEC>(go, col.g + plane + pix, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = fmaf(w[j], go[j], acc[j]);
+        }
         store4<VEC>(dst + plane + T.y * W + T.x0, acc, row_in, T.x0, W);
     }
+}
+
+template <int K, bool VEC, class GT = float, bool ABS = false>
+__global__ __launch_bounds__(NT) void kxk_adjoint_step(const store_t<GT>* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst,
+                                                       int C, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ rs) {
+    adjoint_step_body<K, VEC, GT, ABS, false>(gate, src, dst, C, H, W, tiles_x, tiles_y, rs, Collect{});
+}
+
+// the injecting form, on the folded contract's float32 w'
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void kxk_adjoint_step_inject(const float* __restrict__ gate, const float* __restrict__ src, float* __restrict__ dst, int C,
+                                                              int H, int W, int tiles_x, int tiles_y, Collect col) {
+    adjoint_step_body<K, VEC, float, false, true>(gate, src, dst, C, H, W, tiles_x, tiles_y, nullptr, col);
+}
+
+// the assembling contract's own reduction, per guidance image b and pixel p: dc(b,p) = sum_c G(b,c,p) lev(b,c,p), summed in channel order
+// and written once (dc NULL: left out), and top(b,c,p) = cj(b,p) G(b,c,p), the scaled top adjoint level (top NULL: left out).  G, lev and
+// top are [B][C][H][W]; cj and dc are one plane of [B][T][H][W] (stride: T H W).  VEC: W % 4 == 0 and all five 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(NT) void kxk_conf_grad(const float* __restrict__ G, const float* __restrict__ lev, const float* __restrict__ cj,
+                                                    float* __restrict__ dc, float* __restrict__ top, size_t stride, int C, int H, int W, int tiles_x,
+                                                    int tiles_y) {
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    float w[4] = {0.f, 0.f, 0.f, 0.f}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+    if (top) load4<VEC>(w, cj + (size_t)T.n * stride + pix, row_in, T.x0, W);
+    for (int c = 0; c < C; ++c) {
+        const size_t at = ((size_t)T.n * C + c) * HW + pix;
+        float go[4], h[4];
+        load4<VEC>(go, G + at, row_in, T.x0, W);
+        if (dc) {
+            load4<VEC>(h, lev + at, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sum[j] = fmaf(go[j], h[j], sum[j]);
+        }
+        if (top) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = w[j] * go[j];
+            store4<VEC>(top + at, h, row_in, T.x0, W);
+        }
+    }
+    if (dc) store4<VEC>(dc + (size_t)T.n * stride + pix, sum, row_in, T.x0, W);
 }
 
 // dL/dg for all KK channels of the tile: the levels H_0 = x, H_t = hist + (t - 1) L (t >= 1) and A_t = alev + (t - 1) L (t < n),
@@ -777,6 +912,15 @@ auto with_bool(bool b, F&& f) {
 }
 
 template <int K, bool BIAS = false, class GT = float, bool ABS = false>
+int forward_step(const store_t<GT>* gate, const float* src, float* dst, const Grid& G, int C, int H, int W, hipStream_t st, const float* bias) {
+    with_bool(W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)), [&](auto vec) {
+        hipLaunchKernelGGL((kxk_forward_step<K, decltype(vec)::value, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty,
+                           bias);
+    });
+    return check_launch("kxk_forward_step");
+}
+
+template <int K, bool BIAS = false, class GT = float, bool ABS = false>
 int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hist, int N, int C, int H, int W, int n_iter, void* ws, hipStream_t st,
                   const float* bias = nullptr) {
     const Grid G = grid_of(N, H, W);
@@ -786,14 +930,18 @@ int forward_steps(const store_t<GT>* gate, const float* x, float* out, float* hi
     const float* src = x;
     for (int it = 1; it <= n_iter; ++it) {
         float* dst = it == n_iter ? out : (hist ? hist + (size_t)(it - 1) * L : ((it & 1) ? ping : pong));
-        with_bool(W % 4 == 0 && aligned_quad<GT>(gate) && aligned16(dst) && (!BIAS || aligned16(bias)), [&](auto vec) {
-            hipLaunchKernelGGL((kxk_forward_step<K, decltype(vec)::value, BIAS, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx,
-                               G.ty, bias);
-        });
-        if (int e = check_launch("kxk_forward_step")) return e;
+        if (int e = forward_step<K, BIAS, GT, ABS>(gate, src, dst, G, C, H, W, st, bias)) return e;
         src = dst;
     }
     return 0;
+}
+
+template <int K, class GT = float, bool ABS = false>
+int adjoint_step(const store_t<GT>* gate, const float* src, float* dst, const Grid& G, int C, int H, int W, hipStream_t st, const float* rs) {
+    with_bool(W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)), [&](auto vec) {
+        hipLaunchKernelGGL((kxk_adjoint_step<K, decltype(vec)::value, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty, rs);
+    });
+    return check_launch("kxk_adjoint_step");
 }
 
 // the adjoint steps A_{n-1} .. A_last into alev (A_t at alev + (t - 1) L), A_0 into gx; ABS: rs as kxk_adjoint_step takes it
@@ -805,11 +953,7 @@ int adjoint_steps(const store_t<GT>* gate, const float* gout, float* gx, float* 
     for (int t = n_iter - 1; t >= last; --t) {
         const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * L;
         float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * L;
-        with_bool(W % 4 == 0 && aligned16(dst) && (std::is_same<GT, float>::value || aligned_quad<GT>(gate)), [&](auto vec) {
-            hipLaunchKernelGGL((kxk_adjoint_step<K, decltype(vec)::value, GT, ABS>), dim3(G.blocks), dim3(NT), 0, st, gate, src, dst, C, H, W, G.tx, G.ty,
-                               rs);
-        });
-        if (int e = check_launch("kxk_adjoint_step")) return e;
+        if (int e = adjoint_step<K, GT, ABS>(gate, src, dst, G, C, H, W, st, rs)) return e;
     }
     return 0;
 }
@@ -873,19 +1017,31 @@ int norm_forward(const store_t<GT>* guid, const float* blur, const float* sparse
     return forward_steps<K, true>(wp, blur, out, hist, g.N, g.Cv, H, W, n_iter, bias + kxk_level_floats(g.L), st, bias);
 }
 
+// the parts of the folded contract's backward workspace: w' and b, dL/dw' and dL/db, A_1 .. A_{n-1}, and what follows them (the assembling
+// contract's scaled top level)
+struct NormBackwardWs {
+    float *wp, *bias, *dwp, *dbp, *alev, *top;
+};
+
+template <int K>
+NormBackwardWs norm_backward_ws(void* ws, const NormGeo& g, int H, int W, int n_iter) {
+    const size_t P = kxk_level_floats((size_t)g.N * (K * K - 1) * H * W);
+    NormBackwardWs w;
+    w.wp = (float*)ws;
+    w.bias = w.wp + P;
+    w.dwp = w.bias + kxk_level_floats(g.L);
+    w.dbp = w.dwp + P;
+    w.alev = w.dbp + kxk_level_floats(g.L);
+    w.top = (float*)((char*)w.alev + round256(sizeof(float) * g.L * (size_t)(n_iter - 1)));
+    return w;
+}
+
+// after the adjoint steps: the gate gradient with dL/db (atop: the top adjoint level A_n), the fold's adjoint per pixel, the gather back
 template <int K, class GT = float>
-int norm_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int B, int C,
-                  int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
-    constexpr int KK = K * K - 1;
-    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
-    const size_t P = kxk_level_floats((size_t)g.N * KK * H * W);
-    float* wp = (float*)ws;
-    float* bias = wp + P;
-    float* dwp = bias + kxk_level_floats(g.L);
-    float* dbp = dwp + P;
-    float* alev = dbp + kxk_level_floats(g.L);
-    if (int e = fold<K, GT>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
-    if (int e = adjoint_steps<K>(wp, gout, gx, alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
+int norm_backward_finish(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* atop, store_t<GT>* gg, float* gx,
+                         int B, const NormGeo& g, const NormBackwardWs& w, int H, int W, int n_iter, int norm, hipStream_t st) {
+    float *dwp = w.dwp, *dbp = w.dbp, *alev = w.alev;
+    const float* gout = atop;
     const Grid G = grid_of(g.N, H, W);
     const bool vec = W % 4 == 0;   // dwp and dbp: workspace
     with_bool(vec, [&](auto v) {
@@ -906,6 +1062,98 @@ int norm_backward(const store_t<GT>* guid, const float* blur, const float* spars
         hipLaunchKernelGGL((kxk_unsite<K, decltype(v)::value, GT>), dim3(GB.blocks), dim3(NT), 0, st, dwp, guid, gg, g.cpg, norm, H, W, GB.tx, GB.ty);
     });
     return check_launch("kxk_unsite");
+}
+
+template <int K, class GT = float>
+int norm_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int B, int C,
+                  int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    const NormBackwardWs w = norm_backward_ws<K>(ws, g, H, W, n_iter);
+    if (int e = fold<K, GT>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st)) return e;
+    if (int e = adjoint_steps<K>(w.wp, gout, gx, w.alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
+    return norm_backward_finish<K, GT>(guid, blur, sparse, hist, gout, gg, gx, B, g, w, H, W, n_iter, norm, st);
+}
+
+// ---- the assembling contract: out = sum_j conf_j H_{s_j} over the levels of the folded contract, s_0 < .. < s_{T-1} = n (host array steps),
+// conf [B][T][H][W].  hist: NULL, or H_1 .. H_n (level t at hist + (t - 1) B C H W: H_n is no longer the output) ----
+template <int K, class GT = float>
+int assemble_forward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out, float* hist,
+                     int B, int C, int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+    constexpr int KK = K * K - 1;
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    const size_t HW = (size_t)H * W;
+    float* wp = (float*)ws;
+    float* bias = wp + kxk_level_floats((size_t)g.N * KK * HW);
+    float* ping = bias + kxk_level_floats(g.L);
+    float* pong = ping + kxk_level_floats(g.L);
+    if (int e = fold<K, GT>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    const Grid G = grid_of(g.N, H, W);
+    const float* src = blur;
+    int j = steps[0] == 0 ? 1 : 0;
+    const float* c0 = j ? conf : nullptr;   // a collected level 0 rides on the first step
+    bool started = false;
+    for (int it = 1; it <= n_iter; ++it) {
+        const bool hit = j < T && steps[j] == it;
+        float* dst = hist ? hist + (size_t)(it - 1) * g.L : (it == n_iter ? nullptr : ((it & 1) ? ping : pong));
+        if (!hit && !c0) {
+            if (int e = forward_step<K, true>(wp, src, dst, G, g.Cv, H, W, st, bias)) return e;
+        } else {
+            const Collect col{hit ? conf + (size_t)j * HW : nullptr, c0, out, nullptr, (size_t)T * HW, g.cpg, started ? 1 : 0};
+            with_bool(W % 4 == 0 && aligned16(wp) && aligned16(dst) && aligned16(bias) && aligned16(out) && aligned16(conf), [&](auto vec) {
+                hipLaunchKernelGGL((kxk_forward_step_collect<K, decltype(vec)::value>), dim3(G.blocks), dim3(NT), 0, st, wp, src, dst, g.Cv, H, W, G.tx, G.ty,
+                                   bias, col);
+            });
+            if (int e = check_launch("kxk_forward_step_collect")) return e;
+            started = true;
+            c0 = nullptr;
+            j += hit;
+        }
+        src = dst;
+    }
+    return 0;
+}
+
+// gg, gx and gc (dL/dconf [B][T][H][W]) may each be NULL; ws: the folded backward's, then the scaled top level A_n = conf_{T-1} grad_out
+template <int K, class GT = float>
+int assemble_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* conf, const int* steps, int T, const float* hist,
+                      const float* gout, store_t<GT>* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int n_iter, int norm, void* ws,
+                      hipStream_t st) {
+    const NormGeo g = norm_geo(B, C, sparse_C, H, W);
+    const NormBackwardWs w = norm_backward_ws<K>(ws, g, H, W, n_iter);
+    const size_t HW = (size_t)H * W, stride = (size_t)T * HW;
+    const bool levels = gg || gx;   // the adjoint sweep runs
+    const Grid GB = grid_of(B, H, W);
+    for (int j = 0; j < T; ++j) {   // dL/dconf_j, and with the last one the top level
+        float* top = levels && j == T - 1 ? w.top : nullptr;
+        float* dc = gc ? gc + (size_t)j * HW : nullptr;
+        if (!top && !dc) continue;
+        const float* lev = steps[j] == 0 ? blur : hist + (size_t)(steps[j] - 1) * g.L;
+        const float* cj = conf + (size_t)j * HW;
+        with_bool(W % 4 == 0 && aligned16(gout) && aligned16(conf) && (!dc || (aligned16(lev) && aligned16(gc))), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_conf_grad<decltype(vec)::value>), dim3(GB.blocks), dim3(NT), 0, st, gout, lev, cj, dc, top, stride, C, H, W, GB.tx, GB.ty);
+        });
+        if (int e = check_launch("kxk_conf_grad")) return e;
+    }
+    if (!levels) return 0;
+    if (int e = fold<K, GT>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st)) return e;
+    const Grid G = grid_of(g.N, H, W);
+    int j = T - 2;   // the next collected level below the one being produced
+    for (int t = n_iter - 1; t >= (gx ? 0 : 1); --t) {
+        const float* src = t + 1 == n_iter ? w.top : w.alev + (size_t)t * g.L;
+        float* dst = t == 0 ? gx : w.alev + (size_t)(t - 1) * g.L;
+        if (j >= 0 && steps[j] == t) {
+            const Collect col{conf + (size_t)j * HW, nullptr, nullptr, gout, stride, g.cpg, 0};
+            with_bool(W % 4 == 0 && aligned16(dst) && aligned16(gout) && aligned16(conf), [&](auto vec) {
+                hipLaunchKernelGGL((kxk_adjoint_step_inject<K, decltype(vec)::value>), dim3(G.blocks), dim3(NT), 0, st, w.wp, src, dst, g.Cv, H, W, G.tx, G.ty,
+                                   col);
+            });
+            if (int e = check_launch("kxk_adjoint_step_inject")) return e;
+            --j;
+        } else if (int e = adjoint_step<K>(w.wp, src, dst, G, g.Cv, H, W, st, nullptr)) {
+            return e;
+        }
+    }
+    return norm_backward_finish<K, GT>(guid, blur, sparse, hist, w.top, gg, gx, B, g, w, H, W, n_iter, norm, st);
 }
 
 }  // namespace
@@ -963,6 +1211,30 @@ int kxk_norm_backward(const void* guid, int dtype, const float* blur, const floa
         return with_k<3, 5, 7>(K, [&](auto k) {
             return norm_backward<decltype(k)::value, GT>((const store_t<GT>*)guid, blur, sparse, hist, gout, (store_t<GT>*)gg, gx, B, C, sparse_C, H, W,
                                                         n_iter, norm, ws, st);
+        });
+    });
+}
+
+// the assembling contract; n_iter >= 1, steps (host memory) strictly increasing from >= 0 to n_iter, 1 <= T
+int kxk_assemble_forward(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out,
+                         float* hist, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<3, 5, 7>(K, [&](auto k) {
+            return assemble_forward<decltype(k)::value, GT>((const store_t<GT>*)guid, blur, sparse, conf, steps, T, out, hist, B, C, sparse_C, H, W, n_iter, norm,
+                                                            ws, st);
+        });
+    });
+}
+
+int kxk_assemble_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, const float* hist,
+                          const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                          hipStream_t st) {
+    return with_gate_type(dtype, [&](auto gt) {
+        using GT = typename decltype(gt)::type;
+        return with_k<3, 5, 7>(K, [&](auto k) {
+            return assemble_backward<decltype(k)::value, GT>((const store_t<GT>*)guid, blur, sparse, conf, steps, T, hist, gout, (store_t<GT>*)gg, gx, gc, B, C,
+                                                             sparse_C, H, W, n_iter, norm, ws, st);
         });
     });
 }

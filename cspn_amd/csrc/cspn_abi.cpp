@@ -1185,6 +1185,134 @@ int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const flo
                                    grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
 }
 
+// ---- the assembling contract over K x K levels (cspn2d_*_kxk_assemble*): the folded contract's arguments and checks, plus the confidences, the
+// collected iterations (host memory, read here) and, in the backward, dL/dconf ----
+size_t cspn2d_kxk_assemble_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
+    return cspn2d_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);   // the fold and the ping-pong levels; out is the third buffer
+}
+
+size_t cspn2d_kxk_assemble_history_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!kxk_norm_shape_ok(B, C, 0, H, W, K, n_iter) || n_iter < 1) return 0;
+    return kxk_values_bytes(B, C, H, W) * (size_t)n_iter;   // H_1 .. H_n
+}
+
+size_t cspn2d_backward_kxk_assemble_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
+    const size_t norm = cspn2d_backward_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
+    return norm ? norm + sizeof(float) * kxk_level_floats((size_t)B * C * H * W) : 0;   // then A_n = conf_{T-1} grad_out
+}
+
+// what the assembling entries check before the folded contract's own checks: every pointer by name, the shape, conf's size, the steps
+static int kxk_assemble_check(const char* what, std::initializer_list<std::pair<const char*, const void*>> required, const float* sparse, const int* steps, int T,
+                              int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm) {
+    for (const auto& r : required)
+        if (!r.second) { set_error("%s: %s is NULL", what, r.first); return CSPN_E_BADARG; }
+    if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (n_iter < 1) { set_error("%s: n_iter must be >= 1 (got %d)", what, n_iter); return CSPN_E_BADARG; }
+    if (norm != CSPN_NORM_8SUM && norm != CSPN_NORM_8SUM_ABS) { set_error("%s: norm must be CSPN_NORM_8SUM or CSPN_NORM_8SUM_ABS, got %d", what, norm); return CSPN_E_BADARG; }
+    if ((sparse_C != 0 && sparse_C != 1 && sparse_C != C) || (sparse_C == 0) != (sparse == nullptr)) {
+        set_error("%s: sparse_C must be 0 (sparse NULL), 1 or C = %d (sparse given), got %d", what, C, sparse_C);
+        return CSPN_E_BADARG;
+    }
+    if (T < 1 || T > n_iter + 1) { set_error("%s: T must be in 1 .. n_iter + 1 = %d, got %d", what, n_iter + 1, T); return CSPN_E_BADARG; }
+    const long long px = (long long)H * W, lim = 0x7fffffffLL;
+    if ((long long)B * C * px > lim) { set_error("%s: blur / out of B C H W = %lld elements: a view must stay below 2^31 elements", what, (long long)B * C * px); return CSPN_E_BADARG; }
+    if ((sparse_C > 1 ? (long long)B * C : B) * (K * K - 1) * px > lim) { set_error("%s: guidance (per mask) of more than 2^31 - 1 elements", what); return CSPN_E_BADARG; }
+    if ((long long)B * T * px > lim) { set_error("%s: conf of B T H W = %lld elements: a view must stay below 2^31 elements", what, (long long)B * T * px); return CSPN_E_BADARG; }
+    for (int j = 0; j < T; ++j)
+        if (steps[j] < 0 || (j && steps[j] <= steps[j - 1])) { set_error("%s: steps must be strictly increasing from >= 0 (steps[%d] = %d)", what, j, steps[j]); return CSPN_E_BADARG; }
+    if (steps[T - 1] != n_iter) { set_error("%s: steps[T-1] must be n_iter = %d, got %d", what, n_iter, steps[T - 1]); return CSPN_E_BADARG; }
+    return 0;
+}
+
+static int kxk_assemble_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
+                                      const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W,
+                                      int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"out", out}}, sparse, steps, T, B, C,
+                                   sparse_C, H, W, K, n_iter, norm))
+        return e;
+    if (g16)
+        if (int e = g16_check(what, dtype, guidance, nullptr)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C, cb = vb / C * T;
+    const size_t hb = cspn2d_kxk_assemble_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = cspn2d_kxk_assemble_workspace_bytes(B, C, sparse_C, H, W, K, history ? 1 : n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}, {history, hb}, {ws, ws_bytes}}) ||
+        kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}, {ws, ws_bytes}}) ||
+        kxk_overlaps(ws, ws_bytes, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    return kxk_assemble_forward(guidance, dtype, blur, sparse, conf, steps, T, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, (hipStream_t)stream);
+}
+
+static int kxk_assemble_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
+                                       const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance,
+                                       float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                                       size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"grad_out", grad_out}}, sparse, steps, T, B,
+                                   C, sparse_C, H, W, K, n_iter, norm))
+        return e;
+    if (g16)
+        if (int e = g16_check(what, dtype, guidance, grad_guidance)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C, cb = vb / C * T;
+    const size_t hb = cspn2d_kxk_assemble_history_bytes(B, C, H, W, K, n_iter);
+    const bool reads_history = (grad_guidance && n_iter >= 2) || grad_conf;   // H_1 .. H_{n-1} for the gates, H_{s_j} for the confidences
+    if (reads_history && (!history || history_bytes < hb)) {
+        set_error("%s: grad_guidance and grad_conf need the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_assemble_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t hbu = reads_history ? hb : 0;
+    if ((grad_guidance && ((const void*)grad_guidance == (const void*)grad_blur || (const void*)grad_guidance == (const void*)grad_conf)) ||
+        (grad_blur && grad_blur == grad_conf)) {
+        set_error("%s: grad_guidance, grad_blur and grad_conf must not alias", what);
+        return CSPN_E_BADARG;
+    }
+    const std::initializer_list<std::pair<const void*, size_t>> inputs = {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}, {history, hbu}, {grad_out, vb}};
+    if (kxk_overlaps(grad_guidance, gb, inputs) || kxk_overlaps(grad_blur, vb, inputs) || kxk_overlaps(grad_conf, cb, inputs) || kxk_overlaps(ws, ws_bytes, inputs) ||
+        kxk_overlaps(ws, ws_bytes, {{grad_guidance, gb}, {grad_blur, vb}, {grad_conf, cb}}) ||
+        kxk_overlaps(grad_guidance, gb, {{grad_blur, vb}, {grad_conf, cb}}) || kxk_overlaps(grad_blur, vb, {{grad_conf, cb}})) {
+        set_error("%s: grad_guidance, grad_blur, grad_conf and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_guidance && !grad_blur && !grad_conf) return 0;
+    return kxk_assemble_backward(guidance, dtype, blur, sparse, conf, steps, T, history, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K,
+                                 n_iter, norm, ws, (hipStream_t)stream);
+}
+
+int cspn2d_forward_kxk_assemble_f32(const float* guidance, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out,
+                                    float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                                    size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_assemble_forward_entry("cspn2d_forward_kxk_assemble_f32", guidance, false, 0, blur, sparse, conf, steps, T, out, history, history_bytes, B, C,
+                                      sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
+}
+
+int cspn2d_forward_kxk_assemble_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                    float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm,
+                                    void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return kxk_assemble_forward_entry("cspn2d_forward_kxk_assemble_g16", guidance, true, gate_dtype, blur, sparse, conf, steps, T, out, history, history_bytes, B,
+                                      C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_kxk_assemble_f32(const float* guidance, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                     const float* history, size_t history_bytes, const float* grad_out, float* grad_guidance, float* grad_blur,
+                                     float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes,
+                                     cspn_stream_t stream) {
+    return kxk_assemble_backward_entry("cspn2d_backward_kxk_assemble_f32", guidance, false, 0, blur, sparse, conf, steps, T, history, history_bytes, grad_out,
+                                       grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_kxk_assemble_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                     const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur,
+                                     float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes,
+                                     cspn_stream_t stream) {
+    return kxk_assemble_backward_entry("cspn2d_backward_kxk_assemble_g16", guidance, true, gate_dtype, blur, sparse, conf, steps, T, history, history_bytes,
+                                       grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
+}
+
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----
 static int head_kxk_check(const char* what, int B, int C, int h, int w, int H, int W, int K) {
     if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }

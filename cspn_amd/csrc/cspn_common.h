@@ -127,6 +127,14 @@ int kxk_norm_forward(const void* guid, int dtype, const float* blur, const float
 // ws: the fold, dL/dw', dL/db (one fold's size), then A_1 .. A_{n-1}; gg needs hist (n >= 2), gx and gg may each be NULL
 int kxk_norm_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg, float* gx,
                       int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+// the assembling contract on the same levels: out = sum_j conf_j H_{s_j}, conf [B][T][H][W] shared by the C channels, steps s_0 < .. < s_{T-1} = n_iter
+// in host memory (s_0 >= 0), n_iter >= 1.  ws as kxk_norm_forward; hist NULL or H_1 .. H_n (n levels: H_n is not the output)
+int kxk_assemble_forward(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out,
+                         float* hist, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, hipStream_t st);
+// ws: kxk_norm_backward's, then one level (kxk_level_floats) for A_n = conf_{T-1} gout; gc = dL/dconf; gg, gx, gc may each be NULL; gg (n >= 2) and gc need hist
+int kxk_assemble_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, const float* hist,
+                          const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
+                          hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

@@ -1,6 +1,8 @@
 """Functional front-end over the C ABI: tensors in, tensor out, work enqueued on
 torch's current HIP stream.  PyTorch is plumbing here (device memory + streams);
 all arithmetic happens in libcspn_amd.so."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -799,6 +801,102 @@ def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kerne
              _lib.NORM_TYPES[norm_type]),
             ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
     return gg, gh
+
+
+# ---- assembling K x K levels per pixel (CSPN++): out = sum_j conf_j H_{s_j} over the levels H_t of cspn2d_forward_kxk_norm, H_0 = blur_depth
+# (cspn2d_*_kxk_assemble_f32 / _g16) ----
+def _assemble_steps(steps, n_iter):
+    """steps: ints, strictly increasing, steps[0] >= 0, steps[-1] == n_iter >= 1 -> (tuple, the ctypes array the engine reads)"""
+    try:
+        st = tuple(steps)
+    except TypeError:
+        raise ValueError("steps must be a sequence of ints, got %r" % (steps,)) from None
+    if not st or any(isinstance(s, bool) or not isinstance(s, int) for s in st):
+        raise ValueError("steps must be a non-empty sequence of ints, got %r" % (steps,))
+    n = int(n_iter)
+    if n < 1:
+        raise ValueError("n_iter must be >= 1 for the assembling call (got %r)" % (n_iter,))
+    if st[0] < 0 or any(b <= a for a, b in zip(st, st[1:])) or st[-1] != n:
+        raise ValueError("steps must be strictly increasing, start at >= 0 and end at n_iter = %d, got %r" % (n, st))
+    return st, (ctypes.c_int * len(st))(*st)
+
+
+def _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, extra=()):
+    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    st, c_steps = _assemble_steps(steps, n_iter)
+    if not isinstance(conf, torch.Tensor):
+        raise TypeError("conf must be a torch.Tensor")
+    if tuple(conf.shape) != (B, len(st), H, W):
+        raise ValueError("conf has shape %s, expected (B,len(steps),H,W) = %s" % (tuple(conf.shape), (B, len(st), H, W)))
+    for t, name in extra:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(blur_depth.shape):
+            raise ValueError("%s must be a tensor of shape %s" % (name, tuple(blur_depth.shape)))
+    if any(isinstance(t, torch.Tensor) and t.device != guidance.device for t in (blur_depth, sparse_depth, conf) + tuple(t for t, _ in extra)):
+        raise ValueError("all tensors must live on the same device")
+    g, dt, h, s, *rest = _kxk_norm_args(guidance, blur_depth, sparse_depth, extra)
+    return (g, dt, h, s, _prep_value(conf, "conf"), c_steps, len(st), K, B, C, H, W, sc) + tuple(rest)
+
+
+def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False):
+    """out [B,C,H,W] = sum_j conf[:, j] * H_{steps[j]}: the levels H_t of cspn2d_forward_kxk_norm (H_0 = blur_depth) assembled per pixel
+    inside the engine, one call (cspn2d_forward_kxk_assemble_f32).  conf [B,len(steps),H,W], shared by the C channels and used as given
+    (no softmax); steps strictly increasing ints, steps[0] >= 0, steps[-1] == n_iter >= 1.  return_history: (out, history) with the n levels
+    H_1 .. H_n for cspn2d_backward_kxk_assemble.  guidance may be float16 / bfloat16 and is taken as it is (out is float32 and bitwise the
+    float32 call on guidance.float()); a 16-bit conf, blur_depth or sparse_depth is widened with one cast."""
+    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
+    n = int(n_iter)
+    out = torch.empty_like(h)
+    hist = None
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    hb = 0
+    if return_history:
+        with torch.cuda.device(g.device):
+            hb = _lib.symbol("cspn2d_kxk_assemble_history_bytes")(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    _launch("cspn2d_forward_kxk_assemble_f32" if dt is None else "cspn2d_forward_kxk_assemble_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, n,
+             _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
+                                 need_guidance=True, need_blur=True, need_conf=True):
+    """Gradient of cspn2d_forward_kxk_assemble -> (dL/dguidance [B,K*K-1,H,W] in the guidance's dtype, rounded once, dL/dblur_depth [B,C,H,W],
+    dL/dconf [B,len(steps),H,W]), None where not asked for; one engine call (cspn2d_backward_kxk_assemble_f32): the adjoint sweep of
+    cspn2d_backward_kxk_norm with conf_j grad_out injected at every collected level, and dL/dconf_j = sum_c grad_out H_{steps[j]}.  history: what
+    cspn2d_forward_kxk_assemble(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dconf needs it."""
+    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc, go = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type,
+                                                                        ((grad_out, "grad_out"),))
+    n = int(n_iter)
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    gc = torch.empty_like(cf) if need_conf else None
+    if not (need_guidance or need_blur or need_conf):
+        return gg, gh, gc
+    if h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), gh, gc
+    if history is None and ((need_guidance and n >= 2) or need_conf):
+        _, history = cspn2d_forward_kxk_assemble(g, h, s, cf, steps, K, n, norm_type, return_history=True)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    _launch("cspn2d_backward_kxk_assemble_f32" if dt is None else "cspn2d_backward_kxk_assemble_g16", g.device,
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc),
+             B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_backward_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, n))
+    return gg, gh, gc
+
+
+def assemble_conf(iter_conf, kernel_conf, k, T, like):
+    """the confidences one kernel size of Affinity_PropagateAssemble hands to the engine: iter_conf [B,T,H,W] (None: ones) times
+    kernel_conf[:, k:k+1] (None: no such factor), one differentiable torch op; like: blur_depth (batch, image size, device)"""
+    B, _, H, W = like.shape
+    if iter_conf is None and kernel_conf is None:
+        return torch.ones((B, T, H, W), dtype=torch.float32, device=like.device)
+    if kernel_conf is None:
+        return iter_conf
+    a = kernel_conf[:, k:k + 1]
+    return a.expand(B, T, H, W) if iter_conf is None else iter_conf * a
 
 
 # ---- the demo's module (reference cspn_paddle/demo.py:20-54): abs (:24), each channel's slice of K = 3^d - 1 gates divided by its own

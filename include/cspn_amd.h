@@ -474,6 +474,43 @@ int cspn2d_backward_kxk_norm_g16(const void* guidance, int gate_dtype, const flo
                                  size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
                                  int H, int W, int K, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
+/* ---- assembling K x K propagation levels per pixel (CSPN++, "context-aware" CSPN): the depth-completion contract above, but the result is
+ * a per-pixel weighted sum of collected levels,
+ *     out(b,c,p) = sum_{j<T} conf(b,j,p) H_{s_j}(b,c,p),     H_0 = blur, H_t the levels of cspn2d_forward_kxk_norm_*
+ *   conf [B,T,H,W] float32, shared by the C channels; steps = {s_0 < s_1 < .. < s_{T-1} = n_iter}, s_0 >= 0, T ints in HOST memory, read
+ *   before the call returns; 1 <= T <= n_iter + 1; n_iter >= 1.  The other arguments are those of the _kxk_norm_ entry points.  The engine
+ *   runs the same fold and the same step; a step that produces a collected level also updates out from the level it holds in registers
+ *   (4 + 8 C bytes per pixel more than a plain step's 4 KK + 12 C; the first collected step 4 + 4 C, out is written before it is read, so
+ *   it need not be initialised); a collected level 0 rides on the first step.  The levels ping-pong in two workspace planes and out is
+ *   a third buffer (cspn2d_kxk_assemble_workspace_bytes; with a history: that query's value for n_iter = 1, the fold).
+ *   history: NULL, or n levels H_1 .. H_n ([n][B][C][H][W], cspn2d_kxk_assemble_history_bytes: H_n is not the output here).
+ * Backward: grad_out = dL/dout -> grad_guidance, grad_blur (as the _kxk_norm_ backward) and grad_conf [B,T,H,W]; each may be NULL.
+ *     A_n = conf_{T-1} grad_out (one plane at the end of the workspace), A_t = step^T(A_{t+1}) + [t = s_j] conf_j grad_out, added in the
+ *     adjoint step's store; grad_blur also receives conf_0 grad_out where s_0 = 0; grad_conf(b,j,p) = sum_c grad_out(b,c,p) H_{s_j}(b,c,p),
+ *     summed in channel order, every element written once (no atomics: deterministic).  grad_guidance (n_iter >= 2) and grad_conf need the
+ *     history of a forward with the same arguments.  With T = 1 and conf = 1 every result is bitwise the _kxk_norm_ entry point's.
+ * The _g16 twins take the guidance (and return grad_guidance) in gate_dtype under the rule of the 16-bit block above; conf stays float32.
+ * Errors: a NULL pointer (named in cspn_last_error()), K, norm, sparse_C, n_iter < 1, T or steps out of the rules above, a view of 2^31
+ * elements or more, an output aliasing an input or another output: CSPN_E_BADARG; a workspace or history too small or a workspace not
+ * 256-byte aligned: CSPN_E_WORKSPACE.  The byte-count queries return 0 for arguments the entries refuse. */
+size_t cspn2d_kxk_assemble_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter);
+size_t cspn2d_kxk_assemble_history_bytes(int B, int C, int H, int W, int K, int n_iter);
+size_t cspn2d_backward_kxk_assemble_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter);
+int cspn2d_forward_kxk_assemble_f32(const float* guidance, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                    float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K,
+                                    int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_forward_kxk_assemble_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf,
+                                    const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C, int sparse_C,
+                                    int H, int W, int K, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_assemble_f32(const float* guidance, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                     const float* history, size_t history_bytes, const float* grad_out, float* grad_guidance, float* grad_blur,
+                                     float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm,
+                                     void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_assemble_g16(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf,
+                                     const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out,
+                                     void* grad_guidance, float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K,
+                                     int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
  * S(p) = sum_k a_k(p), summed in channel order in float32:
