@@ -124,6 +124,11 @@ _SYMBOLS.update({
     "cspn2d_forward_kxk_assemble_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 8 + _WS),
     "cspn2d_backward_kxk_assemble_f32": (c_int, [vp] * 5 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 8 + _WS),
     "cspn2d_backward_kxk_assemble_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 8 + _WS),
+    # dilated K x K propagation: the _g16 argument lists with dilation behind K (gate_dtype 0: float32 guidance); the byte queries above apply
+    "cspn2d_forward_kxk_norm_dil": (c_int, [vp, c_int] + [vp] * 4 + [c_size_t] + [c_int] * 9 + _WS),
+    "cspn2d_backward_kxk_norm_dil": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 9 + _WS),
+    "cspn2d_forward_kxk_assemble_dil": (c_int, [vp, c_int] + [vp] * 4 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 9 + _WS),
+    "cspn2d_backward_kxk_assemble_dil": (c_int, [vp, c_int] + [vp] * 4 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 9 + _WS),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

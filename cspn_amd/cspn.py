@@ -175,13 +175,13 @@ class _CSPN2dKxKNormFunction(torch.autograd.Function):
     backward is one cspn2d_backward_kxk_norm_f32 call (the fold is recomputed there)"""
 
     @staticmethod
-    def forward(ctx, guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type):
-        ctx.kernel_size, ctx.n_iter, ctx.norm_type = kernel_size, n_iter, norm_type
+    def forward(ctx, guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, dilation):
+        ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = kernel_size, n_iter, norm_type, dilation
         hist = None
         if ctx.needs_input_grad[0] and n_iter >= 2:
-            out, hist = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, return_history=True)
+            out, hist = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, return_history=True, dilation=dilation)
         else:
-            out = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type)
+            out = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, dilation=dilation)
         ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
         return out
 
@@ -189,8 +189,8 @@ class _CSPN2dKxKNormFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
         gg, gh = F.cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type, hist,
-                                            need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1])
-        return gg, gh, None, None, None, None
+                                            need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1], dilation=ctx.dilation)
+        return gg, gh, None, None, None, None, None
 
 
 class Affinity_PropagateKxK(nn.Module):
@@ -199,15 +199,19 @@ class Affinity_PropagateKxK(nn.Module):
     pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour (K//2 - t, K//2 - l): at K = 3 the
     reference's gate1 .. gate8.  prop_kernel 3 runs today's 3 x 3 path (bitwise Affinity_Propagate); 5 and 7 the K x K engine
     (F.cspn2d_forward_kxk_norm), differentiable w.r.t. guidance and blur_depth.  float16 / bfloat16 guidance goes to the K x K engine as it
-    is (prop_kernel 3: widened first); the result is float32."""
+    is (prop_kernel 3: widened first); the result is float32.
+    dilation 2 puts the neighbour of gate (t, l) at 2 * (K//2 - t, K//2 - l) -- the dilated pass of PENet's refinement (dilated CSPN++),
+    which runs each propagation at dilation 2 and then once more at dilation 1.  It runs the K x K engine for every prop_kernel, 3
+    included (the engine's own K = 3 instance, not the 3 x 3 ring)."""
 
-    def __init__(self, prop_time, prop_kernel, norm_type='8sum'):
+    def __init__(self, prop_time, prop_kernel, norm_type='8sum', dilation=1):
         super(Affinity_PropagateKxK, self).__init__()
         assert prop_kernel in (3, 5, 7), 'the neighbourhood is 3 x 3, 5 x 5 or 7 x 7'
         assert norm_type in ['8sum', '8sum_abs']
         self.prop_time = prop_time
         self.prop_kernel = prop_kernel
         self.norm_type = norm_type
+        self.dilation = F.check_dilation(dilation)
         self.algo = "auto"          # prop_kernel 3: as Affinity_Propagate
         self.keep_history = True
 
@@ -216,14 +220,15 @@ class Affinity_PropagateKxK(nn.Module):
         if n == 0:
             return blur_depth
         blur_depth, sparse_depth = F.widen16(blur_depth, sparse_depth)
-        if self.prop_kernel == 3:
+        if self.prop_kernel == 3 and self.dilation == 1:
             return _apply(F.widen16(guidance), blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
         if torch.is_grad_enabled() and (guidance.requires_grad or blur_depth.requires_grad):
-            return _CSPN2dKxKNormFunction.apply(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
-        return F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type)
+            return _CSPN2dKxKNormFunction.apply(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type, self.dilation)
+        return F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, self.prop_kernel, n, self.norm_type, dilation=self.dilation)
 
     def extra_repr(self):
-        return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
+        return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type) \
+            + (", dilation=%d" % self.dilation if self.dilation != 1 else "")
 
 
 class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
@@ -231,13 +236,14 @@ class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
     will need them, one cspn2d_backward_kxk_assemble call"""
 
     @staticmethod
-    def forward(ctx, guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type):
-        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type = steps, kernel_size, n_iter, norm_type
+    def forward(ctx, guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, dilation):
+        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = steps, kernel_size, n_iter, norm_type, dilation
         hist = None
         if (ctx.needs_input_grad[0] and n_iter >= 2) or ctx.needs_input_grad[3]:
-            out, hist = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, return_history=True)
+            out, hist = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, return_history=True,
+                                                      dilation=dilation)
         else:
-            out = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
+            out = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, dilation=dilation)
         ctx.save_for_backward(guidance, blur_depth, sparse_depth, conf, hist)
         return out
 
@@ -246,12 +252,12 @@ class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
         guidance, blur_depth, sparse_depth, conf, hist = ctx.saved_tensors
         gg, gh, gc = F.cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, ctx.steps, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type,
                                                     hist, need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1],
-                                                    need_conf=ctx.needs_input_grad[3])
-        return gg, gh, None, gc, None, None, None, None
+                                                    need_conf=ctx.needs_input_grad[3], dilation=ctx.dilation)
+        return gg, gh, None, gc, None, None, None, None, None
 
 
 class Affinity_PropagateAssemble(nn.Module):
-    """The propagation of CSPN++ ("context-aware" CSPN; PENet's refinement): Affinity_PropagateKxK over several kernel sizes at once, the result a
+    """The propagation of CSPN++ ("context-aware" CSPN; with dilations, each pass of PENet's dilated refinement): Affinity_PropagateKxK over several kernel sizes at once, the result a
     per-pixel weighted sum over collected iterations and over kernel sizes,
         out = sum_k kernel_conf[:, k] * sum_j iter_conf[k][:, j] * H^{K_k}_{steps[j]},      H^K_0 = blur_depth.
     prop_kernels: kernel sizes out of 3, 5, 7 (3 runs the K x K engine's own K = 3 instance, not the 3 x 3 ring); steps: the collected
@@ -262,9 +268,12 @@ class Affinity_PropagateAssemble(nn.Module):
     confidences is the caller's job.  kernel_conf[:, k:k+1] is multiplied into iter_conf[k] with one torch op, then each kernel size is one
     engine call each way (F.cspn2d_forward_kxk_assemble / F.cspn2d_backward_kxk_assemble) and the results are summed.  Differentiable w.r.t. the
     guidances, blur_depth, iter_conf and kernel_conf.  float16 / bfloat16 guidance goes to the engine as it is; the result is float32.  n_iter
-    overrides prop_time and needs steps that end at it; n_iter == 0 returns blur_depth itself, as the other modules do.  No parameters or buffers."""
+    overrides prop_time and needs steps that end at it; n_iter == 0 returns blur_depth itself, as the other modules do.  No parameters or buffers.
+    dilations: 1 or 2, one int for all or one per entry of prop_kernels (the same kernel size may appear twice with different dilations); the
+    neighbour of gate (t, l) of entry k is dilations[k] * (K//2 - t, K//2 - l).  PENet's refinement is this module at dilation 2 feeding the
+    same module at dilation 1."""
 
-    def __init__(self, prop_time, prop_kernels=(3, 5, 7), steps=None, norm_type='8sum'):
+    def __init__(self, prop_time, prop_kernels=(3, 5, 7), steps=None, norm_type='8sum', dilations=1):
         super(Affinity_PropagateAssemble, self).__init__()
         prop_kernels = tuple(prop_kernels)
         assert len(prop_kernels) >= 1 and all(k in (3, 5, 7) for k in prop_kernels), 'the neighbourhoods are 3 x 3, 5 x 5 or 7 x 7'
@@ -277,6 +286,9 @@ class Affinity_PropagateAssemble(nn.Module):
         self.prop_kernels = prop_kernels
         self.steps = steps
         self.norm_type = norm_type
+        dilations = tuple(dilations) if isinstance(dilations, (tuple, list)) else (dilations,) * len(prop_kernels)
+        assert len(dilations) == len(prop_kernels), 'dilations is one int, or one per entry of prop_kernels'
+        self.dilations = tuple(F.check_dilation(d) for d in dilations)
 
     def forward(self, guidances, blur_depth, sparse_depth=None, iter_conf=None, kernel_conf=None, n_iter=None):
         n = self.prop_time if n_iter is None else int(n_iter)
@@ -291,12 +303,13 @@ class Affinity_PropagateAssemble(nn.Module):
         out = None
         for k, K in enumerate(self.prop_kernels):
             conf = F.assemble_conf(None if iter_conf is None else F.widen16(iter_conf[k]), kernel_conf, k, T, blur_depth)
-            y = _CSPN2dKxKAssembleFunction.apply(guidances[k], blur_depth, sparse_depth, conf, self.steps, K, n, self.norm_type)
+            y = _CSPN2dKxKAssembleFunction.apply(guidances[k], blur_depth, sparse_depth, conf, self.steps, K, n, self.norm_type, self.dilations[k])
             out = y if out is None else out + y
         return out
 
     def extra_repr(self):
-        return "prop_time=%d, prop_kernels=%r, steps=%r, norm_type=%r" % (self.prop_time, self.prop_kernels, self.steps, self.norm_type)
+        return "prop_time=%d, prop_kernels=%r, steps=%r, norm_type=%r" % (self.prop_time, self.prop_kernels, self.steps, self.norm_type) \
+            + (", dilations=%r" % (self.dilations,) if any(d != 1 for d in self.dilations) else "")
 
 
 class CSPN(nn.Module):

@@ -1076,7 +1076,7 @@ size_t cspn2d_kxk_norm_history_bytes(int B, int C, int H, int W, int K, int n_it
 // the checks of the four cspn2d_{forward,backward}_kxk_norm_{f32,g16} entry points, then the engine; g16 and dtype as kxk_forward_entry
 static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, float* out,
                                   float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
-                                  size_t ws_bytes, cspn_stream_t stream) {
+                                  size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
     if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (g16)
         if (int e = g16_check(what, dtype, guidance, nullptr)) return e;
@@ -1101,6 +1101,7 @@ static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g
         if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
         return 0;
     }
+    if (dilation != 1) return kxk_norm_forward_dil(guidance, dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws, st);
     return kxk_norm_forward(guidance, dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
@@ -1117,7 +1118,8 @@ size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int 
 
 static int kxk_norm_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse,
                                    const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C,
-                                   int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+                                   int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream,
+                                   int dilation = 1) {
     if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (g16)
         if (int e = g16_check(what, dtype, guidance, grad_guidance)) return e;
@@ -1146,6 +1148,9 @@ static int kxk_norm_backward_entry(const char* what, const void* guidance, bool 
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
+    if (dilation != 1)
+        return kxk_norm_backward_dil(guidance, dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, dilation, n_iter, norm,
+                                     ws, st);
     return kxk_norm_backward(guidance, dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
 
@@ -1227,7 +1232,7 @@ static int kxk_assemble_check(const char* what, std::initializer_list<std::pair<
 
 static int kxk_assemble_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
                                       const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W,
-                                      int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+                                      int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
     if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"out", out}}, sparse, steps, T, B, C,
                                    sparse_C, H, W, K, n_iter, norm))
         return e;
@@ -1244,13 +1249,16 @@ static int kxk_assemble_forward_entry(const char* what, const void* guidance, bo
         set_error("%s: out, history and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
+    if (dilation != 1)
+        return kxk_assemble_forward_dil(guidance, dtype, blur, sparse, conf, steps, T, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws,
+                                        (hipStream_t)stream);
     return kxk_assemble_forward(guidance, dtype, blur, sparse, conf, steps, T, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, (hipStream_t)stream);
 }
 
 static int kxk_assemble_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
                                        const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance,
                                        float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
-                                       size_t ws_bytes, cspn_stream_t stream) {
+                                       size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
     if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"grad_out", grad_out}}, sparse, steps, T, B,
                                    C, sparse_C, H, W, K, n_iter, norm))
         return e;
@@ -1279,6 +1287,9 @@ static int kxk_assemble_backward_entry(const char* what, const void* guidance, b
         return CSPN_E_BADARG;
     }
     if (!grad_guidance && !grad_blur && !grad_conf) return 0;
+    if (dilation != 1)
+        return kxk_assemble_backward_dil(guidance, dtype, blur, sparse, conf, steps, T, history, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H,
+                                         W, K, dilation, n_iter, norm, ws, (hipStream_t)stream);
     return kxk_assemble_backward(guidance, dtype, blur, sparse, conf, steps, T, history, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K,
                                  n_iter, norm, ws, (hipStream_t)stream);
 }
@@ -1311,6 +1322,48 @@ int cspn2d_backward_kxk_assemble_g16(const void* guidance, int gate_dtype, const
                                      cspn_stream_t stream) {
     return kxk_assemble_backward_entry("cspn2d_backward_kxk_assemble_g16", guidance, true, gate_dtype, blur, sparse, conf, steps, T, history, history_bytes,
                                        grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream);
+}
+
+// ---- the dilated forms (cspn2d_*_kxk_{norm,assemble}_dil): the _g16 entry points with dilation behind K and gate_dtype 0 for float32.  The
+// dilation is checked first, then every check of the counterpart; dilation 1 runs the counterpart's own instances ----
+static int kxk_dilation_check(const char* what, int dilation) {
+    if (kxk_dilation_ok(dilation)) return 0;
+    set_error("%s: dilation must be 1 or 2, got %d", what, dilation);
+    return CSPN_E_BADARG;
+}
+
+int cspn2d_forward_kxk_norm_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,
+                                size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm, void* ws,
+                                size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_dilation_check("cspn2d_forward_kxk_norm_dil", dilation)) return e;
+    return kxk_norm_forward_entry("cspn2d_forward_kxk_norm_dil", guidance, gate_dtype != 0, gate_dtype, blur, sparse, out, history, history_bytes, B, C, sparse_C,
+                                  H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation);
+}
+
+int cspn2d_backward_kxk_norm_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
+                                 size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
+                                 int H, int W, int K, int dilation, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_dilation_check("cspn2d_backward_kxk_norm_dil", dilation)) return e;
+    return kxk_norm_backward_entry("cspn2d_backward_kxk_norm_dil", guidance, gate_dtype != 0, gate_dtype, blur, sparse, history, history_bytes, grad_out,
+                                   grad_guidance, grad_blur, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation);
+}
+
+int cspn2d_forward_kxk_assemble_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                    float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int dilation,
+                                    int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_dilation_check("cspn2d_forward_kxk_assemble_dil", dilation)) return e;
+    return kxk_assemble_forward_entry("cspn2d_forward_kxk_assemble_dil", guidance, gate_dtype != 0, gate_dtype, blur, sparse, conf, steps, T, out, history,
+                                      history_bytes, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation);
+}
+
+int cspn2d_backward_kxk_assemble_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                                     const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur,
+                                     float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm, void* ws,
+                                     size_t ws_bytes, cspn_stream_t stream) {
+    if (int e = kxk_dilation_check("cspn2d_backward_kxk_assemble_dil", dilation)) return e;
+    return kxk_assemble_backward_entry("cspn2d_backward_kxk_assemble_dil", guidance, gate_dtype != 0, gate_dtype, blur, sparse, conf, steps, T, history,
+                                       history_bytes, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes,
+                                       stream, dilation);
 }
 
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----

@@ -135,6 +135,18 @@ int kxk_assemble_forward(const void* guid, int dtype, const float* blur, const f
 int kxk_assemble_backward(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, const float* hist,
                           const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
                           hipStream_t st);
+// the same four at dilation D (cspn2d_kxk_dil.hip): the neighbour offset of gate channel (t, l) is D (K/2 - t, K/2 - l); workspaces and
+// histories as at D = 1.  kxk_dilation_ok: D is 1 or one of the dilated instances; the _dil functions take one of those, not 1
+bool kxk_dilation_ok(int D);
+int kxk_norm_forward_dil(const void* guid, int dtype, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H,
+                         int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_norm_backward_dil(const void* guid, int dtype, const float* blur, const float* sparse, const float* hist, const float* gout, void* gg, float* gx,
+                          int B, int C, int sparse_C, int H, int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_assemble_forward_dil(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out,
+                             float* hist, int B, int C, int sparse_C, int H, int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_assemble_backward_dil(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
+                              const float* hist, const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int D,
+                              int n_iter, int norm, void* ws, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

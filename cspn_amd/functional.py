@@ -736,6 +736,24 @@ def _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, 
     return K, B, C, H, W, sc
 
 
+KXK_DILATIONS = (1, 2)   # what the engine instantiates (cspn2d_kxk_impl.h: Dilations, and 1)
+
+
+def check_dilation(dilation):
+    if isinstance(dilation, bool) or not isinstance(dilation, int) or dilation not in KXK_DILATIONS:
+        raise ValueError("dilation must be one of %r, got %r" % (KXK_DILATIONS, dilation))
+    return dilation
+
+
+def _kxk_entry(stem, dt, dilation):
+    """the entry point of a folded / assembling call and what it takes around the tensors: (name, the dtype argument(s), the dilation
+    argument(s)).  dilation 1 is the _f32 / _g16 entry point used before there was a dilation; any other the _dil one (gate_dtype 0: float32)"""
+    check_dilation(dilation)
+    if dilation == 1:
+        return stem + ("_f32" if dt is None else "_g16"), (() if dt is None else (dt,)), ()
+    return stem + "_dil", (0 if dt is None else dt,), (dilation,)
+
+
 def _kxk_norm_args(guidance, blur_depth, sparse_depth, extra=()):
     g, dt = _prep_gate(guidance, "guidance")
     h = _prep_value(blur_depth, "blur_depth")
@@ -746,15 +764,16 @@ def _kxk_norm_args(guidance, blur_depth, sparse_depth, extra=()):
     return (g, dt, h, s) + tuple(rest)
 
 
-def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False):
+def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False, dilation=1):
     """Affinity_Propagate's forward (reference cspn.py:42-144) over a kernel_size x kernel_size neighbourhood: guidance [B,K*K-1,H,W] raw
     (channel k = the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour
     (K//2 - t, K//2 - l)), blur_depth [B,C,H,W] on the shared guidance, sparse_depth None, [B,1,H,W] or [B,C,H,W] -> [B,C,H,W]
     (cspn2d_forward_kxk_norm_f32).  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_norm.  n_iter == 0
     returns blur_depth itself.  guidance may be float16 / bfloat16 (cspn2d_forward_kxk_norm_g16, K = 3 included: the fold widens it exactly,
     w' stays float32; out is float32 and bitwise the float32 call on guidance.float()); 16-bit blur_depth / sparse_depth are widened with
-    one cast."""
+    one cast.  dilation 1 or 2: the neighbour of gate (t, l) is dilation * (K//2 - t, K//2 - l) (dilated CSPN++; cspn2d_forward_kxk_norm_dil)."""
     K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    check_dilation(dilation)
     n = int(n_iter)
     if n == 0:
         return (blur_depth, None) if return_history else blur_depth
@@ -769,20 +788,21 @@ def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size
             hb = _lib.symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
         hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
     # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
-    _launch("cspn2d_forward_kxk_norm_f32" if dt is None else "cspn2d_forward_kxk_norm_g16", g.device,
-            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type]),
+    name, dta, dil = _kxk_entry("cspn2d_forward_kxk_norm", dt, dilation)
+    _launch(name, g.device, (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
             ("cspn2d_kxk_norm_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
     return (out, hist) if return_history else out
 
 
 def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
-                             need_guidance=True, need_blur=True):
+                             need_guidance=True, need_blur=True, dilation=1):
     """Gradient of cspn2d_forward_kxk_norm -> (dL/dguidance [B,K*K-1,H,W] summed over the C channels or None, dL/dblur_depth [B,C,H,W]
     or None); sparse_depth gets none (cspn.py uses its sign only).  cspn2d_backward_kxk_norm_f32.  history: what
     cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it.
     A float16 / bfloat16 guidance (cspn2d_backward_kxk_norm_g16): dL/dblur_depth is float32 and bitwise the float32 call's, dL/dguidance comes
-    back in the guidance's dtype, the float32 value rounded once."""
+    back in the guidance's dtype, the float32 value rounded once.  dilation: that of the forward (cspn2d_backward_kxk_norm_dil)."""
     K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    check_dilation(dilation)
     if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
         raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
     g, dt, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
@@ -794,11 +814,11 @@ def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kerne
     if h.numel() == 0:
         return (gg.zero_() if gg is not None else None), gh
     if need_guidance and n >= 2 and history is None:
-        _, history = cspn2d_forward_kxk_norm(g, h, s, K, n, norm_type, return_history=True)
+        _, history = cspn2d_forward_kxk_norm(g, h, s, K, n, norm_type, return_history=True, dilation=dilation)
     hb = history.numel() * history.element_size() if history is not None else 0
-    _launch("cspn2d_backward_kxk_norm_f32" if dt is None else "cspn2d_backward_kxk_norm_g16", g.device,
-            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), B, C, sc, H, W, K, n,
-             _lib.NORM_TYPES[norm_type]),
+    name, dta, dil = _kxk_entry("cspn2d_backward_kxk_norm", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
             ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
     return gg, gh
 
@@ -837,12 +857,15 @@ def _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size,
     return (g, dt, h, s, _prep_value(conf, "conf"), c_steps, len(st), K, B, C, H, W, sc) + tuple(rest)
 
 
-def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False):
+def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False,
+                                dilation=1):
     """out [B,C,H,W] = sum_j conf[:, j] * H_{steps[j]}: the levels H_t of cspn2d_forward_kxk_norm (H_0 = blur_depth) assembled per pixel
     inside the engine, one call (cspn2d_forward_kxk_assemble_f32).  conf [B,len(steps),H,W], shared by the C channels and used as given
     (no softmax); steps strictly increasing ints, steps[0] >= 0, steps[-1] == n_iter >= 1.  return_history: (out, history) with the n levels
     H_1 .. H_n for cspn2d_backward_kxk_assemble.  guidance may be float16 / bfloat16 and is taken as it is (out is float32 and bitwise the
-    float32 call on guidance.float()); a 16-bit conf, blur_depth or sparse_depth is widened with one cast."""
+    float32 call on guidance.float()); a 16-bit conf, blur_depth or sparse_depth is widened with one cast.  dilation 1 or 2: the levels are
+    those of cspn2d_forward_kxk_norm at that dilation (cspn2d_forward_kxk_assemble_dil)."""
+    check_dilation(dilation)
     g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
     n = int(n_iter)
     out = torch.empty_like(h)
@@ -854,19 +877,21 @@ def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps,
         with torch.cuda.device(g.device):
             hb = _lib.symbol("cspn2d_kxk_assemble_history_bytes")(B, C, H, W, K, n)
         hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-    _launch("cspn2d_forward_kxk_assemble_f32" if dt is None else "cspn2d_forward_kxk_assemble_g16", g.device,
-            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, n,
-             _lib.NORM_TYPES[norm_type]),
+    name, dta, dil = _kxk_entry("cspn2d_forward_kxk_assemble", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
             ("cspn2d_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
     return (out, hist) if return_history else out
 
 
 def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
-                                 need_guidance=True, need_blur=True, need_conf=True):
+                                 need_guidance=True, need_blur=True, need_conf=True, dilation=1):
     """Gradient of cspn2d_forward_kxk_assemble -> (dL/dguidance [B,K*K-1,H,W] in the guidance's dtype, rounded once, dL/dblur_depth [B,C,H,W],
     dL/dconf [B,len(steps),H,W]), None where not asked for; one engine call (cspn2d_backward_kxk_assemble_f32): the adjoint sweep of
     cspn2d_backward_kxk_norm with conf_j grad_out injected at every collected level, and dL/dconf_j = sum_c grad_out H_{steps[j]}.  history: what
-    cspn2d_forward_kxk_assemble(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dconf needs it."""
+    cspn2d_forward_kxk_assemble(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dconf needs it.
+    dilation: that of the forward (cspn2d_backward_kxk_assemble_dil)."""
+    check_dilation(dilation)
     g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc, go = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type,
                                                                         ((grad_out, "grad_out"),))
     n = int(n_iter)
@@ -878,11 +903,12 @@ def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps
     if h.numel() == 0:
         return (gg.zero_() if gg is not None else None), gh, gc
     if history is None and ((need_guidance and n >= 2) or need_conf):
-        _, history = cspn2d_forward_kxk_assemble(g, h, s, cf, steps, K, n, norm_type, return_history=True)
+        _, history = cspn2d_forward_kxk_assemble(g, h, s, cf, steps, K, n, norm_type, return_history=True, dilation=dilation)
     hb = history.numel() * history.element_size() if history is not None else 0
-    _launch("cspn2d_backward_kxk_assemble_f32" if dt is None else "cspn2d_backward_kxk_assemble_g16", g.device,
-            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc),
-             B, C, sc, H, W, K, n, _lib.NORM_TYPES[norm_type]),
+    name, dta, dil = _kxk_entry("cspn2d_backward_kxk_assemble", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc), B, C, sc, H, W, K, *dil, n,
+             _lib.NORM_TYPES[norm_type]),
             ("cspn2d_backward_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, n))
     return gg, gh, gc
 

@@ -54,7 +54,7 @@ extern "C" {
                               *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*), the 8-plane heads on a 16-bit feature map with float32 guidance
                               *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16), fp16 / bf16 gates and guides on the 3D entry points of the
                               *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16), the backward of the 3D normalising / masked modes
-                              *    (cspn3d_backward_norm_f32) */
+                              *    (cspn3d_backward_norm_f32), dilated K x K propagation (cspn2d_*_kxk_{norm,assemble}_dil) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -510,6 +510,36 @@ int cspn2d_backward_kxk_assemble_g16(const void* guidance, int gate_dtype, const
                                      const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out,
                                      void* grad_guidance, float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K,
                                      int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- dilated K x K propagation (dilated CSPN++, as PENet's refinement runs each of its 3 x 3 / 5 x 5 / 7 x 7 propagations: once with
+ * the neighbours two pixels apart, then once more at distance one): the _kxk_norm_ and _kxk_assemble_ contracts above with the neighbour
+ * offset of gate channel k = (t, l) scaled by dilation D,
+ *     off_k = D * (K/2 - t, K/2 - l),     D = 1 or 2,
+ *   and nothing else changed: G_k(p) = g_k(p + off_k) (zero outside the image), wb_k = G_k / sum_j |G_j|, the (1 - sum_k wb_k) blur term,
+ *   the mask, the steps, the assembled sum.  A pixel whose neighbours all lie outside the image (possible at D = 2: the middle row of a
+ *   3 x 1 image) is 0 / 0 = NaN, as with the reference's torch.div.
+ * Each entry mirrors its _g16 counterpart with `dilation` behind K; gate_dtype is 0 for float32 guidance (grad_guidance float32) or
+ *   CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 under the rule of the 16-bit block above.  The workspace and history sizes do not depend on the
+ *   dilation: cspn2d_kxk_norm_workspace_bytes, cspn2d_kxk_norm_history_bytes, cspn2d_backward_kxk_norm_workspace_bytes and the three
+ *   cspn2d_*kxk_assemble_*_bytes queries apply unchanged.  dilation 1 runs the very kernels of the _f32 / _g16 entry points (bitwise their
+ *   results).  Deterministic: sums in channel order, every element written once.
+ * Errors: those of the counterpart, and a dilation other than 1 or 2: CSPN_E_BADARG ("dilation" in cspn_last_error()), checked first,
+ *   before anything touches the GPU. */
+int cspn2d_forward_kxk_norm_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, float* out, float* history,
+                                size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm,
+                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_norm_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* history,
+                                 size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C, int sparse_C,
+                                 int H, int W, int K, int dilation, int n_iter, int norm, void* workspace, size_t workspace_bytes,
+                                 cspn_stream_t stream);
+int cspn2d_forward_kxk_assemble_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf,
+                                    const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C, int sparse_C,
+                                    int H, int W, int K, int dilation, int n_iter, int norm, void* workspace, size_t workspace_bytes,
+                                    cspn_stream_t stream);
+int cspn2d_backward_kxk_assemble_dil(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* conf,
+                                     const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out,
+                                     void* grad_guidance, float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K,
+                                     int dilation, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
