@@ -88,30 +88,10 @@ __device__ __forceinline__ void push_self(const f2 (&w)[9][2], const Shift& s, f
     a1 = pkfma(w[4][1], s.p0, a1);
 }
 
-
 __device__ __forceinline__ void wg_barrier() {
-#if defined(CSPN_DBG_SYNCTHREADS)
-    __syncthreads();
-#elif defined(CSPN_DBG_FENCE_BARRIER)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#else
     // LDS-only barrier: must not drain the in-flight global prefetch (vmcnt) like __syncthreads() would
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
-
-#ifdef CSPN_DBG_TIMING
-__device__ long long g_tim[8 * 8];  // [wave][phase] cycle totals of block 0
-#define TIM_DECL long long tim_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long tim_t0 = clock64();
-#define TIM(i) do { const long long t_ = clock64(); tim_[i] += t_ - tim_t0; tim_t0 = t_; } while (0)
-#define TIM_FLUSH() do { if (blockIdx.x == 0 && lane == 0) { for (int i_ = 0; i_ < 8; ++i_) g_tim[wv * 8 + i_] = tim_[i_]; } } while (0)
-#else
-#define TIM_DECL
-#define TIM(i) do { } while (0)
-#define TIM_FLUSH() do { } while (0)
-#endif
 
 // ---- the stream of rows a workgroup processes ------------------------------------------------
 struct Geo {
@@ -495,10 +475,9 @@ __global__ __launch_bounds__(NT, 2) void cspn2d_fused_kernel(const float* __rest
 
     auto do_step = [&](auto PT, int tau) {
         tau_cur = tau;
-        TIM(0);
         const bool events = (cnt0 < R && tau >= 3 * wv + cnt0) || rcnt < R || !allact;
-        if (events) { step(PT, std::true_type{}); TIM(3); }
-        else { step(PT, std::false_type{}); TIM(2); }
+        if (events) step(PT, std::true_type{});
+        else step(PT, std::false_type{});
         cnt0 = (cnt0 + 1 == LV) ? 0 : cnt0 + 1;
         rcnt = (rcnt + 1 == LV) ? 0 : rcnt + 1;
         if (tau3 == 2) {                  // the group entering from the next step on
@@ -508,28 +487,14 @@ __global__ __launch_bounds__(NT, 2) void cspn2d_fused_kernel(const float* __rest
             publish_upto(4 * gamma + 10); // descriptors up to group gamma + 2 (ring of 16)
         }
         tau3 = tau3 == 2 ? 0 : tau3 + 1;
-        TIM(1);
         wg_barrier();
-        TIM(4);
     };
     for (int tau = 0; tau <= last_step; tau += 2) {
         do_step(std::integral_constant<int, 0>{}, tau);
         if (tau + 1 > last_step) break;
         do_step(std::integral_constant<int, 1>{}, tau + 1);
     }
-    TIM_FLUSH();
 }
-
-#ifdef CSPN_DBG_TIMING
-}  // namespace
-}  // namespace cspn
-extern "C" int cspn_debug_timing(long long* dst) {
-    (void)hipDeviceSynchronize();
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(cspn::g_tim), sizeof(long long) * 64);
-}
-namespace cspn {
-namespace {
-#endif
 
 int bands_of(int W, int halo) {
     if (W <= BW) return 1;

@@ -24,39 +24,21 @@
 #include "cspn_gate16.h"
 #include "cspn_gate_norm.h"
 
-// P3_ROWS_PLAIN / P3_ROWS_CF / P3_NO_PRIO / P3_LYP: A/B builds of the round-5 row assignment (correct results, tools/r05/build_p3var.sh)
-#if (defined(P3_EXP_NOPOLL) || defined(P3_EXP_NOWAIT) || defined(P3_EXP_LANE_REMAP) || defined(P3_EXP_NT) || defined(P3_PRESLEEP)) && \
-    !defined(P3_EXPERIMENT_BUILD)
-#error "P3_EXP_* switch timing variants that give WRONG RESULTS: tools/build_p3var.sh defines P3_EXPERIMENT_BUILD for them"
-#endif
-
 namespace cspn {
 namespace {
 
-// XG = threads (groups of 8 consecutive x) per tile row.  8: one workgroup of 512 threads per CU, tile 8 x 8 x 64.  4 (-DP3_XG=4):
-// two workgroups of 256 threads per CU, tile 8 x 8 x 32 -- one's exchange round trip under the other's arithmetic.
-#ifndef P3_XG
-#define P3_XG 8
-#endif
-#ifndef P3_BACKOFF
-#define P3_BACKOFF 0   // s_sleep units (64 cycles) between two polls of quads that were not there yet
-#endif
-constexpr int XG = P3_XG, XGS = XG == 8 ? 3 : 2, WG_PER_CU = 8 / XG;
-static_assert(XG == 8 || XG == 4, "x-groups per tile row");
+// XG = threads (groups of 8 consecutive x) per tile row, XGS its log2: one workgroup of 512 threads per CU, tile 8 x 8 x 64.  (Two
+// workgroups of 256 threads per CU on tiles 8 x 8 x 32 were measured and not adopted: profiles/r02_perf_notes.md.)
+constexpr int XG = 8, XGS = 3;
 constexpr int TZ = 8, TY = 8, TX = 8 * XG;       // 8 consecutive x per thread
 constexpr int NTP = 64 * XG;                      // 256 registers per thread, 208 of them gates
 constexpr int LZ = TZ + 2, LY = TY + 2, LXU = TX + 2, LX = TX + 4;   // LDS tile with halo, rows padded to a multiple of 4 floats
-#ifndef P3_LYP
-#define P3_LYP 10
-#endif
-constexpr int LYP = P3_LYP;                      // rows per z plane of the LDS tile as LAID OUT (>= LY; 12 with -DP3_ROWS_CF: the rows
-static_assert(LYP >= LY, "plane pitch");         // (lz, ly) and (lz + 4, ly) are then 64 banks apart)
-constexpr int LTILE = LZ * LYP * LX;             // floats per level buffer
+constexpr int LTILE = LZ * LY * LX;               // floats per level buffer
 constexpr unsigned SPIN_MAX = 1u << 18;
 constexpr unsigned CAPTURED_SEQ = 0xffffffffu;   // what a launch captured into a graph stores in the status word (see persistent3d_launch)
-constexpr int MAX_WG = 256 * WG_PER_CU;
+constexpr int MAX_WG = 256;                       // one workgroup per CU
 // layout of the sync words behind the exchange buffers: [0, MAX_WG + 64 * 9) flags of the first version, the error word, [1024, 1024 + MAX_WG) the XCC table,
-// [2048, ..) the trace stamps -- an A/B build with more workgroups per CU must not let them overlap
+// [2048, ..) the trace stamps (P3_TRACE) -- they must not overlap
 static_assert(MAX_WG + 64 * 9 + 1 <= 1024 && 1024 + MAX_WG <= 2048, "sync-word layout: error word / XCC table / trace stamps overlap");
 
 struct Geo3 {
@@ -101,33 +83,17 @@ constexpr int QROW = 3 * XG, NROWS = TZ * TY, NQA = NROWS * QROW, NQ = NQA + 2 *
 // what a tile fetches per step: 36 halo rows (above / below / beside in y) of 24 quads, and the 200 voxels beside it in x
 constexpr int NHROW = 2 * LY + 2 * TZ, NHQ = NHROW * QROW, NSGL = 2 * LZ * LY, NIT = NHQ + NSGL, NSLOT = (NIT + NTP - 1) / NTP;
 
-// Which row of the tile a thread owns.  A wave = 8 rows x 8 threads (8 voxels along x each).  Round 5 tried three assignments, all
-// bit-identical, all within 1 % of each other at config 5 (profiles/r05_vol3d_rows_first_ab.md: a step is the cross-XCD trip of the
-// publications, not its arithmetic phase):
-//   default            the 28 boundary rows of the 8 x 8 rows first -- rows 0..7 plane lz = 0, 8..15 plane lz = TZ - 1, 16..27 the rows
-//                      ly = 0 / TY - 1 of the planes between, 28..63 the 36 interior rows: waves 0..2 publish whole rows without
-//                      exec-masked halves (-0.6 % against the plain assignment, the best of the three by a hair);
-//   -DP3_ROWS_PLAIN    a wave = one z plane (rounds 2-4);
-//   -DP3_ROWS_CF -DP3_LYP=12   rows (lz, ly) / (lz + 4, ly) / (lz, ly + 1) / (lz + 4, ly + 1) per group of four: the four quarter-rows
-//                      a ds_read_b128 lane group touches ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md, LDS) then tile the 64 banks
-//                      -- 160 -> 96 LDS cycles per neighbour row and workgroup on paper (tools/r05/lds_conflicts.py), -0.4 % measured:
-//                      the arithmetic phase is not bound by LDS conflicts either.
+// Which row of the tile a thread owns.  A wave = 8 rows x 8 threads (8 voxels along x each).  The 28 boundary rows of the 8 x 8 rows
+// come first -- rows 0..7 plane lz = 0, 8..15 plane lz = TZ - 1, 16..27 the rows ly = 0 / TY - 1 of the planes between, 28..63 the 36
+// interior rows: waves 0..2 publish whole rows without exec-masked halves.  Two other assignments were tried (a wave = one z plane, and
+// an LDS-conflict-free grouping on a plane pitch of 12 rows), bit-identical and within 1 % of this one: profiles/r05_vol3d_rows_first_ab.md.
 // [q3][row][xg] in the exchange buffers is indexed by the LOGICAL row lz * TY + ly: readers see no difference.
 __device__ __forceinline__ void row_of(int t, int& lx, int& ly, int& lz) {
     lx = (t & (XG - 1)) * 8;
     const int r = t >> XGS;   // 0 .. 63
-#if defined(P3_ROWS_PLAIN)
-    ly = r & 7;
-    lz = r >> 3;
-#elif defined(P3_ROWS_CF)
-    const int g = r >> 2, k = r & 3;   // group of four rows, row in the group
-    lz = (g & 3) + 4 * (k & 1);
-    ly = 2 * (g >> 2) + (k >> 1);
-#else
     const int i = r - 16, j = r - 28, j6 = (j * 43) >> 8;   // j / 6 for 0 <= j < 36
     lz = r < 8 ? 0 : r < 16 ? TZ - 1 : r < 28 ? 1 + (i >> 1) : 1 + j6;
     ly = r < 8 ? r : r < 16 ? r - 8 : r < 28 ? (i & 1) * (TY - 1) : 1 + j - 6 * j6;
-#endif
 }
 static_assert(TZ == 8 && TY == 8, "row_of enumerates the boundary rows of an 8 x 8 tile cross-section");
 
@@ -156,7 +122,7 @@ __device__ __forceinline__ v4f ldq_sc1(const float4* base, unsigned byte_off) { 
 // to it: no barrier), laid out [quad][wave][lane] so that one request fills 1 KiB.
 // (HASC && MULTI keeps coef beside c' in LDS, 16 KB more: two parked quads fewer)
 template <bool ADJ, bool HASC, bool MULTI = false>
-struct Pre3 { static constexpr int N = ADJ ? 0 : (XG == 8 ? (HASC ? (MULTI ? 8 : 10) : 12) : 12); };
+struct Pre3 { static constexpr int N = ADJ ? 0 : HASC ? (MULTI ? 8 : 10) : 12; };
 
 __device__ __forceinline__ void lds_dma16(unsigned byte_off, const float* base, unsigned lds_dst) {   // lds_dst: wave-uniform
     unsigned keep;
@@ -424,26 +390,13 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         const unsigned a1 = in1 && rowok ? (unsigned)((int)go1 + sh + e1) : 0u;
                         asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][0]) : "v"(a0), "s"(gko) : "memory");
                         asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][1]) : "v"(a1), "s"(gko) : "memory");
-                    } else {
-#if defined(P3_EXP_NT)   // timing experiments (profiles/r02_perf_notes.md): the nontemporal hint costs 10 % of the forward
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 nt" : "=&v"(w[k][0]) : "v"(voff0), "s"(gk) : "memory");
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 nt" : "=&v"(w[k][1]) : "v"(voff1), "s"(gk) : "memory");
-#elif defined(P3_EXP_LANE_REMAP)   // WRONG RESULTS: each instruction reads 128 contiguous bytes per row
-                    const int xa = x0 + (tc & (XG - 1)) * 4;   // (single volume only)
-                    const unsigned ra = (unsigned)((z * g.H + y) * g.W + xa) * 4u;
-                    const unsigned r0_ = (in_zy && xa >= 0 && xa + 3 < g.W) ? ra : 0u, r1_ = (in_zy && xa + 32 >= 0 && xa + 35 < g.W) ? ra + 128u : 0u;
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][0]) : "v"(r0_), "s"(gk) : "memory");
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][1]) : "v"(r1_), "s"(gk) : "memory");
-#else
-                    if (2 * k < NPRE) {   // parked during the chunk before (chunk 0: in front of the loop)
+                    } else if (2 * k < NPRE) {   // parked during the chunk before (chunk 0: in front of the loop)
                         const unsigned pa = lds_addr(s_pre) + (unsigned)tc * 16u + (unsigned)(2 * k * NTP * 16), pb = pa + NTP * 16;
                         asm volatile("ds_read_b128 %0, %1" : "=&v"(w[k][0]) : "v"(pa) : "memory");
                         asm volatile("ds_read_b128 %0, %1" : "=&v"(w[k][1]) : "v"(pb) : "memory");
                     } else {
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][0]) : "v"(voff0), "s"(gk) : "memory");
-                    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][1]) : "v"(voff1), "s"(gk) : "memory");
-                    }
-#endif
+                        asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][0]) : "v"(voff0), "s"(gk) : "memory");
+                        asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(w[k][1]) : "v"(voff1), "s"(gk) : "memory");
                     }
                 }
                 {   // level 0 into both LDS buffers once ITS loads are back (52 gate loads may still be in flight)
@@ -483,7 +436,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     loc(x0 + lx + 4, b1, xq1);
                     const bool in_zy = z < g.D && y < g.H;
                     const bool in0 = in_zy && xq0 >= 0 && xq0 + 3 < g.W && b0 < g.B, in1 = in_zy && xq1 >= 0 && xq1 + 3 < g.W && b1 < g.B;
-                    const int o = ((lz + 1) * LYP + (ly + 1)) * LX + lx + 1;
+                    const int o = ((lz + 1) * LY + (ly + 1)) * LX + lx + 1;
                     const float own8[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
@@ -502,8 +455,8 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         const bool ok = vz >= 0 && vz < g.D && vy >= 0 && vy < g.H && vx >= 0 && vx < g.W && vb < g.B;
                         if (i < NSH) {
                             const float v = ok ? fs[j] : 0.f;
-                            lds[(pz * LYP + py) * LX + px] = v;
-                            lds[LTILE + (pz * LYP + py) * LX + px] = v;
+                            lds[(pz * LY + py) * LX + px] = v;
+                            lds[LTILE + (pz * LY + py) * LX + px] = v;
                         }
                     }
                 }
@@ -580,7 +533,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
                     const float4 q0 = in0 ? *reinterpret_cast<const float4*>(fb + (unsigned)(b0 * FBS + row + xq0)) : zero4;
                     const float4 q1 = in1 ? *reinterpret_cast<const float4*>(fb + (unsigned)(b1 * FBS + row + xq1)) : zero4;
-                    const int o = ((lz + 1) * LYP + (ly + 1)) * LX + lx + 1;
+                    const int o = ((lz + 1) * LY + (ly + 1)) * LX + lx + 1;
                     const float own8[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
@@ -606,8 +559,8 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         loc(x0 + px - 1, vb, vx);
                         const bool ok = vz >= 0 && vz < g.D && vy >= 0 && vy < g.H && vx >= 0 && vx < g.W && vb < g.B;
                         const float v = ok ? fb[(unsigned)(vb * FBS + (vz * g.H + vy) * g.W + vx)] : 0.f;
-                        lds[(pz * LYP + py) * LX + px] = v;
-                        lds[LTILE + (pz * LYP + py) * LX + px] = v;
+                        lds[(pz * LY + py) * LX + px] = v;
+                        lds[LTILE + (pz * LY + py) * LX + px] = v;
                     }
                     __syncthreads();
                 }
@@ -625,12 +578,10 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll 1
                         for (int k = it - 1; k < NPRE / 2; k += g.n_iter) park_gate(c + 1, k, tid_);
                     }
-#if !defined(P3_ROWS_PLAIN) && !defined(P3_ROWS_CF) && !defined(P3_NO_PRIO)
                     // waves 0..3 hold the boundary rows (row_of): raised issue priority for their arithmetic.  Measured: no effect on the
                     // time (the two builds are equal to 0.1 %, profiles/r05_vol3d_rows_first_ab.md); kept because THIS instruction stream
                     // is the one the register allocator fits without a spill in every variant (without it the HASC variant spills two)
                     if (__builtin_amdgcn_readfirstlane(tid_) < 4 * 64) __builtin_amdgcn_s_setprio(3);
-#endif
                     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     if (HASC) {
                         const unsigned ca = lds_addr(s_c) + (unsigned)tid_ * 16u;
@@ -643,7 +594,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                     for (int n = 0; n < 9; ++n) {   // the 9 neighbour rows (dz, dy); three x-taps each
                         const int dz = 1 - n / 3, dy = 1 - n % 3;
-                        const float* row = cur + ((lz + 1 + dz) * LYP + (ly + 1 + dy)) * LX + lx;
+                        const float* row = cur + ((lz + 1 + dz) * LY + (ly + 1 + dy)) * LX + lx;
                         const float4 a0 = *reinterpret_cast<const float4*>(row);        // x-1 .. x+2
                         const float4 a1 = *reinterpret_cast<const float4*>(row + 4);    // x+3 .. x+6
                         const float2 e = *reinterpret_cast<const float2*>(row + 8);     // x+7, x+8
@@ -683,12 +634,10 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     };
                     if (it == g.n_iter) {
                         store_owned(MULTI ? out + (size_t)ch * V : out);
-#if !defined(P3_ROWS_PLAIN) && !defined(P3_ROWS_CF) && !defined(P3_NO_PRIO)
                         __builtin_amdgcn_s_setprio(0);
-#endif
                         break;
                     }
-                    float* own = nxt + ((lz + 1) * LYP + (ly + 1)) * LX + lx + 1;
+                    float* own = nxt + ((lz + 1) * LY + (ly + 1)) * LX + lx + 1;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) own[i] = acc[i];
                     // the level history of the backward (MULTI: volumes laid out [level][B][C][V], like feat / out)
@@ -731,9 +680,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                 else st16_sc1(q, make_float4(acc[7], 0.f, 0.f, tagf));
                             }
                         }
-#if !defined(P3_ROWS_PLAIN) && !defined(P3_ROWS_CF) && !defined(P3_NO_PRIO)
                         __builtin_amdgcn_s_setprio(0);
-#endif
                         // ---- the halo shell: 36 rows of the neighbours above / below / beside in y (24 quads each) and the 200 voxels
                         // beside the tile in x (one value of a neighbour's first or last quad), polled until their tag is this step's
                         unsigned src[NSLOT];   // byte offset of the quad in X
@@ -768,7 +715,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             const int nbw = (tz2 * g.ty + ty2) * g.cx + tx2;
                             const int quad = q3 >= 0 ? (q3 * NROWS + sz * TY + sy) * XG + xg : NQA + xg * NROWS + sz * TY + sy;
                             src[j] = (unsigned)((((int)(target & 1) * g.n_wg + nbw) * NQ + quad) * 16);
-                            dstp[j] = ((pz * LYP + py) * LX + px) | (cnt << 14);
+                            dstp[j] = ((pz * LY + py) * LX + px) | (cnt << 14);
                         }
                         // A neighbour that never publishes (it is not resident: the device is shared with work that holds CUs) must not
                         // hang the kernel nor pass unnoticed: after SPIN_MAX polls (~0.5 s) the values that did not come are
@@ -779,12 +726,6 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         bool pend = false, lost = false;
 #pragma unroll
                         for (int j = 0; j < NSLOT; ++j) pend = pend || dstp[j] >= 0;
-#ifdef P3_PRESLEEP
-                        asm volatile("s_sleep %0" : : "n"(P3_PRESLEEP));
-#endif
-#ifdef P3_EXP_NOPOLL   // WRONG RESULTS, timing only: no halo at all
-                        pend = false;
-#endif
                         while (pend) {
                             v4f qv[NSLOT];
 #pragma unroll
@@ -799,11 +740,7 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                             for (int j = 0; j < NSLOT; ++j) {
                                 if (dstp[j] < 0) continue;
-#ifdef P3_EXP_NOWAIT   // WRONG RESULTS, timing only: take whatever is there
-                                const bool hit = true;
-#else
                                 const bool hit = __float_as_uint(qv[j].w) == target;
-#endif
                                 if (hit || tries >= limit) {
                                     float* lp = nxt + (dstp[j] & 0x1fff);
                                     const int cnt = dstp[j] >> 14;
@@ -818,11 +755,6 @@ __global__ __launch_bounds__(NTP) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                 }
                             }
                             ++tries;
-#if P3_BACKOFF > 0
-                            // a quad that was not there yet will take a good part of a memory-side round trip to appear: polling at
-                            // full speed only multiplies the polled bytes (1.4 GB per forward at config 5, profiles/pmc_traffic.json)
-                            if (pend) __builtin_amdgcn_s_sleep(P3_BACKOFF);
-#endif
                         }
                         if (lost) {
                             *err = 2;
@@ -882,7 +814,7 @@ int resident_wgs() {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
             v = MAX_WG;
-        int occ = WG_PER_CU;
+        int occ = 1;
         const void* fns[] = {(const void*)cspn3d_persistent_kernel<false, false>, (const void*)cspn3d_persistent_kernel<false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false>, (const void*)cspn3d_persistent_kernel<false, false, false, true>,
                              (const void*)cspn3d_persistent_kernel<true, false, false, true>, (const void*)cspn3d_persistent_kernel<false, true, false, true>,

@@ -8,10 +8,10 @@
 //   * head_bwd_x_kernel: one lane = one input pixel; its 9 x 3 x 3 window of g (81 values) is loaded ONCE into registers (27 8-byte loads + the left column from the
 //     neighbouring lane by DPP), then every channel takes 41 packed FMAs over PAIRS of taps with the weights as scalar operands (the pair-of-channels form
 //     broadcasts g, and the compiler hoists the 81 broadcast pairs out of the channel loop: 168 registers).
-//   * head_bwd_w2_kernel: a GEMM -- [81 taps] x [pixels] x [C channels], K = every input pixel of the batch -- on the matrix cores: v_mfma_f32_32x32x2_f32, taps
+//   * head_bwd_w_kernel: a GEMM -- [81 taps] x [pixels] x [C channels], K = every input pixel of the batch -- on the matrix cores: v_mfma_f32_32x32x2_f32, taps
 //     padded to 96 (3 row blocks), channels in blocks of 32; a wave keeps all 3 x 2 accumulator blocks (96 registers) over its share of the pixels and writes them
 //     once; head_bwd_w_reduce_kernel sums the waves' partial sums in a fixed order (deterministic: no atomics).  Tiles of 32 pixels are read coalesced and go
-//     through the wave's own LDS region into the matrix layout (the first version, head_bwd_w_kernel, gathers them: -DDW_V1).
+//     through the wave's own LDS region into the matrix layout.
 #include <cstdint>
 
 #include "cspn_common.h"
@@ -96,127 +96,18 @@ __global__ __launch_bounds__(256) void head_bwd_x_kernel(const float* __restrict
 // ---- dL/dW ----------------------------------------------------------------------------------------------------------------------------
 // D[tap][channel] += sum over pixels A[tap][pixel] B[pixel][channel], A = the window value g[o][2i - 1 + r][2j - 1 + k] (tap t = o * 9 + r * 3 + k, padded to 96),
 // B = x[channel][i][j].  v_mfma_f32_32x32x2_f32: A 32 x 2 (lane l: row l % 32, k = l / 32), B 2 x 32 (lane l: k = l / 32, column l % 32), D 32 x 32 in 16
-// registers (lane l: column l % 32; register q: row (q / 4) * 8 + (l / 32) * 4 + q % 4).  A tile = 8 consecutive pixels of an input row: lanes 0-31 take
-// pixels j0 .. j0 + 3, lanes 32-63 pixels j0 + 4 .. j0 + 7, four MFMA steps per (tap block, channel block) -- a lane reads its tap's four window values (stride 2
-// between pixels) and its channel's four pixels; the next tile's reads are issued before the current tile's MFMAs.  Timing builds (-DDW_ABL, KITTI x 64): matrix
-// instructions alone 0.73-0.90 ms, the reads alone 1.23 ms, together 1.24: the kernel is bound by its gathers -- a lane reads 16-32 bytes of a line of ITS tap / channel
-// plane, 2.4 GB arrive at 1.9 TB/s.  Staging coalesced rows through LDS would leave the matrix cores as the limit (~0.75 ms); not built.
-#ifndef DW_ABL
-#define DW_ABL 0        // timing builds only: 1 = one tile's values for all tiles (no loads in the loop), 2 = no matrix instructions
-#endif
-#ifndef DW_PX
-#define DW_PX 4          // pixels per lane and tile (8: the same load time, two waves per SIMD instead of three, worse overlap: 1.58 vs 1.24 ms)
-#endif
-constexpr int DW_TILE = 2 * DW_PX;
-struct DwTile { float a[3][DW_PX]; float bq[2][DW_PX]; };
-
-template <int NB>
-__global__ __launch_bounds__(256, 2) void head_bwd_w_kernel(const float* __restrict__ x, const float* __restrict__ gg, const float* __restrict__ gb,
-                                                             float* __restrict__ part, const float* __restrict__ part_zero, int C, int c0, int h, int w, int H, int W,
-                                                             int tiles, int tiles_w, int hfed, int nwave) {
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (wave >= nwave) return;
-    const int t0 = (int)((long long)tiles * wave / nwave), t1 = (int)((long long)tiles * (wave + 1) / nwave);   // this wave's share of the tiles
-    const int half = lane >> 5, id = lane & 31;
-    const size_t HWo = (size_t)H * W, hw = (size_t)h * w;
-    // what does not change from tile to tile: the lane's taps (one per row block) and channels (one per column block)
-    int tr[3], tk[3];
-    const float* tsrc[3];          // plane of image 0 (a padding row of the block / no blur head: some valid plane, never used)
-    bool tvalid[3];
-    size_t tstep[3];               // from one image to the next
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) {
-        const int t = tb * 32 + id;
-        const int o = t / 9;
-        tr[tb] = (t - o * 9) / 3;
-        tk[tb] = t - o * 9 - tr[tb] * 3;
-        tvalid[tb] = t < 81 && (o < 8 || gb != nullptr);
-        tsrc[tb] = (tvalid[tb] && o == 8) ? gb : gg + (size_t)(o < 8 ? o : 0) * HWo;
-        tstep[tb] = (tvalid[tb] && o == 8) ? HWo : 8 * HWo;
-    }
-    const float* xsrc[NB];
-    bool xvalid[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) { const int ch = c0 + nb * 32 + id; xvalid[nb] = ch < C; xsrc[nb] = x + (size_t)(ch < C ? ch : 0) * hw; }
-    const float* zero = part_zero;
-    auto load = [&](DwTile& T, int tw, int i, int b) {       // tile tw of input row i of image b
-        const int jb = tw * DW_TILE + DW_PX * half;             // this lane's first pixel
-#pragma unroll
-        for (int tb = 0; tb < 3; ++tb) {
-            const int Y = 2 * i - 1 + tr[tb], Xb = 2 * jb - 1 + tk[tb];
-            const bool rowok = tvalid[tb] && Y >= 0 && Y < H;
-            const float* p = tsrc[tb] + (size_t)b * tstep[tb] + (size_t)Y * W;
-            if (!rowok || (Xb >= 0 && Xb + 2 * DW_PX - 1 < W)) {   // the common case: 2 DW_PX consecutive floats, every other one is a pixel's (a row outside: zeros)
-                float q[2 * DW_PX];
-                __builtin_memcpy(q, rowok ? p + Xb : zero, 8 * DW_PX);
-#pragma unroll
-                for (int s_ = 0; s_ < DW_PX; ++s_) T.a[tb][s_] = q[2 * s_];
-            } else {                                             // the first / last tiles of a row: what lies outside reads a zero word
-#pragma unroll
-                for (int s_ = 0; s_ < DW_PX; ++s_) {
-                    const int X = Xb + 2 * s_;
-                    T.a[tb][s_] = *((X >= 0 && X < W) ? p + X : zero);
-                }
-            }
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const float* p = xsrc[nb] + (size_t)b * C * hw + (size_t)i * w;
-            if (!xvalid[nb] || (jb + DW_PX - 1 < w && 2 * (jb + DW_PX - 1) < W)) {
-                __builtin_memcpy(T.bq[nb], xvalid[nb] ? p + jb : zero, 4 * DW_PX);
-            } else {
-#pragma unroll
-                for (int s_ = 0; s_ < DW_PX; ++s_) {
-                    const int j = jb + s_;
-                    T.bq[nb][s_] = *((j < w && 2 * j < W) ? p + j : zero);      // (beyond the narrowed output: fed nothing)
-                }
-            }
-        }
-    };
-    f16v acc[3][NB];
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[tb][nb][q] = 0.f;
-    DwTile nxt;
-    int tw = (int)((unsigned)t0 % (unsigned)tiles_w), ti = (int)(((unsigned)t0 / (unsigned)tiles_w) % (unsigned)hfed), tb_ = (int)((unsigned)t0 / ((unsigned)tiles_w * (unsigned)hfed));
-    if (t0 < t1) load(nxt, tw, ti, tb_);
-    for (int t = t0; t < t1; ++t) {
-        const DwTile cur = nxt;
-        if (++tw == tiles_w) { tw = 0; if (++ti == hfed) { ti = 0; ++tb_; } }      // the next tile (scalar)
-        if (!(DW_ABL & 1) && t + 1 < t1) load(nxt, tw, ti, tb_);
-#pragma unroll
-        for (int s_ = 0; s_ < DW_PX; ++s_)
-#pragma unroll
-            for (int tb = 0; tb < 3; ++tb)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    if (DW_ABL & 2) acc[tb][nb][0] += cur.a[tb][s_] * cur.bq[nb][s_];
-                    else acc[tb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[tb][s_], cur.bq[nb][s_], acc[tb][nb], 0, 0, 0);
-                }
-    }
-    float* dst = part + (size_t)wave * 3 * NB * 16 * 64 + lane;
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) dst[((tb * NB + nb) * 16 + q) * 64] = acc[tb][nb][q];
-}
-
-// ---- dL/dW, second version: the same GEMM fed through LDS.  A wave reads a tile of 32 pixels COALESCED -- lane = pixel: per channel pair one 256-byte load of x,
-// per (plane, window row) one 256-byte load of g (66 columns: + one load for the two left over of all 27 rows) --, drops the values into its OWN LDS region (no
-// barrier: nobody else touches it) and reads them back in the matrix cores' layout (lane = tap / channel; odd pitches: conflict-free).  60 loads, 60 LDS writes,
-// 80 LDS reads and 96 MFMAs per tile against 8 gathers per 24 MFMAs above (kept behind -DDW_V1): 0.94 ms against 1.24 at KITTI x 64.  Timing builds: the matrix
-// instructions with their LDS reads alone 0.66 ms, the loads + LDS writes alone 0.65, together 0.98 with or without the next tile's loads in flight during the MFMAs
-// (two waves per SIMD at 254 registers).
+// registers (lane l: column l % 32; register q: row (q / 4) * 8 + (l / 32) * 4 + q % 4).  The operands go through LDS: a wave reads a tile of 32 pixels of an
+// input row COALESCED -- lane = pixel: per channel pair one 256-byte load of x, per (plane, window row) one 256-byte load of g (66 columns: + one load for the two
+// left over of all 27 rows) --, drops the values into its OWN LDS region (no barrier: nobody else touches it) and reads them back in the matrix cores' layout
+// (lane = tap / channel; odd pitches: conflict-free); the next tile's loads are issued before the current tile's MFMAs.  60 loads, 60 LDS writes, 80 LDS reads and
+// 96 MFMAs per tile: 0.94 ms at KITTI x 64, two waves per SIMD at 254 registers.  Measured apart: the matrix instructions with their LDS reads 0.66 ms, the loads
+// + LDS writes 0.65, together 0.98 with or without the next tile's loads in flight during the MFMAs.  (A first version let every lane gather its tap's and its
+// channel's values itself and was bound by those gathers at 1.24 ms: profiles/r06_head.md.)
 constexpr int W2_TP = 32, W2_XP = 33, W2_GP = 67;
 template <int NB>
-__global__ __launch_bounds__(256, 2) void head_bwd_w2_kernel(const float* __restrict__ x, const float* __restrict__ gg, const float* __restrict__ gb,
-                                                              float* __restrict__ part, const float* __restrict__ zero, int C, int c0, int h, int w, int H, int W,
-                                                              int tiles, int tiles_w, int hfed, int nwave) {
+__global__ __launch_bounds__(256, 2) void head_bwd_w_kernel(const float* __restrict__ x, const float* __restrict__ gg, const float* __restrict__ gb,
+                                                             float* __restrict__ part, const float* __restrict__ zero, int C, int c0, int h, int w, int H, int W,
+                                                             int tiles, int tiles_w, int hfed, int nwave) {
     constexpr int XT = NB * 32 * W2_XP, GT = 28 * W2_GP;      // x tile [channel][33]; g tile [27 window rows + a row of zeros][67]
     __shared__ float lds[4][XT + GT];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -286,7 +177,6 @@ __global__ __launch_bounds__(256, 2) void head_bwd_w2_kernel(const float* __rest
     };
     if (t0 < t1) { load_x(tw, ti, tb_); load_g(tw, ti, tb_); }
     for (int t = t0; t < t1; ++t) {
-        if (!(DW_ABL & 1) || t == t0) {
         {   // the tile whose values arrived: tw, ti, tb_ still name it
             const int j = tw * W2_TP + id;
             const bool pok = j < w && 2 * j < W;                  // (beyond the narrowed output: fed nothing)
@@ -303,9 +193,8 @@ __global__ __launch_bounds__(256, 2) void head_bwd_w2_kernel(const float* __rest
             const int ol = rl / 3, Yl = 2 * ti - 1 + (rl - ol * 3);
             if (lane < 54) gs[rl * W2_GP + 64 + (lane & 1)] = (X2 < W && Yl >= 0 && Yl < H && (ol < 8 || hasb)) ? gv[27] : 0.f;
         }
-        }   // (DW_ABL & 1: the first tile's values for every tile)
         if (++tw == tiles_w) { tw = 0; if (++ti == hfed) { ti = 0; ++tb_; } }
-        if (!(DW_ABL & 1) && t + 1 < t1) { load_x(tw, ti, tb_); load_g(tw, ti, tb_); }
+        if (t + 1 < t1) { load_x(tw, ti, tb_); load_g(tw, ti, tb_); }
         // ---- 16 steps of two pixels (s, s + 16)
 #pragma unroll 4
         for (int s_ = 0; s_ < 16; ++s_) {
@@ -317,10 +206,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd_w2_kernel(const float* __rest
 #pragma unroll
             for (int tb = 0; tb < 3; ++tb)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    if (DW_ABL & 2) acc[tb][nb][0] += av[tb] * bv[nb];
-                    else acc[tb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tb], bv[nb], acc[tb][nb], 0, 0, 0);
-                }
+                for (int nb = 0; nb < NB; ++nb) acc[tb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[tb], bv[nb], acc[tb][nb], 0, 0, 0);
         }
     }
     float* dst = part + (size_t)wave * 3 * NB * 16 * 64 + lane;
@@ -382,24 +268,15 @@ int head_backward(const float* x, const float* w6, const float* w5, const float*
         hipLaunchKernelGGL(head_zero_line_kernel, dim3(1), dim3(64), 0, st, zero);
         const int hfed = (H + 1) / 2 < h ? (H + 1) / 2 : h;     // input rows whose unpooled row lies inside the (narrowed) output
         const int wfed = (W + 1) / 2 < w ? (W + 1) / 2 : w;
-#ifdef DW_V1
-        const int tiles_w = (wfed + DW_TILE - 1) / DW_TILE;
-#else
         const int tiles_w = (wfed + W2_TP - 1) / W2_TP;
-#endif
         const long long tiles_ll = (long long)B * hfed * tiles_w;
         if (tiles_ll >= (1ll << 31)) { set_error("cspn_guidance_head_backward_f32: too many pixels"); return CSPN_E_UNSUPPORTED; }
         const int tiles = (int)tiles_ll;
         const int nwave = tiles < DW_MAX_WAVES ? tiles : DW_MAX_WAVES;
         for (int c0 = 0; c0 < C; c0 += 64) {                     // 64 channels at a time (two column blocks of the matrix core)
             const int NB = C - c0 > 32 ? 2 : 1;
-#ifndef DW_V1
-            if (NB == 2) hipLaunchKernelGGL(head_bwd_w2_kernel<2>, dim3((nwave + 3) / 4), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, tiles, tiles_w, hfed, nwave);
-            else hipLaunchKernelGGL(head_bwd_w2_kernel<1>, dim3((nwave + 3) / 4), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, tiles, tiles_w, hfed, nwave);
-#else
             if (NB == 2) hipLaunchKernelGGL(head_bwd_w_kernel<2>, dim3((nwave + 3) / 4), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, tiles, tiles_w, hfed, nwave);
             else hipLaunchKernelGGL(head_bwd_w_kernel<1>, dim3((nwave + 3) / 4), dim3(256), 0, st, x, gg, gb, part, zero, C, c0, h, w, H, W, tiles, tiles_w, hfed, nwave);
-#endif
             hipLaunchKernelGGL(head_bwd_w_reduce_kernel, dim3((81 * NB * 32 + 255) / 256), dim3(256), 0, st, part, dw6, dw5, C, c0, NB, nwave);
         }
         if (int e = check_launch("head_bwd_w_kernel")) return e;
