@@ -1,5 +1,5 @@
-"""Seeded draws over the K x K engine's four contracts (cspn2d_kxk.hip) and the 3D normalising / masked modes (cspn3d_*_norm*), each case checked
-against the float64 statement its family's own test file already trusts.  A plain helper module, like memguard.py and helpers.py; not collected.
+"""Seeded draws over the K x K engine's four contracts (cspn2d_kxk.hip), the 3D normalising / masked modes (cspn3d_*_norm*) and the four guidance-head
+paths (cspn_head*.hip, past the 64-channel chunks of their backwards), each case checked against the float64 statement its family's own test file already trusts.  A plain helper module, like memguard.py and helpers.py; not collected.
 tests/test_fuzz_statements.py commits one seed and runs it; `python tests/fuzzcases.py` is the longer soak (FUZZ_CASES, FUZZ_SEED as
 tools/fuzz_parity.py reads them; or one descriptor as its argument, which replays that case).  DESIGN.md §4.3.
 
@@ -11,14 +11,15 @@ tools/fuzz_parity.py reads them; or one descriptor as its argument, which replay
     check(case)                  run() and every assertion; no bound is defined here
 
 Roles, one letter each: g the gate / guidance / guide, x the values (x, blur_depth, feat), s sparse_depth, c conf, o grad_out.  A descriptor's
-`offset` names the roles placed one element off, its `need` (K x K) the gradients asked for: g, x, c."""
+`offset` names the roles placed one element off, its `need` (K x K) the gradients asked for: g, x, c.
+The head family names its roles in full (HEAD_ROLES, joined with '+' in `offset`); its `need` is x, w or xw."""
 import collections
 import functools
 import os
 import random
 import sys
 
-FAMILIES = ("kxk", "3d")
+FAMILIES = ("kxk", "3d", "head")
 CONTRACTS = ("none", "norm", "absnorm", "assemble")
 KERNELS = {"none": (5, 7), "norm": (3, 5, 7), "absnorm": (5, 7), "assemble": (3, 5, 7)}
 ROLES = {"none": "gxo", "norm": "gxso", "absnorm": "gxo", "assemble": "gxsco", "3d": "gxso"}
@@ -38,6 +39,26 @@ N_MAX, T_MAX = 6, 4
 
 KxK = collections.namedtuple("KxK", "family index contract K dtype B C H W n norm mask steps need offset seed")
 Vol = collections.namedtuple("Vol", "family index norm mask C dtype B D H W n algo offset seed")
+
+# the guidance heads: path A cspn_guidance_head[_backward]_f32, B ..._kxk[_backward]_f32, C ..._kxk[_backward]_g16, D cspn_guidance_head[_backward]_g16
+HEAD_PATHS = "ABCD"
+HEAD_ROLES = ("x", "weight_guidance", "weight_blur", "grad_guidance", "grad_blur")
+HEAD_PLANES = {"A": (8,), "B": (24, 48), "C": (24, 48), "D": (8,)}
+HEAD_DTYPES = {"A": ("float32",), "B": ("float32",), "C": ("float16", "bfloat16"), "D": ("float16", "bfloat16")}
+HEAD_NEEDS = ("x", "w", "xw")
+HEAD_NORMS = ("none", "8sum", "8sum_abs")          # path A only: the normalisation fused behind the conv (grad off)
+HEAD_C = (1, 7, 16, 31, 32, 33, 64, 65, 96, 97, 128, 129, 160, 200)
+HEAD_CLASSES = ("C <= 32", "C 33..64", "C 65..96", "C 97..128", "C > 128")   # chunks of 64 channels, one or two column blocks of 32 in the last
+HEAD_W = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32, 33, 62, 63, 64, 65, 100)
+HEAD_H_MAX = 9
+HEAD_ELEMENTS = 120000
+HEAD_OFFSET_P = 0.25       # a free slot offsets each role with this probability: one case in four keeps every tensor as allocated
+# dL/dW: (pixels of a tile, waves of a launch at most) as the host code has them -- cspn_head_backward.hip W2_TP, DW_MAX_WAVES; cspn_head_kxk.hip
+# DW_TILE, 4 * DW_MAX_WG (cspn_head_kxk_common.h); cspn_head_g16_common.h DW_TILE for C and D.  tests/test_fuzz_statements.py reads them out of csrc
+HEAD_DW = {"A": (32, 2048), "B": (8, 1024), "C": (16, 1024), "D": (16, 1024)}
+HEAD_MANY = {"A": (3, 65, 33), "B": (2, 97, 33), "C": (2, 97, 33), "D": (2, 97, 33)}   # B, C, w of the slot with more tiles than waves; h is the smallest that has
+
+Head = collections.namedtuple("Head", "family index path planes dtype B C h w oh ow blur norm need w16 offset seed")
 
 
 # ---- the draw: pure Python ----
@@ -136,12 +157,74 @@ def _draw_3d(rnd, count):
     return cases
 
 
+def chunk_class(C):
+    """which of HEAD_CLASSES: how many 64-channel chunks the backwards' host loops run, and whether the last has one column block or two"""
+    return 0 if C <= 32 else 1 if C <= 64 else 2 if C <= 96 else 3 if C <= 128 else 4
+
+
+def head_out_size(case):
+    return (case.oh, case.ow) if case.oh else (2 * case.h, 2 * case.w)
+
+
+def head_tiles(case):
+    """the tiles of the path's dL/dW launch, as its host code counts them"""
+    H, W = head_out_size(case)
+    px = HEAD_DW[case.path][0]
+    return case.B * min((H + 1) // 2, case.h) * ((min((W + 1) // 2, case.w) + px - 1) // px)
+
+
+def offsets_of(case):
+    return tuple(case.offset.split("+")) if case.offset else ()
+
+
+def _draw_head(rnd, count):
+    """case j belongs to path 'ABCD'[j % 4]; within a path the plane count, dtype, need_*, norm (A), 16-bit weights (C, D) and C are dealt from decks
+    (C over every class of HEAD_CLASSES), slot r < 5 offsets role r alone at W % 4 = 0 and an exact 2x output (the fast stores stay on), slot 5 has
+    more dL/dW tiles than the launch has waves at C > 64 and asks for both gradients, slots 3, 7, 11 ... have no blur head, the rest is free"""
+    decks = {p: {"planes": _Deck(rnd, HEAD_PLANES[p]), "dtype": _Deck(rnd, HEAD_DTYPES[p]), "need": _Deck(rnd, HEAD_NEEDS), "norm": _Deck(rnd, HEAD_NORMS),
+                 "w16": _Deck(rnd, (0, 1)), "C": _Deck(rnd, HEAD_C)} for p in HEAD_PATHS}
+    even = [w for w in HEAD_W if w % 2 == 0]
+    cases = []
+    for j in range(count):
+        path, slot = HEAD_PATHS[j % 4], j // 4
+        planes, dtype = (decks[path][a].deal() for a in ("planes", "dtype"))
+        need = decks[path]["need"].deal() if slot != 5 else "xw"      # (the slot of many tiles asks for both gradients)
+        norm = decks[path]["norm"].deal() if path == "A" else ""
+        w16 = decks[path]["w16"].deal() if path in "CD" else 0
+        blur = int(slot % 4 != 3)
+        B, h, w = rnd.randint(1, 3), rnd.randint(1, HEAD_H_MAX), rnd.choice(HEAD_W)
+        exact = rnd.random() < 0.4
+        if slot == 5:                       # more tiles than waves, two chunks: the smallest h that has
+            B, C, w = HEAD_MANY[path]
+            px, waves = HEAD_DW[path]
+            exact, h = True, waves // (B * ((w + px - 1) // px)) + 1
+        else:
+            C = decks[path]["C"].deal()
+            if slot < len(HEAD_ROLES):
+                w, exact = rnd.choice(even), True
+            while B * C * h * w > HEAD_ELEMENTS:
+                h //= 2
+        oh, ow = (0, 0) if exact else (rnd.randint(max(1, 2 * h - 3), 2 * h), rnd.randint(max(1, 2 * w - 3), 2 * w))
+        roles = [r for r in HEAD_ROLES if blur or not r.endswith("blur")]
+        if slot < len(HEAD_ROLES):
+            offset = HEAD_ROLES[slot]
+            assert offset in roles
+            if offset.startswith("weight"):
+                w16 = 0                     # (16-bit weights reach the engine as fresh .float() copies: their own placement would not)
+        elif slot == 5:
+            offset = ""
+        else:
+            offset = "+".join(r for r in roles if rnd.random() < HEAD_OFFSET_P)
+        cases.append(Head("head", j, path, planes, dtype, B, C, h, w, oh, ow, blur, norm, need, w16, offset, rnd.randrange(1 << 30)))
+    return cases
+
+
 def draw(family, seed, count):
-    """`count` descriptors of `family` ('kxk' or '3d'): the same arguments always give the same list"""
+    """`count` descriptors of `family` ('kxk', '3d' or 'head'): the same arguments always give the same list"""
     if family not in FAMILIES:
         raise ValueError("family must be one of %s, got %r" % (FAMILIES, family))
     rnd = random.Random("%s/%d" % (family, seed))
-    return (_draw_kxk if family == "kxk" else _draw_3d)(rnd, count)
+    return {"kxk": _draw_kxk, "3d": _draw_3d, "head": _draw_head}[family](rnd, count)
 
 
 def steps_of(case):
@@ -163,6 +246,8 @@ def inputs(case):
     """{role: CPU tensor or None}; g in the case's dtype, everything else float32"""
     import torch
     dt = _torch_dtype(case.dtype)
+    if case.family == "head":
+        return _head_inputs(case)
     if case.family == "3d":
         from test_3d_norm_multi import _inputs
         g, x, s, o = _inputs((case.B, case.D, case.H, case.W), case.C, case.seed, mask=case.mask)
@@ -186,8 +271,107 @@ def inputs(case):
     return t
 
 
+def _head_inputs(case):
+    """as the head files make them: x randn, the weights randn / (3 sqrt C), the gradients randn, each from its own generator seeded by the case.  x in the
+    case's dtype; the weights float32 masters, or (w16) tensors of x's dtype; grad_guidance in x's dtype on path C (what cspn2d_backward_kxk_norm hands
+    back), float32 elsewhere; grad_blur float32; without a blur head weight_blur and grad_blur are None"""
+    import torch
+    dt = _torch_dtype(case.dtype)
+    B, C, h, w, P = case.B, case.C, case.h, case.w, case.planes
+    H, W = head_out_size(case)
+    shapes = ((B, C, h, w), (P, C, 3, 3), (1, C, 3, 3), (B, P, H, W), (B, 1, H, W))
+    t = {r: torch.randn(*s, generator=torch.Generator().manual_seed(case.seed + i)) for i, (r, s) in enumerate(zip(HEAD_ROLES, shapes))}
+    for r in ("weight_guidance", "weight_blur"):
+        t[r] = t[r] / (3.0 * C ** 0.5)
+        if case.w16:
+            t[r] = t[r].to(dt)
+    t["x"] = t["x"].to(dt)
+    if case.path == "C":
+        t["grad_guidance"] = t["grad_guidance"].to(dt)
+    if not case.blur:
+        t["weight_blur"] = t["grad_blur"] = None
+    return t
+
+
+HEAD_OUTPUTS = ("guidance", "blur")
+HEAD_GRADS = ("x", "weight_guidance", "weight_blur")
+
+
+def _head_statement(case, dtype):
+    """tests/test_head_kxk.py's statement on the operands rounded the way the path's own file rounds them (test_head_kxk_g16._reference on C,
+    test_head_g16._case on D: whatever the engine takes or rounds to x's dtype dt is rounded to dt first; nothing on A and B) ->
+    ({guidance, blur}, {x, weight_guidance, weight_blur}), None without a blur head.  float64: statement_grads itself"""
+    import torch
+    from test_head_kxk import statement as head_statement, statement_grads
+    dt = _torch_dtype(case.dtype)
+    t = inputs(case)
+    x, wg, wb, gg, gb = (t[r].to(dt).double() if t[r] is not None else None for r in HEAD_ROLES)   # (every one of these widenings is exact)
+    if dtype == torch.float64:
+        g, b, dx, dwg, dwb = statement_grads(x, wg, wb, gg, gb, case.oh, case.ow)
+    else:
+        xs, wgs, wbs = (v.to(dtype).requires_grad_(True) if v is not None else None for v in (x, wg, wb))
+        g, b = head_statement(xs, wgs, wbs, case.oh, case.ow)
+        loss = (g * gg.to(dtype)).sum()
+        if wb is not None:
+            loss = loss + (b * gb.to(dtype)).sum()
+        loss.backward()
+        g, b, dx, dwg, dwb = g.detach(), (b.detach() if b is not None else None), xs.grad, wgs.grad, (wbs.grad if wbs is not None else None)
+    return dict(zip(HEAD_OUTPUTS, (g, b))), dict(zip(HEAD_GRADS, (dx, dwg, dwb)))
+
+
+# the heads' bounds, by reference: max |a - ref| / max |ref| of tests/test_head_kxk.py::_check_all (A: tests/test_head.py, the same figures) for the
+# float32 results, test_head_kxk_g16._err16 <= 1 with the file's p for a result stored in 16 bits (guidance on C, dL/dx on C and D; test_head_g16._check)
+HEAD_REL = {"guidance": 1e-5, "blur": 1e-5, "x": 1e-5, "weight_guidance": 2e-5, "weight_blur": 2e-5}
+HEAD_NORMALISED = 2e-5     # tests/test_head.py::test_head_fuzzed_shapes_vs_oracle: |gate_wb - cspn2d_normalize(statement)| where both are finite
+
+
+def head_sixteen(case):
+    """the results the path stores in x's 16-bit dtype"""
+    return {"A": (), "B": (), "C": ("guidance", "x"), "D": ("x",)}[case.path]
+
+
+def head_fraction(case, name, a, ref):
+    """how much of its bound result `name` uses against the float64 statement"""
+    from test_head_kxk import _rel
+    from test_head_kxk_g16 import DTS, _err16
+    if name in head_sixteen(case):
+        return _err16(a.cpu(), ref, DTS[case.dtype][1])
+    return _rel(a, ref) / HEAD_REL[name]
+
+
+def _normalised_fraction(got, want):
+    """tests/test_head.py:161-166 on numpy arrays: the NaN pattern is equal, the rest within HEAD_NORMALISED"""
+    import numpy as np
+    assert np.array_equal(np.isnan(got), np.isnan(want)), "the NaN pattern of the normalised guidance differs"
+    return float(np.nan_to_num(np.abs(got - want)).max()) / HEAD_NORMALISED
+
+
+def _head_statement_fractions(case):
+    """the float32 statement against the float64 one.  A result the engine stores in 16 bits is held to 2^-p |ref| + 1e-5 max |ref|; its one rounding
+    may use the whole first term, so the UNROUNDED float32 statement is held to the second term alone: the same expression as for a float32 result"""
+    import torch
+    from test_head_kxk import _rel
+    (ref_out, ref_grads), (out, grads) = reference(case), _head_statement(case, torch.float32)
+    fwd = max(_rel(out[k], ref_out[k]) / HEAD_REL[k] for k in HEAD_OUTPUTS if ref_out[k] is not None)
+    if case.norm not in ("", "none"):   # what a float32 guidance costs behind the normalisation (the C oracle's gate_wb, float32 itself)
+        from oracle import cspn2d_gate_wb_oracle
+        fwd = max(fwd, _normalised_fraction(cspn2d_gate_wb_oracle(out["guidance"].numpy(), case.norm),
+                                            cspn2d_gate_wb_oracle(ref_out["guidance"].float().numpy(), case.norm)))
+    return fwd, max(_rel(grads[k], ref_grads[k]) / HEAD_REL[k] for k in HEAD_GRADS if ref_grads[k] is not None)
+
+
+def finite(ref):
+    """every tensor of a reference() is finite"""
+    every = []
+    for part in ref:
+        every += list(part.values()) if isinstance(part, dict) else [part]
+    return all(bool(v.isfinite().all()) for v in every if v is not None)
+
+
 def statement(case, dtype):
     """the family's statement in `dtype` on the case's inputs (a 16-bit g widened exactly) -> (out, {role: gradient})"""
+    if case.family == "head":
+        return _head_statement(case, dtype)
     t = inputs(case)
     leaf = lambda v: v.float().to(dtype).requires_grad_(True)   # noqa: E731
     g, x = leaf(t["g"]), leaf(t["x"])
@@ -243,6 +427,8 @@ def statement_fractions(case):
     """the float32 statement on the CPU against the float64 one, as fractions of the case's bounds -> (forward, gradients): what a correct
     float32 evaluation costs, so that the rest of a bound is the kernel's"""
     import torch
+    if case.family == "head":
+        return _head_statement_fractions(case)
     ref, ref_grads = reference(case)
     out, grads = statement(case, torch.float32)
     fwd, grad = bounds(case)
@@ -263,7 +449,8 @@ def _one_off(t):
 
 def place(case, tensors):
     """{role: device tensor or None}: each tensor on its own, one element off where the case's `offset` names its role, else as allocated"""
-    return {r: None if t is None else (_one_off(t) if r in case.offset else t.cuda()) for r, t in tensors.items()}
+    off = offsets_of(case) if case.family == "head" else case.offset
+    return {r: None if t is None else (_one_off(t) if r in off else t.cuda()) for r, t in tensors.items()}
 
 
 def _widened(case, g16):
@@ -383,9 +570,103 @@ def _run_3d(case):
     return res
 
 
+def _run_head(case):
+    """through cspn_amd.train_utils.guidance_heads / guidance_heads_backward only"""
+    import torch
+    from cspn_amd.train_utils import guidance_heads, guidance_heads_backward
+    kw = {"guidance_dtype": torch.float32} if case.path == "D" else {}
+    oh, ow, off = case.oh, case.ow, offsets_of(case)
+    t = place(case, inputs(case))
+    res = {"placed": t, "before": {r: v.clone() for r, v in t.items() if v is not None}}
+    fwd = lambda **o: guidance_heads(*(o.get(r, t[r]) for r in HEAD_ROLES[:3]), oh, ow, **kw)   # noqa: E731
+    bwd = lambda need_x=True, need_w=True, **o: guidance_heads_backward(*(o.get(r, t[r]) for r in HEAD_ROLES), need_x=need_x, need_w=need_w, **kw)   # noqa: E731
+    res["out"], res["out_again"] = fwd(), fwd()
+    res["grads"], res["grads_again"] = bwd(), bwd()
+    res["grads_subset"] = bwd("x" in case.need, "w" in case.need)
+    if case.w16:    # the float32 masters of the 16-bit weights
+        masters = {r: t[r].float() for r in HEAD_ROLES[1:3] if t[r] is not None}
+        res["out_masters"], res["grads_masters"] = fwd(**masters), bwd(**masters)
+    # one autograd step on leaves that share the placed tensors' memory; what reaches the backward as dL/dguidance and dL/dblur is autograd's own
+    # (as allocated) copy of grad_guidance and grad_blur, so the manual call it is compared with takes copies of those two where the case offsets them
+    leaves = [t[r].detach().requires_grad_(True) if t[r] is not None else None for r in HEAD_ROLES[:3]]
+    g, b = guidance_heads(*leaves, oh, ow, **kw)
+    loss = (g * t["grad_guidance"]).sum()
+    if b is not None:
+        loss = loss + (b * t["grad_blur"]).sum()
+    loss.backward()
+    res["autograd_out"] = (g.detach(), b.detach() if b is not None else None)
+    res["autograd_grads"] = tuple(v.grad if v is not None else None for v in leaves)
+    copies = {r: t[r].clone() for r in HEAD_ROLES[3:] if r in off}
+    res["grads_for_autograd"] = bwd(**copies) if copies else res["grads"]
+    # a misaligned x (C, D) or grad_guidance (C) gives the aligned tensor's bits: tests/test_head_g16.py, tests/test_head_kxk_g16.py
+    twin = {r: t[r].clone() for r in (("x", "grad_guidance") if case.path == "C" else ("x",) if case.path == "D" else ()) if r in off}
+    if twin:
+        res["out_aligned"], res["grads_aligned"] = fwd(**twin), bwd(**twin)
+    if case.norm not in ("", "none"):
+        from cspn_amd import cspn2d_normalize
+        with torch.no_grad():
+            res["normalised"] = fwd_n = guidance_heads(t["x"], t["weight_guidance"], t["weight_blur"], oh, ow, norm_type=case.norm)
+        assert fwd_n[0].dtype == torch.float32
+        res["normalised_statement"] = cspn2d_normalize(reference(case)[0]["guidance"].float().cuda(), case.norm)
+    torch.cuda.synchronize()
+    return res
+
+
+def _check_head(case):
+    """The 16-bit kernels are not the float32 kernels on widened operands (they round the weights and the gradients to x's dtype and run other
+    matrix-core instructions), so the K x K and 3D families' anchor 'bitwise the float32 call on the widened tensor' does not exist here: a 16-bit
+    case is held to the statement on the rounded operands, under its own file's bounds"""
+    import torch
+    res = run(case)
+    what = repr(case)
+    dt = _torch_dtype(case.dtype)
+    out, grads = res["out"], res["grads"]
+    _same(res["out_again"], out, what + " forward, called twice")
+    _same(res["grads_again"], grads, what + " backward, called twice")
+    for i, r in enumerate(HEAD_GRADS):
+        asked = ("x" if r == "x" else "w") in case.need
+        assert bits(res["grads_subset"][i], grads[i] if asked else None), "%s need=%s: d/d%s is not %s" % (what, case.need, r, "the full call's" if asked else "None")
+    assert out[0].dtype == (dt if case.path == "C" else torch.float32) and grads[0].dtype == dt, what + ": dtypes of guidance and dL/dx"
+    if case.blur:
+        assert out[1].dtype == torch.float32 and grads[2] is not None
+    else:
+        assert out[1] is None and grads[2] is None, what + ": a blur or a dL/dW_blur without a blur head"
+    # 16-bit weights: the bits of their float32 masters' call, the weight gradients that call's .to(dt)
+    out32, grads32 = out, grads
+    if case.w16:
+        out32, grads32 = res["out_masters"], res["grads_masters"]
+        _same(out, out32, what + " 16-bit weights against their .float() masters, forward")
+        assert bits(grads[0], grads32[0]), what + ": dL/dx with 16-bit weights against their .float() masters"
+        for i in (1, 2):
+            assert bits(grads[i], grads32[i].to(dt) if grads32[i] is not None else None), what + ": a 16-bit weight's gradient is not the float32 one .to(dtype)"
+    assert all(v is None or v.dtype == torch.float32 for v in grads32[1:]), what
+    _same(res["autograd_out"], out, what + " forward under autograd")
+    _same(res["autograd_grads"], res["grads_for_autograd"], what + " .grad after one autograd step against guidance_heads_backward")
+    if "out_aligned" in res:
+        _same(res["out_aligned"], out, what + " forward: one element off against as allocated")
+        _same(res["grads_aligned"], grads, what + " backward: one element off against as allocated")
+    # against the float64 statement (without a blur head: the statement without one)
+    ref_out, ref_grads = reference(case)
+    assert finite((ref_out, ref_grads)), what + ": the float64 statement is not finite"
+    used = {}
+    for name, a, r in tuple(zip(HEAD_OUTPUTS, out32, (ref_out[k] for k in HEAD_OUTPUTS))) + tuple(zip(HEAD_GRADS, grads32, (ref_grads[k] for k in HEAD_GRADS))):
+        assert (a is None) == (r is None), "%s: %s is None on one side only" % (what, name)
+        if a is not None:
+            key = name if name in HEAD_OUTPUTS else "d/d" + name
+            used[key] = head_fraction(case, name, a, r)
+            assert used[key] <= 1.0, "%s: %s uses %.3g of its bound" % (what, key, used[key])
+    if "normalised" in res:
+        assert bits(res["normalised"][1], out[1]), what + ": blur of the normalising call is not the raw call's"
+        used["normalised"] = _normalised_fraction(res["normalised"][0].cpu().numpy(), res["normalised_statement"].cpu().numpy())
+        assert used["normalised"] <= 1.0, "%s: the normalised guidance uses %.3g of its bound" % (what, used["normalised"])
+    for r, v in res["before"].items():
+        assert bits(res["placed"][r], v), "%s: the calls wrote input %r" % (what, r)
+    return used
+
+
 def run(case):
     """every engine call of the case -> {name: result}"""
-    return (_run_3d if case.family == "3d" else _run_kxk)(case)
+    return {"kxk": _run_kxk, "3d": _run_3d, "head": _run_head}[case.family](case)
 
 
 def _same(a, b, what):
@@ -395,7 +676,9 @@ def _same(a, b, what):
 
 def check(case):
     """run(case), then: the float32 results within the project's bounds of the float64 statement, the bitwise anchors the project claims, the
-    inputs untouched -> {what: fraction of its bound}"""
+    inputs untouched -> {what: fraction of its bound}.  The head family: _check_head"""
+    if case.family == "head":
+        return _check_head(case)
     res = run(case)
     what = repr(case)
     roles = _grad_roles(case)
@@ -463,14 +746,14 @@ def _paths():
 
 
 def main(argv):
-    """FUZZ_CASES K x K cases and half as many 3D ones of FUZZ_SEED, or the one case whose descriptor is the argument; a case whose float32 statement
-    uses more than half of a bound is named and left out (a failure must mean the kernel); stops at the first failure"""
+    """FUZZ_CASES K x K cases, half as many 3D ones and as many head ones of FUZZ_SEED, or the one case whose descriptor is the argument; a case whose
+    float32 statement uses more than half of a bound is named and left out (a failure must mean the kernel); stops at the first failure"""
     _paths()
     if len(argv) > 1:
-        cases = [eval(argv[1], {"__builtins__": {}}, {"KxK": KxK, "Vol": Vol})]
+        cases = [eval(argv[1], {"__builtins__": {}}, {"KxK": KxK, "Vol": Vol, "Head": Head})]
     else:
         count, seed = int(os.environ.get("FUZZ_CASES", "60")), int(os.environ.get("FUZZ_SEED", "1"))
-        cases = draw("kxk", seed, count) + draw("3d", seed, count // 2)
+        cases = draw("kxk", seed, count) + draw("3d", seed, count // 2) + draw("head", seed, count)
     ran = 0
     for case in cases:
         try:
