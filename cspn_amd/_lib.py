@@ -129,6 +129,12 @@ _SYMBOLS.update({
     "cspn2d_backward_kxk_norm_dil": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 9 + _WS),
     "cspn2d_forward_kxk_assemble_dil": (c_int, [vp, c_int] + [vp] * 4 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 9 + _WS),
     "cspn2d_backward_kxk_assemble_dil": (c_int, [vp, c_int] + [vp] * 4 + [c_int, vp, c_size_t] + [vp] * 4 + [c_int] * 9 + _WS),
+    # K x K propagation pinned to the measured depth with a confidence: the _dil argument lists with pin_conf behind sparse and, in the backwards,
+    # grad_sparse and grad_pin behind the other gradients; the byte queries above apply
+    "cspn2d_forward_kxk_norm_pin": (c_int, [vp, c_int] + [vp] * 5 + [c_size_t] + [c_int] * 9 + _WS),
+    "cspn2d_backward_kxk_norm_pin": (c_int, [vp, c_int] + [vp] * 4 + [c_size_t] + [vp] * 5 + [c_int] * 9 + _WS),
+    "cspn2d_forward_kxk_assemble_pin": (c_int, [vp, c_int] + [vp] * 5 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 9 + _WS),
+    "cspn2d_backward_kxk_assemble_pin": (c_int, [vp, c_int] + [vp] * 5 + [c_int, vp, c_size_t] + [vp] * 6 + [c_int] * 9 + _WS),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

@@ -193,6 +193,32 @@ class _CSPN2dKxKNormFunction(torch.autograd.Function):
         return gg, gh, None, None, None, None, None
 
 
+class _CSPN2dKxKNormPinFunction(torch.autograd.Function):
+    """Affinity_PropagateKxK with a pin_conf, every prop_kernel: one cspn2d_forward_kxk_norm_pin call that keeps H_1 .. H_{n-1} where dL/dguidance
+    or dL/dpin_conf will need them (both read the gradient of the folded gates), one cspn2d_backward_kxk_norm_pin call"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, dilation):
+        ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = kernel_size, n_iter, norm_type, dilation
+        hist = None
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and n_iter >= 2:
+            out, hist = F.cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, return_history=True,
+                                                      dilation=dilation)
+        else:
+            out = F.cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, dilation=dilation)
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, pin_conf, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, pin_conf, hist = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gg, gh, gs, gp = F.cspn2d_backward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type,
+                                                        hist, need_guidance=need[0], need_blur=need[1], need_sparse=need[2], need_pin=need[3],
+                                                        dilation=ctx.dilation)
+        return gg, gh, gs, gp, None, None, None, None
+
+
 class Affinity_PropagateKxK(nn.Module):
     """Affinity_Propagate (same constructor, same forward) with prop_kernel 3, 5 or 7 -- what cspn_config['kernel'] asks of the reference
     (torch_resnet_cspn_nyu.py:281,344-347; cspn.py:24 "current only support 3x3").  guidance [B, K*K-1, H, W] raw, channel k the k-th
@@ -202,7 +228,13 @@ class Affinity_PropagateKxK(nn.Module):
     is (prop_kernel 3: widened first); the result is float32.
     dilation 2 puts the neighbour of gate (t, l) at 2 * (K//2 - t, K//2 - l) -- the dilated pass of PENet's refinement (dilated CSPN++),
     which runs each propagation at dilation 2 and then once more at dilation 1.  It runs the K x K engine for every prop_kernel, 3
-    included (the engine's own K = 3 instance, not the 3 x 3 ring)."""
+    included (the engine's own K = 3 instance, not the 3 x 3 ring).
+    forward(..., pin_conf=...) pins softly to the measured depth, as CSPN++-style refinements (PENet's included) do after every step:
+    H <- (1 - m) step(H) + m sparse_depth with m = sign(sparse_depth) * pin_conf, in place of the reference's hard pin to blur_depth.  pin_conf
+    has sparse_depth's shape and is used as given (a sigmoid of a confidence head is the caller's); it needs a sparse_depth.  One engine call
+    each way (F.cspn2d_forward_kxk_norm_pin / F.cspn2d_backward_kxk_norm_pin), differentiable w.r.t. guidance, blur_depth, sparse_depth and
+    pin_conf; it runs the K x K engine for every prop_kernel and dilation (the ring does not pin softly).  pin_conf=None is the module as it
+    was."""
 
     def __init__(self, prop_time, prop_kernel, norm_type='8sum', dilation=1):
         super(Affinity_PropagateKxK, self).__init__()
@@ -215,11 +247,18 @@ class Affinity_PropagateKxK(nn.Module):
         self.algo = "auto"          # prop_kernel 3: as Affinity_Propagate
         self.keep_history = True
 
-    def forward(self, guidance, blur_depth, sparse_depth=None, n_iter=None):
+    def forward(self, guidance, blur_depth, sparse_depth=None, n_iter=None, pin_conf=None):
+        if pin_conf is not None and sparse_depth is None:
+            raise ValueError("pin_conf needs a sparse_depth: it weights the pin to the measured depth")
         n = self.prop_time if n_iter is None else int(n_iter)
         if n == 0:
             return blur_depth
         blur_depth, sparse_depth = F.widen16(blur_depth, sparse_depth)
+        if pin_conf is not None:
+            pin_conf = F.widen16(pin_conf)
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (guidance, blur_depth, sparse_depth, pin_conf)):
+                return _CSPN2dKxKNormPinFunction.apply(guidance, blur_depth, sparse_depth, pin_conf, self.prop_kernel, n, self.norm_type, self.dilation)
+            return F.cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, self.prop_kernel, n, self.norm_type, dilation=self.dilation)
         if self.prop_kernel == 3 and self.dilation == 1:
             return _apply(F.widen16(guidance), blur_depth, sparse_depth, n, self.norm_type, self.algo, self.keep_history)
         if torch.is_grad_enabled() and (guidance.requires_grad or blur_depth.requires_grad):
@@ -256,6 +295,33 @@ class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
         return gg, gh, None, gc, None, None, None, None, None
 
 
+class _CSPN2dKxKAssemblePinFunction(torch.autograd.Function):
+    """one kernel size of Affinity_PropagateAssemble with a pin_conf: one cspn2d_forward_kxk_assemble_pin call that keeps H_1 .. H_n where
+    dL/dguidance, dL/dpin_conf or dL/dconf will need them, one cspn2d_backward_kxk_assemble_pin call"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type, dilation):
+        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = steps, kernel_size, n_iter, norm_type, dilation
+        hist = None
+        if ((ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and n_iter >= 2) or ctx.needs_input_grad[4]:
+            out, hist = F.cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type,
+                                                          return_history=True, dilation=dilation)
+        else:
+            out = F.cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type,
+                                                    dilation=dilation)
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, pin_conf, conf, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, pin_conf, conf, hist = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gg, gh, gc, gs, gp = F.cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, ctx.steps, grad_out, ctx.kernel_size,
+                                                                ctx.n_iter, ctx.norm_type, hist, need_guidance=need[0], need_blur=need[1],
+                                                                need_conf=need[4], need_sparse=need[2], need_pin=need[3], dilation=ctx.dilation)
+        return gg, gh, gs, gp, gc, None, None, None, None, None
+
+
 class Affinity_PropagateAssemble(nn.Module):
     """The propagation of CSPN++ ("context-aware" CSPN; with dilations, each pass of PENet's dilated refinement): Affinity_PropagateKxK over several kernel sizes at once, the result a
     per-pixel weighted sum over collected iterations and over kernel sizes,
@@ -271,7 +337,11 @@ class Affinity_PropagateAssemble(nn.Module):
     overrides prop_time and needs steps that end at it; n_iter == 0 returns blur_depth itself, as the other modules do.  No parameters or buffers.
     dilations: 1 or 2, one int for all or one per entry of prop_kernels (the same kernel size may appear twice with different dilations); the
     neighbour of gate (t, l) of entry k is dilations[k] * (K//2 - t, K//2 - l).  PENet's refinement is this module at dilation 2 feeding the
-    same module at dilation 1."""
+    same module at dilation 1.
+    forward(..., pin_conf=...): the levels are pinned softly to the measured depth after every step, H <- (1 - m) step(H) + m sparse_depth with
+    m = sign(sparse_depth) * pin_conf (Affinity_PropagateKxK).  pin_conf is one tensor of sparse_depth's shape for all kernel sizes, or a
+    sequence with one per entry of prop_kernels (each size has its own confidence head, as in PENet); it needs a sparse_depth.  Gradients then
+    also flow to sparse_depth and pin_conf (F.cspn2d_*_kxk_assemble_pin).  pin_conf=None is the module as it was."""
 
     def __init__(self, prop_time, prop_kernels=(3, 5, 7), steps=None, norm_type='8sum', dilations=1):
         super(Affinity_PropagateAssemble, self).__init__()
@@ -290,11 +360,19 @@ class Affinity_PropagateAssemble(nn.Module):
         assert len(dilations) == len(prop_kernels), 'dilations is one int, or one per entry of prop_kernels'
         self.dilations = tuple(F.check_dilation(d) for d in dilations)
 
-    def forward(self, guidances, blur_depth, sparse_depth=None, iter_conf=None, kernel_conf=None, n_iter=None):
+    def forward(self, guidances, blur_depth, sparse_depth=None, iter_conf=None, kernel_conf=None, n_iter=None, pin_conf=None):
+        if pin_conf is not None and sparse_depth is None:
+            raise ValueError("pin_conf needs a sparse_depth: it weights the pin to the measured depth")
         n = self.prop_time if n_iter is None else int(n_iter)
         if n == 0:
             return blur_depth
         nk, T = len(self.prop_kernels), len(self.steps)
+        if isinstance(pin_conf, (tuple, list)):
+            if len(pin_conf) != nk:
+                raise ValueError("pin_conf is one tensor, or a sequence with one entry per kernel size %s" % (self.prop_kernels,))
+            pins = [F.widen16(p) for p in pin_conf]
+        else:
+            pins = [None if pin_conf is None else F.widen16(pin_conf)] * nk
         if len(guidances) != nk or (iter_conf is not None and len(iter_conf) != nk):
             raise ValueError("guidances and iter_conf need one entry per kernel size %s" % (self.prop_kernels,))
         if kernel_conf is not None and (kernel_conf.dim() != 4 or kernel_conf.shape[1] != nk):
@@ -303,7 +381,11 @@ class Affinity_PropagateAssemble(nn.Module):
         out = None
         for k, K in enumerate(self.prop_kernels):
             conf = F.assemble_conf(None if iter_conf is None else F.widen16(iter_conf[k]), kernel_conf, k, T, blur_depth)
-            y = _CSPN2dKxKAssembleFunction.apply(guidances[k], blur_depth, sparse_depth, conf, self.steps, K, n, self.norm_type, self.dilations[k])
+            if pins[k] is None:
+                y = _CSPN2dKxKAssembleFunction.apply(guidances[k], blur_depth, sparse_depth, conf, self.steps, K, n, self.norm_type, self.dilations[k])
+            else:
+                y = _CSPN2dKxKAssemblePinFunction.apply(guidances[k], blur_depth, sparse_depth, pins[k], conf, self.steps, K, n, self.norm_type,
+                                                        self.dilations[k])
             out = y if out is None else out + y
         return out
 

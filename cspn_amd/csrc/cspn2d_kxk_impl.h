@@ -1,5 +1,7 @@
 // cspn2d_kxk_impl.h -- the 2D K x K engine's kernels and host paths, included by the translation units that instantiate them:
-// cspn2d_kxk.hip (neighbour distance one, every contract) and cspn2d_kxk_dil.hip (the dilated folded / assembling contracts).
+// cspn2d_kxk.hip (neighbour distance one, every contract), cspn2d_kxk_dil.hip (the dilated folded / assembling contracts) and
+// cspn2d_kxk_pin.hip (the folded / assembling contracts pinned to the measured depth with a per-pixel confidence: kxk_fold_pin,
+// kxk_unfold_pixel_pin and the host paths' PIN argument, at every dilation).
 // The 2D NONE op (Paddle contract: gates used as given, centre-sited, no centre term, any sign) over a K x K
 // neighbourhood, K = 2R+1 in {5, 7}, forward and backward.  gate [N][KK][H][W], KK = K*K - 1; values [N][C][H][W], the C channels
 // share the gates (reference cspn_paddle/README.md:54-56).
@@ -714,6 +716,21 @@ __device__ __forceinline__ void mask4(float (&m)[4], float (&u)[4], const float*
     }
 }
 
+// the pinned contract's mask: s = sparse, m = sign(s) pin_conf and u = 1 - m of image n (both one plane per image).  VEC: W % 4 == 0, sparse
+// and pinc 16-byte aligned
+template <bool VEC>
+__device__ __forceinline__ void mask4_pin(float (&m)[4], float (&u)[4], float (&s)[4], const float* __restrict__ sparse, const float* __restrict__ pinc, int n,
+                                          int HW, int pix, bool row_in, int x0, int W) {
+    float p[4];
+    load4<VEC>(s, sparse + (size_t)n * HW + pix, row_in, x0, W);
+    load4<VEC>(p, pinc + (size_t)n * HW + pix, row_in, x0, W);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m[j] = signf(s[j]) * p[j];
+        u[j] = 1.f - m[j];
+    }
+}
+
 // w' [N'][KK][H][W] and b [N'][Cv][H][W] of image n' (guidance image n' / cpg).  VEC: W % 4 == 0, blur 16-byte aligned
 template <int K, bool VEC, class GT = float, int D = 1>
 __global__ __launch_bounds__(NT) void kxk_fold(const store_t<GT>* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
@@ -752,6 +769,51 @@ __global__ __launch_bounds__(NT) void kxk_fold(const store_t<GT>* __restrict__ g
         load4<VEC>(v, blur + plane, row_in, T.x0, W);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= f[j];
+        store4<VEC>(bias + plane, v, row_in, T.x0, W);
+    }
+}
+
+// kxk_fold of the pinned contract, a sibling kernel (kxk_fold itself stays the text, and so the code, it was): m = sign(sparse) pinc,
+// w' = u wb, b = (u c) blur + m sparse, in this form: with pinc = 1 and blur = sparse where sparse > 0 it is (u c + m) blur bit for bit, with
+// pinc = 0 the b of a call without a mask.  VEC: W % 4 == 0, blur, sparse and pinc 16-byte aligned
+template <int K, bool VEC, class GT = float, int D = 1>
+__global__ __launch_bounds__(NT) void kxk_fold_pin(const store_t<GT>* __restrict__ guid, const float* __restrict__ blur, const float* __restrict__ sparse,
+                                                   const float* __restrict__ pinc, float* __restrict__ wp, float* __restrict__ bias, int Cv, int cpg,
+                                                   int norm, int H, int W, int tiles_x, int tiles_y) {
+    constexpr int KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    float G[KK][4];
+    sited_gates<K, GT, D>(G, guid + (size_t)(T.n / cpg) * KK * HW, row_in, T.y, T.x0, H, W, norm == CSPN_NORM_8SUM_ABS);
+    float S[4] = {0.f, 0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f}, m[4], u[4];
+#pragma unroll
+    for (int k = 0; k < KK; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[j] += fabsf(G[k][j]);
+    float sv[4];
+    mask4_pin<VEC>(m, u, sv, sparse, pinc, T.n, HW, pix, row_in, T.x0, W);
+    float* wq = wp + (size_t)T.n * KK * HW + pix;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float wb = G[k][j] / S[j];   // 0 / 0 = NaN, as the reference's torch.div
+            gs[j] += wb;
+            G[k][j] = u[j] * wb;
+        }
+        store4<VEC>(wq + (size_t)k * HW, G[k], row_in, T.x0, W);
+    }
+    float f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = u[j] * (1.f - gs[j]);
+    for (int c = 0; c < Cv; ++c) {
+        const size_t plane = ((size_t)T.n * Cv + c) * HW + pix;
+        float v[4];
+        load4<VEC>(v, blur + plane, row_in, T.x0, W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaf(m[j], sv[j], f[j] * v[j]);
         store4<VEC>(bias + plane, v, row_in, T.x0, W);
     }
 }
@@ -864,6 +926,173 @@ __global__ __launch_bounds__(NT) void kxk_unfold_pixel(const store_t<GT>* __rest
             load4<VEC>(d, db + plane, row_in, T.x0, W);
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = fmaf(u[j] * (1.f - gs[j]) + m[j], d[j], a[j]);
+            store4<VEC>(gx + plane, a, row_in, T.x0, W);
+        }
+    }
+}
+
+// kxk_unfold_pixel of the pinned contract, a sibling kernel (kxk_unfold_pixel itself stays the text, and so the code, it was; the two share
+// mask4_pin's contract with kxk_fold_pin and the channel order of sited_gates): m = sign(sparse) pinc, dwb_k and dG_k as above with that u,
+//   gx_{n',c} = A_0 + (u_i c) db_{n',c}, and per mask plane n'
+//   gsp_{n'} = m sum_c db_{n',c}   and   gpp_{n'} = sign(sparse) (sum_c db_{n',c} (sparse - c blur_{n',c}) - sum_k wb_k dw'_{n',k})
+//   (each may be NULL), the last sum in channel order and formed before dw' is overwritten in place; gpp needs dw' whatever need_g says.
+//   Every element is written once.  VEC: W % 4 == 0, blur, gx, sparse, pinc, gsp and gpp 16-byte aligned
+template <int K, bool VEC, class GT = float, int D = 1>
+__global__ __launch_bounds__(NT) void kxk_unfold_pixel_pin(const store_t<GT>* __restrict__ guid, const float* __restrict__ blur,
+                                                           const float* __restrict__ sparse, const float* __restrict__ pinc, float* __restrict__ dwp,
+                                                           const float* __restrict__ db, float* __restrict__ gx, float* __restrict__ gsp,
+                                                           float* __restrict__ gpp, int need_g, int Cv, int cpg, int norm, int H, int W, int tiles_x,
+                                                           int tiles_y) {
+    constexpr int R = K / 2, KK = K * K - 1;
+    const Tile T = tile_of(tiles_x, tiles_y);
+    const int HW = H * W;
+    const bool row_in = T.y < H;
+    const int pix = T.y * W + T.x0;
+    const store_t<GT>* gb = guid + (size_t)T.n * KK * HW;
+    const bool ab = norm == CSPN_NORM_8SUM_ABS;
+    // G_k of the four pixels (kxk_fold's sited_gates, one channel at a time: the passes below re-read it from the cache rather than
+    // keep KK x 4 values live)
+    auto gate = [&](int t, int l, float (&v)[4]) {
+        const int k = chan<K>(t, l), py = T.y + R * D - t * D;
+        const bool yin = row_in && py >= 0 && py < H;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int px = T.x0 + j + R * D - l * D;
+            const float g = (yin && T.x0 + j < W && px >= 0 && px < W) ? widen<GT>(gb[(size_t)k * HW + py * W + px]) : 0.f;
+            v[j] = ab ? fabsf(g) : g;
+        }
+    };
+    float S[4] = {0.f, 0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < K; ++t)
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            float v[4];
+            gate(t, l, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) S[j] += fabsf(v[j]);
+        }
+    const int n0 = T.n * cpg;
+    // dL/dsparse and dL/dpin come first: they read dw' of image n0, which the guidance gradient below overwrites in place
+    if (gsp || gpp) {
+        float cc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < K; ++t)
+            for (int l = 0; l < K; ++l) {
+                if (t == R && l == R) continue;
+                float v[4];
+                gate(t, l, v);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) cc[j] += v[j] / S[j];
+            }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cc[j] = 1.f - cc[j];
+        for (int i = 0; i < cpg; ++i) {
+            const size_t mp = (size_t)(n0 + i) * HW + pix;
+            float m[4], u[4], s[4], ds[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f};
+            mask4_pin<VEC>(m, u, s, sparse, pinc, n0 + i, HW, pix, row_in, T.x0, W);
+            for (int c = 0; c < Cv; ++c) {
+                const size_t plane = ((size_t)(n0 + i) * Cv + c) * HW + pix;
+                float v[4], d[4];
+                load4<VEC>(v, blur + plane, row_in, T.x0, W);
+                load4<VEC>(d, db + plane, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ds[j] += d[j];
+                    e[j] = fmaf(d[j], s[j] - cc[j] * v[j], e[j]);
+                }
+            }
+            if (gpp) {
+                float wd[4] = {0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < K; ++t)
+                    for (int l = 0; l < K; ++l) {
+                        if (t == R && l == R) continue;
+                        float v[4], d[4];
+                        gate(t, l, v);
+                        load4<VEC>(d, dwp + ((size_t)(n0 + i) * KK + chan<K>(t, l)) * HW + pix, row_in, T.x0, W);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) wd[j] = fmaf(v[j] / S[j], d[j], wd[j]);
+                    }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e[j] = signf(s[j]) * (e[j] - wd[j]);
+                store4<VEC>(gpp + mp, e, row_in, T.x0, W);
+            }
+            if (gsp) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ds[j] *= m[j];
+                store4<VEC>(gsp + mp, ds, row_in, T.x0, W);
+            }
+        }
+    }
+    if (need_g) {
+        // u_i and sum_c blur db of image n0 + i
+        auto ubd = [&](int i, float (&u)[4], float (&bd)[4]) {
+            float m[4], s[4];
+            mask4_pin<VEC>(m, u, s, sparse, pinc, n0 + i, HW, pix, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bd[j] = 0.f;
+            for (int c = 0; c < Cv; ++c) {
+                const size_t plane = ((size_t)(n0 + i) * Cv + c) * HW + pix;
+                float v[4], d[4];
+                load4<VEC>(v, blur + plane, row_in, T.x0, W);
+                load4<VEC>(d, db + plane, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bd[j] = fmaf(v[j], d[j], bd[j]);
+            }
+        };
+        float u0[4], bd0[4];
+        ubd(0, u0, bd0);
+        auto dwb = [&](int k, float (&d)[4]) {
+            load4<VEC>(d, dwp + ((size_t)n0 * KK + k) * HW + pix, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = u0[j] * (d[j] - bd0[j]);
+            for (int i = 1; i < cpg; ++i) {
+                float u[4], bd[4], e[4];
+                ubd(i, u, bd);
+                load4<VEC>(e, dwp + ((size_t)(n0 + i) * KK + k) * HW + pix, row_in, T.x0, W);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[j] = fmaf(u[j], e[j] - bd[j], d[j]);
+            }
+        };
+        float dot[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < K; ++t)
+            for (int l = 0; l < K; ++l) {
+                if (t == R && l == R) continue;
+                float v[4], d[4];
+                gate(t, l, v);
+                dwb(chan<K>(t, l), d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dot[j] = fmaf(v[j] / S[j], d[j], dot[j]);
+            }
+        for (int t = 0; t < K; ++t)
+            for (int l = 0; l < K; ++l) {
+                if (t == R && l == R) continue;
+                const int k = chan<K>(t, l);
+                float v[4], d[4];
+                gate(t, l, v);
+                dwb(k, d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[j] = (d[j] - signf(v[j]) * dot[j]) / S[j];
+                store4<VEC>(dwp + ((size_t)n0 * KK + k) * HW + pix, d, row_in, T.x0, W);
+            }
+    }
+    if (!gx) return;
+    for (int t = 0; t < K; ++t)
+        for (int l = 0; l < K; ++l) {
+            if (t == R && l == R) continue;
+            float v[4];
+            gate(t, l, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gs[j] += v[j] / S[j];   // c = 1 - sum_k wb_k, in channel order as kxk_fold
+        }
+    for (int i = 0; i < cpg; ++i) {
+        float m[4], u[4], s[4];
+        mask4_pin<VEC>(m, u, s, sparse, pinc, n0 + i, HW, pix, row_in, T.x0, W);
+        for (int c = 0; c < Cv; ++c) {
+            const size_t plane = ((size_t)(n0 + i) * Cv + c) * HW + pix;
+            float a[4], d[4];
+            load4<VEC>(a, gx + plane, row_in, T.x0, W);
+            load4<VEC>(d, db + plane, row_in, T.x0, W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = fmaf(u[j] * (1.f - gs[j]), d[j], a[j]);
             store4<VEC>(gx + plane, a, row_in, T.x0, W);
         }
     }
@@ -1017,25 +1246,36 @@ NormGeo norm_geo(int B, int C, int sparse_C, int H, int W) {
     return NormGeo{pc ? B * C : B, pc ? 1 : C, pc ? C : 1, (size_t)B * C * H * W};
 }
 
-template <int K, class GT = float, int D = 1>
-int fold(const store_t<GT>* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st) {
+// PIN (a trailing template argument of the host paths below, default off): the pinned contract, pin (KxkPin, cspn_common.h) its confidence
+// and where dL/dsparse and dL/dpin go.  Only the fold and its adjoint differ; the steps between them are the unpinned contract's
+template <int K, class GT = float, int D = 1, bool PIN = false>
+int fold(const store_t<GT>* guid, const float* blur, const float* sparse, float* wp, float* bias, const NormGeo& g, int norm, int H, int W, hipStream_t st,
+         const KxkPin& pin = KxkPin{}) {
     const Grid G = grid_of(g.N, H, W);
-    with_bool(W % 4 == 0 && aligned16(blur), [&](auto vec) {
-        hipLaunchKernelGGL((kxk_fold<K, decltype(vec)::value, GT, D>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W,
-                           G.tx, G.ty);
-    });
-    return check_launch("kxk_fold");
+    if constexpr (PIN) {
+        with_bool(W % 4 == 0 && aligned16(blur) && aligned16(sparse) && aligned16(pin.conf), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_fold_pin<K, decltype(vec)::value, GT, D>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, pin.conf, wp, bias, g.Cv,
+                               g.cpg, norm, H, W, G.tx, G.ty);
+        });
+        return check_launch("kxk_fold_pin");
+    } else {
+        with_bool(W % 4 == 0 && aligned16(blur), [&](auto vec) {
+            hipLaunchKernelGGL((kxk_fold<K, decltype(vec)::value, GT, D>), dim3(G.blocks), dim3(NT), 0, st, guid, blur, sparse, wp, bias, g.Cv, g.cpg, norm, H, W,
+                               G.tx, G.ty);
+        });
+        return check_launch("kxk_fold");
+    }
 }
 
 // the steps run on the float32 w' and b whatever the guidance's type
-template <int K, class GT = float, int D = 1>
+template <int K, class GT = float, int D = 1, bool PIN = false>
 int norm_forward(const store_t<GT>* guid, const float* blur, const float* sparse, float* out, float* hist, int B, int C, int sparse_C, int H, int W,
-                 int n_iter, int norm, void* ws, hipStream_t st) {
+                 int n_iter, int norm, void* ws, hipStream_t st, const KxkPin& pin = KxkPin{}) {
     constexpr int KK = K * K - 1;
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     float* wp = (float*)ws;
     float* bias = wp + kxk_level_floats((size_t)g.N * KK * H * W);
-    if (int e = fold<K, GT, D>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT, D, PIN>(guid, blur, sparse, wp, bias, g, norm, H, W, st, pin)) return e;
     return forward_steps<K, true, float, false, D>(wp, blur, out, hist, g.N, g.Cv, H, W, n_iter, bias + kxk_level_floats(g.L), st, bias);
 }
 
@@ -1059,25 +1299,35 @@ NormBackwardWs norm_backward_ws(void* ws, const NormGeo& g, int H, int W, int n_
 }
 
 // after the adjoint steps: the gate gradient with dL/db (atop: the top adjoint level A_n), the fold's adjoint per pixel, the gather back
-template <int K, class GT = float, int D = 1>
+// PIN: dL/dpin needs dL/dw' as the guidance gradient does, so it too asks for the gate gradient's GATES pass (and its history)
+template <int K, class GT = float, int D = 1, bool PIN = false>
 int norm_backward_finish(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* atop, store_t<GT>* gg, float* gx,
-                         int B, const NormGeo& g, const NormBackwardWs& w, int H, int W, int n_iter, int norm, hipStream_t st) {
+                         int B, const NormGeo& g, const NormBackwardWs& w, int H, int W, int n_iter, int norm, hipStream_t st, const KxkPin& pin = KxkPin{}) {
     float *dwp = w.dwp, *dbp = w.dbp, *alev = w.alev;
     const float* gout = atop;
     const Grid G = grid_of(g.N, H, W);
     const bool vec = W % 4 == 0;   // dwp and dbp: workspace
     with_bool(vec, [&](auto v) {
-        with_bool(gg != nullptr, [&](auto gates) {
+        with_bool(gg != nullptr || (PIN && pin.gp != nullptr), [&](auto gates) {
             hipLaunchKernelGGL((kxk_gate_grad<K, decltype(v)::value, true, decltype(gates)::value, float, false, D>), dim3(G.blocks), dim3(NT), 0, st, blur, hist, alev, gout,
                                dwp, n_iter, g.L, g.Cv, H, W, G.tx, G.ty, dbp, nullptr);
         });
     });
     if (int e = check_launch("kxk_gate_grad")) return e;
     const Grid GB = grid_of(B, H, W);
-    with_bool(vec && aligned16(blur) && (!gx || aligned16(gx)), [&](auto v) {
-        hipLaunchKernelGGL((kxk_unfold_pixel<K, decltype(v)::value, GT, D>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0, g.Cv,
-                           g.cpg, norm, H, W, GB.tx, GB.ty);
-    });
+    if constexpr (PIN) {
+        with_bool(vec && aligned16(blur) && (!gx || aligned16(gx)) && aligned16(sparse) && aligned16(pin.conf) && (!pin.gs || aligned16(pin.gs)) &&
+                      (!pin.gp || aligned16(pin.gp)),
+                  [&](auto v) {
+                      hipLaunchKernelGGL((kxk_unfold_pixel_pin<K, decltype(v)::value, GT, D>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, pin.conf, dwp,
+                                         dbp, gx, pin.gs, pin.gp, gg ? 1 : 0, g.Cv, g.cpg, norm, H, W, GB.tx, GB.ty);
+                  });
+    } else {
+        with_bool(vec && aligned16(blur) && (!gx || aligned16(gx)), [&](auto v) {
+            hipLaunchKernelGGL((kxk_unfold_pixel<K, decltype(v)::value, GT, D>), dim3(GB.blocks), dim3(NT), 0, st, guid, blur, sparse, dwp, dbp, gx, gg ? 1 : 0,
+                               g.Cv, g.cpg, norm, H, W, GB.tx, GB.ty);
+        });
+    }
     if (int e = check_launch("kxk_unfold_pixel")) return e;
     if (!gg) return 0;
     with_bool(vec && aligned_quad<GT>(guid) && aligned_quad<GT>(gg), [&](auto v) {
@@ -1086,21 +1336,21 @@ int norm_backward_finish(const store_t<GT>* guid, const float* blur, const float
     return check_launch("kxk_unsite");
 }
 
-template <int K, class GT = float, int D = 1>
+template <int K, class GT = float, int D = 1, bool PIN = false>
 int norm_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* hist, const float* gout, store_t<GT>* gg, float* gx, int B, int C,
-                  int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+                  int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, const KxkPin& pin = KxkPin{}) {
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     const NormBackwardWs w = norm_backward_ws<K>(ws, g, H, W, n_iter);
-    if (int e = fold<K, GT, D>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT, D, PIN>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st, pin)) return e;
     if (int e = adjoint_steps<K, float, false, D>(w.wp, gout, gx, w.alev, gx ? 0 : 1, g.N, g.Cv, H, W, n_iter, st)) return e;
-    return norm_backward_finish<K, GT, D>(guid, blur, sparse, hist, gout, gg, gx, B, g, w, H, W, n_iter, norm, st);
+    return norm_backward_finish<K, GT, D, PIN>(guid, blur, sparse, hist, gout, gg, gx, B, g, w, H, W, n_iter, norm, st, pin);
 }
 
 // ---- the assembling contract: out = sum_j conf_j H_{s_j} over the levels of the folded contract, s_0 < .. < s_{T-1} = n (host array steps),
 // conf [B][T][H][W].  hist: NULL, or H_1 .. H_n (level t at hist + (t - 1) B C H W: H_n is no longer the output) ----
-template <int K, class GT = float, int D = 1>
+template <int K, class GT = float, int D = 1, bool PIN = false>
 int assemble_forward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* conf, const int* steps, int T, float* out, float* hist,
-                     int B, int C, int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st) {
+                     int B, int C, int sparse_C, int H, int W, int n_iter, int norm, void* ws, hipStream_t st, const KxkPin& pin = KxkPin{}) {
     constexpr int KK = K * K - 1;
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     const size_t HW = (size_t)H * W;
@@ -1108,7 +1358,7 @@ int assemble_forward(const store_t<GT>* guid, const float* blur, const float* sp
     float* bias = wp + kxk_level_floats((size_t)g.N * KK * HW);
     float* ping = bias + kxk_level_floats(g.L);
     float* pong = ping + kxk_level_floats(g.L);
-    if (int e = fold<K, GT, D>(guid, blur, sparse, wp, bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT, D, PIN>(guid, blur, sparse, wp, bias, g, norm, H, W, st, pin)) return e;
     const Grid G = grid_of(g.N, H, W);
     const float* src = blur;
     int j = steps[0] == 0 ? 1 : 0;
@@ -1136,14 +1386,14 @@ int assemble_forward(const store_t<GT>* guid, const float* blur, const float* sp
 }
 
 // gg, gx and gc (dL/dconf [B][T][H][W]) may each be NULL; ws: the folded backward's, then the scaled top level A_n = conf_{T-1} grad_out
-template <int K, class GT = float, int D = 1>
+template <int K, class GT = float, int D = 1, bool PIN = false>
 int assemble_backward(const store_t<GT>* guid, const float* blur, const float* sparse, const float* conf, const int* steps, int T, const float* hist,
                       const float* gout, store_t<GT>* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int n_iter, int norm, void* ws,
-                      hipStream_t st) {
+                      hipStream_t st, const KxkPin& pin = KxkPin{}) {
     const NormGeo g = norm_geo(B, C, sparse_C, H, W);
     const NormBackwardWs w = norm_backward_ws<K>(ws, g, H, W, n_iter);
     const size_t HW = (size_t)H * W, stride = (size_t)T * HW;
-    const bool levels = gg || gx;   // the adjoint sweep runs
+    const bool levels = gg || gx || (PIN && (pin.gs || pin.gp));   // the adjoint sweep runs
     const Grid GB = grid_of(B, H, W);
     for (int j = 0; j < T; ++j) {   // dL/dconf_j, and with the last one the top level
         float* top = levels && j == T - 1 ? w.top : nullptr;
@@ -1157,7 +1407,7 @@ int assemble_backward(const store_t<GT>* guid, const float* blur, const float* s
         if (int e = check_launch("kxk_conf_grad")) return e;
     }
     if (!levels) return 0;
-    if (int e = fold<K, GT, D>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st)) return e;
+    if (int e = fold<K, GT, D, PIN>(guid, blur, sparse, w.wp, w.bias, g, norm, H, W, st, pin)) return e;
     const Grid G = grid_of(g.N, H, W);
     int j = T - 2;   // the next collected level below the one being produced
     for (int t = n_iter - 1; t >= (gx ? 0 : 1); --t) {
@@ -1175,7 +1425,7 @@ int assemble_backward(const store_t<GT>* guid, const float* blur, const float* s
             return e;
         }
     }
-    return norm_backward_finish<K, GT, D>(guid, blur, sparse, hist, w.top, gg, gx, B, g, w, H, W, n_iter, norm, st);
+    return norm_backward_finish<K, GT, D, PIN>(guid, blur, sparse, hist, w.top, gg, gx, B, g, w, H, W, n_iter, norm, st, pin);
 }
 
 }  // namespace

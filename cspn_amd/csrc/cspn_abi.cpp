@@ -1076,7 +1076,7 @@ size_t cspn2d_kxk_norm_history_bytes(int B, int C, int H, int W, int K, int n_it
 // the checks of the four cspn2d_{forward,backward}_kxk_norm_{f32,g16} entry points, then the engine; g16 and dtype as kxk_forward_entry
 static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, float* out,
                                   float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
-                                  size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
+                                  size_t ws_bytes, cspn_stream_t stream, int dilation = 1, const KxkPin* pin = nullptr) {
     if (!guidance || !blur || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (g16)
         if (int e = g16_check(what, dtype, guidance, nullptr)) return e;
@@ -1091,7 +1091,8 @@ static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g
     const size_t wb = need ? ws_bytes : 0;
     if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hb}, {ws, wb}}) ||
         kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}})) {
+        kxk_overlaps(ws, wb, {{guidance, gb}, {blur, vb}, {sparse, sb}}) ||
+        (pin && (kxk_overlaps(out, vb, {{pin->conf, sb}}) || kxk_overlaps(history, hb, {{pin->conf, sb}}) || kxk_overlaps(ws, wb, {{pin->conf, sb}})))) {
         set_error("%s: out, history and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
@@ -1101,6 +1102,7 @@ static int kxk_norm_forward_entry(const char* what, const void* guidance, bool g
         if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
         return 0;
     }
+    if (pin) return kxk_norm_forward_pin(guidance, dtype, blur, sparse, *pin, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws, st);
     if (dilation != 1) return kxk_norm_forward_dil(guidance, dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws, st);
     return kxk_norm_forward(guidance, dtype, blur, sparse, out, history, B, C, sparse_C, H, W, K, n_iter, norm, ws, st);
 }
@@ -1119,20 +1121,24 @@ size_t cspn2d_backward_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int 
 static int kxk_norm_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse,
                                    const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur, int B, int C,
                                    int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream,
-                                   int dilation = 1) {
+                                   int dilation = 1, const KxkPin* pin = nullptr) {
     if (!guidance || !blur || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (g16)
         if (int e = g16_check(what, dtype, guidance, grad_guidance)) return e;
     if (int e = kxk_norm_check(what, sparse, B, C, sparse_C, H, W, K, n_iter, norm)) return e;
     const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C;
     const size_t hb = cspn2d_kxk_norm_history_bytes(B, C, H, W, K, n_iter);
-    if (grad_guidance && hb && (!history || history_bytes < hb)) {
-        set_error("%s: the guidance gradient needs the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+    float* const grad_sparse = pin ? pin->gs : nullptr;
+    float* const grad_pin = pin ? pin->gp : nullptr;
+    const bool gates = grad_guidance || grad_pin;   // dL/dpin needs dL/dw' as the guidance gradient does
+    if (gates && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the guidance gradient%s needs the forward's history: need %zu bytes, got %zu", what, pin ? " and grad_pin" : "", hb,
+                  history ? history_bytes : 0);
         return CSPN_E_BADARG;
     }
     const size_t need = cspn2d_backward_kxk_norm_workspace_bytes(B, C, sparse_C, H, W, K, n_iter);
     if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0, hbu = grad_guidance ? hb : 0;
+    const size_t wb = need ? ws_bytes : 0, hbu = gates ? hb : 0;
     if (grad_guidance && (const void*)grad_guidance == (const void*)grad_blur) { set_error("%s: grad_guidance and grad_blur must not alias", what); return CSPN_E_BADARG; }
     if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_blur, vb}, {ws, wb}}) ||
         kxk_overlaps(grad_blur, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
@@ -1140,14 +1146,29 @@ static int kxk_norm_backward_entry(const char* what, const void* guidance, bool 
         set_error("%s: grad_guidance, grad_blur and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
-    if (!grad_guidance && !grad_blur) return 0;
+    if (pin) {
+        const std::initializer_list<std::pair<const void*, size_t>> inputs = {{guidance, gb}, {blur, vb}, {sparse, sb}, {pin->conf, sb}, {history, hbu}, {grad_out, vb}};
+        if (kxk_overlaps(grad_guidance, gb, {{pin->conf, sb}}) || kxk_overlaps(grad_blur, vb, {{pin->conf, sb}}) || kxk_overlaps(ws, wb, {{pin->conf, sb}}) ||
+            kxk_overlaps(grad_sparse, sb, inputs) || kxk_overlaps(grad_pin, sb, inputs) ||
+            kxk_overlaps(grad_sparse, sb, {{grad_guidance, gb}, {grad_blur, vb}, {grad_pin, sb}, {ws, wb}}) ||
+            kxk_overlaps(grad_pin, sb, {{grad_guidance, gb}, {grad_blur, vb}, {ws, wb}})) {
+            set_error("%s: grad_sparse, grad_pin, the other gradients and the workspace must not alias an input or each other", what);
+            return CSPN_E_BADARG;
+        }
+    }
+    if (!grad_guidance && !grad_blur && !grad_sparse && !grad_pin) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (n_iter == 0) {   // the identity: dL/dblur = dL/dout, no gate is read
         hipError_t e = grad_blur ? hipMemcpyAsync(grad_blur, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_sparse) e = hipMemsetAsync(grad_sparse, 0, sb, st);
+        if (e == hipSuccess && grad_pin) e = hipMemsetAsync(grad_pin, 0, sb, st);
         if (e == hipSuccess && grad_guidance) e = hipMemsetAsync(grad_guidance, 0, gb, st);
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
+    if (pin)
+        return kxk_norm_backward_pin(guidance, dtype, blur, sparse, *pin, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, dilation, n_iter,
+                                     norm, ws, st);
     if (dilation != 1)
         return kxk_norm_backward_dil(guidance, dtype, blur, sparse, history, grad_out, grad_guidance, grad_blur, B, C, sparse_C, H, W, K, dilation, n_iter, norm,
                                      ws, st);
@@ -1232,7 +1253,8 @@ static int kxk_assemble_check(const char* what, std::initializer_list<std::pair<
 
 static int kxk_assemble_forward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
                                       const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W,
-                                      int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
+                                      int K, int n_iter, int norm, void* ws, size_t ws_bytes, cspn_stream_t stream, int dilation = 1,
+                                      const KxkPin* pin = nullptr) {
     if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"out", out}}, sparse, steps, T, B, C,
                                    sparse_C, H, W, K, n_iter, norm))
         return e;
@@ -1245,10 +1267,14 @@ static int kxk_assemble_forward_entry(const char* what, const void* guidance, bo
     if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
     if (kxk_overlaps(out, vb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}, {history, hb}, {ws, ws_bytes}}) ||
         kxk_overlaps(history, hb, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}, {ws, ws_bytes}}) ||
-        kxk_overlaps(ws, ws_bytes, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}})) {
+        kxk_overlaps(ws, ws_bytes, {{guidance, gb}, {blur, vb}, {sparse, sb}, {conf, cb}}) ||
+        (pin && (kxk_overlaps(out, vb, {{pin->conf, sb}}) || kxk_overlaps(history, hb, {{pin->conf, sb}}) || kxk_overlaps(ws, ws_bytes, {{pin->conf, sb}})))) {
         set_error("%s: out, history and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
+    if (pin)
+        return kxk_assemble_forward_pin(guidance, dtype, blur, sparse, *pin, conf, steps, T, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws,
+                                        (hipStream_t)stream);
     if (dilation != 1)
         return kxk_assemble_forward_dil(guidance, dtype, blur, sparse, conf, steps, T, out, history, B, C, sparse_C, H, W, K, dilation, n_iter, norm, ws,
                                         (hipStream_t)stream);
@@ -1258,7 +1284,7 @@ static int kxk_assemble_forward_entry(const char* what, const void* guidance, bo
 static int kxk_assemble_backward_entry(const char* what, const void* guidance, bool g16, int dtype, const float* blur, const float* sparse, const float* conf,
                                        const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance,
                                        float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K, int n_iter, int norm, void* ws,
-                                       size_t ws_bytes, cspn_stream_t stream, int dilation = 1) {
+                                       size_t ws_bytes, cspn_stream_t stream, int dilation = 1, const KxkPin* pin = nullptr) {
     if (int e = kxk_assemble_check(what, {{"guidance", guidance}, {"blur", blur}, {"conf", conf}, {"steps", steps}, {"grad_out", grad_out}}, sparse, steps, T, B,
                                    C, sparse_C, H, W, K, n_iter, norm))
         return e;
@@ -1266,7 +1292,9 @@ static int kxk_assemble_backward_entry(const char* what, const void* guidance, b
         if (int e = g16_check(what, dtype, guidance, grad_guidance)) return e;
     const size_t vb = kxk_values_bytes(B, C, H, W), gb = vb / C * (K * K - 1) / (g16 ? 2 : 1), sb = vb / C * sparse_C, cb = vb / C * T;
     const size_t hb = cspn2d_kxk_assemble_history_bytes(B, C, H, W, K, n_iter);
-    const bool reads_history = (grad_guidance && n_iter >= 2) || grad_conf;   // H_1 .. H_{n-1} for the gates, H_{s_j} for the confidences
+    float* const grad_sparse = pin ? pin->gs : nullptr;
+    float* const grad_pin = pin ? pin->gp : nullptr;
+    const bool reads_history = ((grad_guidance || grad_pin) && n_iter >= 2) || grad_conf;   // H_1 .. H_{n-1} for the gates (dL/dpin too), H_{s_j} for the confidences
     if (reads_history && (!history || history_bytes < hb)) {
         set_error("%s: grad_guidance and grad_conf need the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
         return CSPN_E_BADARG;
@@ -1286,7 +1314,20 @@ static int kxk_assemble_backward_entry(const char* what, const void* guidance, b
         set_error("%s: grad_guidance, grad_blur, grad_conf and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
-    if (!grad_guidance && !grad_blur && !grad_conf) return 0;
+    if (pin) {
+        const std::initializer_list<std::pair<const void*, size_t>> all = {{guidance, gb}, {blur, vb}, {sparse, sb}, {pin->conf, sb}, {conf, cb}, {history, hbu},
+                                                                           {grad_out, vb}, {grad_guidance, gb}, {grad_blur, vb}, {grad_conf, cb}, {ws, ws_bytes}};
+        if (kxk_overlaps(grad_guidance, gb, {{pin->conf, sb}}) || kxk_overlaps(grad_blur, vb, {{pin->conf, sb}}) || kxk_overlaps(grad_conf, cb, {{pin->conf, sb}}) ||
+            kxk_overlaps(ws, ws_bytes, {{pin->conf, sb}}) || kxk_overlaps(grad_sparse, sb, all) || kxk_overlaps(grad_pin, sb, all) ||
+            kxk_overlaps(grad_sparse, sb, {{grad_pin, sb}})) {
+            set_error("%s: grad_sparse, grad_pin, the other gradients and the workspace must not alias an input or each other", what);
+            return CSPN_E_BADARG;
+        }
+    }
+    if (!grad_guidance && !grad_blur && !grad_conf && !grad_sparse && !grad_pin) return 0;
+    if (pin)
+        return kxk_assemble_backward_pin(guidance, dtype, blur, sparse, *pin, conf, steps, T, history, grad_out, grad_guidance, grad_blur, grad_conf, B, C,
+                                         sparse_C, H, W, K, dilation, n_iter, norm, ws, (hipStream_t)stream);
     if (dilation != 1)
         return kxk_assemble_backward_dil(guidance, dtype, blur, sparse, conf, steps, T, history, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H,
                                          W, K, dilation, n_iter, norm, ws, (hipStream_t)stream);
@@ -1364,6 +1405,63 @@ int cspn2d_backward_kxk_assemble_dil(const void* guidance, int gate_dtype, const
     return kxk_assemble_backward_entry("cspn2d_backward_kxk_assemble_dil", guidance, gate_dtype != 0, gate_dtype, blur, sparse, conf, steps, T, history,
                                        history_bytes, grad_out, grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes,
                                        stream, dilation);
+}
+
+// ---- the pinned forms (cspn2d_*_kxk_{norm,assemble}_pin): the _dil entry points with pin_conf behind sparse and, in the backwards, grad_sparse and
+// grad_pin behind the other gradients.  The pin is checked first (sparse and pin_conf given, sparse_C != 0), then every check of the _dil counterpart ----
+static int kxk_pin_check(const char* what, const float* sparse, const float* pin_conf, int sparse_C) {
+    if (sparse && pin_conf && sparse_C != 0) return 0;
+    set_error("%s: the pin needs sparse and pin_conf (both non-NULL) with sparse_C 1 or C, got sparse %s, pin_conf %s, sparse_C %d", what,
+              sparse ? "given" : "NULL", pin_conf ? "given" : "NULL", sparse_C);
+    return CSPN_E_BADARG;
+}
+
+int cspn2d_forward_kxk_norm_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf, float* out,
+                                float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm,
+                                void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_forward_kxk_norm_pin";
+    if (int e = kxk_pin_check(what, sparse, pin_conf, sparse_C)) return e;
+    if (int e = kxk_dilation_check(what, dilation)) return e;
+    const KxkPin pin{pin_conf, nullptr, nullptr};
+    return kxk_norm_forward_entry(what, guidance, gate_dtype != 0, gate_dtype, blur, sparse, out, history, history_bytes, B, C, sparse_C, H, W, K, n_iter, norm,
+                                  ws, ws_bytes, stream, dilation, &pin);
+}
+
+int cspn2d_backward_kxk_norm_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                 const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur,
+                                 float* grad_sparse, float* grad_pin, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm,
+                                 void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_backward_kxk_norm_pin";
+    if (int e = kxk_pin_check(what, sparse, pin_conf, sparse_C)) return e;
+    if (int e = kxk_dilation_check(what, dilation)) return e;
+    const KxkPin pin{pin_conf, grad_sparse, grad_pin};
+    return kxk_norm_backward_entry(what, guidance, gate_dtype != 0, gate_dtype, blur, sparse, history, history_bytes, grad_out, grad_guidance, grad_blur, B, C,
+                                   sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation, &pin);
+}
+
+int cspn2d_forward_kxk_assemble_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                    const float* conf, const int* steps, int T, float* out, float* history, size_t history_bytes, int B, int C,
+                                    int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm, void* ws, size_t ws_bytes,
+                                    cspn_stream_t stream) {
+    const char* what = "cspn2d_forward_kxk_assemble_pin";
+    if (int e = kxk_pin_check(what, sparse, pin_conf, sparse_C)) return e;
+    if (int e = kxk_dilation_check(what, dilation)) return e;
+    const KxkPin pin{pin_conf, nullptr, nullptr};
+    return kxk_assemble_forward_entry(what, guidance, gate_dtype != 0, gate_dtype, blur, sparse, conf, steps, T, out, history, history_bytes, B, C, sparse_C,
+                                      H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation, &pin);
+}
+
+int cspn2d_backward_kxk_assemble_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                     const float* conf, const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out,
+                                     void* grad_guidance, float* grad_blur, float* grad_conf, float* grad_sparse, float* grad_pin, int B, int C,
+                                     int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm, void* ws, size_t ws_bytes,
+                                     cspn_stream_t stream) {
+    const char* what = "cspn2d_backward_kxk_assemble_pin";
+    if (int e = kxk_pin_check(what, sparse, pin_conf, sparse_C)) return e;
+    if (int e = kxk_dilation_check(what, dilation)) return e;
+    const KxkPin pin{pin_conf, grad_sparse, grad_pin};
+    return kxk_assemble_backward_entry(what, guidance, gate_dtype != 0, gate_dtype, blur, sparse, conf, steps, T, history, history_bytes, grad_out,
+                                       grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation, &pin);
 }
 
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----

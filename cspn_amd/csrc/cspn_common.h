@@ -147,6 +147,23 @@ int kxk_assemble_forward_dil(const void* guid, int dtype, const float* blur, con
 int kxk_assemble_backward_dil(const void* guid, int dtype, const float* blur, const float* sparse, const float* conf, const int* steps, int T,
                               const float* hist, const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int D,
                               int n_iter, int norm, void* ws, hipStream_t st);
+// the same four pinned to the measured depth with a per-pixel confidence (cspn2d_kxk_pin.hip), at D = 1 or a dilated instance: after every
+// step H = u step(H) + m sparse, m = sign(sparse) conf, u = 1 - m (folded: w' = u wb, b = (u c) blur + m sparse).  conf has the planes of
+// sparse (sparse_C 1 or C, never 0); gs = dL/dsparse and gp = dL/dpin (the same planes) may each be NULL; gp needs hist as gg does
+struct KxkPin {
+    const float* conf = nullptr;
+    float* gs = nullptr;
+    float* gp = nullptr;
+};
+int kxk_norm_forward_pin(const void* guid, int dtype, const float* blur, const float* sparse, const KxkPin& pin, float* out, float* hist, int B, int C,
+                         int sparse_C, int H, int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_norm_backward_pin(const void* guid, int dtype, const float* blur, const float* sparse, const KxkPin& pin, const float* hist, const float* gout, void* gg,
+                          float* gx, int B, int C, int sparse_C, int H, int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_assemble_forward_pin(const void* guid, int dtype, const float* blur, const float* sparse, const KxkPin& pin, const float* conf, const int* steps, int T,
+                             float* out, float* hist, int B, int C, int sparse_C, int H, int W, int K, int D, int n_iter, int norm, void* ws, hipStream_t st);
+int kxk_assemble_backward_pin(const void* guid, int dtype, const float* blur, const float* sparse, const KxkPin& pin, const float* conf, const int* steps, int T,
+                              const float* hist, const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int D,
+                              int n_iter, int norm, void* ws, hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

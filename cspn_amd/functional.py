@@ -913,6 +913,149 @@ def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps
     return gg, gh, gc
 
 
+# ---- the two contracts above pinned to the measured depth with a per-pixel confidence (CSPN++ / PENet; cspn2d_*_kxk_{norm,assemble}_pin): after
+# every step H = (1 - m) step(H) + m sparse_depth with m = sign(sparse_depth) * pin_conf.  Functions of their own: the four above keep their
+# parameter lists ----
+def _pin_check(blur_depth, sparse_depth, pin_conf):
+    """sparse_depth and pin_conf: both given, the same shape, [B,1,H,W] or [B,C,H,W] (sparse_depth's shape itself is checked by _kxk_norm_shape)"""
+    if sparse_depth is None or pin_conf is None:
+        raise ValueError("the pinned contract needs a sparse_depth and a pin_conf (a pin_conf without a sparse_depth pins nothing)")
+    if not isinstance(pin_conf, torch.Tensor) or not isinstance(sparse_depth, torch.Tensor) or tuple(pin_conf.shape) != tuple(sparse_depth.shape):
+        raise ValueError("pin_conf must be a tensor of sparse_depth's shape %s ([B,1,H,W] or [B,C,H,W]), got %s"
+                         % (tuple(getattr(sparse_depth, "shape", ())), tuple(getattr(pin_conf, "shape", ()))))
+    if isinstance(blur_depth, torch.Tensor) and pin_conf.device != blur_depth.device:
+        raise ValueError("all tensors must live on the same device")
+
+
+def _pin_entry(stem, dt, dilation):
+    """the pinned entry point of a folded / assembling call: one for every guidance dtype (gate_dtype 0: float32) and every dilation"""
+    check_dilation(dilation)
+    return stem + "_pin", (0 if dt is None else dt,), (dilation,)
+
+
+def cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth=None, pin_conf=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False,
+                                dilation=1):
+    """cspn2d_forward_kxk_norm pinned to the measured depth with a per-pixel confidence: after every step
+        H <- (1 - m) * step(H) + m * sparse_depth,      m = sign(sparse_depth) * pin_conf,      H_0 = blur_depth,
+    one engine call (cspn2d_forward_kxk_norm_pin).  sparse_depth enters by its value as well as its sign; pin_conf has sparse_depth's shape
+    ([B,1,H,W]: one mask for the C channels, or [B,C,H,W]) and is used as given (no sigmoid, no clamp).  With pin_conf = 1, sparse_depth >= 0
+    and blur_depth = sparse_depth where it is measured the result is bitwise cspn2d_forward_kxk_norm's; with pin_conf = 0 bitwise that of the
+    call without a mask.  Everything else (guidance dtypes, return_history, n_iter == 0 returns blur_depth itself, dilation) as there; a 16-bit
+    sparse_depth or pin_conf is widened with one cast."""
+    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    _pin_check(blur_depth, sparse_depth, pin_conf)
+    check_dilation(dilation)
+    n = int(n_iter)
+    if n == 0:
+        return (blur_depth, None) if return_history else blur_depth
+    g, dt, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
+    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
+    out = torch.empty_like(h)
+    hist = None
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    hb = 0
+    if return_history:
+        with torch.cuda.device(g.device):
+            hb = _lib.symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    name, dta, dil = _pin_entry("cspn2d_forward_kxk_norm", dt, dilation)
+    _launch(name, g.device, (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_kxk_norm_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
+                                 need_guidance=True, need_blur=True, need_sparse=True, need_pin=True, dilation=1):
+    """Gradient of cspn2d_forward_kxk_norm_pin -> (dL/dguidance in the guidance's dtype, dL/dblur_depth, dL/dsparse_depth, dL/dpin_conf), None
+    where not asked for; one engine call (cspn2d_backward_kxk_norm_pin).  dL/dsparse_depth goes through the value (the sign has no
+    derivative); dL/dpin_conf is exactly 0 where sparse_depth == 0.  Both are float32 with sparse_depth's shape.  history: what
+    cspn2d_forward_kxk_norm_pin(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dpin_conf needs it
+    (n_iter >= 2: both read the gradient of the folded gates)."""
+    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+    _pin_check(blur_depth, sparse_depth, pin_conf)
+    check_dilation(dilation)
+    if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
+        raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
+    g, dt, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
+    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
+    n = int(n_iter)
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    gs = torch.empty_like(s) if need_sparse else None
+    gp = torch.empty_like(p) if need_pin else None
+    if not (need_guidance or need_blur or need_sparse or need_pin):
+        return gg, gh, gs, gp
+    if h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), gh, gs, gp
+    if (need_guidance or need_pin) and n >= 2 and history is None:
+        _, history = cspn2d_forward_kxk_norm_pin(g, h, s, p, K, n, norm_type, return_history=True, dilation=dilation)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    name, dta, dil = _pin_entry("cspn2d_backward_kxk_norm", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gs), _ptr(gp), B, C, sc, H, W, K, *dil, n,
+             _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
+    return gg, gh, gs, gp
+
+
+def cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size=5, n_iter=24, norm_type="8sum",
+                                    return_history=False, dilation=1):
+    """cspn2d_forward_kxk_assemble over the levels of cspn2d_forward_kxk_norm_pin: out = sum_j conf[:, j] * H_{steps[j]}, one engine call
+    (cspn2d_forward_kxk_assemble_pin).  pin_conf as there; everything else as the unpinned call."""
+    check_dilation(dilation)
+    _pin_check(blur_depth, sparse_depth, pin_conf)
+    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
+    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
+    n = int(n_iter)
+    out = torch.empty_like(h)
+    hist = None
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    hb = 0
+    if return_history:
+        with torch.cuda.device(g.device):
+            hb = _lib.symbol("cspn2d_kxk_assemble_history_bytes")(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    name, dta, dil = _pin_entry("cspn2d_forward_kxk_assemble", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n,
+             _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, grad_out, kernel_size=5, n_iter=24, norm_type="8sum",
+                                     history=None, need_guidance=True, need_blur=True, need_conf=True, need_sparse=True, need_pin=True, dilation=1):
+    """Gradient of cspn2d_forward_kxk_assemble_pin -> (dL/dguidance, dL/dblur_depth, dL/dconf, dL/dsparse_depth, dL/dpin_conf), None where not
+    asked for; one engine call (cspn2d_backward_kxk_assemble_pin).  history: what cspn2d_forward_kxk_assemble_pin(..., return_history=True)
+    returned; None runs that forward first where dL/dguidance, dL/dpin_conf (n_iter >= 2) or dL/dconf needs it."""
+    check_dilation(dilation)
+    _pin_check(blur_depth, sparse_depth, pin_conf)
+    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc, go = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type,
+                                                                        ((grad_out, "grad_out"),))
+    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
+    n = int(n_iter)
+    gg = torch.empty_like(g) if need_guidance else None
+    gh = torch.empty_like(h) if need_blur else None
+    gc = torch.empty_like(cf) if need_conf else None
+    gs = torch.empty_like(s) if need_sparse else None
+    gp = torch.empty_like(p) if need_pin else None
+    if not (need_guidance or need_blur or need_conf or need_sparse or need_pin):
+        return gg, gh, gc, gs, gp
+    if h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), gh, gc, gs, gp
+    if history is None and (((need_guidance or need_pin) and n >= 2) or need_conf):
+        _, history = cspn2d_forward_kxk_assemble_pin(g, h, s, p, cf, steps, K, n, norm_type, return_history=True, dilation=dilation)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    name, dta, dil = _pin_entry("cspn2d_backward_kxk_assemble", dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc), _ptr(gs), _ptr(gp),
+             B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
+            ("cspn2d_backward_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, n))
+    return gg, gh, gc, gs, gp
+
+
 def assemble_conf(iter_conf, kernel_conf, k, T, like):
     """the confidences one kernel size of Affinity_PropagateAssemble hands to the engine: iter_conf [B,T,H,W] (None: ones) times
     kernel_conf[:, k:k+1] (None: no such factor), one differentiable torch op; like: blur_depth (batch, image size, device)"""

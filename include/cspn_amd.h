@@ -54,7 +54,8 @@ extern "C" {
                               *    gate normalisation inside the K x K engine (cspn2d_*_kxk_absnorm_*), the 8-plane heads on a 16-bit feature map with float32 guidance
                               *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16), fp16 / bf16 gates and guides on the 3D entry points of the
                               *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16), the backward of the 3D normalising / masked modes
-                              *    (cspn3d_backward_norm_f32), dilated K x K propagation (cspn2d_*_kxk_{norm,assemble}_dil) */
+                              *    (cspn3d_backward_norm_f32), dilated K x K propagation (cspn2d_*_kxk_{norm,assemble}_dil),
+                              *    K x K propagation pinned to the measured depth with a confidence (cspn2d_*_kxk_{norm,assemble}_pin) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -540,6 +541,47 @@ int cspn2d_backward_kxk_assemble_dil(const void* guidance, int gate_dtype, const
                                      const int* steps, int T, const float* history, size_t history_bytes, const float* grad_out,
                                      void* grad_guidance, float* grad_blur, float* grad_conf, int B, int C, int sparse_C, int H, int W, int K,
                                      int dilation, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- K x K propagation pinned to the measured depth with a per-pixel confidence (CSPN++ / PENet: after every step the value at a
+ * measured pixel is replaced by the measurement, weighted by a learned confidence): the _kxk_norm_ / _kxk_assemble_ contracts above,
+ * dilation included, with the blend after every step
+ *     sigma = sign(sparse),   m = sigma * pin_conf,   u = 1 - m
+ *     H_{t+1}(p) = u (sum_k wb_k H_t(p + off_k) + cc blur) + m sparse,      H_0 = blur,   cc = 1 - sum_k wb_k
+ *   folded as w'_k = u wb_k and b = (u cc) blur + m sparse, evaluated in exactly this form.  sparse enters by its value as well as its
+ *   sign; pin_conf is float32 with the planes of sparse ([B,sparse_C,H,W], sparse_C 1 or C) and is used as given: no sigmoid, no clamp.
+ *   With pin_conf = 1, sparse >= 0 and blur = sparse where sparse > 0 the results are bitwise those of the unpinned entry points; with
+ *   pin_conf = 0 bitwise those of the call without a mask.  The assembled sum over collected levels is unchanged on top of these levels.
+ * Gradients, with dw'_k and db_c the gradients of the folded w' and b (i over the images of one guidance image, c over the channels
+ *   that share a mask plane):
+ *     dwb_k      = sum_i u_i (dw'_{i,k} - sum_c blur_{i,c} db_{i,c})      -> grad_guidance as in the unpinned contract
+ *     grad_blur  = A_0 + (u cc) db_c
+ *     grad_sparse = m sum_c db_c                                          (through the value; the sign has no derivative)
+ *     grad_pin   = sigma (sum_c db_c (sparse - cc blur_c) - sum_k wb_k dw'_k)   (exactly 0 where sparse == 0)
+ *   grad_sparse and grad_pin have the planes of sparse and may each be NULL, as may grad_guidance, grad_blur and grad_conf.  grad_pin
+ *   needs dw', hence with n_iter >= 2 the forward's history, like grad_guidance.
+ * Each entry has the arguments of its _dil counterpart with pin_conf behind sparse (and grad_sparse, grad_pin behind the other
+ *   gradients); gate_dtype 0 is float32 guidance, CSPN_DTYPE_F16 / CSPN_DTYPE_BF16 under the rule of the 16-bit block above (float32
+ *   results bitwise those on the widened guidance, grad_guidance rounded once).  Workspaces and histories are those of the unpinned
+ *   contract: the six cspn2d_*kxk_{norm,assemble}_*_bytes queries apply with the call's sparse_C.  Deterministic: sums in channel order,
+ *   every element written once, no atomics.
+ * Errors: a NULL sparse or pin_conf, or sparse_C == 0: CSPN_E_BADARG ("pin" in cspn_last_error()), checked first; then every check of
+ *   the _dil counterpart, all before anything touches the GPU. */
+int cspn2d_forward_kxk_norm_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                float* out, float* history, size_t history_bytes, int B, int C, int sparse_C, int H, int W, int K,
+                                int dilation, int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_norm_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                 const float* history, size_t history_bytes, const float* grad_out, void* grad_guidance, float* grad_blur,
+                                 float* grad_sparse, float* grad_pin, int B, int C, int sparse_C, int H, int W, int K, int dilation,
+                                 int n_iter, int norm, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_forward_kxk_assemble_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                    const float* conf, const int* steps, int T, float* out, float* history, size_t history_bytes, int B,
+                                    int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm, void* workspace,
+                                    size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_kxk_assemble_pin(const void* guidance, int gate_dtype, const float* blur, const float* sparse, const float* pin_conf,
+                                     const float* conf, const int* steps, int T, const float* history, size_t history_bytes,
+                                     const float* grad_out, void* grad_guidance, float* grad_blur, float* grad_conf, float* grad_sparse,
+                                     float* grad_pin, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm,
+                                     void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
