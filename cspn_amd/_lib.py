@@ -135,6 +135,14 @@ _SYMBOLS.update({
     "cspn2d_backward_kxk_norm_pin": (c_int, [vp, c_int] + [vp] * 4 + [c_size_t] + [vp] * 5 + [c_int] * 9 + _WS),
     "cspn2d_forward_kxk_assemble_pin": (c_int, [vp, c_int] + [vp] * 5 + [c_int] + [vp] * 2 + [c_size_t] + [c_int] * 9 + _WS),
     "cspn2d_backward_kxk_assemble_pin": (c_int, [vp, c_int] + [vp] * 5 + [c_int, vp, c_size_t] + [vp] * 6 + [c_int] * 9 + _WS),
+    # non-local propagation with learned offsets (K = 3): aff, offset, x, sparse (or NULL) in front; the sampling operator on its own
+    "cspn2d_nl_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_nl_history_bytes": (c_size_t, [c_int] * 6),
+    "cspn2d_forward_nl_f32": (c_int, [vp] * 6 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_nl_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_backward_nl_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_nl_sample_f32": (c_int, [vp] * 3 + [c_int] * 4 + [vp]),
+    "cspn2d_nl_sample_backward_f32": (c_int, [vp] * 5 + [c_int] * 4 + [vp]),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

@@ -1464,6 +1464,119 @@ int cspn2d_backward_kxk_assemble_pin(const void* guidance, int gate_dtype, const
                                        grad_guidance, grad_blur, grad_conf, B, C, sparse_C, H, W, K, n_iter, norm, ws, ws_bytes, stream, dilation, &pin);
 }
 
+// ---- non-local propagation with learned offsets (cspn2d_nl.hip): K = 3 only; the error rules of the cspn2d_*_kxk_f32 entry points ----
+static bool nl_shape_ok(int B, int C, int H, int W, int K, int n_iter) {
+    return B > 0 && C > 0 && H > 0 && W > 0 && K == 3 && n_iter >= 0 && (long long)B * C * H * W <= 0x7fffffffLL &&
+           (long long)B * 2 * (K * K - 1) * H * W <= 0x7fffffffLL;
+}
+
+static int nl_check_shape(const char* what, int B, int C, int H, int W, int K, int n_iter) {
+    if (K != 3) { set_error("%s: K must be 3 (5 and 7 are not built), got %d", what, K); return CSPN_E_UNSUPPORTED; }
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (n_iter < 0) { set_error("%s: n_iter must be >= 0 (got %d)", what, n_iter); return CSPN_E_BADARG; }
+    if (!nl_shape_ok(B, C, H, W, K, n_iter)) { set_error("%s: tensor too large for 32-bit element indexing", what); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
+static size_t nl_level_bytes(int B, int C, int H, int W) { return sizeof(float) * kxk_level_floats((size_t)B * C * H * W); }
+
+size_t cspn2d_nl_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse) {
+    if (!nl_shape_ok(B, C, H, W, K, n_iter)) return 0;
+    return nl_level_bytes(B, C, H, W) * (size_t)nl_forward_levels(n_iter, has_sparse != 0);
+}
+
+size_t cspn2d_nl_history_bytes(int B, int C, int H, int W, int K, int n_iter) {
+    if (!nl_shape_ok(B, C, H, W, K, n_iter) || n_iter < 2) return 0;
+    return kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1);
+}
+
+size_t cspn2d_backward_nl_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse) {
+    if (!nl_shape_ok(B, C, H, W, K, n_iter)) return 0;
+    return nl_level_bytes(B, C, H, W) * (size_t)nl_backward_levels(n_iter, has_sparse != 0);
+}
+
+int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, float* out, float* history,
+                          size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_forward_nl_f32";
+    if (!aff || !offset || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), ab = vb / C * (K * K - 1), ob = 2 * ab, sb = sparse ? vb / C : 0;
+    const size_t hb = cspn2d_nl_history_bytes(B, C, H, W, K, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    // with a history the levels go there: the workspace keeps the pinned H_0 alone (the n_iter = 1 count)
+    const size_t need = cspn2d_nl_workspace_bytes(B, C, H, W, K, history && n_iter > 1 ? 1 : n_iter, sparse != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hb}, {ws, wb}}) ||
+        kxk_overlaps(history, hb, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) return identity_copy(out, x, vb / sizeof(float), st);
+    return nl_forward(aff, offset, x, sparse, out, history, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
+                           const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                           void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_backward_nl_f32";
+    if (!aff || !offset || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), ab = vb / C * (K * K - 1), ob = 2 * ab, sb = sparse ? vb / C : 0;
+    const size_t hb = cspn2d_nl_history_bytes(B, C, H, W, K, n_iter);
+    const bool gates = grad_aff || grad_offset;
+    if (gates && hb && (!history || history_bytes < hb)) {
+        set_error("%s: grad_aff and grad_offset need the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_nl_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = gates ? hb : 0;
+    if (kxk_overlaps(grad_aff, ab, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_offset, ob}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_offset, ob, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_x, vb, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_aff, grad_offset, grad_x and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!gates && !grad_x) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) {   // the identity: dL/dx = dL/dout, neither aff nor offset is read
+        hipError_t e = grad_x ? hipMemcpyAsync(grad_x, grad_out, vb, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && grad_aff) e = hipMemsetAsync(grad_aff, 0, ab, st);
+        if (e == hipSuccess && grad_offset) e = hipMemsetAsync(grad_offset, 0, ob, st);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+        return 0;
+    }
+    return nl_backward(aff, offset, x, sparse, history, grad_out, grad_aff, grad_offset, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_nl_sample_f32(const float* offset, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream) {
+    const char* what = "cspn2d_nl_sample_f32";
+    if (!offset || !f || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
+    if (kxk_overlaps(out, kb, {{offset, 2 * kb}, {f, fb}})) { set_error("%s: out must not alias an input", what); return CSPN_E_BADARG; }
+    return nl_sample(offset, f, out, B, H, W, K, (hipStream_t)stream);
+}
+
+int cspn2d_nl_sample_backward_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B, int H, int W,
+                                  int K, cspn_stream_t stream) {
+    const char* what = "cspn2d_nl_sample_backward_f32";
+    if (!offset || !f || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
+    if (kxk_overlaps(grad_f, fb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {grad_offset, 2 * kb}}) ||
+        kxk_overlaps(grad_offset, 2 * kb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}})) {
+        set_error("%s: grad_f and grad_offset must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_f && !grad_offset) return 0;
+    return nl_sample_backward(offset, f, grad_out, grad_f, grad_offset, B, H, W, K, (hipStream_t)stream);
+}
+
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----
 static int head_kxk_check(const char* what, int B, int C, int h, int w, int H, int W, int K) {
     if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }

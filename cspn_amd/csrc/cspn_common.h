@@ -165,6 +165,25 @@ int kxk_assemble_backward_pin(const void* guid, int dtype, const float* blur, co
                               const float* hist, const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int D,
                               int n_iter, int norm, void* ws, hipStream_t st);
 
+// ---- non-local propagation with learned offsets, K = 3 (cspn2d_nl.hip): aff [B][KK][H][W] used as given, off [B][2 KK][H][W] (dy_k, dx_k
+// interleaved), values [B][C][H][W] on shared aff / off, sparse NULL or [B][H][W] (pinned where > 0).  Neighbour k's base is (t - R, l - R):
+// the deformable convolution's sign, the opposite of the K x K engine's ----
+// levels of kxk_level_floats(B C H W) floats in the forward's workspace: the pinned H_0 (with sparse) and the ping-pong pair; with a history
+// the levels go there and only the pinned H_0 is left (the n_iter = 1 count)
+inline int nl_forward_levels(int n_iter, bool sparse) { return n_iter <= 0 ? 0 : (sparse ? (n_iter >= 2 ? 2 : 1) : (n_iter >= 3 ? 2 : n_iter - 1)); }
+// the backward's: the adjoint levels 1 .. n-1 as the scatter leaves them, then (with sparse) the pinned H_0 of the gate gradient
+inline int nl_backward_levels(int n_iter, bool sparse) { return n_iter <= 0 ? 0 : n_iter - 1 + (sparse ? 1 : 0); }
+// hist: NULL, or the pinned levels 1 .. n-1, level t at hist + (t - 1) B C H W
+int nl_forward(const float* aff, const float* off, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W, int K,
+               int n_iter, void* ws, hipStream_t st);
+// gaff, goff and gx may each be NULL; gaff / goff need hist where n_iter >= 2.  NOT run-to-run bitwise: the adjoint scatters with float atomics
+int nl_backward(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
+                float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+// the sampling operator out_k(p) = bil(f, p + base_k + d_k(p)), f [B][H][W] -> out [B][KK][H][W], and its backward (gf by the scatter, goff
+// written once; either may be NULL)
+int nl_sample(const float* off, const float* f, float* out, int B, int H, int W, int K, hipStream_t st);
+int nl_sample_backward(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, hipStream_t st);
+
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels
 // gdt: the storage type of g and gg; 16-bit: where the fused sweeps can run, the workspace also holds the float32 copy of the gates the

@@ -1056,6 +1056,133 @@ def cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_con
     return gg, gh, gc, gs, gp
 
 
+# ---- non-local propagation with learned offsets (NLSPN's refinement step; cspn2d_nl.hip): every pixel reads its K*K - 1 neighbours by bilinear
+# interpolation at p + base_k + offset_k(p).  Neighbour k is the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre and its base is
+# (t - K//2, l - K//2): the deformable convolution's sign, THE OPPOSITE of the K x K engine's (K//2 - t, K//2 - l) above.  float32 only ----
+def _nl_kernel_size(kernel_size):
+    K = _check_kernel_size(kernel_size, 4)
+    if K != 3:
+        raise ValueError("non-local propagation is built for kernel_size 3 only (5 and 7 are not), got %d" % K)
+    return K
+
+
+def _nl_tensor(t, name, shape=None, channels=None):
+    """float32 and nothing else (16-bit affinities and offsets are not built), checked before the device; [B, channels, H, W] or exactly `shape`"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32 (got %s): the non-local entry points take no other dtype" % (name, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    if shape is None and (t.dim() != 4 or (channels is not None and t.shape[1] != channels)):
+        raise ValueError("%s must be [B,%s,H,W], got %s" % (name, "C" if channels is None else channels, tuple(t.shape)))
+
+
+def _nl_offset(offset, K):
+    _nl_tensor(offset, "offset", channels=2 * (K * K - 1))
+    return offset.shape[0], offset.shape[2], offset.shape[3]
+
+
+def _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, extra=()):
+    """-> K, B, C, H, W, n and the tensors on the GPU, contiguous: aff, offset, x, sparse_depth (or None), *extra (each of x's shape)"""
+    K = _nl_kernel_size(kernel_size)
+    B, H, W = _nl_offset(offset, K)
+    _nl_tensor(aff, "aff", (B, K * K - 1, H, W))
+    _nl_tensor(x, "x", channels=None)
+    if x.shape[0] != B or tuple(x.shape[2:]) != (H, W) or x.shape[1] < 1:
+        raise ValueError("x has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(x.shape), B, H, W))
+    C = x.shape[1]
+    if sparse_depth is not None:
+        _nl_tensor(sparse_depth, "sparse_depth", (B, 1, H, W))
+    for t, name in extra:
+        _nl_tensor(t, name, (B, C, H, W))
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError("n_iter must be an int >= 0 (got %r)" % (n_iter,))
+    return K, B, C, H, W, int(n_iter)
+
+
+def _nl_prep(*named):
+    ts = [None if t is None else _prep(t, name) for t, name in named]
+    if any(t is not None and t.device != ts[0].device for t in ts):
+        raise ValueError("all tensors must live on the same device")
+    return ts
+
+
+def cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size=3, return_history=False):
+    """Non-local propagation, affinities as given (cspn2d_forward_nl_f32): aff [B,8,H,W] any sign, normalised by the caller; offset [B,16,H,W],
+    channel 2k is dy_k and 2k+1 is dx_k; x [B,C,H,W], the C channels share aff and offset; sparse_depth [B,1,H,W] or None, pinned where > 0:
+        Ht = sparse_depth where sparse_depth > 0 else H       (before every step)
+        H <- (1 - sum_k aff_k) * Ht + sum_k aff_k * bil(Ht, p + base_k + offset_k(p)),      H_0 = x, n_iter times; the result is not pinned
+    base_k = (t - 1, l - 1) for the k-th (t, l) of the 3 x 3 raster without the centre: the deformable convolution's sign, the opposite of the
+    K x K functions'.  bil takes its fractions from the offset (offset - floor(offset)), a corner outside the image contributes 0, every finite
+    offset is valid.  return_history: (out, history) for cspn2d_backward_nl.  n_iter == 0 returns x.  float32 only: any other dtype is a
+    TypeError.  Bitwise reproducible."""
+    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter)
+    if n == 0:
+        return (x, None) if return_history else x
+    a, o, h, s = _nl_prep((aff, "aff"), (offset, "offset"), (x, "x"), (sparse_depth, "sparse_depth"))
+    out = torch.empty_like(h)
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    hist, hb = None, 0
+    if return_history:   # the levels go to the history; the workspace keeps the pinned H_0 alone
+        with torch.cuda.device(a.device):
+            hb = _lib.symbol("cspn2d_nl_history_bytes")(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=a.device)
+    _launch("cspn2d_forward_nl_f32", a.device, (_ptr(a), _ptr(o), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
+            ("cspn2d_nl_workspace_bytes", B, C, H, W, K, 1 if return_history else n, int(s is not None)))
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
+    """Gradient of cspn2d_forward_nl -> (dL/daff [B,8,H,W] and dL/doffset [B,16,H,W], each summed over the C channels, dL/dx [B,C,H,W]), None where
+    not asked for; cspn2d_backward_nl_f32.  sparse_depth has no gradient; floor has none either, so dL/doffset is the derivative of the bilinear
+    fractions.  history: what cspn2d_forward_nl(..., return_history=True) returned; None runs that forward first where dL/daff or dL/doffset needs it
+    (n_iter >= 2).  NOT run-to-run bitwise: the adjoint scatters with float atomics, whose sums depend on arrival order in their last bits."""
+    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, ((grad_out, "grad_out"),))
+    a, o, h, s, go = _nl_prep((aff, "aff"), (offset, "offset"), (x, "x"), (sparse_depth, "sparse_depth"), (grad_out, "grad_out"))
+    ga = torch.empty_like(a) if need_aff else None
+    gd = torch.empty_like(o) if need_offset else None
+    gx = torch.empty_like(h) if need_x else None
+    if not (need_aff or need_offset or need_x) or h.numel() == 0:
+        return ga, gd, gx
+    if (need_aff or need_offset) and n >= 2 and history is None:
+        _, history = cspn2d_forward_nl(a, o, h, s, n, K, return_history=True)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    _launch("cspn2d_backward_nl_f32", a.device,
+            (_ptr(a), _ptr(o), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
+            ("cspn2d_backward_nl_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
+    return ga, gd, gx
+
+
+def cspn2d_nl_sample(offset, f, kernel_size=3):
+    """The sampling operator of cspn2d_forward_nl on its own: out[:, k](p) = bil(f, p + base_k + offset_k(p)), f [B,1,H,W] -> [B,8,H,W]
+    (cspn2d_nl_sample_f32).  Bitwise reproducible."""
+    K = _nl_kernel_size(kernel_size)
+    B, H, W = _nl_offset(offset, K)
+    _nl_tensor(f, "f", (B, 1, H, W))
+    o, v = _nl_prep((offset, "offset"), (f, "f"))
+    out = torch.empty((B, K * K - 1, H, W), dtype=torch.float32, device=o.device)
+    if out.numel():
+        _launch("cspn2d_nl_sample_f32", o.device, (_ptr(o), _ptr(v), _ptr(out), B, H, W, K))
+    return out
+
+
+def cspn2d_nl_sample_backward(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
+    """Gradient of cspn2d_nl_sample -> (dL/df [B,1,H,W], dL/doffset [B,16,H,W]), None where not asked for (cspn2d_nl_sample_backward_f32).  dL/df is
+    scattered with float atomics: not run-to-run bitwise; dL/doffset is written once."""
+    K = _nl_kernel_size(kernel_size)
+    B, H, W = _nl_offset(offset, K)
+    _nl_tensor(f, "f", (B, 1, H, W))
+    _nl_tensor(grad_out, "grad_out", (B, K * K - 1, H, W))
+    o, v, go = _nl_prep((offset, "offset"), (f, "f"), (grad_out, "grad_out"))
+    gf = torch.empty_like(v) if need_f else None
+    gd = torch.empty_like(o) if need_offset else None
+    if (need_f or need_offset) and v.numel():
+        _launch("cspn2d_nl_sample_backward_f32", o.device, (_ptr(o), _ptr(v), _ptr(go), _ptr(gf), _ptr(gd), B, H, W, K))
+    return gf, gd
+
+
 def assemble_conf(iter_conf, kernel_conf, k, T, like):
     """the confidences one kernel size of Affinity_PropagateAssemble hands to the engine: iter_conf [B,T,H,W] (None: ones) times
     kernel_conf[:, k:k+1] (None: no such factor), one differentiable torch op; like: blur_depth (batch, image size, device)"""

@@ -1,0 +1,141 @@
+"""Non-local spatial propagation (the refinement module of NLSPN and of the models built on it) on the engine's non-local kernels.
+
+Every pixel learns real-valued offsets for its K*K - 1 neighbours; a step reads them by bilinear interpolation at p + base_k + offset_k(p) -- a
+modulated deformable convolution with an all-ones weight, iterated on the same offsets and affinities.  The engine runs the iteration
+(cspn_amd.functional.cspn2d_forward_nl / cspn2d_backward_nl) and the sampling of a confidence map at the same sites (cspn2d_nl_sample); the affinity
+normalisation is a handful of torch ops, run once per call through autograd.
+
+Neighbour k is the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre and its base is (t - K//2, l - K//2): the deformable
+convolution's sign, the OPPOSITE of Affinity_PropagateKxK's (K//2 - t, K//2 - l).
+
+The backward is NOT run-to-run bitwise: the adjoint of the gather is a scatter with float atomics, whose sums depend on arrival order in their
+last bits.  The forward is bitwise reproducible.
+
+This module allocates nothing itself: every buffer comes from cspn_amd.functional."""
+import torch
+import torch.nn as nn
+
+from . import functional as F
+
+AFFINITIES = ('AS', 'ASS', 'TC', 'TGASS')
+
+
+class _NonLocalFunction(torch.autograd.Function):
+    """one cspn2d_forward_nl call that keeps the levels where dL/daff or dL/doffset will need them, one cspn2d_backward_nl call"""
+
+    @staticmethod
+    def forward(ctx, aff, offset, x, sparse_depth, n_iter, kernel_size):
+        ctx.n_iter, ctx.kernel_size = n_iter, kernel_size
+        hist = None
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and n_iter >= 2:
+            out, hist = F.cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size, return_history=True)
+        else:
+            out = F.cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size)
+        ctx.save_for_backward(aff, offset, x, sparse_depth, hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        aff, offset, x, sparse_depth, hist = ctx.saved_tensors
+        ga, gd, gx = F.cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out.contiguous(), ctx.n_iter, ctx.kernel_size, hist,
+                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return ga, gd, gx, None, None, None
+
+
+class _NLSampleFunction(torch.autograd.Function):
+    """cspn2d_nl_sample and its backward: f [B,1,H,W] read at the K*K - 1 sites of every pixel"""
+
+    @staticmethod
+    def forward(ctx, offset, f, kernel_size):
+        ctx.kernel_size = kernel_size
+        ctx.save_for_backward(offset, f)
+        return F.cspn2d_nl_sample(offset, f, kernel_size)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        offset, f = ctx.saved_tensors
+        gf, gd = F.cspn2d_nl_sample_backward(offset, f, grad_out.contiguous(), ctx.kernel_size, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gd, gf, None
+
+
+def nl_sample(offset, f, kernel_size=3):
+    """differentiable cspn2d_nl_sample: out[:, k](p) = bil(f, p + base_k + offset_k(p)), gradients to f and offset"""
+    if torch.is_grad_enabled() and (offset.requires_grad or f.requires_grad):
+        return _NLSampleFunction.apply(offset, f, kernel_size)
+    return F.cspn2d_nl_sample(offset, f, kernel_size)
+
+
+def nl_propagate(aff, offset, x, sparse_depth, n_iter, kernel_size=3):
+    """differentiable cspn2d_forward_nl on affinities as given, gradients to aff, offset and x (sparse_depth has none)"""
+    if torch.is_grad_enabled() and (aff.requires_grad or offset.requires_grad or x.requires_grad):
+        return _NonLocalFunction.apply(aff, offset, x, sparse_depth, n_iter, kernel_size)
+    return F.cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size)
+
+
+class NonLocal_Propagate(nn.Module):
+    """forward(affinity [B,8,H,W] raw, offset [B,16,H,W], feat [B,C,H,W], confidence=None [B,1,H,W], sparse_depth=None [B,1,H,W], n_iter=None)
+    -> [B,C,H,W] after prop_time (or n_iter) non-local steps.  Per call, in torch and through autograd, with KK = prop_kernel**2 - 1:
+        1. squash     'TC': a = tanh(g) / KK;  'TGASS': a = tanh(g) / (scale + 1e-8);  'AS', 'ASS': a = g
+        2. confidence (where given)  a_k <- a_k * bil(confidence, p + base_k + offset_k(p))      (cspn2d_nl_sample)
+        3. abs-sum    with S = sum_k |a_k|:  'AS': a / (S + 1e-4);  'ASS' and 'TGASS': a / max(S + 1e-4, 1);  'TC': a
+    then the engine's iteration on these affinities: H <- (1 - sum_k a_k) Ht + sum_k a_k bil(Ht, p + base_k + offset_k(p)), where Ht is H with
+    sparse_depth put back where sparse_depth > 0 (preserve_input and a sparse_depth given; otherwise no mask).  offset channel 2k is dy_k, 2k + 1
+    is dx_k; base_k = (t - 1, l - 1) in raster order without the centre: the deformable convolution's sign.
+    scale is a parameter the module owns ('TGASS' only, initialised to affinity_gamma * KK): the module's only state.
+    THESE FOUR RULES ARE THE CONTRACT; they were written down from the published module's description, not from its source: compare them with
+    your model's before you port it.
+    Gradients flow to affinity, offset, feat, confidence and scale; the backward is not run-to-run bitwise (float atomics in the adjoint)."""
+
+    def __init__(self, prop_time, prop_kernel=3, affinity='TGASS', affinity_gamma=0.5, preserve_input=True):
+        super(NonLocal_Propagate, self).__init__()
+        if prop_kernel != 3:
+            raise ValueError("non-local propagation is built for prop_kernel 3 only (5 and 7 are not), got %r" % (prop_kernel,))
+        if affinity not in AFFINITIES:
+            raise ValueError("affinity must be one of %s, got %r" % (AFFINITIES, affinity))
+        if isinstance(prop_time, bool) or int(prop_time) != prop_time or prop_time < 0:
+            raise ValueError("prop_time must be an int >= 0, got %r" % (prop_time,))
+        self.prop_time = int(prop_time)
+        self.prop_kernel = prop_kernel
+        self.affinity = affinity
+        self.affinity_gamma = float(affinity_gamma)
+        self.preserve_input = bool(preserve_input)
+        self.num_neighbors = prop_kernel * prop_kernel - 1
+        if affinity == 'TGASS':
+            self.scale = nn.Parameter(self.affinity_gamma * self.num_neighbors * torch.ones(1))
+
+    def normalize(self, affinity, offset=None, confidence=None):
+        """steps 1 - 3 above -> the affinities the engine uses as given"""
+        a = affinity
+        if self.affinity == 'TC':
+            a = torch.tanh(a) / self.num_neighbors
+        elif self.affinity == 'TGASS':
+            a = torch.tanh(a) / (self.scale + 1e-8)
+        if confidence is not None:
+            a = a * nl_sample(offset, confidence, self.prop_kernel)
+        if self.affinity == 'TC':
+            return a
+        S = a.abs().sum(1, keepdim=True) + 1e-4
+        if self.affinity != 'AS':
+            S = S.clamp(min=1.0)
+        return a / S
+
+    def forward(self, affinity, offset, feat, confidence=None, sparse_depth=None, n_iter=None):
+        n = self.prop_time if n_iter is None else int(n_iter)
+        if n < 0:
+            raise ValueError("n_iter must be >= 0 (got %r)" % (n_iter,))
+        KK = self.num_neighbors
+        for t, name, ch in ((affinity, "affinity", KK), (offset, "offset", 2 * KK)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != ch:
+                raise ValueError("%s must be [B,%d,H,W], got %s" % (name, ch, tuple(getattr(t, "shape", ()))))
+        if confidence is not None and (not isinstance(confidence, torch.Tensor) or confidence.dim() != 4
+                                       or tuple(confidence.shape) != (affinity.shape[0], 1) + tuple(affinity.shape[2:])):
+            raise ValueError("confidence must be [B,1,H,W] = %s, got %s" % ((affinity.shape[0], 1) + tuple(affinity.shape[2:]),
+                                                                           tuple(getattr(confidence, "shape", ()))))
+        if n == 0:
+            return feat
+        aff = self.normalize(affinity, offset, confidence)
+        return nl_propagate(aff, offset, feat, sparse_depth if self.preserve_input else None, n, self.prop_kernel)
+
+    def extra_repr(self):
+        return "prop_time=%d, prop_kernel=%d, affinity=%r, affinity_gamma=%g, preserve_input=%r" % (
+            self.prop_time, self.prop_kernel, self.affinity, self.affinity_gamma, self.preserve_input)

@@ -583,6 +583,61 @@ int cspn2d_backward_kxk_assemble_pin(const void* guidance, int gate_dtype, const
                                      float* grad_pin, int B, int C, int sparse_C, int H, int W, int K, int dilation, int n_iter, int norm,
                                      void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
+/* ---- non-local propagation with learned offsets (the refinement step of NLSPN and of the models built on it): every pixel reads its
+ * K K - 1 neighbours by bilinear interpolation at p + base_k + d_k(p), a modulated deformable convolution with an all-ones weight,
+ * iterated on the same offsets and affinities.  K = 3 (KK = 8) only: any other K is CSPN_E_UNSUPPORTED ("K" in cspn_last_error()).
+ * Tensors, all float32, contiguous NCHW:
+ *     aff    [B,KK,H,W]     used as given, any sign: the caller has normalised them
+ *     offset [B,2 KK,H,W]   channel 2k is dy_k, channel 2k + 1 is dx_k (the deformable convolution's layout without the centre pair)
+ *     x, out [B,C,H,W]      the C channels share aff and offset
+ *     sparse [B,1,H,W] or NULL   measured depth, pinned where > 0
+ * Neighbour k is the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre; its base is base_k = (t - R, l - R), R = K / 2.
+ *   THIS IS THE DEFORMABLE CONVOLUTION'S SIGN, THE OPPOSITE OF THE K x K ENTRY POINTS' off_k = (R - t, R - l) above.
+ *     m = [sparse > 0] (0 without sparse)      c(p) = 1 - sum_k aff_k(p)      H_0 = x
+ *     Ht_t = (1 - m) H_t + m sparse                                            (before every step)
+ *     H_{t+1}(p) = c(p) Ht_t(p) + sum_k aff_k(p) bil(Ht_t, p + base_k + d_k(p))      out = H_n (not pinned)
+ *     bil(F, p + base + d):  fy = dy - floor(dy), fx = dx - floor(dx)  (the fraction of the OFFSET: exact in float32),
+ *                            (y0, x0) = p + base + (floor dy, floor dx) in integer arithmetic,
+ *                            (1-fy)(1-fx) F[y0,x0] + (1-fy) fx F[y0,x0+1] + fy (1-fx) F[y0+1,x0] + fy fx F[y0+1,x0+1],
+ *                            a corner outside the image contributes 0
+ *   Every finite offset is valid (+-1e9 included: floor d is clamped before it is converted, everything out there is outside the image).
+ *   A NaN or infinite offset gives an unspecified value but never an access outside the tensors.  n_iter = 0 copies x.
+ * Gradients, A_n = grad_out, for t = n-1 .. 0:
+ *     At_t(q) = c(q) A_{t+1}(q) + sum_{p,k} aff_k(p) w_{p,k->q} A_{t+1}(p)     (the transpose of the gather: a scatter)
+ *     A_t = (1 - m) At_t,   grad_x = A_0,   sparse gets no gradient
+ *     grad_aff_k(p) = sum_t sum_c A_{t+1}(p) (bil_k(Ht_t)(p) - Ht_t(p))
+ *     grad_dy_k(p)  = sum_t sum_c A_{t+1}(p) aff_k(p) [(1-fx)(F[y0+1,x0] - F[y0,x0]) + fx (F[y0+1,x0+1] - F[y0,x0+1])], F = Ht_t, outside 0;
+ *     grad_dx_k likewise in x: floor has zero derivative and d fy / d dy = 1.
+ *   grad_aff, grad_offset and grad_x may each be NULL.  grad_aff and grad_offset need, for n_iter >= 2, the history of a forward with the
+ *   same arguments.
+ * THE BACKWARD IS NOT RUN-TO-RUN BITWISE, the first such path of this library: the scatter adds with float atomics (one hardware
+ *   float add each, no compare-and-swap loop) in arrival order, so At_t and through it every gradient can differ in its last bits between
+ *   two identical calls.  The forward and cspn2d_nl_sample_f32 are bitwise reproducible; cspn2d_nl_sample_backward_f32's grad_f is not.
+ * history: H_1 .. H_{n-1} as the steps store them (pinned), cspn2d_nl_history_bytes() bytes.  Workspaces, 256-byte aligned:
+ *   cspn2d_nl_workspace_bytes(.., n_iter, has_sparse) for a forward without a history; with one, the levels go to the history and the
+ *   forward needs cspn2d_nl_workspace_bytes(.., 1, has_sparse) (the pinned H_0).  cspn2d_backward_nl_workspace_bytes(): At_1 .. At_{n-1}
+ *   and, with sparse, the pinned H_0.
+ * cspn2d_nl_sample_f32: the sampling operator on its own, out_k(p) = bil(f, p + base_k + d_k(p)), f [B,1,H,W] -> out [B,KK,H,W]
+ *   (confidence-modulated affinities need it); its backward gives grad_f [B,1,H,W] by the scatter and grad_offset [B,2 KK,H,W] written
+ *   once, each may be NULL.
+ * Errors, as cspn2d_forward_kxk_f32 / cspn2d_backward_kxk_f32: a null input, a size <= 0, n_iter < 0, or an output, history or
+ *   workspace overlapping an input or another output: CSPN_E_BADARG; K != 3, or B C H W or B 2KK H W above 2^31 - 1 elements:
+ *   CSPN_E_UNSUPPORTED; a workspace or history too small, or a workspace not 256-byte aligned: CSPN_E_WORKSPACE.  The byte queries return
+ *   0 where nothing is needed or the shape is invalid.  Any 4-byte aligned pointers and any H, W >= 1; 16-byte loads of aff, offset and the
+ *   levels where W % 4 == 0 and the pointers are 16-byte aligned. */
+size_t cspn2d_nl_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse);
+size_t cspn2d_nl_history_bytes(int B, int C, int H, int W, int K, int n_iter);
+int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, float* out, float* history,
+                          size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* workspace, size_t workspace_bytes,
+                          cspn_stream_t stream);
+size_t cspn2d_backward_nl_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse);
+int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history,
+                           size_t history_bytes, const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C,
+                           int H, int W, int K, int n_iter, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_nl_sample_f32(const float* offset, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream);
+int cspn2d_nl_sample_backward_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B,
+                                  int H, int W, int K, cspn_stream_t stream);
+
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
  * S(p) = sum_k a_k(p), summed in channel order in float32:
