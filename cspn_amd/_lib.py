@@ -143,6 +143,11 @@ _SYMBOLS.update({
     "cspn2d_backward_nl_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
     "cspn2d_nl_sample_f32": (c_int, [vp] * 3 + [c_int] * 4 + [vp]),
     "cspn2d_nl_sample_backward_f32": (c_int, [vp] * 5 + [c_int] * 4 + [vp]),
+    # their run-to-run bitwise twins (cspn2d_nl_det.hip): the same arguments; the sampling backward takes a workspace here
+    "cspn2d_backward_nl_det_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_backward_nl_det_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_nl_sample_backward_det_workspace_bytes": (c_size_t, [c_int] * 4),
+    "cspn2d_nl_sample_backward_det_f32": (c_int, [vp] * 5 + [c_int] * 4 + _WS),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

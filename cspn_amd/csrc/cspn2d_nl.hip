@@ -21,56 +21,17 @@
 // order), nl_gate_grad (one pixel per lane, the 8 + 16
 // sums in registers over t, then c; every element written once), nl_sample / nl_sample_backward (the sampling operator on the same helpers).
 // THE ADJOINT IS NOT RUN-TO-RUN BITWISE: the float atomics add in arrival order, so At_t, and through it every gradient, can differ in its
-// last bits between two calls.  The forward (and nl_sample) is bitwise reproducible.
-#include "cspn_common.h"
+// last bits between two calls.  The forward (and nl_sample) is bitwise reproducible.  cspn2d_nl_det.hip holds a second backward that is: the same
+// levels through a gathering adjoint, then this unit's nl_gate_grad (nl_gate_gradients).
+#include "cspn2d_nl_taps.h"
 
 namespace cspn {
 
 namespace {
 
-constexpr int NT = 256;
+using namespace nl;   // NT, the bases, Tap / tap_of, Pixel / pixel_of, Grid / pixel_grid: cspn2d_nl_taps.h
+
 constexpr int QX = 16, TW = 4 * QX, TH = NT / QX;   // forward: a 64 x 16 pixel tile, four pixels of a row per thread
-constexpr int PW = 64, PH = NT / PW;                // per-pixel kernels: a 64 x 4 pixel tile, a wave is 64 adjacent pixels of a row
-constexpr float FLOOR_LIM = 536870912.f;            // 2^29: p + base + floor(d) stays an int, and is outside every image (H W <= 2^27)
-
-template <int K>
-__host__ __device__ constexpr int base_y(int k) { return (k + (k >= (K / 2) * (K + 1) ? 1 : 0)) / K - K / 2; }
-template <int K>
-__host__ __device__ constexpr int base_x(int k) { return (k + (k >= (K / 2) * (K + 1) ? 1 : 0)) % K - K / 2; }
-
-// the sample p + base + d of one pixel and neighbour: i00 the in-plane index of corner (y0, x0) with both coordinates clamped into the
-// image, sx / sy the steps to the corners at x0 + 1 / y0 + 1 after their clamp (0 or 1, 0 or W): all four addresses are inside the plane.
-// ok: bit i set where corner i (00, 01, 10, 11) is inside the image; w: the corner weights, zero where it is not
-struct Tap {
-    int i00, sx, sy;
-    int cy0, cx0;   // corner (y0, x0), clamped: i00 = cy0 W + cx0
-    unsigned ok;
-    float fy, fx;
-    float w[4];
-};
-
-__device__ __forceinline__ Tap tap_of(float dy, float dx, int y, int x, int by, int bx, int H, int W) {
-    Tap t;
-    const float gy = floorf(dy), gx = floorf(dx);
-    t.fy = dy - gy;
-    t.fx = dx - gx;
-    const int y0 = y + by + (int)fminf(fmaxf(gy, -FLOOR_LIM), FLOOR_LIM), x0 = x + bx + (int)fminf(fmaxf(gx, -FLOOR_LIM), FLOOR_LIM);
-    const int y1 = y0 + 1, x1 = x0 + 1;
-    const bool oy0 = !(y0 >= 0 && y0 < H), oy1 = !(y1 >= 0 && y1 < H), ox0 = !(x0 >= 0 && x0 < W), ox1 = !(x1 >= 0 && x1 < W);
-    const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1), cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-    t.i00 = cy0 * W + cx0;
-    t.cy0 = cy0;
-    t.cx0 = cx0;
-    t.sx = cx1 - cx0;
-    t.sy = (cy1 - cy0) * W;
-    t.ok = ((oy0 || ox0) ? 0u : 1u) | ((oy0 || ox1) ? 0u : 2u) | ((oy1 || ox0) ? 0u : 4u) | ((oy1 || ox1) ? 0u : 8u);
-    const float gy1 = 1.f - t.fy, gx1 = 1.f - t.fx;
-    t.w[0] = (t.ok & 1u) ? gy1 * gx1 : 0.f;
-    t.w[1] = (t.ok & 2u) ? gy1 * t.fx : 0.f;
-    t.w[2] = (t.ok & 4u) ? t.fy * gx1 : 0.f;
-    t.w[3] = (t.ok & 8u) ? t.fy * t.fx : 0.f;
-    return t;
-}
 
 // F[i] through a 32-bit byte offset from the plane's (wave-uniform) base: one address register a load instead of two (i < H W <= 2^27)
 __device__ __forceinline__ float at32(const float* __restrict__ F, int i) {
@@ -125,23 +86,6 @@ __device__ __forceinline__ Quad quad_of(int tiles_x, int tiles_y, int H) {
     q.x0 = tx * TW + 4 * (threadIdx.x % QX);
     q.row_in = q.y < H;
     return q;
-}
-
-struct Pixel {
-    int n, y, x;
-    bool in;
-};
-
-__device__ __forceinline__ Pixel pixel_of(int tiles_x, int tiles_y, int H, int W) {
-    int b = blockIdx.x;
-    Pixel p;
-    const int tx = b % tiles_x;
-    b /= tiles_x;
-    p.y = (b % tiles_y) * PH + threadIdx.x / PW;
-    p.n = b / tiles_y;
-    p.x = tx * PW + threadIdx.x % PW;
-    p.in = p.y < H && p.x < W;
-    return p;
 }
 
 // dst = sparse where sparse > 0, else src (ZERO: else-branch kept, the pinned pixels set to 0: A_0 = (1 - m) At_0), all C channels; in place
@@ -412,23 +356,10 @@ __global__ __launch_bounds__(NT) void nl_sample_backward_kernel(const float* __r
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-struct Grid {
-    int tx, ty;
-    unsigned blocks;
-};
-
 Grid quad_grid(int N, int H, int W) {
     Grid g;
     g.tx = (W + TW - 1) / TW;
     g.ty = (H + TH - 1) / TH;
-    g.blocks = (unsigned)((size_t)N * g.tx * g.ty);
-    return g;
-}
-
-Grid pixel_grid(int N, int H, int W) {
-    Grid g;
-    g.tx = (W + PW - 1) / PW;
-    g.ty = (H + PH - 1) / PH;
     g.blocks = (unsigned)((size_t)N * g.tx * g.ty);
     return g;
 }
@@ -472,12 +403,30 @@ int forward(const float* aff, const float* off, const float* x, const float* spa
     return 0;
 }
 
+// the gate gradients from the adjoint levels at the start of ws (the scatter's, or the gather's of cspn2d_nl_det.hip: nl_gate_grad reads both)
+template <int K>
+int gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
+                   int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
+    if (!gaff && !goff) return 0;
+    const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
+    float* alev = (float*)ws;
+    const Grid g = pixel_grid(B, H, W);
+    const float* h0 = x;
+    if (sparse) {
+        float* p = alev + (size_t)(n_iter - 1) * LS;
+        if (int e = pin_levels<false>(x, sparse, p, B, C, H, W, st)) return e;
+        h0 = p;
+    }
+    hipLaunchKernelGGL((nl_gate_grad<K>), dim3(g.blocks), dim3(NT), 0, st, aff, off, h0, hist, alev, gout, sparse, gaff, goff, n_iter, L, LS, C, H, W, g.tx,
+                       g.ty);
+    return check_launch("nl_gate_grad");
+}
+
 template <int K>
 int backward(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
              float* gx, int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
     const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
     float* alev = (float*)ws;   // At_1 .. At_{n-1}
-    const Grid g = pixel_grid(B, H, W);
     Grid ga;   // the adjoint step's 64 x 16 tiles
     ga.tx = (W + AW - 1) / AW;
     ga.ty = (H + AH - 1) / AH;
@@ -493,16 +442,7 @@ int backward(const float* aff, const float* off, const float* x, const float* sp
     }
     if (gx && sparse)
         if (int e = pin_levels<true>(gx, sparse, gx, B, C, H, W, st)) return e;
-    if (!gaff && !goff) return 0;
-    const float* h0 = x;
-    if (sparse) {
-        float* p = alev + (size_t)(n_iter - 1) * LS;
-        if (int e = pin_levels<false>(x, sparse, p, B, C, H, W, st)) return e;
-        h0 = p;
-    }
-    hipLaunchKernelGGL((nl_gate_grad<K>), dim3(g.blocks), dim3(NT), 0, st, aff, off, h0, hist, alev, gout, sparse, gaff, goff, n_iter, L, LS, C, H, W, g.tx,
-                       g.ty);
-    return check_launch("nl_gate_grad");
+    return gate_gradients<K>(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, n_iter, ws, st);
 }
 
 }  // namespace
@@ -517,6 +457,12 @@ int nl_backward(const float* aff, const float* off, const float* x, const float*
                 float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
     (void)K;
     return backward<3>(aff, off, x, sparse, hist, gout, gaff, goff, gx, B, C, H, W, n_iter, ws, st);
+}
+
+int nl_gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
+                      float* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+    (void)K;
+    return gate_gradients<3>(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, n_iter, ws, st);
 }
 
 int nl_sample(const float* off, const float* f, float* out, int B, int H, int W, int K, hipStream_t st) {

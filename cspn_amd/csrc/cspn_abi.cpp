@@ -1518,10 +1518,23 @@ int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x,
     return nl_forward(aff, offset, x, sparse, out, history, B, C, H, W, K, n_iter, ws, st);
 }
 
-int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
-                           const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
-                           void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    const char* what = "cspn2d_backward_nl_f32";
+// the index of the deterministic backwards behind the levels (cspn_common.h: NlDetIndex); has_c: the propagation's (with the plane c)
+static size_t nl_det_index_bytes(int B, int H, int W, bool has_c) { return NlDetIndex((size_t)B * H * W, has_c).bytes; }
+
+size_t cspn2d_backward_nl_det_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse) {
+    if (!nl_shape_ok(B, C, H, W, K, n_iter) || n_iter == 0) return 0;   // n_iter 0: the identity, no adjoint step and no index
+    return cspn2d_backward_nl_workspace_bytes(B, C, H, W, K, n_iter, has_sparse) + nl_det_index_bytes(B, H, W, true);
+}
+
+size_t cspn2d_nl_sample_backward_det_workspace_bytes(int B, int H, int W, int K) {
+    if (!nl_shape_ok(B, 1, H, W, K, 0)) return 0;
+    return nl_det_index_bytes(B, H, W, false);
+}
+
+// cspn2d_backward_nl_f32 and its deterministic twin: one set of checks, det picks the workspace and the adjoint
+static int nl_backward_entry(const char* what, bool det, const float* aff, const float* offset, const float* x, const float* sparse, const float* history,
+                             size_t history_bytes, const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W,
+                             int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (!aff || !offset || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (int e = nl_check_shape(what, B, C, H, W, K, n_iter)) return e;
     const size_t vb = kxk_values_bytes(B, C, H, W), ab = vb / C * (K * K - 1), ob = 2 * ab, sb = sparse ? vb / C : 0;
@@ -1531,7 +1544,8 @@ int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x
         set_error("%s: grad_aff and grad_offset need the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
         return CSPN_E_BADARG;
     }
-    const size_t need = cspn2d_backward_nl_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr);
+    const size_t need = det ? cspn2d_backward_nl_det_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr)
+                            : cspn2d_backward_nl_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr);
     if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
     const size_t wb = need ? ws_bytes : 0, hbu = gates ? hb : 0;
     if (kxk_overlaps(grad_aff, ab, {{aff, ab}, {offset, ob}, {x, vb}, {sparse, sb}, {history, hbu}, {grad_out, vb}, {grad_offset, ob}, {grad_x, vb}, {ws, wb}}) ||
@@ -1550,7 +1564,21 @@ int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return nl_backward(aff, offset, x, sparse, history, grad_out, grad_aff, grad_offset, grad_x, B, C, H, W, K, n_iter, ws, st);
+    return (det ? nl_backward_det : nl_backward)(aff, offset, x, sparse, history, grad_out, grad_aff, grad_offset, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
+                           const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                           void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_backward_entry("cspn2d_backward_nl_f32", false, aff, offset, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x, B, C,
+                             H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_nl_det_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
+                               const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                               void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_backward_entry("cspn2d_backward_nl_det_f32", true, aff, offset, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x, B,
+                             C, H, W, K, n_iter, ws, ws_bytes, stream);
 }
 
 int cspn2d_nl_sample_f32(const float* offset, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream) {
@@ -1575,6 +1603,25 @@ int cspn2d_nl_sample_backward_f32(const float* offset, const float* f, const flo
     }
     if (!grad_f && !grad_offset) return 0;
     return nl_sample_backward(offset, f, grad_out, grad_f, grad_offset, B, H, W, K, (hipStream_t)stream);
+}
+
+int cspn2d_nl_sample_backward_det_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B, int H, int W,
+                                      int K, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_nl_sample_backward_det_f32";
+    if (!offset || !f || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
+    const size_t need = cspn2d_nl_sample_backward_det_workspace_bytes(B, H, W, K);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(grad_f, fb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {grad_offset, 2 * kb}, {ws, wb}}) ||
+        kxk_overlaps(grad_offset, 2 * kb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}})) {
+        set_error("%s: grad_f, grad_offset and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_f && !grad_offset) return 0;
+    return nl_sample_backward_det(offset, f, grad_out, grad_f, grad_offset, B, H, W, K, ws, (hipStream_t)stream);
 }
 
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----

@@ -183,6 +183,41 @@ int nl_backward(const float* aff, const float* off, const float* x, const float*
 // written once; either may be NULL)
 int nl_sample(const float* off, const float* f, float* out, int B, int H, int W, int K, hipStream_t st);
 int nl_sample_backward(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, hipStream_t st);
+// the tail of nl_backward: gaff / goff (each may be NULL) from the levels A_1 .. A_{n-1} at the start of ws, (1 - m) already applied or not;
+// with sparse, the pinned H_0 goes to the level behind them
+int nl_gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
+                      float* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+// ---- the same two backwards, run-to-run bitwise (cspn2d_nl_det.hip): the adjoint gathers through an inverted index of the operator and sums
+// in an order-independent way; no float atomics ----
+constexpr unsigned NL_DET_LONG = 128;        // lists longer than this are summed by a whole wave
+constexpr size_t NL_DET_SCAN_TILE = 2048;    // counts a workgroup of the scan's first pass
+// the index over P = B H W destinations, in bytes from its start (every part 256-byte aligned): the worklist counter, the starts (P + 1
+// uint32), the fill cursors (P uint32) -- these three zeroed by each call --, the plane c (P floats; the propagation's index only), the
+// worklist (work_cap uint32: at most 32 P / 129 lists are longer than NL_DET_LONG), the scan's partial sums (one uint32 a tile), the
+// entries (8 bytes each, at most 32 P)
+struct NlDetIndex {
+    size_t counter, start, cursor, zeroed, cplane, work, sums, entries, bytes, cap;
+    unsigned work_cap, tiles;
+    NlDetIndex(size_t P, bool has_c) {
+        work_cap = (unsigned)(P / 4 + 1);
+        tiles = (unsigned)((P + NL_DET_SCAN_TILE - 1) / NL_DET_SCAN_TILE);
+        cap = 32 * P;
+        counter = 0;
+        start = 256;
+        cursor = start + round256(4 * (P + 1));
+        zeroed = cplane = cursor + round256(4 * P);
+        work = cplane + (has_c ? round256(4 * P) : 0);
+        sums = work + round256(4 * (size_t)work_cap);
+        entries = sums + round256(4 * (size_t)tiles);
+        bytes = entries + 8 * cap;
+    }
+};
+// ws: nl_backward's levels, then the index (with the plane c)
+int nl_backward_det(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
+                    float* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+// ws: the index (without the plane c)
+int nl_sample_backward_det(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, void* ws,
+                           hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----
 // C > 1: feat / gout / gf are [B][C][V] on shared gates; gg [B][26][V] is the sum over the channels

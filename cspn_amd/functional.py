@@ -1134,11 +1134,8 @@ def cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size=3, retur
     return (out, hist) if return_history else out
 
 
-def cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
-    """Gradient of cspn2d_forward_nl -> (dL/daff [B,8,H,W] and dL/doffset [B,16,H,W], each summed over the C channels, dL/dx [B,C,H,W]), None where
-    not asked for; cspn2d_backward_nl_f32.  sparse_depth has no gradient; floor has none either, so dL/doffset is the derivative of the bilinear
-    fractions.  history: what cspn2d_forward_nl(..., return_history=True) returned; None runs that forward first where dL/daff or dL/doffset needs it
-    (n_iter >= 2).  NOT run-to-run bitwise: the adjoint scatters with float atomics, whose sums depend on arrival order in their last bits."""
+def _nl_backward(stem, aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x):
+    """cspn2d_backward_nl and its deterministic twin: stem + "_f32" is the entry point, stem + "_workspace_bytes" its size query"""
     K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, ((grad_out, "grad_out"),))
     a, o, h, s, go = _nl_prep((aff, "aff"), (offset, "offset"), (x, "x"), (sparse_depth, "sparse_depth"), (grad_out, "grad_out"))
     ga = torch.empty_like(a) if need_aff else None
@@ -1149,10 +1146,27 @@ def cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_si
     if (need_aff or need_offset) and n >= 2 and history is None:
         _, history = cspn2d_forward_nl(a, o, h, s, n, K, return_history=True)
     hb = history.numel() * history.element_size() if history is not None else 0
-    _launch("cspn2d_backward_nl_f32", a.device,
+    _launch(stem + "_f32", a.device,
             (_ptr(a), _ptr(o), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
-            ("cspn2d_backward_nl_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
+            (stem + "_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
     return ga, gd, gx
+
+
+def cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
+    """Gradient of cspn2d_forward_nl -> (dL/daff [B,8,H,W] and dL/doffset [B,16,H,W], each summed over the C channels, dL/dx [B,C,H,W]), None where
+    not asked for; cspn2d_backward_nl_f32.  sparse_depth has no gradient; floor has none either, so dL/doffset is the derivative of the bilinear
+    fractions.  history: what cspn2d_forward_nl(..., return_history=True) returned; None runs that forward first where dL/daff or dL/doffset needs it
+    (n_iter >= 2).  NOT run-to-run bitwise: the adjoint scatters with float atomics, whose sums depend on arrival order in their last bits
+    (cspn2d_backward_nl_det is)."""
+    return _nl_backward("cspn2d_backward_nl", aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x)
+
+
+def cspn2d_backward_nl_det(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
+    """cspn2d_backward_nl as a deterministic function of its inputs (cspn2d_backward_nl_det_f32): RUN-TO-RUN BITWISE in all three gradients.  The
+    adjoint gathers through an inverted index of the operator, built once per call, and sums each destination's terms in an order-independent way
+    (quantised to a common exponent, added in int64; include/cspn_amd.h); no float atomics.  The same arguments and return convention; the results
+    agree with cspn2d_backward_nl's within rounding, not bit for bit.  The index costs about 270 bytes a pixel of workspace (B H W pixels)."""
+    return _nl_backward("cspn2d_backward_nl_det", aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x)
 
 
 def cspn2d_nl_sample(offset, f, kernel_size=3):
@@ -1168,9 +1182,7 @@ def cspn2d_nl_sample(offset, f, kernel_size=3):
     return out
 
 
-def cspn2d_nl_sample_backward(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
-    """Gradient of cspn2d_nl_sample -> (dL/df [B,1,H,W], dL/doffset [B,16,H,W]), None where not asked for (cspn2d_nl_sample_backward_f32).  dL/df is
-    scattered with float atomics: not run-to-run bitwise; dL/doffset is written once."""
+def _nl_sample_backward(det, offset, f, grad_out, kernel_size, need_f, need_offset):
     K = _nl_kernel_size(kernel_size)
     B, H, W = _nl_offset(offset, K)
     _nl_tensor(f, "f", (B, 1, H, W))
@@ -1179,8 +1191,25 @@ def cspn2d_nl_sample_backward(offset, f, grad_out, kernel_size=3, need_f=True, n
     gf = torch.empty_like(v) if need_f else None
     gd = torch.empty_like(o) if need_offset else None
     if (need_f or need_offset) and v.numel():
-        _launch("cspn2d_nl_sample_backward_f32", o.device, (_ptr(o), _ptr(v), _ptr(go), _ptr(gf), _ptr(gd), B, H, W, K))
+        args = (_ptr(o), _ptr(v), _ptr(go), _ptr(gf), _ptr(gd), B, H, W, K)
+        if det:
+            _launch("cspn2d_nl_sample_backward_det_f32", o.device, args, ("cspn2d_nl_sample_backward_det_workspace_bytes", B, H, W, K))
+        else:
+            _launch("cspn2d_nl_sample_backward_f32", o.device, args)
     return gf, gd
+
+
+def cspn2d_nl_sample_backward(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
+    """Gradient of cspn2d_nl_sample -> (dL/df [B,1,H,W], dL/doffset [B,16,H,W]), None where not asked for (cspn2d_nl_sample_backward_f32).  dL/df is
+    scattered with float atomics: not run-to-run bitwise (cspn2d_nl_sample_backward_det is); dL/doffset is written once."""
+    return _nl_sample_backward(False, offset, f, grad_out, kernel_size, need_f, need_offset)
+
+
+def cspn2d_nl_sample_backward_det(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
+    """cspn2d_nl_sample_backward as a deterministic function of its inputs (cspn2d_nl_sample_backward_det_f32): RUN-TO-RUN BITWISE.  dL/df is
+    gathered through the inverted index of the sampling operator and summed in an order-independent way, as in cspn2d_backward_nl_det; about 260
+    bytes a pixel of workspace."""
+    return _nl_sample_backward(True, offset, f, grad_out, kernel_size, need_f, need_offset)
 
 
 def assemble_conf(iter_conf, kernel_conf, k, T, like):

@@ -8,8 +8,10 @@ normalisation is a handful of torch ops, run once per call through autograd.
 Neighbour k is the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre and its base is (t - K//2, l - K//2): the deformable
 convolution's sign, the OPPOSITE of Affinity_PropagateKxK's (K//2 - t, K//2 - l).
 
-The backward is NOT run-to-run bitwise: the adjoint of the gather is a scatter with float atomics, whose sums depend on arrival order in their
-last bits.  The forward is bitwise reproducible.
+The default backward is NOT run-to-run bitwise: the adjoint of the gather is a scatter with float atomics, whose sums depend on arrival order in
+their last bits.  The forward is bitwise reproducible.  A second backward is: under torch.use_deterministic_algorithms(True), or where asked for
+(nl_propagate / nl_sample: deterministic=True; the module: its attribute `deterministic`), the gradients come from cspn2d_backward_nl_det and
+cspn2d_nl_sample_backward_det, which gather through an inverted index (about 270 bytes a pixel of workspace) and sum order-independently.
 
 This module allocates nothing itself: every buffer comes from cspn_amd.functional."""
 import torch
@@ -20,12 +22,17 @@ from . import functional as F
 AFFINITIES = ('AS', 'ASS', 'TC', 'TGASS')
 
 
+def _deterministic(forced):
+    """which backward runs: what the caller forced, else torch's flag at the time of the backward"""
+    return torch.are_deterministic_algorithms_enabled() if forced is None else bool(forced)
+
+
 class _NonLocalFunction(torch.autograd.Function):
     """one cspn2d_forward_nl call that keeps the levels where dL/daff or dL/doffset will need them, one cspn2d_backward_nl call"""
 
     @staticmethod
-    def forward(ctx, aff, offset, x, sparse_depth, n_iter, kernel_size):
-        ctx.n_iter, ctx.kernel_size = n_iter, kernel_size
+    def forward(ctx, aff, offset, x, sparse_depth, n_iter, kernel_size, deterministic):
+        ctx.n_iter, ctx.kernel_size, ctx.deterministic = n_iter, kernel_size, deterministic
         hist = None
         if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and n_iter >= 2:
             out, hist = F.cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size, return_history=True)
@@ -37,38 +44,42 @@ class _NonLocalFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         aff, offset, x, sparse_depth, hist = ctx.saved_tensors
-        ga, gd, gx = F.cspn2d_backward_nl(aff, offset, x, sparse_depth, grad_out.contiguous(), ctx.n_iter, ctx.kernel_size, hist,
-                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return ga, gd, gx, None, None, None
+        backward = F.cspn2d_backward_nl_det if _deterministic(ctx.deterministic) else F.cspn2d_backward_nl
+        ga, gd, gx = backward(aff, offset, x, sparse_depth, grad_out.contiguous(), ctx.n_iter, ctx.kernel_size, hist,
+                              ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return ga, gd, gx, None, None, None, None
 
 
 class _NLSampleFunction(torch.autograd.Function):
     """cspn2d_nl_sample and its backward: f [B,1,H,W] read at the K*K - 1 sites of every pixel"""
 
     @staticmethod
-    def forward(ctx, offset, f, kernel_size):
-        ctx.kernel_size = kernel_size
+    def forward(ctx, offset, f, kernel_size, deterministic):
+        ctx.kernel_size, ctx.deterministic = kernel_size, deterministic
         ctx.save_for_backward(offset, f)
         return F.cspn2d_nl_sample(offset, f, kernel_size)
 
     @staticmethod
     def backward(ctx, grad_out):
         offset, f = ctx.saved_tensors
-        gf, gd = F.cspn2d_nl_sample_backward(offset, f, grad_out.contiguous(), ctx.kernel_size, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        return gd, gf, None
+        backward = F.cspn2d_nl_sample_backward_det if _deterministic(ctx.deterministic) else F.cspn2d_nl_sample_backward
+        gf, gd = backward(offset, f, grad_out.contiguous(), ctx.kernel_size, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gd, gf, None, None
 
 
-def nl_sample(offset, f, kernel_size=3):
-    """differentiable cspn2d_nl_sample: out[:, k](p) = bil(f, p + base_k + offset_k(p)), gradients to f and offset"""
+def nl_sample(offset, f, kernel_size=3, deterministic=None):
+    """differentiable cspn2d_nl_sample: out[:, k](p) = bil(f, p + base_k + offset_k(p)), gradients to f and offset.  deterministic: True / False
+    picks the run-to-run bitwise backward or the scatter; None follows torch.are_deterministic_algorithms_enabled() when the backward runs"""
     if torch.is_grad_enabled() and (offset.requires_grad or f.requires_grad):
-        return _NLSampleFunction.apply(offset, f, kernel_size)
+        return _NLSampleFunction.apply(offset, f, kernel_size, deterministic)
     return F.cspn2d_nl_sample(offset, f, kernel_size)
 
 
-def nl_propagate(aff, offset, x, sparse_depth, n_iter, kernel_size=3):
-    """differentiable cspn2d_forward_nl on affinities as given, gradients to aff, offset and x (sparse_depth has none)"""
+def nl_propagate(aff, offset, x, sparse_depth, n_iter, kernel_size=3, deterministic=None):
+    """differentiable cspn2d_forward_nl on affinities as given, gradients to aff, offset and x (sparse_depth has none).  deterministic: as in
+    nl_sample"""
     if torch.is_grad_enabled() and (aff.requires_grad or offset.requires_grad or x.requires_grad):
-        return _NonLocalFunction.apply(aff, offset, x, sparse_depth, n_iter, kernel_size)
+        return _NonLocalFunction.apply(aff, offset, x, sparse_depth, n_iter, kernel_size, deterministic)
     return F.cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size)
 
 
@@ -84,7 +95,11 @@ class NonLocal_Propagate(nn.Module):
     scale is a parameter the module owns ('TGASS' only, initialised to affinity_gamma * KK): the module's only state.
     THESE FOUR RULES ARE THE CONTRACT; they were written down from the published module's description, not from its source: compare them with
     your model's before you port it.
-    Gradients flow to affinity, offset, feat, confidence and scale; the backward is not run-to-run bitwise (float atomics in the adjoint)."""
+    Gradients flow to affinity, offset, feat, confidence and scale; the default backward is not run-to-run bitwise (float atomics in the adjoint).
+    deterministic (a class attribute, None; set it on an instance): True takes the run-to-run bitwise backward for the propagation and the confidence
+    sampling, False the scatter, None follows torch.are_deterministic_algorithms_enabled() when the backward runs."""
+
+    deterministic = None
 
     def __init__(self, prop_time, prop_kernel=3, affinity='TGASS', affinity_gamma=0.5, preserve_input=True):
         super(NonLocal_Propagate, self).__init__()
@@ -111,7 +126,7 @@ class NonLocal_Propagate(nn.Module):
         elif self.affinity == 'TGASS':
             a = torch.tanh(a) / (self.scale + 1e-8)
         if confidence is not None:
-            a = a * nl_sample(offset, confidence, self.prop_kernel)
+            a = a * nl_sample(offset, confidence, self.prop_kernel, self.deterministic)
         if self.affinity == 'TC':
             return a
         S = a.abs().sum(1, keepdim=True) + 1e-4
@@ -134,7 +149,7 @@ class NonLocal_Propagate(nn.Module):
         if n == 0:
             return feat
         aff = self.normalize(affinity, offset, confidence)
-        return nl_propagate(aff, offset, feat, sparse_depth if self.preserve_input else None, n, self.prop_kernel)
+        return nl_propagate(aff, offset, feat, sparse_depth if self.preserve_input else None, n, self.prop_kernel, self.deterministic)
 
     def extra_repr(self):
         return "prop_time=%d, prop_kernel=%d, affinity=%r, affinity_gamma=%g, preserve_input=%r" % (

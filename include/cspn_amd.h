@@ -613,6 +613,7 @@ int cspn2d_backward_kxk_assemble_pin(const void* guidance, int gate_dtype, const
  * THE BACKWARD IS NOT RUN-TO-RUN BITWISE, the first such path of this library: the scatter adds with float atomics (one hardware
  *   float add each, no compare-and-swap loop) in arrival order, so At_t and through it every gradient can differ in its last bits between
  *   two identical calls.  The forward and cspn2d_nl_sample_f32 are bitwise reproducible; cspn2d_nl_sample_backward_f32's grad_f is not.
+ *   cspn2d_backward_nl_det_f32 and cspn2d_nl_sample_backward_det_f32 (below) are run-to-run bitwise in every gradient.
  * history: H_1 .. H_{n-1} as the steps store them (pinned), cspn2d_nl_history_bytes() bytes.  Workspaces, 256-byte aligned:
  *   cspn2d_nl_workspace_bytes(.., n_iter, has_sparse) for a forward without a history; with one, the levels go to the history and the
  *   forward needs cspn2d_nl_workspace_bytes(.., 1, has_sparse) (the pinned H_0).  cspn2d_backward_nl_workspace_bytes(): At_1 .. At_{n-1}
@@ -637,6 +638,42 @@ int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x
 int cspn2d_nl_sample_f32(const float* offset, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream);
 int cspn2d_nl_sample_backward_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B,
                                   int H, int W, int K, cspn_stream_t stream);
+
+/* ---- the same two backwards, RUN-TO-RUN BITWISE (cspn2d_nl_det.hip): a deterministic function of their inputs, with no float atomics.
+ * The contract, arguments, error rules and messages are those of cspn2d_backward_nl_f32 / cspn2d_nl_sample_backward_f32 above; the
+ * sampling backward takes a workspace here (the scatter form takes none), in the argument order of cspn2d_backward_nl_f32, and the
+ * workspace may alias no tensor.  Results agree with the scatter forms within rounding, not bit for bit.
+ * The adjoint of the gather is formed as a gather: per call (it is the same for all n_iter steps) an inverted index of the operator is
+ * built in CSR form over the P = B H W destinations q -- count the taps per destination (integer atomics), an exclusive scan of the P
+ * counts (three plain passes), fill the lists (an integer atomic cursor per destination).  An entry is 8 bytes: the uint32 code
+ * p 32 + k 4 + corner (p the source pixel within the image) and the float32 coefficient fl32(aff_k(p) w_corner(p, k)) (the sampling
+ * operator: w alone); only taps with a non-zero weight enter.  The starts are uint32: at most 32 P <= 2^32 - 2 entries, by the guard
+ * B 2KK H W <= 2^31 - 1.  The order of a list's entries is arbitrary; the sum does not depend on it:
+ *     terms   tau_0 = fl32(c(q) A_{t+1}(q)),  tau_i = fl32(coef_i A_{t+1}(p_i));  m of them
+ *     e = floor(log2 max |tau_i|),  L = ceil(log2 m),  s = 61 - e - L
+ *     q_i = llrint(ldexp((double)tau_i, s))   (exact scaling, round to nearest even, |q_i| <= 2^(62 - L)),  S = sum q_i in int64 (associative)
+ *     At_t(q) = ldexpf((float)S, -s)  (one rounding to nearest);  A_t = (1 - m(q)) At_t(q) is what is stored
+ *   all terms zero: +0; a NaN term, or infinities of both signs: the quiet NaN 0x7fc00000; else an infinite term: that infinity.  The
+ *   result is a function of the multiset of terms alone.  Its error against the exact sum of the tau_i is one float32 rounding plus at
+ *   most m 2^(-s-1) <= 2^(2L - 62) max |tau_i|.  Lists of more than 128 entries are summed by a whole wave (the integer sum makes any
+ *   split reproducible), shorter ones by one lane.  grad_aff / grad_offset come from the kernel of the scatter form (every element
+ *   written once, sums in a fixed order) on these levels; the sampling backward's grad_offset likewise.
+ * Workspaces, 256-byte aligned, closed forms with r(b) = b rounded up to a multiple of 256 and P = B H W:
+ *     index(P, c) = 256 + r(4 (P + 1)) + r(4 P) + c r(4 P) + r(4 (P / 4 + 1)) + r(4 ceil(P / 2048)) + 256 P
+ *                   (the worklist counter, the starts, the fill cursors, the plane c(q), the worklist, the scan's partials, the entries)
+ *     cspn2d_backward_nl_det_workspace_bytes(..)        = cspn2d_backward_nl_workspace_bytes(..) + index(P, 1)      (the levels first;
+ *                                                          0 for n_iter = 0: the identity has no adjoint step)
+ *     cspn2d_nl_sample_backward_det_workspace_bytes(..) = index(P, 0)
+ *   about 270 bytes a pixel beyond the scatter form's.  Both are pure host arithmetic and return 0 for every argument set for which the
+ *   queries above return 0.  Everything the index reads before it writes (counts, cursors, the worklist counter) is zeroed by the call
+ *   itself, in stream order. */
+size_t cspn2d_backward_nl_det_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse);
+int cspn2d_backward_nl_det_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history,
+                               size_t history_bytes, const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B,
+                               int C, int H, int W, int K, int n_iter, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_nl_sample_backward_det_workspace_bytes(int B, int H, int W, int K);
+int cspn2d_nl_sample_backward_det_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset,
+                                      int B, int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
