@@ -148,6 +148,13 @@ _SYMBOLS.update({
     "cspn2d_backward_nl_det_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
     "cspn2d_nl_sample_backward_det_workspace_bytes": (c_size_t, [c_int] * 4),
     "cspn2d_nl_sample_backward_det_f32": (c_int, [vp] * 5 + [c_int] * 4 + _WS),
+    # the six on fp16 / bf16 affinities and offsets: a dtype code behind aff and behind offset, the twins' arguments otherwise
+    "cspn2d_forward_nl_g16": (c_int, [vp, c_int, vp, c_int] + [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_nl_g16": (c_int, [vp, c_int, vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_backward_nl_det_g16": (c_int, [vp, c_int, vp, c_int] + [vp] * 3 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_nl_sample_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_int] * 4 + [vp]),
+    "cspn2d_nl_sample_backward_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 4 + [vp]),
+    "cspn2d_nl_sample_backward_det_g16": (c_int, [vp, c_int] + [vp] * 4 + [c_int] * 4 + _WS),
     # the demo module's contract inside the K x K engine: the raw guide in the gates' place, argument lists as the four kxk entry points
     "cspn2d_forward_kxk_absnorm_f32": (c_int, [vp] * 4 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_forward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 3 + [c_size_t] + [c_int] * 6 + _WS),

@@ -23,6 +23,10 @@
 // THE ADJOINT IS NOT RUN-TO-RUN BITWISE: the float atomics add in arrival order, so At_t, and through it every gradient, can differ in its
 // last bits between two calls.  The forward (and nl_sample) is bitwise reproducible.  cspn2d_nl_det.hip holds a second backward that is: the same
 // levels through a gathering adjoint, then this unit's nl_gate_grad (nl_gate_gradients).
+// Storage types: aff is stored as AT and offset as OT, each float, __half or __hip_bfloat16 (the pairs (float, float), (float, T), (T, T); the
+// *_g16 entry points).  A 16-bit value is widened exactly where it is read (cspn_gate16.h: widen, ld4g), after which tap_of and every sum are the
+// float32 code: the results are bitwise those on the widened tensors.  grad_aff is stored as AT and grad_offset as OT: the float32 sum, rounded
+// once to nearest even at its single store (narrow_value).  x, sparse, out, the history and every workspace level are float32 for every pair.
 #include "cspn2d_nl_taps.h"
 
 namespace cspn {
@@ -71,6 +75,20 @@ __device__ __forceinline__ void store4(float* __restrict__ p, const float (&v)[4
     }
 }
 
+// four aff / offset values of a row as float32; VEC: W % 4 == 0 and the plane aligned to four of its elements (16 bytes, or 8 for a 16-bit type)
+template <class GT, bool VEC>
+__device__ __forceinline__ void load4g(float (&v)[4], const store_t<GT>* __restrict__ p, bool row_in, int x0, int W) {
+    if constexpr (std::is_same<GT, float>::value) {
+        load4<VEC>(v, p, row_in, x0, W);
+    } else if (VEC) {
+        const float4 q = (row_in && x0 < W) ? ld4g<GT>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (row_in && x0 + j < W) ? widen<GT>(p[j]) : 0.f;
+    }
+}
+
 struct Quad {
     int n, y, x0;
     bool row_in;
@@ -108,18 +126,18 @@ __global__ __launch_bounds__(NT) void nl_pin(const float* src, const float* __re
 }
 
 // one forward step for all C channels: dst = step(src), src already pinned; pin != NULL: dst is stored pinned (the level the next step
-// reads), NULL: raw (the last step).  VEC: W % 4 == 0 and aff, off, src, dst, pin 16-byte aligned.  Per pixel and neighbour the thread keeps
+// reads), NULL: raw (the last step).  VEC: W % 4 == 0, src, dst, pin 16-byte aligned and aff, off to four of their elements.  Per pixel and neighbour the thread keeps
 // the corner index, the two fractions, the affinity and six bits (the two corner steps, the four inside flags) over the channel loop: the
 // four weights as products would be 128 more registers for four pixels
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void nl_forward_step(const float* __restrict__ aff, const float* __restrict__ off, const float* __restrict__ src,
+template <int K, bool VEC, class AT, class OT>
+__global__ __launch_bounds__(NT) void nl_forward_step(const store_t<AT>* __restrict__ aff, const store_t<OT>* __restrict__ off, const float* __restrict__ src,
                                                       float* __restrict__ dst, const float* __restrict__ pin, int C, int H, int W, int tiles_x,
                                                       int tiles_y) {
     constexpr int KK = K * K - 1;
     const Quad q = quad_of(tiles_x, tiles_y, H);
     const int HW = H * W, pix = q.y * W + q.x0;
-    const float* ap = aff + (size_t)q.n * KK * HW + pix;
-    const float* op = off + (size_t)q.n * 2 * KK * HW + pix;
+    const store_t<AT>* ap = aff + (size_t)q.n * KK * HW + pix;
+    const store_t<OT>* op = off + (size_t)q.n * 2 * KK * HW + pix;
     int i00[KK][4];
     unsigned bits[(KK + 3) / 4][4];   // a byte per neighbour: sx, sy != 0, ok
     float fy[KK][4], fx[KK][4], a[KK][4], cc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -130,9 +148,9 @@ __global__ __launch_bounds__(NT) void nl_forward_step(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
         float dy[4], dx[4];
-        load4<VEC>(a[k], ap + (size_t)k * HW, q.row_in, q.x0, W);
-        load4<VEC>(dy, op + (size_t)(2 * k) * HW, q.row_in, q.x0, W);
-        load4<VEC>(dx, op + (size_t)(2 * k + 1) * HW, q.row_in, q.x0, W);
+        load4g<AT, VEC>(a[k], ap + (size_t)k * HW, q.row_in, q.x0, W);
+        load4g<OT, VEC>(dy, op + (size_t)(2 * k) * HW, q.row_in, q.x0, W);
+        load4g<OT, VEC>(dx, op + (size_t)(2 * k + 1) * HW, q.row_in, q.x0, W);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const Tap t = tap_of(dy[j], dx[j], q.y, q.x0 + j, base_y<K>(k), base_x<K>(k), H, W);
@@ -187,12 +205,13 @@ constexpr int AW = 64, AH = 16, AR = 6, LW = AW + 2 * AR, LH = AH + 2 * AR;
 
 __device__ __forceinline__ void scatter_add(float* lds, float* D, int cy, int cx, int wy0, int wx0, int W, float v) {
     const int ly = cy - wy0, lx = cx - wx0;
-    if ((unsigned)ly < (unsigned)LH && (unsigned)lx < (unsigned)LW) atomicAdd(lds + ly * LW + lx, v);
+    // (the LDS add at workgroup scope: LDS has no other, and two adds of one scope are merged into one flat atomic on a selected address)
+    if ((unsigned)ly < (unsigned)LH && (unsigned)lx < (unsigned)LW) __hip_atomic_fetch_add(lds + ly * LW + lx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else atomicAdd(D + cy * W + cx, v);
 }
 
-template <int K>
-__global__ __launch_bounds__(NT) void nl_adjoint_step(const float* __restrict__ aff, const float* __restrict__ off, const float* __restrict__ src,
+template <int K, class AT, class OT>
+__global__ __launch_bounds__(NT) void nl_adjoint_step(const store_t<AT>* __restrict__ aff, const store_t<OT>* __restrict__ off, const float* __restrict__ src,
                                                       const float* __restrict__ mask, float* dst, int C, int H, int W, int tiles_x, int tiles_y) {
     constexpr int KK = K * K - 1;
     __shared__ float lds[LH * LW];
@@ -213,13 +232,13 @@ __global__ __launch_bounds__(NT) void nl_adjoint_step(const float* __restrict__ 
             if (!(y < H && x < W)) continue;
             if (mask && mask[(size_t)n * HW + pix] > 0.f) continue;   // A(p) = 0: nothing to add
             const float a = src[plane + pix];
-            const float* ap = aff + (size_t)n * KK * HW + pix;
-            const float* op = off + (size_t)n * 2 * KK * HW + pix;
+            const store_t<AT>* ap = aff + (size_t)n * KK * HW + pix;
+            const store_t<OT>* op = off + (size_t)n * 2 * KK * HW + pix;
             float cc = 0.f;
 #pragma unroll
             for (int k = 0; k < KK; ++k) {
-                const float g = ap[(size_t)k * HW];
-                const Tap t = tap_of(op[(size_t)(2 * k) * HW], op[(size_t)(2 * k + 1) * HW], y, x, base_y<K>(k), base_x<K>(k), H, W);
+                const float g = widen<AT>(ap[(size_t)k * HW]);
+                const Tap t = tap_of(widen<OT>(op[(size_t)(2 * k) * HW]), widen<OT>(op[(size_t)(2 * k + 1) * HW]), y, x, base_y<K>(k), base_x<K>(k), H, W);
                 cc += g;
                 const float ga = g * a;
                 const int cy1 = t.cy0 + (t.sy ? 1 : 0), cx1 = t.cx0 + t.sx;
@@ -241,23 +260,24 @@ __global__ __launch_bounds__(NT) void nl_adjoint_step(const float* __restrict__ 
 }
 
 // grad_aff [B][KK][H][W] and grad_offset [B][2 KK][H][W] (either may be NULL), one pixel per lane.  Levels: Ht_0 = h0, Ht_t = hist + (t - 1) L;
-// A_{t+1} = gout (t + 1 = n) or (1 - m) alev[t LA] (mask NULL: no m).  The sums run over t, then c, in registers; each element is written once
-template <int K>
-__global__ __launch_bounds__(NT, 4) void nl_gate_grad(const float* __restrict__ aff, const float* __restrict__ off, const float* __restrict__ h0,
+// A_{t+1} = gout (t + 1 = n) or (1 - m) alev[t LA] (mask NULL: no m).  The sums run over t, then c, in registers; each element is written once,
+// gaff in the type of aff and goff in the type of off (the float32 value rounded at that store)
+template <int K, class AT, class OT>
+__global__ __launch_bounds__(NT, 4) void nl_gate_grad(const store_t<AT>* __restrict__ aff, const store_t<OT>* __restrict__ off, const float* __restrict__ h0,
                                                    const float* __restrict__ hist, const float* __restrict__ alev, const float* __restrict__ gout,
-                                                   const float* __restrict__ mask, float* __restrict__ gaff, float* __restrict__ goff, int n_iter,
+                                                   const float* __restrict__ mask, store_t<AT>* __restrict__ gaff, store_t<OT>* __restrict__ goff, int n_iter,
                                                    size_t L, size_t LA, int C, int H, int W, int tiles_x, int tiles_y) {
     constexpr int KK = K * K - 1;
     const Pixel p = pixel_of(tiles_x, tiles_y, H, W);
     if (!p.in) return;
     const int HW = H * W, pix = p.y * W + p.x;
-    const float* op = off + (size_t)p.n * 2 * KK * HW + pix;
+    const store_t<OT>* op = off + (size_t)p.n * 2 * KK * HW + pix;
     const bool masked = mask && mask[(size_t)p.n * HW + pix] > 0.f;
     Tap tap[KK];
     float ga[KK], gy[KK], gx[KK];
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
-        tap[k] = tap_of(op[(size_t)(2 * k) * HW], op[(size_t)(2 * k + 1) * HW], p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
+        tap[k] = tap_of(widen<OT>(op[(size_t)(2 * k) * HW]), widen<OT>(op[(size_t)(2 * k + 1) * HW]), p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
         ga[k] = gy[k] = gx[k] = 0.f;
     }
     for (int it = 0; it < n_iter; ++it) {
@@ -284,36 +304,36 @@ __global__ __launch_bounds__(NT, 4) void nl_gate_grad(const float* __restrict__ 
         }
     }
     if (gaff) {
-        float* g = gaff + (size_t)p.n * KK * HW + pix;
+        store_t<AT>* g = gaff + (size_t)p.n * KK * HW + pix;
 #pragma unroll
-        for (int k = 0; k < KK; ++k) g[(size_t)k * HW] = ga[k];
+        for (int k = 0; k < KK; ++k) g[(size_t)k * HW] = narrow_value<AT>(ga[k]);
     }
     if (goff) {
-        const float* ap = aff + (size_t)p.n * KK * HW + pix;
-        float* g = goff + (size_t)p.n * 2 * KK * HW + pix;
+        const store_t<AT>* ap = aff + (size_t)p.n * KK * HW + pix;
+        store_t<OT>* g = goff + (size_t)p.n * 2 * KK * HW + pix;
 #pragma unroll
         for (int k = 0; k < KK; ++k) {
-            const float a = ap[(size_t)k * HW];
-            g[(size_t)(2 * k) * HW] = a * gy[k];
-            g[(size_t)(2 * k + 1) * HW] = a * gx[k];
+            const float a = widen<AT>(ap[(size_t)k * HW]);
+            g[(size_t)(2 * k) * HW] = narrow_value<OT>(a * gy[k]);
+            g[(size_t)(2 * k + 1) * HW] = narrow_value<OT>(a * gx[k]);
         }
     }
 }
 
 // the sampling operator: out_k(p) = bil(f, p + base_k + d_k(p)), f [B][H][W] -> out [B][KK][H][W]
-template <int K>
-__global__ __launch_bounds__(NT) void nl_sample_kernel(const float* __restrict__ off, const float* __restrict__ f, float* __restrict__ out, int H, int W,
+template <int K, class OT>
+__global__ __launch_bounds__(NT) void nl_sample_kernel(const store_t<OT>* __restrict__ off, const float* __restrict__ f, float* __restrict__ out, int H, int W,
                                                        int tiles_x, int tiles_y) {
     constexpr int KK = K * K - 1;
     const Pixel p = pixel_of(tiles_x, tiles_y, H, W);
     if (!p.in) return;
     const int HW = H * W, pix = p.y * W + p.x;
-    const float* op = off + (size_t)p.n * 2 * KK * HW + pix;
+    const store_t<OT>* op = off + (size_t)p.n * 2 * KK * HW + pix;
     const float* F = f + (size_t)p.n * HW;
     float* o = out + (size_t)p.n * KK * HW + pix;
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
-        const Tap t = tap_of(op[(size_t)(2 * k) * HW], op[(size_t)(2 * k + 1) * HW], p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
+        const Tap t = tap_of(widen<OT>(op[(size_t)(2 * k) * HW]), widen<OT>(op[(size_t)(2 * k + 1) * HW]), p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
         float v = t.w[0] * F[t.i00];
         v = fmaf(t.w[1], F[t.i00 + t.sx], v);
         v = fmaf(t.w[2], F[t.i00 + t.sy], v);
@@ -322,22 +342,22 @@ __global__ __launch_bounds__(NT) void nl_sample_kernel(const float* __restrict__
     }
 }
 
-// its backward: gf [B][H][W] (zeroed in stream order) += the scattered gout, goff [B][2 KK][H][W] written once; either may be NULL
-template <int K>
-__global__ __launch_bounds__(NT) void nl_sample_backward_kernel(const float* __restrict__ off, const float* __restrict__ f, const float* __restrict__ gout,
-                                                                float* gf, float* __restrict__ goff, int H, int W, int tiles_x, int tiles_y) {
+// its backward: gf [B][H][W] (zeroed in stream order) += the scattered gout, goff [B][2 KK][H][W] written once, in the type of off; either may be NULL
+template <int K, class OT>
+__global__ __launch_bounds__(NT) void nl_sample_backward_kernel(const store_t<OT>* __restrict__ off, const float* __restrict__ f, const float* __restrict__ gout,
+                                                                float* gf, store_t<OT>* __restrict__ goff, int H, int W, int tiles_x, int tiles_y) {
     constexpr int KK = K * K - 1;
     const Pixel p = pixel_of(tiles_x, tiles_y, H, W);
     if (!p.in) return;
     const int HW = H * W, pix = p.y * W + p.x;
-    const float* op = off + (size_t)p.n * 2 * KK * HW + pix;
+    const store_t<OT>* op = off + (size_t)p.n * 2 * KK * HW + pix;
     const float* gp = gout + (size_t)p.n * KK * HW + pix;
     const float* F = f + (size_t)p.n * HW;
     float* D = gf ? gf + (size_t)p.n * HW : nullptr;
-    float* g = goff ? goff + (size_t)p.n * 2 * KK * HW + pix : nullptr;
+    store_t<OT>* g = goff ? goff + (size_t)p.n * 2 * KK * HW + pix : nullptr;
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
-        const Tap t = tap_of(op[(size_t)(2 * k) * HW], op[(size_t)(2 * k + 1) * HW], p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
+        const Tap t = tap_of(widen<OT>(op[(size_t)(2 * k) * HW]), widen<OT>(op[(size_t)(2 * k + 1) * HW]), p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
         const float a = gp[(size_t)k * HW];
         if (D) {
             if (t.w[0] != 0.f) atomicAdd(D + t.i00, t.w[0] * a);
@@ -348,8 +368,8 @@ __global__ __launch_bounds__(NT) void nl_sample_backward_kernel(const float* __r
         if (g) {
             float c[4];
             corners_of(t, F, c);
-            g[(size_t)(2 * k) * HW] = a * ((1.f - t.fx) * (c[2] - c[0]) + t.fx * (c[3] - c[1]));
-            g[(size_t)(2 * k + 1) * HW] = a * ((1.f - t.fy) * (c[1] - c[0]) + t.fy * (c[3] - c[2]));
+            g[(size_t)(2 * k) * HW] = narrow_value<OT>(a * ((1.f - t.fx) * (c[2] - c[0]) + t.fx * (c[3] - c[1])));
+            g[(size_t)(2 * k + 1) * HW] = narrow_value<OT>(a * ((1.f - t.fy) * (c[1] - c[0]) + t.fy * (c[3] - c[2])));
         }
     }
 }
@@ -374,13 +394,14 @@ int pin_levels(const float* src, const float* sparse, float* dst, int B, int C, 
     return check_launch("nl_pin");
 }
 
-template <int K>
-int forward(const float* aff, const float* off, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W, int n_iter,
-            void* ws, hipStream_t st) {
+template <int K, class AT, class OT>
+int forward(const store_t<AT>* aff, const store_t<OT>* off, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W,
+            int n_iter, void* ws, hipStream_t st) {
+    constexpr int adt = std::is_same<AT, float>::value ? 0 : CSPN_DTYPE_F16, odt = std::is_same<OT, float>::value ? 0 : CSPN_DTYPE_F16;   // (the width alone)
     const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
     float* lv[2] = {(float*)ws, (float*)ws + LS};
     const Grid g = quad_grid(B, H, W);
-    const bool vec0 = W % 4 == 0 && aligned16(aff) && aligned16(off) && (!sparse || aligned16(sparse));
+    const bool vec0 = quads_ok(W, adt, {aff}, {sparse}) && quads_ok(W, odt, {off}, {});
     const float* src = x;
     int slot = 0;
     if (sparse) {
@@ -393,9 +414,9 @@ int forward(const float* aff, const float* off, const float* x, const float* spa
         float* dst = last ? out : (hist ? hist + (size_t)t * L : lv[slot]);
         const float* pin = last ? nullptr : sparse;
         if (vec0 && aligned16(src) && aligned16(dst))
-            hipLaunchKernelGGL((nl_forward_step<K, true>), dim3(g.blocks), dim3(NT), 0, st, aff, off, src, dst, pin, C, H, W, g.tx, g.ty);
+            hipLaunchKernelGGL((nl_forward_step<K, true, AT, OT>), dim3(g.blocks), dim3(NT), 0, st, aff, off, src, dst, pin, C, H, W, g.tx, g.ty);
         else
-            hipLaunchKernelGGL((nl_forward_step<K, false>), dim3(g.blocks), dim3(NT), 0, st, aff, off, src, dst, pin, C, H, W, g.tx, g.ty);
+            hipLaunchKernelGGL((nl_forward_step<K, false, AT, OT>), dim3(g.blocks), dim3(NT), 0, st, aff, off, src, dst, pin, C, H, W, g.tx, g.ty);
         if (int e = check_launch("nl_forward_step")) return e;
         src = dst;
         if (!hist && !last) slot ^= 1;
@@ -404,9 +425,9 @@ int forward(const float* aff, const float* off, const float* x, const float* spa
 }
 
 // the gate gradients from the adjoint levels at the start of ws (the scatter's, or the gather's of cspn2d_nl_det.hip: nl_gate_grad reads both)
-template <int K>
-int gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
-                   int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
+template <int K, class AT, class OT>
+int gate_gradients(const store_t<AT>* aff, const store_t<OT>* off, const float* x, const float* sparse, const float* hist, const float* gout,
+                   store_t<AT>* gaff, store_t<OT>* goff, int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
     if (!gaff && !goff) return 0;
     const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
     float* alev = (float*)ws;
@@ -417,14 +438,14 @@ int gate_gradients(const float* aff, const float* off, const float* x, const flo
         if (int e = pin_levels<false>(x, sparse, p, B, C, H, W, st)) return e;
         h0 = p;
     }
-    hipLaunchKernelGGL((nl_gate_grad<K>), dim3(g.blocks), dim3(NT), 0, st, aff, off, h0, hist, alev, gout, sparse, gaff, goff, n_iter, L, LS, C, H, W, g.tx,
-                       g.ty);
+    hipLaunchKernelGGL((nl_gate_grad<K, AT, OT>), dim3(g.blocks), dim3(NT), 0, st, aff, off, h0, hist, alev, gout, sparse, gaff, goff, n_iter, L, LS, C, H, W,
+                       g.tx, g.ty);
     return check_launch("nl_gate_grad");
 }
 
-template <int K>
-int backward(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
-             float* gx, int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
+template <int K, class AT, class OT>
+int backward(const store_t<AT>* aff, const store_t<OT>* off, const float* x, const float* sparse, const float* hist, const float* gout, store_t<AT>* gaff,
+             store_t<OT>* goff, float* gx, int B, int C, int H, int W, int n_iter, void* ws, hipStream_t st) {
     const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
     float* alev = (float*)ws;   // At_1 .. At_{n-1}
     Grid ga;   // the adjoint step's 64 x 16 tiles
@@ -437,49 +458,72 @@ int backward(const float* aff, const float* off, const float* x, const float* sp
         float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * LS;
         hipError_t e = hipMemsetAsync(dst, 0, sizeof(float) * L, st);
         if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        hipLaunchKernelGGL((nl_adjoint_step<K>), dim3(ga.blocks), dim3(NT), 0, st, aff, off, src, top ? nullptr : sparse, dst, C, H, W, ga.tx, ga.ty);
+        hipLaunchKernelGGL((nl_adjoint_step<K, AT, OT>), dim3(ga.blocks), dim3(NT), 0, st, aff, off, src, top ? nullptr : sparse, dst, C, H, W, ga.tx,
+                           ga.ty);
         if (int err = check_launch("nl_adjoint_step")) return err;
     }
     if (gx && sparse)
         if (int e = pin_levels<true>(gx, sparse, gx, B, C, H, W, st)) return e;
-    return gate_gradients<K>(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, n_iter, ws, st);
+    return gate_gradients<K, AT, OT>(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, n_iter, ws, st);
 }
 
 }  // namespace
 
-int nl_forward(const float* aff, const float* off, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W, int K,
-               int n_iter, void* ws, hipStream_t st) {
-    (void)K;   // 3: checked by the caller; 5 and 7 are further instances of the templates
-    return forward<3>(aff, off, x, sparse, out, hist, B, C, H, W, n_iter, ws, st);
-}
-
-int nl_backward(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
-                float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+// K is 3: checked by the caller; 5 and 7 are further instances of the templates.  adt / odt: one of the pairs of with_nl_types, checked by the caller
+int nl_forward(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W,
+               int K, int n_iter, void* ws, hipStream_t st) {
     (void)K;
-    return backward<3>(aff, off, x, sparse, hist, gout, gaff, goff, gx, B, C, H, W, n_iter, ws, st);
+    return with_nl_types(adt, odt, [&](auto ta, auto to) {
+        using AT = typename decltype(ta)::type;
+        using OT = typename decltype(to)::type;
+        return forward<3, AT, OT>((const store_t<AT>*)aff, (const store_t<OT>*)off, x, sparse, out, hist, B, C, H, W, n_iter, ws, st);
+    });
 }
 
-int nl_gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
-                      float* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+int nl_backward(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout, void* gaff,
+                void* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
     (void)K;
-    return gate_gradients<3>(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, n_iter, ws, st);
+    return with_nl_types(adt, odt, [&](auto ta, auto to) {
+        using AT = typename decltype(ta)::type;
+        using OT = typename decltype(to)::type;
+        return backward<3, AT, OT>((const store_t<AT>*)aff, (const store_t<OT>*)off, x, sparse, hist, gout, (store_t<AT>*)gaff, (store_t<OT>*)goff, gx, B, C, H,
+                                   W, n_iter, ws, st);
+    });
 }
 
-int nl_sample(const float* off, const float* f, float* out, int B, int H, int W, int K, hipStream_t st) {
+int nl_gate_gradients(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout,
+                      void* gaff, void* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+    (void)K;
+    return with_nl_types(adt, odt, [&](auto ta, auto to) {
+        using AT = typename decltype(ta)::type;
+        using OT = typename decltype(to)::type;
+        return gate_gradients<3, AT, OT>((const store_t<AT>*)aff, (const store_t<OT>*)off, x, sparse, hist, gout, (store_t<AT>*)gaff, (store_t<OT>*)goff, B, C,
+                                         H, W, n_iter, ws, st);
+    });
+}
+
+int nl_sample(const void* off, int odt, const float* f, float* out, int B, int H, int W, int K, hipStream_t st) {
     (void)K;
     const Grid g = pixel_grid(B, H, W);
-    hipLaunchKernelGGL((nl_sample_kernel<3>), dim3(g.blocks), dim3(NT), 0, st, off, f, out, H, W, g.tx, g.ty);
+    with_gate_type(odt, [&](auto to) {
+        using OT = typename decltype(to)::type;
+        hipLaunchKernelGGL((nl_sample_kernel<3, OT>), dim3(g.blocks), dim3(NT), 0, st, (const store_t<OT>*)off, f, out, H, W, g.tx, g.ty);
+    });
     return check_launch("nl_sample");
 }
 
-int nl_sample_backward(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, hipStream_t st) {
+int nl_sample_backward(const void* off, int odt, const float* f, const float* gout, float* gf, void* goff, int B, int H, int W, int K, hipStream_t st) {
     (void)K;
     if (gf) {
         hipError_t e = hipMemsetAsync(gf, 0, sizeof(float) * (size_t)B * H * W, st);
         if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
     }
     const Grid g = pixel_grid(B, H, W);
-    hipLaunchKernelGGL((nl_sample_backward_kernel<3>), dim3(g.blocks), dim3(NT), 0, st, off, f, gout, gf, goff, H, W, g.tx, g.ty);
+    with_gate_type(odt, [&](auto to) {
+        using OT = typename decltype(to)::type;
+        hipLaunchKernelGGL((nl_sample_backward_kernel<3, OT>), dim3(g.blocks), dim3(NT), 0, st, (const store_t<OT>*)off, f, gout, gf, (store_t<OT>*)goff, H, W,
+                           g.tx, g.ty);
+    });
     return check_launch("nl_sample_backward");
 }
 

@@ -28,6 +28,9 @@
 //                  loop over the list, a wave reduction of the maximum and one of the int64 sum (a list holds up to 32 H W entries when every
 //                  offset points at one pixel).  The sampling operator: the same index with aff = NULL, the gather reads grad_out[n][k][p]
 //                  with k from the code; grad_offset is written once by cspn2d_nl.hip's kernel.
+//   storage types  aff stored as AT, offset as OT (cspn2d_nl.hip): nl_index_taps widens them where it reads them, so the coefficients
+//                  fl32(aff w) and the plane c are formed from the widened values, and the index, the gathers and every level are what they are for
+//                  float32 tensors.
 #include "cspn2d_nl_taps.h"
 
 namespace cspn {
@@ -40,23 +43,23 @@ constexpr int SCAN_PER = (int)(NL_DET_SCAN_TILE / NT);   // counts a thread
 static_assert(SCAN_PER * NT == (int)NL_DET_SCAN_TILE, "a scan tile is a whole number of counts a thread");
 
 // count (FILL false: start[q] += 1, and the plane c) or fill (FILL true: the entry at start[q] + cursor[q]++) the taps of one source pixel
-template <int K, bool FILL>
-__global__ __launch_bounds__(NT) void nl_index_taps(const float* __restrict__ aff, const float* __restrict__ off, unsigned* start, unsigned* cursor,
+template <int K, bool FILL, class AT, class OT>
+__global__ __launch_bounds__(NT) void nl_index_taps(const store_t<AT>* __restrict__ aff, const store_t<OT>* __restrict__ off, unsigned* start, unsigned* cursor,
                                                     uint2* __restrict__ ent, size_t cap, float* __restrict__ cpl, int H, int W, int tiles_x,
                                                     int tiles_y) {
     constexpr int KK = K * K - 1;
     const Pixel p = pixel_of(tiles_x, tiles_y, H, W);
     if (!p.in) return;
     const int HW = H * W, pix = p.y * W + p.x;
-    const float* op = off + (size_t)p.n * 2 * KK * HW + pix;
-    const float* ap = aff ? aff + (size_t)p.n * KK * HW + pix : nullptr;
+    const store_t<OT>* op = off + (size_t)p.n * 2 * KK * HW + pix;
+    const store_t<AT>* ap = aff ? aff + (size_t)p.n * KK * HW + pix : nullptr;
     unsigned* st = start + (size_t)p.n * HW;
     unsigned* cu = cursor + (size_t)p.n * HW;
     float cc = 0.f;
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
-        const float g = ap ? ap[(size_t)k * HW] : 1.f;
-        const Tap t = tap_of(op[(size_t)(2 * k) * HW], op[(size_t)(2 * k + 1) * HW], p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
+        const float g = ap ? widen<AT>(ap[(size_t)k * HW]) : 1.f;
+        const Tap t = tap_of(widen<OT>(op[(size_t)(2 * k) * HW]), widen<OT>(op[(size_t)(2 * k + 1) * HW]), p.y, p.x, base_y<K>(k), base_x<K>(k), H, W);
         cc += g;
         // a weight is zero where its corner is outside the image: every destination lies inside, at the clamped coordinates
         const int d[4] = {t.i00, t.i00 + t.sx, t.i00 + t.sy, t.i00 + t.sy + t.sx};
@@ -290,15 +293,15 @@ struct Index {
     }
 };
 
-template <int K>
-int build_index(const Index& ix, const float* aff, const float* off, int B, int H, int W, hipStream_t st) {
+template <int K, class AT, class OT>
+int build_index(const Index& ix, const store_t<AT>* aff, const store_t<OT>* off, int B, int H, int W, hipStream_t st) {
     const size_t P = (size_t)B * H * W;
     // the worklist counter, the counts and the cursors lie in a row: zeroed here, in stream order
     hipError_t e = hipMemsetAsync(ix.nwork, 0, ix.lay.zeroed, st);
     if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
     const Grid g = pixel_grid(B, H, W);
-    hipLaunchKernelGGL((nl_index_taps<K, false>), dim3(g.blocks), dim3(NT), 0, st, aff, off, ix.start, ix.cursor, ix.ent, ix.lay.cap, ix.cpl, H, W, g.tx,
-                       g.ty);
+    hipLaunchKernelGGL((nl_index_taps<K, false, AT, OT>), dim3(g.blocks), dim3(NT), 0, st, aff, off, ix.start, ix.cursor, ix.ent, ix.lay.cap, ix.cpl, H, W,
+                       g.tx, g.ty);
     if (int err = check_launch("nl_index_taps (count)")) return err;
     hipLaunchKernelGGL(nl_scan_tiles, dim3(ix.lay.tiles), dim3(NT), 0, st, ix.start, ix.sums, ix.work, ix.nwork, ix.lay.work_cap, P);
     if (int err = check_launch("nl_scan_tiles")) return err;
@@ -306,8 +309,8 @@ int build_index(const Index& ix, const float* aff, const float* off, int B, int 
     if (int err = check_launch("nl_scan_sums")) return err;
     hipLaunchKernelGGL(nl_scan_add, dim3(ix.lay.tiles), dim3(NT), 0, st, ix.start, ix.sums, P);
     if (int err = check_launch("nl_scan_add")) return err;
-    hipLaunchKernelGGL((nl_index_taps<K, true>), dim3(g.blocks), dim3(NT), 0, st, aff, off, ix.start, ix.cursor, ix.ent, ix.lay.cap, ix.cpl, H, W, g.tx,
-                       g.ty);
+    hipLaunchKernelGGL((nl_index_taps<K, true, AT, OT>), dim3(g.blocks), dim3(NT), 0, st, aff, off, ix.start, ix.cursor, ix.ent, ix.lay.cap, ix.cpl, H, W,
+                       g.tx, g.ty);
     return check_launch("nl_index_taps (fill)");
 }
 
@@ -325,31 +328,40 @@ int gather(const Index& ix, const float* src, const float* mask, float* dst, int
 
 }  // namespace
 
-int nl_backward_det(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
-                    float* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
+int nl_backward_det(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout,
+                    void* gaff, void* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st) {
     const size_t L = (size_t)B * C * H * W, LS = kxk_level_floats(L);
     float* alev = (float*)ws;   // A_1 .. A_{n-1} (and the pinned H_0 of the gate gradient), then the index
     const int lowest = gx ? 0 : 1;
     if (n_iter - 1 >= lowest) {
         const Index ix((char*)ws + sizeof(float) * LS * (size_t)nl_backward_levels(n_iter, sparse != nullptr), (size_t)B * H * W, true);
-        if (int e = build_index<3>(ix, aff, off, B, H, W, st)) return e;
+        const int e = with_nl_types(adt, odt, [&](auto ta, auto to) {
+            using AT = typename decltype(ta)::type;
+            using OT = typename decltype(to)::type;
+            return build_index<3, AT, OT>(ix, (const store_t<AT>*)aff, (const store_t<OT>*)off, B, H, W, st);
+        });
+        if (e) return e;
         for (int t = n_iter - 1; t >= lowest; --t) {
             const float* src = t + 1 == n_iter ? gout : alev + (size_t)t * LS;
             float* dst = t == 0 ? gx : alev + (size_t)(t - 1) * LS;
             if (int e = gather<false>(ix, src, sparse, dst, B, C, K * K - 1, H, W, st)) return e;
         }
     }
-    return nl_gate_gradients(aff, off, x, sparse, hist, gout, gaff, goff, B, C, H, W, K, n_iter, ws, st);
+    return nl_gate_gradients(aff, adt, off, odt, x, sparse, hist, gout, gaff, goff, B, C, H, W, K, n_iter, ws, st);
 }
 
-int nl_sample_backward_det(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, void* ws,
+int nl_sample_backward_det(const void* off, int odt, const float* f, const float* gout, float* gf, void* goff, int B, int H, int W, int K, void* ws,
                            hipStream_t st) {
     if (gf) {
         const Index ix(ws, (size_t)B * H * W, false);
-        if (int e = build_index<3>(ix, nullptr, off, B, H, W, st)) return e;
+        const int e = with_gate_type(odt, [&](auto to) {
+            using OT = typename decltype(to)::type;
+            return build_index<3, float, OT>(ix, (const float*)nullptr, (const store_t<OT>*)off, B, H, W, st);
+        });
+        if (e) return e;
         if (int e = gather<true>(ix, gout, nullptr, gf, B, 1, K * K - 1, H, W, st)) return e;
     }
-    return goff ? nl_sample_backward(off, f, gout, nullptr, goff, B, H, W, K, st) : 0;
+    return goff ? nl_sample_backward(off, odt, f, gout, nullptr, goff, B, H, W, K, st) : 0;
 }
 
 }  // namespace cspn

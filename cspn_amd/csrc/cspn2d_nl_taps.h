@@ -1,7 +1,8 @@
 // cspn2d_nl_taps.h -- what the non-local kernels share (cspn2d_nl.hip, cspn2d_nl_det.hip): the neighbour bases, the sample of one pixel and
-// neighbour (tap_of), and the one-pixel-per-lane tiling.  The contract is stated in cspn2d_nl.hip.
+// neighbour (tap_of), the one-pixel-per-lane tiling, and the storage types of aff / offset.  The contract is stated in cspn2d_nl.hip.
 #pragma once
 #include "cspn_common.h"
+#include "cspn_gate16.h"
 
 namespace cspn {
 namespace nl {
@@ -77,6 +78,24 @@ inline Grid pixel_grid(int N, int H, int W) {
     g.ty = (H + PH - 1) / PH;
     g.blocks = (unsigned)((size_t)N * g.tx * g.ty);
     return g;
+}
+
+// the one rounding of a float32 gradient at its store (cspn_gate16.h: narrow).  The value is first taken out of the compiler's reach: folded into
+// the conversion, a product a * b becomes fma(a, b, +0) (v_fma_mixlo_f16), whose zero results are all +0, where the float32 kernel stores a * b
+// with its sign.  The float32 instance has no such fold and stays the code it was
+template <class GT>
+__device__ __forceinline__ store_t<GT> narrow_value(float v) {
+    if constexpr (!std::is_same<GT, float>::value) asm volatile("" : "+v"(v));
+    return narrow<GT>(v);
+}
+
+// host side: f(Tag<AT>{}, Tag<OT>{}) for the storage types of aff and offset.  The pairs the entry points let through (cspn_abi.cpp:
+// nl_dtype_check): (0, 0), (0, T) and (T, T), T = CSPN_DTYPE_F16 or CSPN_DTYPE_BF16; no other pair has an instance
+template <class F>
+auto with_nl_types(int adt, int odt, F f) {
+    if (odt == 0) return f(Tag<float>{}, Tag<float>{});
+    if (odt == CSPN_DTYPE_F16) return adt == 0 ? f(Tag<float>{}, Tag<__half>{}) : f(Tag<__half>{}, Tag<__half>{});
+    return adt == 0 ? f(Tag<float>{}, Tag<__hip_bfloat16>{}) : f(Tag<__hip_bfloat16>{}, Tag<__hip_bfloat16>{});
 }
 
 }  // namespace nl

@@ -1495,12 +1495,34 @@ size_t cspn2d_backward_nl_workspace_bytes(int B, int C, int H, int W, int K, int
     return nl_level_bytes(B, C, H, W) * (size_t)nl_backward_levels(n_iter, has_sparse != 0);
 }
 
-int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, float* out, float* history,
-                          size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    const char* what = "cspn2d_forward_nl_f32";
+// the storage types of aff and offset (the *_g16 twins; 0, 0 from the float32 entry points): the last of the checks.  tensors16: every tensor
+// stored in those types, NULL where absent
+static int nl_dtype_check(const char* what, int aff_dtype, int offset_dtype, std::initializer_list<const void*> aff16,
+                          std::initializer_list<const void*> offset16) {
+    for (int dt : {aff_dtype, offset_dtype})
+        if (dt != 0 && dt != CSPN_DTYPE_F16 && dt != CSPN_DTYPE_BF16) {
+            set_error("%s: a dtype code must be 0 (float32), CSPN_DTYPE_F16 (1) or CSPN_DTYPE_BF16 (2), got %d", what, dt);
+            return CSPN_E_BADARG;
+        }
+    if (offset_dtype == 0 ? aff_dtype != 0 : (aff_dtype != 0 && aff_dtype != offset_dtype)) {
+        set_error("%s: dtype pair (aff %d, offset %d) is not built: (0, 0), (0, T) and (T, T) are, T = 1 (fp16) or 2 (bf16)", what, aff_dtype, offset_dtype);
+        return CSPN_E_UNSUPPORTED;
+    }
+    uintptr_t bits = 0;
+    if (aff_dtype != 0) for (const void* t : aff16) bits |= (uintptr_t)t;
+    if (offset_dtype != 0) for (const void* t : offset16) bits |= (uintptr_t)t;
+    if (bits & 1u) { set_error("%s: a 16-bit tensor must be 2-byte aligned", what); return CSPN_E_BADARG; }
+    return 0;
+}
+
+// cspn2d_forward_nl_f32 and its _g16 twin: one set of checks; the dtypes size the ranges of aff and offset and are checked last
+static int nl_forward_entry(const char* what, const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse,
+                            float* out, float* history, size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                            cspn_stream_t stream) {
     if (!aff || !offset || !x || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (int e = nl_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), ab = vb / C * (K * K - 1), ob = 2 * ab, sb = sparse ? vb / C : 0;
+    const size_t vb = kxk_values_bytes(B, C, H, W), sb = sparse ? vb / C : 0;
+    const size_t ab = vb / C / sizeof(float) * (K * K - 1) * gate_bytes(aff_dtype), ob = vb / C / sizeof(float) * 2 * (K * K - 1) * gate_bytes(offset_dtype);
     const size_t hb = cspn2d_nl_history_bytes(B, C, H, W, K, n_iter);
     if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
     // with a history the levels go there: the workspace keeps the pinned H_0 alone (the n_iter = 1 count)
@@ -1513,9 +1535,22 @@ int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x,
         set_error("%s: out, history and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
+    if (int e = nl_dtype_check(what, aff_dtype, offset_dtype, {aff}, {offset})) return e;
     hipStream_t st = (hipStream_t)stream;
     if (n_iter == 0) return identity_copy(out, x, vb / sizeof(float), st);
-    return nl_forward(aff, offset, x, sparse, out, history, B, C, H, W, K, n_iter, ws, st);
+    return nl_forward(aff, aff_dtype, offset, offset_dtype, x, sparse, out, history, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_forward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, float* out, float* history,
+                          size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_forward_entry("cspn2d_forward_nl_f32", aff, 0, offset, 0, x, sparse, out, history, history_bytes, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_forward_nl_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse, float* out,
+                          float* history, size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes,
+                          cspn_stream_t stream) {
+    return nl_forward_entry("cspn2d_forward_nl_g16", aff, aff_dtype, offset, offset_dtype, x, sparse, out, history, history_bytes, B, C, H, W, K, n_iter, ws,
+                            ws_bytes, stream);
 }
 
 // the index of the deterministic backwards behind the levels (cspn_common.h: NlDetIndex); has_c: the propagation's (with the plane c)
@@ -1531,13 +1566,15 @@ size_t cspn2d_nl_sample_backward_det_workspace_bytes(int B, int H, int W, int K)
     return nl_det_index_bytes(B, H, W, false);
 }
 
-// cspn2d_backward_nl_f32 and its deterministic twin: one set of checks, det picks the workspace and the adjoint
-static int nl_backward_entry(const char* what, bool det, const float* aff, const float* offset, const float* x, const float* sparse, const float* history,
-                             size_t history_bytes, const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W,
-                             int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+// cspn2d_backward_nl_f32, its deterministic twin and their _g16 twins: one set of checks, det picks the workspace and the adjoint; the dtypes
+// size the ranges of aff, offset and their gradients and are checked last
+static int nl_backward_entry(const char* what, bool det, const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x,
+                             const float* sparse, const float* history, size_t history_bytes, const float* grad_out, void* grad_aff, void* grad_offset,
+                             float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (!aff || !offset || !x || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (int e = nl_check_shape(what, B, C, H, W, K, n_iter)) return e;
-    const size_t vb = kxk_values_bytes(B, C, H, W), ab = vb / C * (K * K - 1), ob = 2 * ab, sb = sparse ? vb / C : 0;
+    const size_t vb = kxk_values_bytes(B, C, H, W), sb = sparse ? vb / C : 0;
+    const size_t ab = vb / C / sizeof(float) * (K * K - 1) * gate_bytes(aff_dtype), ob = vb / C / sizeof(float) * 2 * (K * K - 1) * gate_bytes(offset_dtype);
     const size_t hb = cspn2d_nl_history_bytes(B, C, H, W, K, n_iter);
     const bool gates = grad_aff || grad_offset;
     if (gates && hb && (!history || history_bytes < hb)) {
@@ -1555,6 +1592,7 @@ static int nl_backward_entry(const char* what, bool det, const float* aff, const
         set_error("%s: grad_aff, grad_offset, grad_x and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
+    if (int e = nl_dtype_check(what, aff_dtype, offset_dtype, {aff, grad_aff}, {offset, grad_offset})) return e;
     if (!gates && !grad_x) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (n_iter == 0) {   // the identity: dL/dx = dL/dout, neither aff nor offset is read
@@ -1564,64 +1602,110 @@ static int nl_backward_entry(const char* what, bool det, const float* aff, const
         if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return (int)e; }
         return 0;
     }
-    return (det ? nl_backward_det : nl_backward)(aff, offset, x, sparse, history, grad_out, grad_aff, grad_offset, grad_x, B, C, H, W, K, n_iter, ws, st);
+    return (det ? nl_backward_det : nl_backward)(aff, aff_dtype, offset, offset_dtype, x, sparse, history, grad_out, grad_aff, grad_offset, grad_x, B, C, H, W,
+                                                 K, n_iter, ws, st);
 }
 
 int cspn2d_backward_nl_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
                            const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
                            void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    return nl_backward_entry("cspn2d_backward_nl_f32", false, aff, offset, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x, B, C,
-                             H, W, K, n_iter, ws, ws_bytes, stream);
+    return nl_backward_entry("cspn2d_backward_nl_f32", false, aff, 0, offset, 0, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x, B,
+                             C, H, W, K, n_iter, ws, ws_bytes, stream);
 }
 
 int cspn2d_backward_nl_det_f32(const float* aff, const float* offset, const float* x, const float* sparse, const float* history, size_t history_bytes,
                                const float* grad_out, float* grad_aff, float* grad_offset, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
                                void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    return nl_backward_entry("cspn2d_backward_nl_det_f32", true, aff, offset, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x, B,
-                             C, H, W, K, n_iter, ws, ws_bytes, stream);
+    return nl_backward_entry("cspn2d_backward_nl_det_f32", true, aff, 0, offset, 0, x, sparse, history, history_bytes, grad_out, grad_aff, grad_offset, grad_x,
+                             B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_nl_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse, const float* history,
+                           size_t history_bytes, const float* grad_out, void* grad_aff, void* grad_offset, float* grad_x, int B, int C, int H, int W, int K,
+                           int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_backward_entry("cspn2d_backward_nl_g16", false, aff, aff_dtype, offset, offset_dtype, x, sparse, history, history_bytes, grad_out, grad_aff,
+                             grad_offset, grad_x, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+int cspn2d_backward_nl_det_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse,
+                               const float* history, size_t history_bytes, const float* grad_out, void* grad_aff, void* grad_offset, float* grad_x, int B,
+                               int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_backward_entry("cspn2d_backward_nl_det_g16", true, aff, aff_dtype, offset, offset_dtype, x, sparse, history, history_bytes, grad_out, grad_aff,
+                             grad_offset, grad_x, B, C, H, W, K, n_iter, ws, ws_bytes, stream);
+}
+
+// the sampling operator and its two backwards, with their _g16 twins: offset_dtype sizes the ranges of offset and grad_offset, and is checked last
+static int nl_sample_entry(const char* what, const void* offset, int offset_dtype, const float* f, float* out, int B, int H, int W, int K,
+                           cspn_stream_t stream) {
+    if (!offset || !f || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1), ob = kb / sizeof(float) * 2 * gate_bytes(offset_dtype);
+    if (kxk_overlaps(out, kb, {{offset, ob}, {f, fb}})) { set_error("%s: out must not alias an input", what); return CSPN_E_BADARG; }
+    if (int e = nl_dtype_check(what, 0, offset_dtype, {}, {offset})) return e;
+    return nl_sample(offset, offset_dtype, f, out, B, H, W, K, (hipStream_t)stream);
 }
 
 int cspn2d_nl_sample_f32(const float* offset, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream) {
-    const char* what = "cspn2d_nl_sample_f32";
-    if (!offset || !f || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    return nl_sample_entry("cspn2d_nl_sample_f32", offset, 0, f, out, B, H, W, K, stream);
+}
+
+int cspn2d_nl_sample_g16(const void* offset, int offset_dtype, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream) {
+    return nl_sample_entry("cspn2d_nl_sample_g16", offset, offset_dtype, f, out, B, H, W, K, stream);
+}
+
+static int nl_sample_backward_entry(const char* what, const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f,
+                                    void* grad_offset, int B, int H, int W, int K, cspn_stream_t stream) {
+    if (!offset || !f || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
-    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
-    if (kxk_overlaps(out, kb, {{offset, 2 * kb}, {f, fb}})) { set_error("%s: out must not alias an input", what); return CSPN_E_BADARG; }
-    return nl_sample(offset, f, out, B, H, W, K, (hipStream_t)stream);
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1), ob = kb / sizeof(float) * 2 * gate_bytes(offset_dtype);
+    if (kxk_overlaps(grad_f, fb, {{offset, ob}, {f, fb}, {grad_out, kb}, {grad_offset, ob}}) ||
+        kxk_overlaps(grad_offset, ob, {{offset, ob}, {f, fb}, {grad_out, kb}})) {
+        set_error("%s: grad_f and grad_offset must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (int e = nl_dtype_check(what, 0, offset_dtype, {}, {offset, grad_offset})) return e;
+    if (!grad_f && !grad_offset) return 0;
+    return nl_sample_backward(offset, offset_dtype, f, grad_out, grad_f, grad_offset, B, H, W, K, (hipStream_t)stream);
 }
 
 int cspn2d_nl_sample_backward_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B, int H, int W,
                                   int K, cspn_stream_t stream) {
-    const char* what = "cspn2d_nl_sample_backward_f32";
+    return nl_sample_backward_entry("cspn2d_nl_sample_backward_f32", offset, 0, f, grad_out, grad_f, grad_offset, B, H, W, K, stream);
+}
+
+int cspn2d_nl_sample_backward_g16(const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f, void* grad_offset, int B,
+                                  int H, int W, int K, cspn_stream_t stream) {
+    return nl_sample_backward_entry("cspn2d_nl_sample_backward_g16", offset, offset_dtype, f, grad_out, grad_f, grad_offset, B, H, W, K, stream);
+}
+
+static int nl_sample_backward_det_entry(const char* what, const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f,
+                                        void* grad_offset, int B, int H, int W, int K, void* ws, size_t ws_bytes, cspn_stream_t stream) {
     if (!offset || !f || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
     if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
-    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
-    if (kxk_overlaps(grad_f, fb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {grad_offset, 2 * kb}}) ||
-        kxk_overlaps(grad_offset, 2 * kb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}})) {
-        set_error("%s: grad_f and grad_offset must not alias an input or each other", what);
+    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1), ob = kb / sizeof(float) * 2 * gate_bytes(offset_dtype);
+    const size_t need = cspn2d_nl_sample_backward_det_workspace_bytes(B, H, W, K);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(grad_f, fb, {{offset, ob}, {f, fb}, {grad_out, kb}, {grad_offset, ob}, {ws, wb}}) ||
+        kxk_overlaps(grad_offset, ob, {{offset, ob}, {f, fb}, {grad_out, kb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{offset, ob}, {f, fb}, {grad_out, kb}})) {
+        set_error("%s: grad_f, grad_offset and the workspace must not alias an input or each other", what);
         return CSPN_E_BADARG;
     }
+    if (int e = nl_dtype_check(what, 0, offset_dtype, {}, {offset, grad_offset})) return e;
     if (!grad_f && !grad_offset) return 0;
-    return nl_sample_backward(offset, f, grad_out, grad_f, grad_offset, B, H, W, K, (hipStream_t)stream);
+    return nl_sample_backward_det(offset, offset_dtype, f, grad_out, grad_f, grad_offset, B, H, W, K, ws, (hipStream_t)stream);
 }
 
 int cspn2d_nl_sample_backward_det_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset, int B, int H, int W,
                                       int K, void* ws, size_t ws_bytes, cspn_stream_t stream) {
-    const char* what = "cspn2d_nl_sample_backward_det_f32";
-    if (!offset || !f || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
-    if (int e = nl_check_shape(what, B, 1, H, W, K, 0)) return e;
-    const size_t fb = kxk_values_bytes(B, 1, H, W), kb = fb * (K * K - 1);
-    const size_t need = cspn2d_nl_sample_backward_det_workspace_bytes(B, H, W, K);
-    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
-    const size_t wb = need ? ws_bytes : 0;
-    if (kxk_overlaps(grad_f, fb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {grad_offset, 2 * kb}, {ws, wb}}) ||
-        kxk_overlaps(grad_offset, 2 * kb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}, {ws, wb}}) ||
-        kxk_overlaps(ws, wb, {{offset, 2 * kb}, {f, fb}, {grad_out, kb}})) {
-        set_error("%s: grad_f, grad_offset and the workspace must not alias an input or each other", what);
-        return CSPN_E_BADARG;
-    }
-    if (!grad_f && !grad_offset) return 0;
-    return nl_sample_backward_det(offset, f, grad_out, grad_f, grad_offset, B, H, W, K, ws, (hipStream_t)stream);
+    return nl_sample_backward_det_entry("cspn2d_nl_sample_backward_det_f32", offset, 0, f, grad_out, grad_f, grad_offset, B, H, W, K, ws, ws_bytes, stream);
+}
+
+int cspn2d_nl_sample_backward_det_g16(const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f, void* grad_offset, int B,
+                                      int H, int W, int K, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    return nl_sample_backward_det_entry("cspn2d_nl_sample_backward_det_g16", offset, offset_dtype, f, grad_out, grad_f, grad_offset, B, H, W, K, ws, ws_bytes,
+                                        stream);
 }
 
 // ---- the guidance heads for K x K propagation (cspn_head_kxk.hip); K = 3 is the 8-plane head's own entry points ----

@@ -167,26 +167,28 @@ int kxk_assemble_backward_pin(const void* guid, int dtype, const float* blur, co
 
 // ---- non-local propagation with learned offsets, K = 3 (cspn2d_nl.hip): aff [B][KK][H][W] used as given, off [B][2 KK][H][W] (dy_k, dx_k
 // interleaved), values [B][C][H][W] on shared aff / off, sparse NULL or [B][H][W] (pinned where > 0).  Neighbour k's base is (t - R, l - R):
-// the deformable convolution's sign, the opposite of the K x K engine's ----
+// the deformable convolution's sign, the opposite of the K x K engine's.  adt / odt: the storage types of aff (and gaff) and of off (and goff),
+// 0 float32 or CSPN_DTYPE_F16 / CSPN_DTYPE_BF16, in one of the pairs (0, 0), (0, T), (T, T) (checked by the caller); 16-bit values are widened
+// exactly where they are read, 16-bit gradients are the float32 sums rounded once at their store; values, levels and workspaces stay float32 ----
 // levels of kxk_level_floats(B C H W) floats in the forward's workspace: the pinned H_0 (with sparse) and the ping-pong pair; with a history
 // the levels go there and only the pinned H_0 is left (the n_iter = 1 count)
 inline int nl_forward_levels(int n_iter, bool sparse) { return n_iter <= 0 ? 0 : (sparse ? (n_iter >= 2 ? 2 : 1) : (n_iter >= 3 ? 2 : n_iter - 1)); }
 // the backward's: the adjoint levels 1 .. n-1 as the scatter leaves them, then (with sparse) the pinned H_0 of the gate gradient
 inline int nl_backward_levels(int n_iter, bool sparse) { return n_iter <= 0 ? 0 : n_iter - 1 + (sparse ? 1 : 0); }
 // hist: NULL, or the pinned levels 1 .. n-1, level t at hist + (t - 1) B C H W
-int nl_forward(const float* aff, const float* off, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W, int K,
-               int n_iter, void* ws, hipStream_t st);
+int nl_forward(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, float* out, float* hist, int B, int C, int H, int W,
+               int K, int n_iter, void* ws, hipStream_t st);
 // gaff, goff and gx may each be NULL; gaff / goff need hist where n_iter >= 2.  NOT run-to-run bitwise: the adjoint scatters with float atomics
-int nl_backward(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff, float* goff,
-                float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+int nl_backward(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout, void* gaff,
+                void* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
 // the sampling operator out_k(p) = bil(f, p + base_k + d_k(p)), f [B][H][W] -> out [B][KK][H][W], and its backward (gf by the scatter, goff
 // written once; either may be NULL)
-int nl_sample(const float* off, const float* f, float* out, int B, int H, int W, int K, hipStream_t st);
-int nl_sample_backward(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, hipStream_t st);
+int nl_sample(const void* off, int odt, const float* f, float* out, int B, int H, int W, int K, hipStream_t st);
+int nl_sample_backward(const void* off, int odt, const float* f, const float* gout, float* gf, void* goff, int B, int H, int W, int K, hipStream_t st);
 // the tail of nl_backward: gaff / goff (each may be NULL) from the levels A_1 .. A_{n-1} at the start of ws, (1 - m) already applied or not;
 // with sparse, the pinned H_0 goes to the level behind them
-int nl_gate_gradients(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
-                      float* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+int nl_gate_gradients(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout,
+                      void* gaff, void* goff, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
 // ---- the same two backwards, run-to-run bitwise (cspn2d_nl_det.hip): the adjoint gathers through an inverted index of the operator and sums
 // in an order-independent way; no float atomics ----
 constexpr unsigned NL_DET_LONG = 128;        // lists longer than this are summed by a whole wave
@@ -213,10 +215,10 @@ struct NlDetIndex {
     }
 };
 // ws: nl_backward's levels, then the index (with the plane c)
-int nl_backward_det(const float* aff, const float* off, const float* x, const float* sparse, const float* hist, const float* gout, float* gaff,
-                    float* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+int nl_backward_det(const void* aff, int adt, const void* off, int odt, const float* x, const float* sparse, const float* hist, const float* gout,
+                    void* gaff, void* goff, float* gx, int B, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
 // ws: the index (without the plane c)
-int nl_sample_backward_det(const float* off, const float* f, const float* gout, float* gf, float* goff, int B, int H, int W, int K, void* ws,
+int nl_sample_backward_det(const void* off, int odt, const float* f, const float* gout, float* gf, void* goff, int B, int H, int W, int K, void* ws,
                            hipStream_t st);
 
 // ---- backward of the 3D op, Paddle contract only (cspn3d_backward.hip) ----

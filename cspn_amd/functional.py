@@ -1058,7 +1058,8 @@ def cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_con
 
 # ---- non-local propagation with learned offsets (NLSPN's refinement step; cspn2d_nl.hip): every pixel reads its K*K - 1 neighbours by bilinear
 # interpolation at p + base_k + offset_k(p).  Neighbour k is the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre and its base is
-# (t - K//2, l - K//2): the deformable convolution's sign, THE OPPOSITE of the K x K engine's (K//2 - t, K//2 - l) above.  float32 only ----
+# (t - K//2, l - K//2): the deformable convolution's sign, THE OPPOSITE of the K x K engine's (K//2 - t, K//2 - l) above.  The six functions are
+# float32 only; their *_g16 twins below them take aff and offset in float16 / bfloat16 as well ----
 def _nl_kernel_size(kernel_size):
     K = _check_kernel_size(kernel_size, 4)
     if K != 3:
@@ -1066,28 +1067,41 @@ def _nl_kernel_size(kernel_size):
     return K
 
 
-def _nl_tensor(t, name, shape=None, channels=None):
-    """float32 and nothing else (16-bit affinities and offsets are not built), checked before the device; [B, channels, H, W] or exactly `shape`"""
+def _nl_tensor(t, name, shape=None, channels=None, g16=False):
+    """float32 and nothing else (g16, for aff and offset of the *_g16 functions: float16 and bfloat16 as well), checked before the device;
+    [B, channels, H, W] or exactly `shape`"""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32 (got %s): the non-local entry points take no other dtype" % (name, t.dtype))
+    if g16 and t.dtype != torch.float32 and t.dtype not in _GATE16:
+        raise TypeError("%s must be float32, float16 or bfloat16 (got %s)" % (name, t.dtype))
+    if not g16 and t.dtype != torch.float32:
+        raise TypeError("%s must be float32 (got %s): the non-local entry points take no other dtype%s"
+                        % (name, t.dtype, " (16-bit aff and offset: the *_g16 functions)" if name in ("aff", "offset") else ""))
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     if shape is None and (t.dim() != 4 or (channels is not None and t.shape[1] != channels)):
         raise ValueError("%s must be [B,%s,H,W], got %s" % (name, "C" if channels is None else channels, tuple(t.shape)))
 
 
-def _nl_offset(offset, K):
-    _nl_tensor(offset, "offset", channels=2 * (K * K - 1))
+def _nl_offset(offset, K, g16=False):
+    _nl_tensor(offset, "offset", channels=2 * (K * K - 1), g16=g16)
     return offset.shape[0], offset.shape[2], offset.shape[3]
 
 
-def _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, extra=()):
+def _nl_pair(aff, offset):
+    """the *_g16 functions' pairs (aff, offset): (float32, float32), (float32, T) and (T, T), T float16 or bfloat16; anything else is a TypeError"""
+    if aff.dtype != offset.dtype and aff.dtype != torch.float32:
+        raise TypeError("aff %s with offset %s is not built: float32 or the offset's dtype with a 16-bit offset, float32 with a float32 one"
+                        % (aff.dtype, offset.dtype))
+
+
+def _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, extra=(), g16=False):
     """-> K, B, C, H, W, n and the tensors on the GPU, contiguous: aff, offset, x, sparse_depth (or None), *extra (each of x's shape)"""
     K = _nl_kernel_size(kernel_size)
-    B, H, W = _nl_offset(offset, K)
-    _nl_tensor(aff, "aff", (B, K * K - 1, H, W))
+    B, H, W = _nl_offset(offset, K, g16)
+    _nl_tensor(aff, "aff", (B, K * K - 1, H, W), g16=g16)
+    if g16:
+        _nl_pair(aff, offset)
     _nl_tensor(x, "x", channels=None)
     if x.shape[0] != B or tuple(x.shape[2:]) != (H, W) or x.shape[1] < 1:
         raise ValueError("x has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(x.shape), B, H, W))
@@ -1102,22 +1116,20 @@ def _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, extra=()):
 
 
 def _nl_prep(*named):
-    ts = [None if t is None else _prep(t, name) for t, name in named]
+    """on the GPU, contiguous, in the dtype _nl_tensor has let through"""
+    ts = [None if t is None else _prep(t, name, dtype=t.dtype) for t, name in named]
     if any(t is not None and t.device != ts[0].device for t in ts):
         raise ValueError("all tensors must live on the same device")
     return ts
 
 
-def cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size=3, return_history=False):
-    """Non-local propagation, affinities as given (cspn2d_forward_nl_f32): aff [B,8,H,W] any sign, normalised by the caller; offset [B,16,H,W],
-    channel 2k is dy_k and 2k+1 is dx_k; x [B,C,H,W], the C channels share aff and offset; sparse_depth [B,1,H,W] or None, pinned where > 0:
-        Ht = sparse_depth where sparse_depth > 0 else H       (before every step)
-        H <- (1 - sum_k aff_k) * Ht + sum_k aff_k * bil(Ht, p + base_k + offset_k(p)),      H_0 = x, n_iter times; the result is not pinned
-    base_k = (t - 1, l - 1) for the k-th (t, l) of the 3 x 3 raster without the centre: the deformable convolution's sign, the opposite of the
-    K x K functions'.  bil takes its fractions from the offset (offset - floor(offset)), a corner outside the image contributes 0, every finite
-    offset is valid.  return_history: (out, history) for cspn2d_backward_nl.  n_iter == 0 returns x.  float32 only: any other dtype is a
-    TypeError.  Bitwise reproducible."""
-    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter)
+def _nl_typed(t):
+    """a pointer of a *_g16 entry point with the dtype code behind it"""
+    return _ptr(t), _GATE16.get(t.dtype, 0)
+
+
+def _nl_forward(g16, aff, offset, x, sparse_depth, n_iter, kernel_size, return_history):
+    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, g16=g16)
     if n == 0:
         return (x, None) if return_history else x
     a, o, h, s = _nl_prep((aff, "aff"), (offset, "offset"), (x, "x"), (sparse_depth, "sparse_depth"))
@@ -1129,14 +1141,27 @@ def cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size=3, retur
         with torch.cuda.device(a.device):
             hb = _lib.symbol("cspn2d_nl_history_bytes")(B, C, H, W, K, n)
         hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=a.device)
-    _launch("cspn2d_forward_nl_f32", a.device, (_ptr(a), _ptr(o), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
+    gates = (*_nl_typed(a), *_nl_typed(o)) if g16 else (_ptr(a), _ptr(o))
+    _launch("cspn2d_forward_nl_g16" if g16 else "cspn2d_forward_nl_f32", a.device, (*gates, _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
             ("cspn2d_nl_workspace_bytes", B, C, H, W, K, 1 if return_history else n, int(s is not None)))
     return (out, hist) if return_history else out
 
 
-def _nl_backward(stem, aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x):
-    """cspn2d_backward_nl and its deterministic twin: stem + "_f32" is the entry point, stem + "_workspace_bytes" its size query"""
-    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, ((grad_out, "grad_out"),))
+def cspn2d_forward_nl(aff, offset, x, sparse_depth, n_iter, kernel_size=3, return_history=False):
+    """Non-local propagation, affinities as given (cspn2d_forward_nl_f32): aff [B,8,H,W] any sign, normalised by the caller; offset [B,16,H,W],
+    channel 2k is dy_k and 2k+1 is dx_k; x [B,C,H,W], the C channels share aff and offset; sparse_depth [B,1,H,W] or None, pinned where > 0:
+        Ht = sparse_depth where sparse_depth > 0 else H       (before every step)
+        H <- (1 - sum_k aff_k) * Ht + sum_k aff_k * bil(Ht, p + base_k + offset_k(p)),      H_0 = x, n_iter times; the result is not pinned
+    base_k = (t - 1, l - 1) for the k-th (t, l) of the 3 x 3 raster without the centre: the deformable convolution's sign, the opposite of the
+    K x K functions'.  bil takes its fractions from the offset (offset - floor(offset)), a corner outside the image contributes 0, every finite
+    offset is valid.  return_history: (out, history) for cspn2d_backward_nl.  n_iter == 0 returns x.  float32 only: any other dtype is a
+    TypeError (cspn2d_forward_nl_g16 takes 16-bit aff and offset).  Bitwise reproducible."""
+    return _nl_forward(False, aff, offset, x, sparse_depth, n_iter, kernel_size, return_history)
+
+
+def _nl_backward(stem, aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x, g16=False):
+    """cspn2d_backward_nl and its deterministic twin: stem + "_f32" (g16: "_g16") is the entry point, stem + "_workspace_bytes" its size query"""
+    K, B, C, H, W, n = _nl_args(aff, offset, x, sparse_depth, kernel_size, n_iter, ((grad_out, "grad_out"),), g16)
     a, o, h, s, go = _nl_prep((aff, "aff"), (offset, "offset"), (x, "x"), (sparse_depth, "sparse_depth"), (grad_out, "grad_out"))
     ga = torch.empty_like(a) if need_aff else None
     gd = torch.empty_like(o) if need_offset else None
@@ -1144,10 +1169,11 @@ def _nl_backward(stem, aff, offset, x, sparse_depth, grad_out, n_iter, kernel_si
     if not (need_aff or need_offset or need_x) or h.numel() == 0:
         return ga, gd, gx
     if (need_aff or need_offset) and n >= 2 and history is None:
-        _, history = cspn2d_forward_nl(a, o, h, s, n, K, return_history=True)
+        _, history = (cspn2d_forward_nl_g16 if g16 else cspn2d_forward_nl)(a, o, h, s, n, K, return_history=True)
     hb = history.numel() * history.element_size() if history is not None else 0
-    _launch(stem + "_f32", a.device,
-            (_ptr(a), _ptr(o), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
+    gates = (*_nl_typed(a), *_nl_typed(o)) if g16 else (_ptr(a), _ptr(o))
+    _launch(stem + ("_g16" if g16 else "_f32"), a.device,
+            (*gates, _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
             (stem + "_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
     return ga, gd, gx
 
@@ -1169,33 +1195,41 @@ def cspn2d_backward_nl_det(aff, offset, x, sparse_depth, grad_out, n_iter, kerne
     return _nl_backward("cspn2d_backward_nl_det", aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x)
 
 
-def cspn2d_nl_sample(offset, f, kernel_size=3):
-    """The sampling operator of cspn2d_forward_nl on its own: out[:, k](p) = bil(f, p + base_k + offset_k(p)), f [B,1,H,W] -> [B,8,H,W]
-    (cspn2d_nl_sample_f32).  Bitwise reproducible."""
+def _nl_sample(g16, offset, f, kernel_size):
     K = _nl_kernel_size(kernel_size)
-    B, H, W = _nl_offset(offset, K)
+    B, H, W = _nl_offset(offset, K, g16)
     _nl_tensor(f, "f", (B, 1, H, W))
     o, v = _nl_prep((offset, "offset"), (f, "f"))
     out = torch.empty((B, K * K - 1, H, W), dtype=torch.float32, device=o.device)
     if out.numel():
-        _launch("cspn2d_nl_sample_f32", o.device, (_ptr(o), _ptr(v), _ptr(out), B, H, W, K))
+        if g16:
+            _launch("cspn2d_nl_sample_g16", o.device, (*_nl_typed(o), _ptr(v), _ptr(out), B, H, W, K))
+        else:
+            _launch("cspn2d_nl_sample_f32", o.device, (_ptr(o), _ptr(v), _ptr(out), B, H, W, K))
     return out
 
 
-def _nl_sample_backward(det, offset, f, grad_out, kernel_size, need_f, need_offset):
+def cspn2d_nl_sample(offset, f, kernel_size=3):
+    """The sampling operator of cspn2d_forward_nl on its own: out[:, k](p) = bil(f, p + base_k + offset_k(p)), f [B,1,H,W] -> [B,8,H,W]
+    (cspn2d_nl_sample_f32).  Bitwise reproducible."""
+    return _nl_sample(False, offset, f, kernel_size)
+
+
+def _nl_sample_backward(det, offset, f, grad_out, kernel_size, need_f, need_offset, g16=False):
     K = _nl_kernel_size(kernel_size)
-    B, H, W = _nl_offset(offset, K)
+    B, H, W = _nl_offset(offset, K, g16)
     _nl_tensor(f, "f", (B, 1, H, W))
     _nl_tensor(grad_out, "grad_out", (B, K * K - 1, H, W))
     o, v, go = _nl_prep((offset, "offset"), (f, "f"), (grad_out, "grad_out"))
     gf = torch.empty_like(v) if need_f else None
     gd = torch.empty_like(o) if need_offset else None
     if (need_f or need_offset) and v.numel():
-        args = (_ptr(o), _ptr(v), _ptr(go), _ptr(gf), _ptr(gd), B, H, W, K)
+        args = ((*_nl_typed(o),) if g16 else (_ptr(o),)) + (_ptr(v), _ptr(go), _ptr(gf), _ptr(gd), B, H, W, K)
+        tail = "_g16" if g16 else "_f32"
         if det:
-            _launch("cspn2d_nl_sample_backward_det_f32", o.device, args, ("cspn2d_nl_sample_backward_det_workspace_bytes", B, H, W, K))
+            _launch("cspn2d_nl_sample_backward_det" + tail, o.device, args, ("cspn2d_nl_sample_backward_det_workspace_bytes", B, H, W, K))
         else:
-            _launch("cspn2d_nl_sample_backward_f32", o.device, args)
+            _launch("cspn2d_nl_sample_backward" + tail, o.device, args)
     return gf, gd
 
 
@@ -1210,6 +1244,44 @@ def cspn2d_nl_sample_backward_det(offset, f, grad_out, kernel_size=3, need_f=Tru
     gathered through the inverted index of the sampling operator and summed in an order-independent way, as in cspn2d_backward_nl_det; about 260
     bytes a pixel of workspace."""
     return _nl_sample_backward(True, offset, f, grad_out, kernel_size, need_f, need_offset)
+
+
+# ---- the same six on float16 / bfloat16 affinities and offsets (the cspn2d_*_nl*_g16 entry points): what a head under torch.autocast emits, taken
+# as it is.  aff / offset come in the pairs (float32, float32), (float32, T), (T, T), T float16 or bfloat16; any other pair, or float64, is a
+# TypeError raised before the device.  Everything else is float32.  A 16-bit value is widened exactly where the kernels read it, so every result
+# is bitwise the float32 function's on aff.float(), offset.float(); dL/daff and dL/doffset come back in the dtype of aff and of offset, the float32
+# value rounded once.  Signatures, workspaces and histories are the twins' ----
+def cspn2d_forward_nl_g16(aff, offset, x, sparse_depth, n_iter, kernel_size=3, return_history=False):
+    """cspn2d_forward_nl on aff / offset in float32, float16 or bfloat16 (cspn2d_forward_nl_g16): out and the history are float32 and bitwise
+    cspn2d_forward_nl(aff.float(), offset.float(), ...); no widened copy is made."""
+    return _nl_forward(True, aff, offset, x, sparse_depth, n_iter, kernel_size, return_history)
+
+
+def cspn2d_backward_nl_g16(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
+    """cspn2d_backward_nl on aff / offset in float32, float16 or bfloat16 (cspn2d_backward_nl_g16): dL/daff in aff's dtype, dL/doffset in offset's
+    (the float32 sums rounded once, to nearest even), dL/dx float32.  Not run-to-run bitwise, as its twin."""
+    return _nl_backward("cspn2d_backward_nl", aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x, True)
+
+
+def cspn2d_backward_nl_det_g16(aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size=3, history=None, need_aff=True, need_offset=True, need_x=True):
+    """cspn2d_backward_nl_det on aff / offset in float32, float16 or bfloat16 (cspn2d_backward_nl_det_g16), RUN-TO-RUN BITWISE: dL/dx is bitwise
+    cspn2d_backward_nl_det's on the widened tensors, dL/daff and dL/doffset are bitwise its results cast to aff's and offset's dtype."""
+    return _nl_backward("cspn2d_backward_nl_det", aff, offset, x, sparse_depth, grad_out, n_iter, kernel_size, history, need_aff, need_offset, need_x, True)
+
+
+def cspn2d_nl_sample_g16(offset, f, kernel_size=3):
+    """cspn2d_nl_sample on an offset in float32, float16 or bfloat16 (cspn2d_nl_sample_g16): bitwise cspn2d_nl_sample(offset.float(), f)."""
+    return _nl_sample(True, offset, f, kernel_size)
+
+
+def cspn2d_nl_sample_backward_g16(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
+    """cspn2d_nl_sample_backward on an offset in float32, float16 or bfloat16 (cspn2d_nl_sample_backward_g16): dL/doffset in the offset's dtype."""
+    return _nl_sample_backward(False, offset, f, grad_out, kernel_size, need_f, need_offset, True)
+
+
+def cspn2d_nl_sample_backward_det_g16(offset, f, grad_out, kernel_size=3, need_f=True, need_offset=True):
+    """cspn2d_nl_sample_backward_det on an offset in float32, float16 or bfloat16 (cspn2d_nl_sample_backward_det_g16): RUN-TO-RUN BITWISE."""
+    return _nl_sample_backward(True, offset, f, grad_out, kernel_size, need_f, need_offset, True)
 
 
 def assemble_conf(iter_conf, kernel_conf, k, T, like):

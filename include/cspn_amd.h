@@ -675,6 +675,46 @@ size_t cspn2d_nl_sample_backward_det_workspace_bytes(int B, int H, int W, int K)
 int cspn2d_nl_sample_backward_det_f32(const float* offset, const float* f, const float* grad_out, float* grad_f, float* grad_offset,
                                       int B, int H, int W, int K, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
+/* ---- the six non-local entry points on fp16 / bf16 affinities and offsets: what a head under mixed precision emits, taken as it is.
+ * Each mirrors its _f32 twin above, with a dtype code right behind the pointer it describes: aff is stored as aff_dtype, offset as
+ * offset_dtype, each 0 (float32), CSPN_DTYPE_F16 or CSPN_DTYPE_BF16.  grad_aff is stored as aff_dtype, grad_offset as offset_dtype.  x, sparse,
+ * out, history, grad_out, grad_x, f, grad_f and every workspace level stay float32: the byte queries of the twins serve these calls
+ * unchanged, and no widened copy of aff or offset is made anywhere.
+ *     pair (aff_dtype, offset_dtype)
+ *     (0, 0)    the float32 kernels: bitwise the _f32 entry point
+ *     (0, T)    float32 affinities (normalised in float32 by the caller, as NonLocal_Propagate does) on offsets as emitted
+ *     (T, T)    both 16-bit, T = CSPN_DTYPE_F16 or CSPN_DTYPE_BF16
+ *   (T, 0) and fp16 mixed with bf16: CSPN_E_UNSUPPORTED; a code outside {0, 1, 2}: CSPN_E_BADARG; both with "dtype" in cspn_last_error().
+ * The contract is the twins' with two storage types: a 16-bit value is widened to float32 exactly where it is read (fp16 subnormals kept,
+ *   bf16 = its bits shifted left by 16), after which every operation is the float32 kernel's.  So the fraction d - floor(d) is the widened
+ *   offset's, every finite 16-bit offset is valid, and an fp16 offset that has overflowed to +-inf, or a NaN, gives an unspecified value but
+ *   never an access outside the tensors (every corner is outside the image, through the same clamp).
+ *     out, history     bitwise cspn2d_forward_nl_f32 on the widened aff and offset, on the vector and on the guarded scalar kernels
+ *     _det backwards   grad_x (grad_f) bitwise the _det_f32 twin on the widened tensors; grad_aff / grad_offset bitwise that twin's float32
+ *                      value rounded once, to nearest even (fp16 subnormals kept), at its single store
+ *     scatter backwards  the same within the scatter's run-to-run differences
+ *     cspn2d_nl_sample_g16   bitwise cspn2d_nl_sample_f32 on the widened offset
+ * Checks: the twins', in their order and with their messages (null pointers, shape, n_iter, K != 3, the 32-bit indexing guard, history,
+ *   workspace, aliasing with the ranges of aff, offset and their gradients counted in the stored element size); the dtype checks come last.
+ *   A 16-bit tensor must be 2-byte aligned.  8-byte loads of four 16-bit values (16-byte loads of float32 ones) in the forward where
+ *   W % 4 == 0 and every tensor is aligned to four of its elements; any other alignment or width takes the guarded scalar kernel. */
+int cspn2d_forward_nl_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse, float* out,
+                          float* history, size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* workspace,
+                          size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_nl_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse,
+                           const float* history, size_t history_bytes, const float* grad_out, void* grad_aff, void* grad_offset, float* grad_x,
+                           int B, int C, int H, int W, int K, int n_iter, void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+int cspn2d_backward_nl_det_g16(const void* aff, int aff_dtype, const void* offset, int offset_dtype, const float* x, const float* sparse,
+                               const float* history, size_t history_bytes, const float* grad_out, void* grad_aff, void* grad_offset,
+                               float* grad_x, int B, int C, int H, int W, int K, int n_iter, void* workspace, size_t workspace_bytes,
+                               cspn_stream_t stream);
+int cspn2d_nl_sample_g16(const void* offset, int offset_dtype, const float* f, float* out, int B, int H, int W, int K, cspn_stream_t stream);
+int cspn2d_nl_sample_backward_g16(const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f, void* grad_offset,
+                                  int B, int H, int W, int K, cspn_stream_t stream);
+int cspn2d_nl_sample_backward_det_g16(const void* offset, int offset_dtype, const float* f, const float* grad_out, float* grad_f,
+                                      void* grad_offset, int B, int H, int W, int K, void* workspace, size_t workspace_bytes,
+                                      cspn_stream_t stream);
+
 /* ---- the demo module's contract (reference cspn_paddle/demo.py:20-54) inside the K x K engine, K = 5 or 7: guide [B,KK,H,W] raw, any
  * sign, in the channel order of the NONE op; x / out [B,C,H,W], the C channels share the guide.  With a_k = |g_k| and
  * S(p) = sum_k a_k(p), summed in channel order in float32:
