@@ -161,6 +161,11 @@ _SYMBOLS.update({
     "cspn2d_backward_kxk_absnorm_workspace_bytes": (c_size_t, [c_int] * 6),
     "cspn2d_backward_kxk_absnorm_f32": (c_int, [vp] * 3 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
     "cspn2d_backward_kxk_absnorm_g16": (c_int, [vp, c_int] + [vp] * 2 + [c_size_t] + [vp] * 3 + [c_int] * 6 + _WS),
+    # K x K propagation with per-step attention (K = 3, 5 or 7): guidance, att, x, sparse (or NULL) in front
+    "cspn2d_kxk_dyn_workspace_bytes": (c_size_t, [c_int] * 8),
+    "cspn2d_forward_kxk_dyn_f32": (c_int, [vp] * 6 + [c_size_t] + [c_int] * 6 + _WS),
+    "cspn2d_backward_kxk_dyn_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_backward_kxk_dyn_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
     # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
     "cspn_guidance_head_kxk_workspace_bytes": (c_size_t, [c_int] * 5),
     "cspn_guidance_head_kxk_f32": (c_int, [vp] * 5 + [c_int] * 7 + _WS),

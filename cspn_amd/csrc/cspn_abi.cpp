@@ -1061,6 +1061,90 @@ int cspn2d_backward_kxk_absnorm_g16(const void* guide, int gate_dtype, const flo
                               ws_bytes, stream);
 }
 
+// ---- K x K propagation with per-step attention, K = 3, 5 or 7 (cspn2d_kxk_dyn.hip): the checks of the kxk_absnorm entry points, with att,
+// grad_att and sparse among the ranges.  The n (R+1) attention planes are addressed in size_t by every kernel; an image's planes fit an int ----
+static bool kxk_dyn_shape_ok(int B, int C, int H, int W, int K, int n_iter) {
+    const long long px = (long long)H * W;
+    return B > 0 && C > 0 && H > 0 && W > 0 && (K == 3 || K == 5 || K == 7) && n_iter >= 0 && (long long)B * C * px <= 0x7fffffffLL &&
+           (long long)B * (K * K - 1) * px <= 0x7fffffffLL && (long long)B * n_iter * (K / 2 + 1) * px <= 0x7fffffffLL;
+}
+
+static int kxk_dyn_check_shape(const char* what, int B, int C, int H, int W, int K, int n_iter) {
+    if (K != 3 && K != 5 && K != 7) { set_error("%s: K must be 3, 5 or 7, got %d", what, K); return CSPN_E_BADARG; }
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (n_iter < 0) { set_error("%s: n_iter must be >= 0 (got %d)", what, n_iter); return CSPN_E_BADARG; }
+    if (!kxk_dyn_shape_ok(B, C, H, W, K, n_iter)) { set_error("%s: tensor too large for 32-bit element indexing", what); return CSPN_E_UNSUPPORTED; }
+    return 0;
+}
+
+// H~_1 .. H~_{n-1}: cspn2d_kxk_history_bytes, which does not take K = 3
+static size_t kxk_dyn_history_bytes(int B, int C, int H, int W, int n_iter) { return n_iter < 2 ? 0 : kxk_values_bytes(B, C, H, W) * (size_t)(n_iter - 1); }
+
+size_t cspn2d_kxk_dyn_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse, int keep_history) {
+    if (!kxk_dyn_shape_ok(B, C, H, W, K, n_iter) || n_iter < 1) return 0;
+    return round256(sizeof(float) * kxk_level_floats((size_t)B * C * H * W) * (size_t)kxk_dyn_forward_levels(n_iter, has_sparse != 0, keep_history != 0));
+}
+
+size_t cspn2d_backward_kxk_dyn_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse) {
+    if (!kxk_dyn_shape_ok(B, C, H, W, K, n_iter) || n_iter < 1) return 0;
+    return KxkDynBackwardWs(B, C, H, W, K, n_iter, has_sparse != 0).bytes;
+}
+
+int cspn2d_forward_kxk_dyn_f32(const float* guidance, const float* att, const float* x, const float* sparse, float* out, float* history,
+                               size_t history_bytes, int B, int C, int H, int W, int K, int n_iter, void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_forward_kxk_dyn_f32";
+    if (!guidance || !x || !out || (!att && n_iter > 0)) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_dyn_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), pb = vb / C, gb = pb * (K * K - 1), ab = pb * (size_t)n_iter * (K / 2 + 1);
+    const size_t hb = kxk_dyn_history_bytes(B, C, H, W, n_iter);
+    if (history && history_bytes < hb) { set_error("%s: history buffer too small: need %zu bytes, got %zu", what, hb, history_bytes); return CSPN_E_WORKSPACE; }
+    const size_t need = cspn2d_kxk_dyn_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr, history != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0;
+    if (kxk_overlaps(out, vb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {history, hb}, {ws, wb}}) ||
+        kxk_overlaps(history, hb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}})) {
+        set_error("%s: out, history and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) return identity_copy(out, x, vb / sizeof(float), st);
+    return kxk_dyn_forward(guidance, att, x, sparse, out, history, B, C, H, W, K, n_iter, ws, st);
+}
+
+int cspn2d_backward_kxk_dyn_f32(const float* guidance, const float* att, const float* x, const float* sparse, const float* history, size_t history_bytes,
+                                const float* grad_out, float* grad_guidance, float* grad_att, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
+                                void* ws, size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_backward_kxk_dyn_f32";
+    if (!guidance || !x || !grad_out || (!att && n_iter > 0)) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = kxk_dyn_check_shape(what, B, C, H, W, K, n_iter)) return e;
+    const size_t vb = kxk_values_bytes(B, C, H, W), pb = vb / C, gb = pb * (K * K - 1), ab = pb * (size_t)n_iter * (K / 2 + 1);
+    const size_t hb = kxk_dyn_history_bytes(B, C, H, W, n_iter);
+    const bool grads = grad_guidance || grad_att;
+    if (grads && hb && (!history || history_bytes < hb)) {
+        set_error("%s: the guidance and attention gradients need the forward's history: need %zu bytes, got %zu", what, hb, history ? history_bytes : 0);
+        return CSPN_E_BADARG;
+    }
+    const size_t need = cspn2d_backward_kxk_dyn_workspace_bytes(B, C, H, W, K, n_iter, sparse != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    const size_t wb = need ? ws_bytes : 0, hbu = grads ? hb : 0;
+    if ((grad_guidance && ((void*)grad_guidance == (void*)grad_x || (void*)grad_guidance == (void*)grad_att)) || (grad_att && (void*)grad_att == (void*)grad_x)) {
+        set_error("%s: grad_guidance, grad_att and grad_x must not alias", what);
+        return CSPN_E_BADARG;
+    }
+    if (kxk_overlaps(grad_guidance, gb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {history, hbu}, {grad_out, vb}, {grad_att, ab}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_att, ab, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {history, hbu}, {grad_out, vb}, {grad_x, vb}, {ws, wb}}) ||
+        kxk_overlaps(grad_x, vb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {history, hbu}, {grad_out, vb}, {ws, wb}}) ||
+        kxk_overlaps(ws, wb, {{guidance, gb}, {att, ab}, {x, vb}, {sparse, pb}, {history, hbu}, {grad_out, vb}})) {
+        set_error("%s: grad_guidance, grad_att, grad_x and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grads && !grad_x) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_iter == 0) return identity_backward(grad_x, grad_out, vb / sizeof(float), grad_guidance, gb, st);   // no attention plane exists
+    return kxk_dyn_backward(guidance, att, x, sparse, history, grad_out, grad_guidance, grad_att, grad_x, B, C, H, W, K, n_iter, ws, st);
+}
+
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip) ----
 size_t cspn2d_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
     if (!kxk_norm_shape_ok(B, C, sparse_C, H, W, K, n_iter) || n_iter < 1) return 0;

@@ -165,6 +165,32 @@ int kxk_assemble_backward_pin(const void* guid, int dtype, const float* blur, co
                               const float* hist, const float* gout, void* gg, float* gx, float* gc, int B, int C, int sparse_C, int H, int W, int K, int D,
                               int n_iter, int norm, void* ws, hipStream_t st);
 
+// ---- K x K propagation with per-step attention, K = 3, 5 or 7 (cspn2d_kxk_dyn.hip): guid [N][K*K-1][H][W] raw and centre-sited, att
+// [N][n (R+1)][H][W] used as given (channel s (R+1) + r: r = 0 the pixel's own term of step s, r >= 1 its ring r), values [N][C][H][W] on the
+// shared guid / att, sparse NULL or [N][H][W] (pinned where > 0 before every step; the result is not pinned).  float32 throughout ----
+// levels of kxk_level_floats(N C H W) floats in the forward's workspace: the pinned H_0 (with sparse), then the ping-pong pair unless the levels
+// go to a history
+inline int kxk_dyn_forward_levels(int n_iter, bool sparse, bool history) {
+    return n_iter <= 0 ? 0 : (sparse ? 1 : 0) + (history ? 0 : (n_iter >= 3 ? 2 : n_iter - 1));
+}
+// the backward's workspace, in bytes from its start (every part 256-byte aligned): A_1 .. A_{n-1}, the 2 R ring-sum planes of the raw gates
+// ([N][2 R][H][W]), and with sparse the pinned H_0
+struct KxkDynBackwardWs {
+    size_t rings, h0, bytes;
+    KxkDynBackwardWs(int N, int C, int H, int W, int K, int n_iter, bool sparse) {
+        const size_t HW = (size_t)H * W, L = (size_t)N * C * HW;
+        rings = round256(sizeof(float) * L * (size_t)(n_iter - 1));
+        h0 = rings + round256(sizeof(float) * (size_t)N * 2 * (K / 2) * HW);
+        bytes = h0 + (sparse ? round256(sizeof(float) * L) : 0);
+    }
+};
+// hist: NULL, or the pinned levels 1 .. n-1, level t at hist + (t - 1) N C H W
+int kxk_dyn_forward(const float* guid, const float* att, const float* x, const float* sparse, float* out, float* hist, int N, int C, int H, int W, int K,
+                    int n_iter, void* ws, hipStream_t st);
+// gg (summed over C), ga and gx may each be NULL; gg / ga need hist where n_iter >= 2
+int kxk_dyn_backward(const float* guid, const float* att, const float* x, const float* sparse, const float* hist, const float* gout, float* gg, float* ga,
+                     float* gx, int N, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
+
 // ---- non-local propagation with learned offsets, K = 3 (cspn2d_nl.hip): aff [B][KK][H][W] used as given, off [B][2 KK][H][W] (dy_k, dx_k
 // interleaved), values [B][C][H][W] on shared aff / off, sparse NULL or [B][H][W] (pinned where > 0).  Neighbour k's base is (t - R, l - R):
 // the deformable convolution's sign, the opposite of the K x K engine's.  adt / odt: the storage types of aff (and gaff) and of off (and goff),

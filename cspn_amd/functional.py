@@ -631,6 +631,92 @@ def cspn2d_backward_kxk_absnorm(guide, x, grad_out, kernel_size, n_iter, history
     return _kxk_backward(guide, x, grad_out, kernel_size, n_iter, history, need_guide, need_x, "_absnorm")
 
 
+# ---- K x K propagation with per-step attention, K = 3, 5 or 7 (cspn2d_kxk_dyn.hip) ----
+def _dyn_args(guidance, att, x, sparse, kernel_size, n_iter, extra=()):
+    """shapes and dtypes of the cspn2d_*_kxk_dyn calls -> (g, a, h, s, K, B, C, H, W, n) + the extra tensors, prepared.  float32 only: any other
+    dtype is a TypeError"""
+    K = _check_kernel_size(kernel_size, 4)
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError("n_iter must be an int >= 0 (got %r)" % (n_iter,))
+    n, R = int(n_iter), K // 2
+    named = [(guidance, "guidance"), (att, "att"), (x, "x")] + ([(sparse, "sparse")] if sparse is not None else []) + list(extra)
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32 (got %s): the per-step attention contract has no 16-bit kernels" % (name, t.dtype))
+    if guidance.dim() != 4 or guidance.shape[1] != K * K - 1:
+        raise ValueError("guidance must be [B,%d,H,W] for kernel_size %d, got %s" % (K * K - 1, K, tuple(guidance.shape)))
+    B, _, H, W = guidance.shape
+    if tuple(att.shape) != (B, n * (R + 1), H, W):
+        raise ValueError("att must be [B,n_iter*(K//2+1),H,W] = %s, got %s" % ((B, n * (R + 1), H, W), tuple(att.shape)))
+    if x.dim() != 4 or x.shape[0] != B or tuple(x.shape[2:]) != (H, W) or x.shape[1] < 1:
+        raise ValueError("x has shape %s, expected (B,C,H,W) = (%d,C,%d,%d)" % (tuple(x.shape), B, H, W))
+    C = x.shape[1]
+    if sparse is not None and tuple(sparse.shape) != (B, 1, H, W):
+        raise ValueError("sparse must be [B,1,H,W] = %s, got %s" % ((B, 1, H, W), tuple(sparse.shape)))
+    for t, name in extra:
+        if tuple(t.shape) != (B, C, H, W):
+            raise ValueError("%s must be a tensor of shape %s" % (name, (B, C, H, W)))
+    ts = [t if n == 0 and not extra else _prep(t, name) for t, name in named]   # (a forward of no step returns x, wherever it lives)
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("all tensors must live on the same device")
+    g, a, h = ts[:3]
+    s = ts[3] if sparse is not None else None
+    return (g, a, h, s, K, B, C, H, W, n) + tuple(ts[4 if sparse is not None else 3:])
+
+
+def _dyn_history_bytes(B, C, H, W, K, n):
+    """H~_1 .. H~_{n-1}: cspn2d_kxk_history_bytes, which knows K = 5 and 7; for K = 3 the same count from the query that does"""
+    return _lib.symbol("cspn2d_kxk_history_bytes" if K != 3 else "cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
+
+
+def cspn2d_forward_kxk_dyn(guidance, att, x, kernel_size, n_iter, sparse=None, return_history=False):
+    """K x K propagation with per-step attention (cspn2d_forward_kxk_dyn_f32), K = kernel_size in {3, 5, 7}, R = K // 2: guidance [B,K*K-1,H,W] raw,
+    any sign, read at the pixel, in the gate channel order of cspn2d_forward_kxk; att [B,n_iter*(R+1),H,W] used as given, channel t*(R+1) + r:
+    r = 0 the pixel's own term of step t (it only enters the divisor), r >= 1 ring r = max(|dy|, |dx|) of step t; x [B,C,H,W], the C channels share
+    guidance and att; sparse [B,1,H,W] or None, pinned where > 0 before every step (the result is not pinned):
+        w^_k = att[t, ring(k)] * g_k      D = att[t, 0] + sum_k |w^_k|      w_k = w^_k / D      c = 1 - sum_k w_k
+        H <- c * Ht + sum_k w_k * Ht(p + off_k),   Ht = sparse where sparse > 0 else H,   H_0 = x, n_iter times; zero outside the image
+    No modulated or normalised gate is stored.  D = 0 gives the statement's non-finite pattern.  return_history: (out, history) with the pinned
+    levels 1 .. n-1 for cspn2d_backward_kxk_dyn.  n_iter == 0 returns x.  float32 only: any other dtype is a TypeError.  Bitwise reproducible."""
+    g, a, h, s, K, B, C, H, W, n = _dyn_args(guidance, att, x, sparse, kernel_size, n_iter)
+    if n == 0:
+        return (x, None) if return_history else x
+    out = torch.empty_like(h)
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    hist, hb = None, 0
+    if return_history:   # the levels go to the history; the workspace keeps the pinned H_0 alone
+        with torch.cuda.device(g.device):
+            hb = _dyn_history_bytes(B, C, H, W, K, n)
+        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    _launch("cspn2d_forward_kxk_dyn_f32", g.device, (_ptr(g), _ptr(a), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
+            ("cspn2d_kxk_dyn_workspace_bytes", B, C, H, W, K, n, int(s is not None), int(return_history)))
+    return (out, hist) if return_history else out
+
+
+def cspn2d_backward_kxk_dyn(guidance, att, x, grad_out, kernel_size, n_iter, sparse=None, history=None, need_guidance=True, need_att=True, need_x=True):
+    """Gradient of cspn2d_forward_kxk_dyn -> (dL/dguidance [B,K*K-1,H,W] and dL/datt [B,n_iter*(R+1),H,W], each summed over the C channels, dL/dx
+    [B,C,H,W]), None where not asked for; cspn2d_backward_kxk_dyn_f32.  sparse has no gradient.  The adjoint steps read att_r A / D from one staged
+    tile per ring, the gradient pass keeps the raw gates and their K*K-1 sums in registers over all steps and writes every element once: no
+    dL/dw tensor exists.  history: what cspn2d_forward_kxk_dyn(..., return_history=True) returned; None runs that forward first where dL/dguidance
+    or dL/datt needs it (n_iter >= 2).  No atomics: run-to-run bitwise."""
+    g, a, h, s, K, B, C, H, W, n, go = _dyn_args(guidance, att, x, sparse, kernel_size, n_iter, ((grad_out, "grad_out"),))
+    gg = torch.empty_like(g) if need_guidance else None
+    ga = torch.empty_like(a) if need_att else None
+    gx = torch.empty_like(h) if need_x else None
+    if not (need_guidance or need_att or need_x) or h.numel() == 0:
+        return (gg.zero_() if gg is not None else None), ga, gx
+    if (need_guidance or need_att) and n >= 2 and history is None:
+        _, history = cspn2d_forward_kxk_dyn(g, a, h, K, n, s, return_history=True)
+    hb = history.numel() * history.element_size() if history is not None else 0
+    _launch("cspn2d_backward_kxk_dyn_f32", g.device,
+            (_ptr(g), _ptr(a), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(ga), _ptr(gx), B, C, H, W, K, n),
+            ("cspn2d_backward_kxk_dyn_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
+    return gg, ga, gx
+
+
 class _AffinityPropagateKxKFunction(torch.autograd.Function):
     """2D K x K, any C on shared gates: the forward keeps H_1 .. H_{n-1}, the backward is one cspn2d_backward_kxk_f32 call"""
 

@@ -55,7 +55,8 @@ extern "C" {
                               *    (cspn_guidance_head_g16, cspn_guidance_head_backward_g16), fp16 / bf16 gates and guides on the 3D entry points of the
                               *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16), the backward of the 3D normalising / masked modes
                               *    (cspn3d_backward_norm_f32), dilated K x K propagation (cspn2d_*_kxk_{norm,assemble}_dil),
-                              *    K x K propagation pinned to the measured depth with a confidence (cspn2d_*_kxk_{norm,assemble}_pin) */
+                              *    K x K propagation pinned to the measured depth with a confidence (cspn2d_*_kxk_{norm,assemble}_pin),
+                              *    K x K propagation with per-step attention (cspn2d_*_kxk_dyn_*) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -742,6 +743,45 @@ int cspn2d_backward_kxk_absnorm_f32(const float* guide, const float* x, const fl
 int cspn2d_backward_kxk_absnorm_g16(const void* guide, int gate_dtype, const float* x, const float* history, size_t history_bytes,
                                     const float* grad_out, void* grad_guide, float* grad_x, int B, int C, int H, int W, int K, int n_iter,
                                     void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- K x K propagation with per-step attention (the "dynamic, centre-sited" contract), K = 3, 5 or 7, R = K / 2, KK = K*K - 1, float32,
+ * contiguous NCHW.  Where every contract above uses the same affinities on every step, here a small head emits an attention for every step
+ * and every distance ring of the neighbourhood, plus one for the pixel itself; the affinities are re-weighted and re-normalised on each step.
+ *   guidance [B,KK,H,W]        raw, any sign, centre-sited (read at p), in the channel order of the NONE op: off_k = (R - t, R - l)
+ *   att      [B,n (R+1),H,W]   used as given, any sign; channel t (R+1) + r: r = 0 is the pixel's own term of step t (it only enters the
+ *                              divisor), r >= 1 is ring r of step t, ring(k) = max(|dy|, |dx|) of off_k
+ *   x / out  [B,C,H,W]         the C channels share guidance and att
+ *   sparse   [B,1,H,W] or NULL pinned where > 0: the level is pinned before every step, out = H_n is not
+ * With m = [sparse > 0], H_0 = x, Ht_t = (1 - m) H_t + m sparse:
+ *     wh_k = att_{t,ring(k)}(p) g_k(p)     D_t(p) = att_{t,0}(p) + sum_k |wh_k|     w_k = wh_k / D_t     c_t = 1 - sum_k w_k
+ *     H_{t+1}(p) = c_t(p) Ht_t(p) + sum_k w_k(p) Ht_t(p + off_k)
+ *   a neighbour outside the image contributes 0 (its w_k still counts in D and c).  The sum runs on wh_k in channel order and is scaled by
+ *   1 / D_t once, after it; c_t is formed as (att_{t,0} + sum_k (|wh_k| - wh_k)) / D_t.
+ * Backward, A_n = grad_out, e_k = sum_c A_{t+1}(p) (Ht_t(p + off_k) - Ht_t(p)), T = sum_k w_k e_k:
+ *     At_t(q) = c_t(q) A_{t+1}(q) + sum_k wh_k(q') (A_{t+1} / D_t)(q'),  q' = q - off_k      A_t = (1 - m) At_t      grad_x = A_0
+ *     dL/dwh_k = (e_k - sign(wh_k) T) / D_t      grad_att_{t,0} = -T / D_t      grad_att_{t,r} = sum_{k in ring r} g_k dL/dwh_k
+ *     grad_guidance_k = sum_t att_{t,ring(k)} dL/dwh_k                                       sign(0) = 0; sparse has no gradient
+ * D_t = 0 gives the non-finite pattern of these formulas; nothing is guarded.  No modulated or normalised gate and no gradient of one is stored:
+ * guidance and att are the only gate-sized tensors.  No atomics: forward and backward are run-to-run bitwise.
+ * history (optional in the forward): Ht_1 .. Ht_{n-1}, [n-1][B][C][H][W], (n_iter - 1) B C H W floats -- cspn2d_kxk_history_bytes for K = 5 / 7,
+ *   the same count (cspn2d_kxk_norm_history_bytes) for K = 3; grad_guidance and grad_att need it where n_iter >= 2.
+ * Workspaces: cspn2d_kxk_dyn_workspace_bytes(..., has_sparse, keep_history) holds the pinned H_0 (with sparse) and, without a history, the
+ *   ping-pong levels; cspn2d_backward_kxk_dyn_workspace_bytes(..., has_sparse) holds A_1 .. A_{n-1}, 2 R planes [B,H,W] of ring sums of the
+ *   guidance and (with sparse) the pinned H_0.  Both are pure host arithmetic, multiples of 256, and 0 wherever the arguments are rejected
+ *   (K not 3 / 5 / 7, a size <= 0, n_iter <= 0, a tensor of more than 2^31 - 1 elements).
+ * grad_guidance (summed over C), grad_att and grad_x may each be NULL.  n_iter == 0: out = x, grad_x = grad_out, grad_guidance = 0.
+ * Arguments, ranges, alignment (workspace 256 bytes; any tensor alignment is taken, 16-byte aligned tensors with W % 4 == 0 run the vector
+ * kernels) and error codes as the kxk_absnorm entry points; att, grad_att and sparse take part in the aliasing checks.  B n (R+1) H W beyond
+ * 2^31 - 1 is CSPN_E_UNSUPPORTED; the attention planes are addressed in size_t throughout. */
+size_t cspn2d_kxk_dyn_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse, int keep_history);
+int cspn2d_forward_kxk_dyn_f32(const float* guidance, const float* att, const float* x, const float* sparse, float* out, float* history,
+                               size_t history_bytes, int B, int C, int H, int W, int K, int n_iter,
+                               void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_kxk_dyn_workspace_bytes(int B, int C, int H, int W, int K, int n_iter, int has_sparse);
+int cspn2d_backward_kxk_dyn_f32(const float* guidance, const float* att, const float* x, const float* sparse, const float* history,
+                                size_t history_bytes, const float* grad_out, float* grad_guidance, float* grad_att, float* grad_x,
+                                int B, int C, int H, int W, int K, int n_iter,
+                                void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
