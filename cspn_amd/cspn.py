@@ -170,53 +170,70 @@ class Affinity_Propagate3d(nn.Module):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type)
 
 
-class _CSPN2dKxKNormFunction(torch.autograd.Function):
-    """Affinity_PropagateKxK with prop_kernel 5 / 7: the forward keeps H_1 .. H_{n-1} where the guidance gradient needs them, the
-    backward is one cspn2d_backward_kxk_norm_f32 call (the fold is recomputed there)"""
+class _CSPN2dKxKFoldFunction(torch.autograd.Function):
+    """The folded and the assembling K x K contracts under autograd, pinned or not (F._fold_forward / F._fold_backward): one forward engine call
+    that keeps the history where a gradient that reads it is needed -- dL/dguidance or dL/dpin_conf at n_iter >= 2 (both read the gradient of the
+    folded gates), dL/dconf always (it reads the collected levels) -- and one backward engine call.  The four classes below say which inputs
+    they have; their forward's parameter list is what autograd numbers needs_input_grad by, always in this order: guidance, blur_depth,
+    sparse_depth, [pin_conf,] [conf, steps,] kernel_size, n_iter, norm_type, dilation."""
+
+    @staticmethod
+    def run(ctx, guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, dilation):
+        """assemble: None or (conf, steps)"""
+        ctx.pinned, ctx.steps, ctx.args, ctx.dilation = pinned, assemble and assemble[1], (kernel_size, n_iter, norm_type), dilation
+        need = ctx.needs_input_grad
+        keep = ((need[0] or (pinned and need[3])) and n_iter >= 2) or (assemble is not None and need[3 + pinned])
+        out = F._fold_forward(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, keep, dilation)
+        out, hist = out if keep else (out, None)
+        ctx.save_for_backward(guidance, blur_depth, sparse_depth, *((pin_conf,) if pinned else ()), *(assemble[:1] if assemble else ()), hist)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        guidance, blur_depth, sparse_depth, *rest, hist = ctx.saved_tensors
+        pinned = ctx.pinned
+        pin_conf = rest.pop(0) if pinned else None
+        assemble = (rest.pop(0), ctx.steps) if ctx.steps is not None else None
+        need = ctx.needs_input_grad
+        # (a flag read at the position of an input the class does not have is dropped by F._fold_backward, which knows the contract)
+        gg, gh, gc, gs, gp = F._fold_backward(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, grad_out, *ctx.args, hist, ctx.dilation,
+                                              need_guidance=need[0], need_blur=need[1], need_conf=need[3 + pinned], need_sparse=need[2], need_pin=need[3])
+        grads = (gg, gh, gs) + ((gp,) if pinned else ()) + ((gc,) if assemble else ())
+        return grads + (None,) * (len(need) - len(grads))
+
+
+class _CSPN2dKxKNormFunction(_CSPN2dKxKFoldFunction):
+    """Affinity_PropagateKxK without a pin_conf: cspn2d_forward_kxk_norm keeping H_1 .. H_{n-1}, cspn2d_backward_kxk_norm (the fold is recomputed
+    there)"""
 
     @staticmethod
     def forward(ctx, guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, dilation):
-        ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = kernel_size, n_iter, norm_type, dilation
-        hist = None
-        if ctx.needs_input_grad[0] and n_iter >= 2:
-            out, hist = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, return_history=True, dilation=dilation)
-        else:
-            out = F.cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth, kernel_size, n_iter, norm_type, dilation=dilation)
-        ctx.save_for_backward(guidance, blur_depth, sparse_depth, hist)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        guidance, blur_depth, sparse_depth, hist = ctx.saved_tensors
-        gg, gh = F.cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type, hist,
-                                            need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1], dilation=ctx.dilation)
-        return gg, gh, None, None, None, None, None
+        return _CSPN2dKxKFoldFunction.run(ctx, guidance, blur_depth, sparse_depth, None, False, None, kernel_size, n_iter, norm_type, dilation)
 
 
-class _CSPN2dKxKNormPinFunction(torch.autograd.Function):
-    """Affinity_PropagateKxK with a pin_conf, every prop_kernel: one cspn2d_forward_kxk_norm_pin call that keeps H_1 .. H_{n-1} where dL/dguidance
-    or dL/dpin_conf will need them (both read the gradient of the folded gates), one cspn2d_backward_kxk_norm_pin call"""
+class _CSPN2dKxKNormPinFunction(_CSPN2dKxKFoldFunction):
+    """Affinity_PropagateKxK with a pin_conf, every prop_kernel: cspn2d_forward_kxk_norm_pin keeping H_1 .. H_{n-1}, cspn2d_backward_kxk_norm_pin"""
 
     @staticmethod
     def forward(ctx, guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, dilation):
-        ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = kernel_size, n_iter, norm_type, dilation
-        hist = None
-        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and n_iter >= 2:
-            out, hist = F.cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, return_history=True,
-                                                      dilation=dilation)
-        else:
-            out = F.cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, kernel_size, n_iter, norm_type, dilation=dilation)
-        ctx.save_for_backward(guidance, blur_depth, sparse_depth, pin_conf, hist)
-        return out
+        return _CSPN2dKxKFoldFunction.run(ctx, guidance, blur_depth, sparse_depth, pin_conf, True, None, kernel_size, n_iter, norm_type, dilation)
+
+
+class _CSPN2dKxKAssembleFunction(_CSPN2dKxKFoldFunction):
+    """one kernel size of Affinity_PropagateAssemble: cspn2d_forward_kxk_assemble keeping H_1 .. H_n, cspn2d_backward_kxk_assemble"""
 
     @staticmethod
-    def backward(ctx, grad_out):
-        guidance, blur_depth, sparse_depth, pin_conf, hist = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        gg, gh, gs, gp = F.cspn2d_backward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type,
-                                                        hist, need_guidance=need[0], need_blur=need[1], need_sparse=need[2], need_pin=need[3],
-                                                        dilation=ctx.dilation)
-        return gg, gh, gs, gp, None, None, None, None
+    def forward(ctx, guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, dilation):
+        return _CSPN2dKxKFoldFunction.run(ctx, guidance, blur_depth, sparse_depth, None, False, (conf, steps), kernel_size, n_iter, norm_type, dilation)
+
+
+class _CSPN2dKxKAssemblePinFunction(_CSPN2dKxKFoldFunction):
+    """one kernel size of Affinity_PropagateAssemble with a pin_conf: cspn2d_forward_kxk_assemble_pin keeping H_1 .. H_n,
+    cspn2d_backward_kxk_assemble_pin"""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type, dilation):
+        return _CSPN2dKxKFoldFunction.run(ctx, guidance, blur_depth, sparse_depth, pin_conf, True, (conf, steps), kernel_size, n_iter, norm_type, dilation)
 
 
 class Affinity_PropagateKxK(nn.Module):
@@ -268,58 +285,6 @@ class Affinity_PropagateKxK(nn.Module):
     def extra_repr(self):
         return "prop_time=%d, prop_kernel=%d, norm_type=%r" % (self.prop_time, self.prop_kernel, self.norm_type) \
             + (", dilation=%d" % self.dilation if self.dilation != 1 else "")
-
-
-class _CSPN2dKxKAssembleFunction(torch.autograd.Function):
-    """one kernel size of Affinity_PropagateAssemble: one cspn2d_forward_kxk_assemble call that keeps H_1 .. H_n where dL/dguidance or dL/dconf
-    will need them, one cspn2d_backward_kxk_assemble call"""
-
-    @staticmethod
-    def forward(ctx, guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, dilation):
-        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = steps, kernel_size, n_iter, norm_type, dilation
-        hist = None
-        if (ctx.needs_input_grad[0] and n_iter >= 2) or ctx.needs_input_grad[3]:
-            out, hist = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, return_history=True,
-                                                      dilation=dilation)
-        else:
-            out = F.cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, dilation=dilation)
-        ctx.save_for_backward(guidance, blur_depth, sparse_depth, conf, hist)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        guidance, blur_depth, sparse_depth, conf, hist = ctx.saved_tensors
-        gg, gh, gc = F.cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, ctx.steps, grad_out, ctx.kernel_size, ctx.n_iter, ctx.norm_type,
-                                                    hist, need_guidance=ctx.needs_input_grad[0], need_blur=ctx.needs_input_grad[1],
-                                                    need_conf=ctx.needs_input_grad[3], dilation=ctx.dilation)
-        return gg, gh, None, gc, None, None, None, None, None
-
-
-class _CSPN2dKxKAssemblePinFunction(torch.autograd.Function):
-    """one kernel size of Affinity_PropagateAssemble with a pin_conf: one cspn2d_forward_kxk_assemble_pin call that keeps H_1 .. H_n where
-    dL/dguidance, dL/dpin_conf or dL/dconf will need them, one cspn2d_backward_kxk_assemble_pin call"""
-
-    @staticmethod
-    def forward(ctx, guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type, dilation):
-        ctx.steps, ctx.kernel_size, ctx.n_iter, ctx.norm_type, ctx.dilation = steps, kernel_size, n_iter, norm_type, dilation
-        hist = None
-        if ((ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and n_iter >= 2) or ctx.needs_input_grad[4]:
-            out, hist = F.cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type,
-                                                          return_history=True, dilation=dilation)
-        else:
-            out = F.cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, kernel_size, n_iter, norm_type,
-                                                    dilation=dilation)
-        ctx.save_for_backward(guidance, blur_depth, sparse_depth, pin_conf, conf, hist)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        guidance, blur_depth, sparse_depth, pin_conf, conf, hist = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        gg, gh, gc, gs, gp = F.cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, ctx.steps, grad_out, ctx.kernel_size,
-                                                                ctx.n_iter, ctx.norm_type, hist, need_guidance=need[0], need_blur=need[1],
-                                                                need_conf=need[4], need_sparse=need[2], need_pin=need[3], dilation=ctx.dilation)
-        return gg, gh, gs, gp, gc, None, None, None, None, None
 
 
 class Affinity_PropagateAssemble(nn.Module):

@@ -1,6 +1,7 @@
 """Functional front-end over the C ABI: tensors in, tensor out, work enqueued on
 torch's current HIP stream.  PyTorch is plumbing here (device memory + streams);
 all arithmetic happens in libcspn_amd.so."""
+import collections
 import ctypes
 
 import torch
@@ -58,6 +59,18 @@ def _workspace(nbytes, device):
 
 def _ptr(t):
     return t.data_ptr() if t is not None else None
+
+
+def _history(query, device, *args):
+    """the history a forward writes its levels to, sized by the query `query`(*args) -> (a float32 tensor of at least one element, its bytes as
+    the engine is told them)"""
+    with torch.cuda.device(device):
+        hb = _lib.symbol(query)(*args)
+    return torch.empty(max(hb // 4, 1), dtype=torch.float32, device=device), hb
+
+
+def _history_bytes(history):
+    return history.numel() * history.element_size() if history is not None else 0
 
 
 def _launch(name, device, args, ws_query=None, what=None):
@@ -567,14 +580,10 @@ def _kxk_forward(gate, x, kernel_size, n_iter, return_history, contract):
         return (x, None) if return_history else x
     g, dt, h, K, N, C, H, W = _kxk_args(gate, x, kernel_size, gate_name="guide" if contract else "gate")
     out = torch.empty_like(h)
-    hist = None
     if out.numel() == 0:
         return (out, None) if return_history else out
-    hb = 0
-    if return_history:   # the levels go to the history: no workspace
-        with torch.cuda.device(g.device):
-            hb = _lib.symbol("cspn2d_kxk_history_bytes")(N, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    # with a history the levels go there: no workspace
+    hist, hb = _history("cspn2d_kxk_history_bytes", g.device, N, C, H, W, K, n) if return_history else (None, 0)
     args = (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(out), _ptr(hist), hb, N, C, H, W, K, n)
     _launch("cspn2d_forward_kxk%s_%s" % (contract, "f32" if dt is None else "g16"), g.device, args + ((None, 0) if return_history else ()),
             None if return_history else ("cspn2d_kxk_workspace_bytes", N, C, H, W, K, n))
@@ -603,9 +612,8 @@ def _kxk_backward(gate, x, grad_out, kernel_size, n_iter, history, need_gate, ne
         return (gg.zero_() if gg is not None else None), gx
     if need_gate and n >= 2 and history is None:
         _, history = _kxk_forward(g, h, K, n, True, contract)
-    hb = history.numel() * history.element_size() if history is not None else 0
     _launch("cspn2d_backward_kxk%s_%s" % (contract, "f32" if dt is None else "g16"), g.device,
-            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gx), N, C, H, W, K, n),
+            (_ptr(g), *(() if dt is None else (dt,)), _ptr(h), _ptr(history), _history_bytes(history), _ptr(go), _ptr(gg), _ptr(gx), N, C, H, W, K, n),
             ("cspn2d_backward_kxk%s_workspace_bytes" % contract, N, C, H, W, K, n))
     return gg, gx
 
@@ -666,9 +674,9 @@ def _dyn_args(guidance, att, x, sparse, kernel_size, n_iter, extra=()):
     return (g, a, h, s, K, B, C, H, W, n) + tuple(ts[4 if sparse is not None else 3:])
 
 
-def _dyn_history_bytes(B, C, H, W, K, n):
+def _dyn_history_query(K):
     """H~_1 .. H~_{n-1}: cspn2d_kxk_history_bytes, which knows K = 5 and 7; for K = 3 the same count from the query that does"""
-    return _lib.symbol("cspn2d_kxk_history_bytes" if K != 3 else "cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
+    return "cspn2d_kxk_history_bytes" if K != 3 else "cspn2d_kxk_norm_history_bytes"
 
 
 def cspn2d_forward_kxk_dyn(guidance, att, x, kernel_size, n_iter, sparse=None, return_history=False):
@@ -686,11 +694,8 @@ def cspn2d_forward_kxk_dyn(guidance, att, x, kernel_size, n_iter, sparse=None, r
     out = torch.empty_like(h)
     if out.numel() == 0:
         return (out, None) if return_history else out
-    hist, hb = None, 0
-    if return_history:   # the levels go to the history; the workspace keeps the pinned H_0 alone
-        with torch.cuda.device(g.device):
-            hb = _dyn_history_bytes(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
+    # with a history the levels go there; the workspace keeps the pinned H_0 alone
+    hist, hb = _history(_dyn_history_query(K), g.device, B, C, H, W, K, n) if return_history else (None, 0)
     _launch("cspn2d_forward_kxk_dyn_f32", g.device, (_ptr(g), _ptr(a), _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
             ("cspn2d_kxk_dyn_workspace_bytes", B, C, H, W, K, n, int(s is not None), int(return_history)))
     return (out, hist) if return_history else out
@@ -710,9 +715,8 @@ def cspn2d_backward_kxk_dyn(guidance, att, x, grad_out, kernel_size, n_iter, spa
         return (gg.zero_() if gg is not None else None), ga, gx
     if (need_guidance or need_att) and n >= 2 and history is None:
         _, history = cspn2d_forward_kxk_dyn(g, a, h, K, n, s, return_history=True)
-    hb = history.numel() * history.element_size() if history is not None else 0
     _launch("cspn2d_backward_kxk_dyn_f32", g.device,
-            (_ptr(g), _ptr(a), _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(ga), _ptr(gx), B, C, H, W, K, n),
+            (_ptr(g), _ptr(a), _ptr(h), _ptr(s), _ptr(history), _history_bytes(history), _ptr(go), _ptr(gg), _ptr(ga), _ptr(gx), B, C, H, W, K, n),
             ("cspn2d_backward_kxk_dyn_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
     return gg, ga, gx
 
@@ -840,79 +844,23 @@ def _kxk_entry(stem, dt, dilation):
     return stem + "_dil", (0 if dt is None else dt,), (dilation,)
 
 
-def _kxk_norm_args(guidance, blur_depth, sparse_depth, extra=()):
-    g, dt = _prep_gate(guidance, "guidance")
-    h = _prep_value(blur_depth, "blur_depth")
-    s = _prep_value(sparse_depth, "sparse_depth") if sparse_depth is not None else None
-    rest = [_prep_value(t, name, tuple(h.shape)) for t, name in extra]
-    if any(t.device != g.device for t in [h] + ([s] if s is not None else []) + rest):
-        raise ValueError("all tensors must live on the same device")
-    return (g, dt, h, s) + tuple(rest)
-
-
-def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False, dilation=1):
-    """Affinity_Propagate's forward (reference cspn.py:42-144) over a kernel_size x kernel_size neighbourhood: guidance [B,K*K-1,H,W] raw
-    (channel k = the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour
-    (K//2 - t, K//2 - l)), blur_depth [B,C,H,W] on the shared guidance, sparse_depth None, [B,1,H,W] or [B,C,H,W] -> [B,C,H,W]
-    (cspn2d_forward_kxk_norm_f32).  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_norm.  n_iter == 0
-    returns blur_depth itself.  guidance may be float16 / bfloat16 (cspn2d_forward_kxk_norm_g16, K = 3 included: the fold widens it exactly,
-    w' stays float32; out is float32 and bitwise the float32 call on guidance.float()); 16-bit blur_depth / sparse_depth are widened with
-    one cast.  dilation 1 or 2: the neighbour of gate (t, l) is dilation * (K//2 - t, K//2 - l) (dilated CSPN++; cspn2d_forward_kxk_norm_dil)."""
-    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
+def _pin_entry(stem, dt, dilation):
+    """the pinned entry point of a folded / assembling call: one for every guidance dtype (gate_dtype 0: float32) and every dilation"""
     check_dilation(dilation)
-    n = int(n_iter)
-    if n == 0:
-        return (blur_depth, None) if return_history else blur_depth
-    g, dt, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
-    out = torch.empty_like(h)
-    hist = None
-    if out.numel() == 0:
-        return (out, None) if return_history else out
-    hb = 0
-    if return_history:
-        with torch.cuda.device(g.device):
-            hb = _lib.symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-    # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
-    name, dta, dil = _kxk_entry("cspn2d_forward_kxk_norm", dt, dilation)
-    _launch(name, g.device, (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_kxk_norm_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
-    return (out, hist) if return_history else out
+    return stem + "_pin", (0 if dt is None else dt,), (dilation,)
 
 
-def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
-                             need_guidance=True, need_blur=True, dilation=1):
-    """Gradient of cspn2d_forward_kxk_norm -> (dL/dguidance [B,K*K-1,H,W] summed over the C channels or None, dL/dblur_depth [B,C,H,W]
-    or None); sparse_depth gets none (cspn.py uses its sign only).  cspn2d_backward_kxk_norm_f32.  history: what
-    cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it.
-    A float16 / bfloat16 guidance (cspn2d_backward_kxk_norm_g16): dL/dblur_depth is float32 and bitwise the float32 call's, dL/dguidance comes
-    back in the guidance's dtype, the float32 value rounded once.  dilation: that of the forward (cspn2d_backward_kxk_norm_dil)."""
-    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
-    check_dilation(dilation)
-    if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
-        raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
-    g, dt, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
-    n = int(n_iter)
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    if not (need_guidance or need_blur):
-        return gg, gh
-    if h.numel() == 0:
-        return (gg.zero_() if gg is not None else None), gh
-    if need_guidance and n >= 2 and history is None:
-        _, history = cspn2d_forward_kxk_norm(g, h, s, K, n, norm_type, return_history=True, dilation=dilation)
-    hb = history.numel() * history.element_size() if history is not None else 0
-    name, dta, dil = _kxk_entry("cspn2d_backward_kxk_norm", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
-    return gg, gh
+def _pin_check(sparse_depth, pin_conf):
+    """sparse_depth and pin_conf: both given, the same shape, [B,1,H,W] or [B,C,H,W] (sparse_depth's shape itself is checked by _kxk_norm_shape)"""
+    if sparse_depth is None or pin_conf is None:
+        raise ValueError("the pinned contract needs a sparse_depth and a pin_conf (a pin_conf without a sparse_depth pins nothing)")
+    if not isinstance(pin_conf, torch.Tensor) or not isinstance(sparse_depth, torch.Tensor) or tuple(pin_conf.shape) != tuple(sparse_depth.shape):
+        raise ValueError("pin_conf must be a tensor of sparse_depth's shape %s ([B,1,H,W] or [B,C,H,W]), got %s"
+                         % (tuple(getattr(sparse_depth, "shape", ())), tuple(getattr(pin_conf, "shape", ()))))
 
 
-# ---- assembling K x K levels per pixel (CSPN++): out = sum_j conf_j H_{s_j} over the levels H_t of cspn2d_forward_kxk_norm, H_0 = blur_depth
-# (cspn2d_*_kxk_assemble_f32 / _g16) ----
 def _assemble_steps(steps, n_iter):
-    """steps: ints, strictly increasing, steps[0] >= 0, steps[-1] == n_iter >= 1 -> (tuple, the ctypes array the engine reads)"""
+    """steps: ints, strictly increasing, steps[0] >= 0, steps[-1] == n_iter >= 1 -> the ctypes array the engine reads"""
     try:
         st = tuple(steps)
     except TypeError:
@@ -924,25 +872,133 @@ def _assemble_steps(steps, n_iter):
         raise ValueError("n_iter must be >= 1 for the assembling call (got %r)" % (n_iter,))
     if st[0] < 0 or any(b <= a for a, b in zip(st, st[1:])) or st[-1] != n:
         raise ValueError("steps must be strictly increasing, start at >= 0 and end at n_iter = %d, got %r" % (n, st))
-    return st, (ctypes.c_int * len(st))(*st)
+    return (ctypes.c_int * len(st))(*st)
 
 
-def _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type, extra=()):
+# The one host path of the eight public calls below: the folded contract (cspn2d_*_kxk_norm) and the assembling one (cspn2d_*_kxk_assemble), each
+# with and without a pin.  A call is described by three things: `pinned` (pin_conf exists; None is then an error, not the unpinned call), `assemble`
+# (None, or the pair (conf, steps)) and the dilation.  What they decide, and nothing else differs between the eight:
+#   * the names: cspn2d_{forward,backward}_kxk_<kind> through _kxk_entry (unpinned: _f32 / _g16 / _dil) or _pin_entry, and the size queries
+#     cspn2d_kxk_<kind>_{history,workspace}_bytes and cspn2d_backward_kxk_<kind>_workspace_bytes, <kind> = norm or assemble (_FOLD_NAMES);
+#   * the engine's arguments (include/cspn_amd.h): pin_conf directly behind sparse, then conf, steps, T; in the backward grad_conf, then
+#     grad_sparse and grad_pin, behind grad_blur;
+#   * n_iter == 0: the folded forward returns blur_depth itself, wherever it lives; the assembling calls refuse it (_assemble_steps);
+#   * a backward without a history runs the forward first where dL/dguidance or dL/dpin_conf (n_iter >= 2: both read the gradient of the folded
+#     gates) or dL/dconf (always: it reads the collected levels) is asked for.
+_FoldNames = collections.namedtuple("_FoldNames", "forward backward history_bytes forward_workspace_bytes backward_workspace_bytes")
+_FOLD_NAMES = {   # by `assemble is not None`: the stems of the entry points (_kxk_entry / _pin_entry add the suffix) and the size queries
+    False: _FoldNames("cspn2d_forward_kxk_norm", "cspn2d_backward_kxk_norm", "cspn2d_kxk_norm_history_bytes",
+                      "cspn2d_kxk_norm_workspace_bytes", "cspn2d_backward_kxk_norm_workspace_bytes"),
+    True: _FoldNames("cspn2d_forward_kxk_assemble", "cspn2d_backward_kxk_assemble", "cspn2d_kxk_assemble_history_bytes",
+                     "cspn2d_kxk_assemble_workspace_bytes", "cspn2d_backward_kxk_assemble_workspace_bytes"),
+}
+
+
+def _fold_checks(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, dilation):
+    """what every one of the eight calls checks first, in one order: kernel_size, norm_type, n_iter and the shapes; the pin; conf and steps; the
+    dilation (a backward goes on with grad_out; the device comes last, in _fold_tensors) -> K, B, C, H, W, sparse_depth's planes, the steps as the
+    engine reads them (None: the folded contract)"""
     K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
-    st, c_steps = _assemble_steps(steps, n_iter)
-    if not isinstance(conf, torch.Tensor):
-        raise TypeError("conf must be a torch.Tensor")
-    if tuple(conf.shape) != (B, len(st), H, W):
-        raise ValueError("conf has shape %s, expected (B,len(steps),H,W) = %s" % (tuple(conf.shape), (B, len(st), H, W)))
-    for t, name in extra:
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(blur_depth.shape):
-            raise ValueError("%s must be a tensor of shape %s" % (name, tuple(blur_depth.shape)))
-    if any(isinstance(t, torch.Tensor) and t.device != guidance.device for t in (blur_depth, sparse_depth, conf) + tuple(t for t, _ in extra)):
+    if pinned:
+        _pin_check(sparse_depth, pin_conf)
+    c_steps = None
+    if assemble is not None:
+        conf, steps = assemble
+        c_steps = _assemble_steps(steps, n_iter)
+        if not isinstance(conf, torch.Tensor):
+            raise TypeError("conf must be a torch.Tensor")
+        if tuple(conf.shape) != (B, len(c_steps), H, W):
+            raise ValueError("conf has shape %s, expected (B,len(steps),H,W) = %s" % (tuple(conf.shape), (B, len(c_steps), H, W)))
+    check_dilation(dilation)
+    return K, B, C, H, W, sc, c_steps
+
+
+def _fold_tensors(guidance, blur_depth, *others):
+    """one device for all, then every tensor as the engine takes it: the guidance in its dtype, the values float32 (a 16-bit one widened with one
+    cast) -> guidance, its dtype code, blur_depth, *others (None stays None)"""
+    if any(isinstance(t, torch.Tensor) and t.device != guidance.device for t in (blur_depth,) + tuple(t for t, _ in others)):
         raise ValueError("all tensors must live on the same device")
-    g, dt, h, s, *rest = _kxk_norm_args(guidance, blur_depth, sparse_depth, extra)
-    return (g, dt, h, s, _prep_value(conf, "conf"), c_steps, len(st), K, B, C, H, W, sc) + tuple(rest)
+    g, dt = _prep_gate(guidance, "guidance")
+    return (g, dt, _prep_value(blur_depth, "blur_depth")) + tuple(None if t is None else _prep_value(t, name) for t, name in others)
 
 
+def _fold_forward(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, return_history, dilation):
+    """cspn2d_forward_kxk_{norm,assemble}[_pin] -> out, or (out, history) with return_history"""
+    K, B, C, H, W, sc, c_steps = _fold_checks(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, dilation)
+    n = int(n_iter)
+    if n == 0:   # (the folded contract alone gets here)
+        return (blur_depth, None) if return_history else blur_depth
+    g, dt, h, s, p, cf = _fold_tensors(guidance, blur_depth, (sparse_depth, "sparse_depth"), (pin_conf if pinned else None, "pin_conf"),
+                                       (assemble[0] if assemble else None, "conf"))
+    out = torch.empty_like(h)
+    if out.numel() == 0:
+        return (out, None) if return_history else out
+    names = _FOLD_NAMES[assemble is not None]
+    # with a history the levels go there and the workspace holds only the fold (the query's n_iter = 1 size)
+    hist, hb = _history(names.history_bytes, g.device, B, C, H, W, K, n) if return_history else (None, 0)
+    name, dta, dil = (_pin_entry if pinned else _kxk_entry)(names.forward, dt, dilation)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), *((_ptr(p),) if pinned else ()), *((_ptr(cf), c_steps, len(c_steps)) if assemble else ()),
+             _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
+            (names.forward_workspace_bytes, B, C, sc, H, W, K, 1 if return_history else n))
+    return (out, hist) if return_history else out
+
+
+def _fold_backward(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, grad_out, kernel_size, n_iter, norm_type, history, dilation,
+                   need_guidance, need_blur, need_conf=False, need_sparse=False, need_pin=False):
+    """cspn2d_backward_kxk_{norm,assemble}[_pin] -> (dL/dguidance, dL/dblur_depth, dL/dconf, dL/dsparse_depth, dL/dpin_conf), None for what the
+    contract does not have or the caller does not need"""
+    K, B, C, H, W, sc, c_steps = _fold_checks(guidance, blur_depth, sparse_depth, pin_conf, pinned, assemble, kernel_size, n_iter, norm_type, dilation)
+    if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
+        raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
+    g, dt, h, s, p, cf, go = _fold_tensors(guidance, blur_depth, (sparse_depth, "sparse_depth"), (pin_conf if pinned else None, "pin_conf"),
+                                           (assemble[0] if assemble else None, "conf"), (grad_out, "grad_out"))
+    n = int(n_iter)
+    need = (need_guidance, need_blur, need_conf and assemble is not None, need_sparse and pinned, need_pin and pinned)
+    grads = [torch.empty_like(t) if wanted else None for t, wanted in zip((g, h, cf, s, p), need)]
+    if not any(need):
+        return tuple(grads)
+    if h.numel() == 0:
+        if grads[0] is not None:
+            grads[0].zero_()
+        return tuple(grads)
+    if history is None and (((need[0] or need[4]) and n >= 2) or need[2]):
+        _, history = _fold_forward(g, h, s, p, pinned, (cf, assemble[1]) if assemble else None, K, n, norm_type, True, dilation)
+    names = _FOLD_NAMES[assemble is not None]
+    name, dta, dil = (_pin_entry if pinned else _kxk_entry)(names.backward, dt, dilation)
+    gg, gh, gc, gs, gp = (_ptr(t) for t in grads)
+    _launch(name, g.device,
+            (_ptr(g), *dta, _ptr(h), _ptr(s), *((_ptr(p),) if pinned else ()), *((_ptr(cf), c_steps, len(c_steps)) if assemble else ()),
+             _ptr(history), _history_bytes(history), _ptr(go), gg, gh, *((gc,) if assemble else ()), *((gs, gp) if pinned else ()),
+             B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
+            (names.backward_workspace_bytes, B, C, sc, H, W, K, n))
+    return tuple(grads)
+
+
+def cspn2d_forward_kxk_norm(guidance, blur_depth, sparse_depth=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False, dilation=1):
+    """Affinity_Propagate's forward (reference cspn.py:42-144) over a kernel_size x kernel_size neighbourhood: guidance [B,K*K-1,H,W] raw
+    (channel k = the k-th pair (t, l) in raster order over {0..K-1}^2 without the centre, its gate sited at the neighbour
+    (K//2 - t, K//2 - l)), blur_depth [B,C,H,W] on the shared guidance, sparse_depth None, [B,1,H,W] or [B,C,H,W] -> [B,C,H,W]
+    (cspn2d_forward_kxk_norm_f32).  return_history: (out, history) with H_1 .. H_{n-1} for cspn2d_backward_kxk_norm.  n_iter == 0
+    returns blur_depth itself.  guidance may be float16 / bfloat16 (cspn2d_forward_kxk_norm_g16, K = 3 included: the fold widens it exactly,
+    w' stays float32; out is float32 and bitwise the float32 call on guidance.float()); 16-bit blur_depth / sparse_depth are widened with
+    one cast.  dilation 1 or 2: the neighbour of gate (t, l) is dilation * (K//2 - t, K//2 - l) (dilated CSPN++; cspn2d_forward_kxk_norm_dil)."""
+    return _fold_forward(guidance, blur_depth, sparse_depth, None, False, None, kernel_size, n_iter, norm_type, return_history, dilation)
+
+
+def cspn2d_backward_kxk_norm(guidance, blur_depth, sparse_depth, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
+                             need_guidance=True, need_blur=True, dilation=1):
+    """Gradient of cspn2d_forward_kxk_norm -> (dL/dguidance [B,K*K-1,H,W] summed over the C channels or None, dL/dblur_depth [B,C,H,W]
+    or None); sparse_depth gets none (cspn.py uses its sign only).  cspn2d_backward_kxk_norm_f32.  history: what
+    cspn2d_forward_kxk_norm(..., return_history=True) returned; None runs that forward first where the guidance gradient needs it.
+    A float16 / bfloat16 guidance (cspn2d_backward_kxk_norm_g16): dL/dblur_depth is float32 and bitwise the float32 call's, dL/dguidance comes
+    back in the guidance's dtype, the float32 value rounded once.  dilation: that of the forward (cspn2d_backward_kxk_norm_dil)."""
+    return _fold_backward(guidance, blur_depth, sparse_depth, None, False, None, grad_out, kernel_size, n_iter, norm_type, history, dilation,
+                          need_guidance, need_blur)[:2]
+
+
+# ---- assembling K x K levels per pixel (CSPN++): out = sum_j conf_j H_{s_j} over the levels H_t of cspn2d_forward_kxk_norm, H_0 = blur_depth
+# (cspn2d_*_kxk_assemble_f32 / _g16) ----
 def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False,
                                 dilation=1):
     """out [B,C,H,W] = sum_j conf[:, j] * H_{steps[j]}: the levels H_t of cspn2d_forward_kxk_norm (H_0 = blur_depth) assembled per pixel
@@ -951,23 +1007,7 @@ def cspn2d_forward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps,
     H_1 .. H_n for cspn2d_backward_kxk_assemble.  guidance may be float16 / bfloat16 and is taken as it is (out is float32 and bitwise the
     float32 call on guidance.float()); a 16-bit conf, blur_depth or sparse_depth is widened with one cast.  dilation 1 or 2: the levels are
     those of cspn2d_forward_kxk_norm at that dilation (cspn2d_forward_kxk_assemble_dil)."""
-    check_dilation(dilation)
-    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
-    n = int(n_iter)
-    out = torch.empty_like(h)
-    hist = None
-    if out.numel() == 0:
-        return (out, None) if return_history else out
-    hb = 0
-    if return_history:
-        with torch.cuda.device(g.device):
-            hb = _lib.symbol("cspn2d_kxk_assemble_history_bytes")(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-    name, dta, dil = _kxk_entry("cspn2d_forward_kxk_assemble", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
-    return (out, hist) if return_history else out
+    return _fold_forward(guidance, blur_depth, sparse_depth, None, False, (conf, steps), kernel_size, n_iter, norm_type, return_history, dilation)
 
 
 def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
@@ -977,48 +1017,13 @@ def cspn2d_backward_kxk_assemble(guidance, blur_depth, sparse_depth, conf, steps
     cspn2d_backward_kxk_norm with conf_j grad_out injected at every collected level, and dL/dconf_j = sum_c grad_out H_{steps[j]}.  history: what
     cspn2d_forward_kxk_assemble(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dconf needs it.
     dilation: that of the forward (cspn2d_backward_kxk_assemble_dil)."""
-    check_dilation(dilation)
-    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc, go = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type,
-                                                                        ((grad_out, "grad_out"),))
-    n = int(n_iter)
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    gc = torch.empty_like(cf) if need_conf else None
-    if not (need_guidance or need_blur or need_conf):
-        return gg, gh, gc
-    if h.numel() == 0:
-        return (gg.zero_() if gg is not None else None), gh, gc
-    if history is None and ((need_guidance and n >= 2) or need_conf):
-        _, history = cspn2d_forward_kxk_assemble(g, h, s, cf, steps, K, n, norm_type, return_history=True, dilation=dilation)
-    hb = history.numel() * history.element_size() if history is not None else 0
-    name, dta, dil = _kxk_entry("cspn2d_backward_kxk_assemble", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc), B, C, sc, H, W, K, *dil, n,
-             _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_backward_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, n))
-    return gg, gh, gc
+    return _fold_backward(guidance, blur_depth, sparse_depth, None, False, (conf, steps), grad_out, kernel_size, n_iter, norm_type, history, dilation,
+                          need_guidance, need_blur, need_conf)[:3]
 
 
 # ---- the two contracts above pinned to the measured depth with a per-pixel confidence (CSPN++ / PENet; cspn2d_*_kxk_{norm,assemble}_pin): after
 # every step H = (1 - m) step(H) + m sparse_depth with m = sign(sparse_depth) * pin_conf.  Functions of their own: the four above keep their
 # parameter lists ----
-def _pin_check(blur_depth, sparse_depth, pin_conf):
-    """sparse_depth and pin_conf: both given, the same shape, [B,1,H,W] or [B,C,H,W] (sparse_depth's shape itself is checked by _kxk_norm_shape)"""
-    if sparse_depth is None or pin_conf is None:
-        raise ValueError("the pinned contract needs a sparse_depth and a pin_conf (a pin_conf without a sparse_depth pins nothing)")
-    if not isinstance(pin_conf, torch.Tensor) or not isinstance(sparse_depth, torch.Tensor) or tuple(pin_conf.shape) != tuple(sparse_depth.shape):
-        raise ValueError("pin_conf must be a tensor of sparse_depth's shape %s ([B,1,H,W] or [B,C,H,W]), got %s"
-                         % (tuple(getattr(sparse_depth, "shape", ())), tuple(getattr(pin_conf, "shape", ()))))
-    if isinstance(blur_depth, torch.Tensor) and pin_conf.device != blur_depth.device:
-        raise ValueError("all tensors must live on the same device")
-
-
-def _pin_entry(stem, dt, dilation):
-    """the pinned entry point of a folded / assembling call: one for every guidance dtype (gate_dtype 0: float32) and every dilation"""
-    check_dilation(dilation)
-    return stem + "_pin", (0 if dt is None else dt,), (dilation,)
-
-
 def cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth=None, pin_conf=None, kernel_size=5, n_iter=24, norm_type="8sum", return_history=False,
                                 dilation=1):
     """cspn2d_forward_kxk_norm pinned to the measured depth with a per-pixel confidence: after every step
@@ -1028,27 +1033,7 @@ def cspn2d_forward_kxk_norm_pin(guidance, blur_depth, sparse_depth=None, pin_con
     and blur_depth = sparse_depth where it is measured the result is bitwise cspn2d_forward_kxk_norm's; with pin_conf = 0 bitwise that of the
     call without a mask.  Everything else (guidance dtypes, return_history, n_iter == 0 returns blur_depth itself, dilation) as there; a 16-bit
     sparse_depth or pin_conf is widened with one cast."""
-    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
-    _pin_check(blur_depth, sparse_depth, pin_conf)
-    check_dilation(dilation)
-    n = int(n_iter)
-    if n == 0:
-        return (blur_depth, None) if return_history else blur_depth
-    g, dt, h, s = _kxk_norm_args(guidance, blur_depth, sparse_depth)
-    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
-    out = torch.empty_like(h)
-    hist = None
-    if out.numel() == 0:
-        return (out, None) if return_history else out
-    hb = 0
-    if return_history:
-        with torch.cuda.device(g.device):
-            hb = _lib.symbol("cspn2d_kxk_norm_history_bytes")(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-    name, dta, dil = _pin_entry("cspn2d_forward_kxk_norm", dt, dilation)
-    _launch(name, g.device, (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_kxk_norm_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
-    return (out, hist) if return_history else out
+    return _fold_forward(guidance, blur_depth, sparse_depth, pin_conf, True, None, kernel_size, n_iter, norm_type, return_history, dilation)
 
 
 def cspn2d_backward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, grad_out, kernel_size=5, n_iter=24, norm_type="8sum", history=None,
@@ -1058,30 +1043,8 @@ def cspn2d_backward_kxk_norm_pin(guidance, blur_depth, sparse_depth, pin_conf, g
     derivative); dL/dpin_conf is exactly 0 where sparse_depth == 0.  Both are float32 with sparse_depth's shape.  history: what
     cspn2d_forward_kxk_norm_pin(..., return_history=True) returned; None runs that forward first where dL/dguidance or dL/dpin_conf needs it
     (n_iter >= 2: both read the gradient of the folded gates)."""
-    K, B, C, H, W, sc = _kxk_norm_shape(guidance, blur_depth, sparse_depth, kernel_size, norm_type, n_iter)
-    _pin_check(blur_depth, sparse_depth, pin_conf)
-    check_dilation(dilation)
-    if not isinstance(grad_out, torch.Tensor) or tuple(grad_out.shape) != tuple(blur_depth.shape):
-        raise ValueError("grad_out must be a tensor of shape %s" % (tuple(blur_depth.shape),))
-    g, dt, h, s, go = _kxk_norm_args(guidance, blur_depth, sparse_depth, ((grad_out, "grad_out"),))
-    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
-    n = int(n_iter)
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    gs = torch.empty_like(s) if need_sparse else None
-    gp = torch.empty_like(p) if need_pin else None
-    if not (need_guidance or need_blur or need_sparse or need_pin):
-        return gg, gh, gs, gp
-    if h.numel() == 0:
-        return (gg.zero_() if gg is not None else None), gh, gs, gp
-    if (need_guidance or need_pin) and n >= 2 and history is None:
-        _, history = cspn2d_forward_kxk_norm_pin(g, h, s, p, K, n, norm_type, return_history=True, dilation=dilation)
-    hb = history.numel() * history.element_size() if history is not None else 0
-    name, dta, dil = _pin_entry("cspn2d_backward_kxk_norm", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gs), _ptr(gp), B, C, sc, H, W, K, *dil, n,
-             _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_backward_kxk_norm_workspace_bytes", B, C, sc, H, W, K, n))
+    gg, gh, _, gs, gp = _fold_backward(guidance, blur_depth, sparse_depth, pin_conf, True, None, grad_out, kernel_size, n_iter, norm_type, history, dilation,
+                                       need_guidance, need_blur, False, need_sparse, need_pin)
     return gg, gh, gs, gp
 
 
@@ -1089,26 +1052,7 @@ def cspn2d_forward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf
                                     return_history=False, dilation=1):
     """cspn2d_forward_kxk_assemble over the levels of cspn2d_forward_kxk_norm_pin: out = sum_j conf[:, j] * H_{steps[j]}, one engine call
     (cspn2d_forward_kxk_assemble_pin).  pin_conf as there; everything else as the unpinned call."""
-    check_dilation(dilation)
-    _pin_check(blur_depth, sparse_depth, pin_conf)
-    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type)
-    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
-    n = int(n_iter)
-    out = torch.empty_like(h)
-    hist = None
-    if out.numel() == 0:
-        return (out, None) if return_history else out
-    hb = 0
-    if return_history:
-        with torch.cuda.device(g.device):
-            hb = _lib.symbol("cspn2d_kxk_assemble_history_bytes")(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=g.device)
-    name, dta, dil = _pin_entry("cspn2d_forward_kxk_assemble", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(cf), c_steps, T, _ptr(out), _ptr(hist), hb, B, C, sc, H, W, K, *dil, n,
-             _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, 1 if return_history else n))
-    return (out, hist) if return_history else out
+    return _fold_forward(guidance, blur_depth, sparse_depth, pin_conf, True, (conf, steps), kernel_size, n_iter, norm_type, return_history, dilation)
 
 
 def cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_conf, conf, steps, grad_out, kernel_size=5, n_iter=24, norm_type="8sum",
@@ -1116,30 +1060,8 @@ def cspn2d_backward_kxk_assemble_pin(guidance, blur_depth, sparse_depth, pin_con
     """Gradient of cspn2d_forward_kxk_assemble_pin -> (dL/dguidance, dL/dblur_depth, dL/dconf, dL/dsparse_depth, dL/dpin_conf), None where not
     asked for; one engine call (cspn2d_backward_kxk_assemble_pin).  history: what cspn2d_forward_kxk_assemble_pin(..., return_history=True)
     returned; None runs that forward first where dL/dguidance, dL/dpin_conf (n_iter >= 2) or dL/dconf needs it."""
-    check_dilation(dilation)
-    _pin_check(blur_depth, sparse_depth, pin_conf)
-    g, dt, h, s, cf, c_steps, T, K, B, C, H, W, sc, go = _assemble_args(guidance, blur_depth, sparse_depth, conf, steps, kernel_size, n_iter, norm_type,
-                                                                        ((grad_out, "grad_out"),))
-    p = _prep_value(pin_conf, "pin_conf", tuple(s.shape))
-    n = int(n_iter)
-    gg = torch.empty_like(g) if need_guidance else None
-    gh = torch.empty_like(h) if need_blur else None
-    gc = torch.empty_like(cf) if need_conf else None
-    gs = torch.empty_like(s) if need_sparse else None
-    gp = torch.empty_like(p) if need_pin else None
-    if not (need_guidance or need_blur or need_conf or need_sparse or need_pin):
-        return gg, gh, gc, gs, gp
-    if h.numel() == 0:
-        return (gg.zero_() if gg is not None else None), gh, gc, gs, gp
-    if history is None and (((need_guidance or need_pin) and n >= 2) or need_conf):
-        _, history = cspn2d_forward_kxk_assemble_pin(g, h, s, p, cf, steps, K, n, norm_type, return_history=True, dilation=dilation)
-    hb = history.numel() * history.element_size() if history is not None else 0
-    name, dta, dil = _pin_entry("cspn2d_backward_kxk_assemble", dt, dilation)
-    _launch(name, g.device,
-            (_ptr(g), *dta, _ptr(h), _ptr(s), _ptr(p), _ptr(cf), c_steps, T, _ptr(history), hb, _ptr(go), _ptr(gg), _ptr(gh), _ptr(gc), _ptr(gs), _ptr(gp),
-             B, C, sc, H, W, K, *dil, n, _lib.NORM_TYPES[norm_type]),
-            ("cspn2d_backward_kxk_assemble_workspace_bytes", B, C, sc, H, W, K, n))
-    return gg, gh, gc, gs, gp
+    return _fold_backward(guidance, blur_depth, sparse_depth, pin_conf, True, (conf, steps), grad_out, kernel_size, n_iter, norm_type, history, dilation,
+                          need_guidance, need_blur, need_conf, need_sparse, need_pin)
 
 
 # ---- non-local propagation with learned offsets (NLSPN's refinement step; cspn2d_nl.hip): every pixel reads its K*K - 1 neighbours by bilinear
@@ -1222,11 +1144,8 @@ def _nl_forward(g16, aff, offset, x, sparse_depth, n_iter, kernel_size, return_h
     out = torch.empty_like(h)
     if out.numel() == 0:
         return (out, None) if return_history else out
-    hist, hb = None, 0
-    if return_history:   # the levels go to the history; the workspace keeps the pinned H_0 alone
-        with torch.cuda.device(a.device):
-            hb = _lib.symbol("cspn2d_nl_history_bytes")(B, C, H, W, K, n)
-        hist = torch.empty(max(hb // 4, 1), dtype=torch.float32, device=a.device)
+    # with a history the levels go there; the workspace keeps the pinned H_0 alone
+    hist, hb = _history("cspn2d_nl_history_bytes", a.device, B, C, H, W, K, n) if return_history else (None, 0)
     gates = (*_nl_typed(a), *_nl_typed(o)) if g16 else (_ptr(a), _ptr(o))
     _launch("cspn2d_forward_nl_g16" if g16 else "cspn2d_forward_nl_f32", a.device, (*gates, _ptr(h), _ptr(s), _ptr(out), _ptr(hist), hb, B, C, H, W, K, n),
             ("cspn2d_nl_workspace_bytes", B, C, H, W, K, 1 if return_history else n, int(s is not None)))
@@ -1256,10 +1175,9 @@ def _nl_backward(stem, aff, offset, x, sparse_depth, grad_out, n_iter, kernel_si
         return ga, gd, gx
     if (need_aff or need_offset) and n >= 2 and history is None:
         _, history = (cspn2d_forward_nl_g16 if g16 else cspn2d_forward_nl)(a, o, h, s, n, K, return_history=True)
-    hb = history.numel() * history.element_size() if history is not None else 0
     gates = (*_nl_typed(a), *_nl_typed(o)) if g16 else (_ptr(a), _ptr(o))
     _launch(stem + ("_g16" if g16 else "_f32"), a.device,
-            (*gates, _ptr(h), _ptr(s), _ptr(history), hb, _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
+            (*gates, _ptr(h), _ptr(s), _ptr(history), _history_bytes(history), _ptr(go), _ptr(ga), _ptr(gd), _ptr(gx), B, C, H, W, K, n),
             (stem + "_workspace_bytes", B, C, H, W, K, n, int(s is not None)))
     return ga, gd, gx
 
