@@ -16,6 +16,9 @@ from .nlspn import NonLocal_Propagate  # noqa: F401
 # K x K propagation with per-step attention: importable from the package, its functions are cspn_amd.functional.cspn2d_*_kxk_dyn (not in
 # __all__: DESIGN.md §3.4k)
 from .dyspn import Dynamic_Propagate  # noqa: F401
+# line-scan propagation (SPN's three-way recurrence): importable from the package, its functions are cspn_amd.functional.cspn2d_*_scan (not in
+# __all__: DESIGN.md §3.4l)
+from .spn import LineScan_Propagate  # noqa: F401
 
 __all__ = ["Affinity_Propagate", "Affinity_Propagate3d", "Affinity_PropagateKxK", "propagate_prenorm", "cspn2d_forward", "cspn2d_normalize", "cspn2d_normalize_backward", "cspn2d_backward", "cspn2d_forward_multi", "cspn2d_backward_multi", "cspn3d_forward", "cspn3d_forward_multi", "cspn3d_backward", "cspn3d_backward_multi", "cspn3d_backward_norm", "cspn3d_forward_norm", "cspn3d_check_status", "affinity_propagate",
            "CSPN", "gate_absnorm", "absnorm_propagate", "cspn2d_forward_kxk", "cspn2d_backward_kxk", "cspn2d_forward_kxk_norm",

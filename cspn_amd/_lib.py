@@ -166,6 +166,11 @@ _SYMBOLS.update({
     "cspn2d_forward_kxk_dyn_f32": (c_int, [vp] * 6 + [c_size_t] + [c_int] * 6 + _WS),
     "cspn2d_backward_kxk_dyn_workspace_bytes": (c_size_t, [c_int] * 7),
     "cspn2d_backward_kxk_dyn_f32": (c_int, [vp] * 5 + [c_size_t] + [vp] * 4 + [c_int] * 6 + _WS),
+    # line-scan propagation, SPN's three-way recurrence (cspn2d_scan.hip): x, gates, lam (or NULL) in front; B, C, Cg, H, W, dirs (a 4-bit mask)
+    "cspn2d_scan_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_forward_scan_f32": (c_int, [vp] * 4 + [c_int] * 6 + _WS),
+    "cspn2d_backward_scan_workspace_bytes": (c_size_t, [c_int] * 7),
+    "cspn2d_backward_scan_f32": (c_int, [vp] * 8 + [c_int] * 6 + _WS),
     # the guidance heads for K x K propagation (K*K-1 guidance planes + the blur plane), K = 3 (the 8-plane head), 5 or 7
     "cspn_guidance_head_kxk_workspace_bytes": (c_size_t, [c_int] * 5),
     "cspn_guidance_head_kxk_f32": (c_int, [vp] * 5 + [c_int] * 7 + _WS),

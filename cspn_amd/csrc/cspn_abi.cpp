@@ -1145,6 +1145,83 @@ int cspn2d_backward_kxk_dyn_f32(const float* guidance, const float* att, const f
     return kxk_dyn_backward(guidance, att, x, sparse, history, grad_out, grad_guidance, grad_att, grad_x, B, C, H, W, K, n_iter, ws, st);
 }
 
+// ---- line-scan propagation, SPN's three-way recurrence (cspn2d_scan.hip); added to ABI 5 after its release, purely additive: the checks of
+// the kxk_dyn entry points.  A line (H for directions 0 / 1, W for 2 / 3) has at most SCAN_MAX_LINE pixels ----
+static bool scan_args_ok(int B, int C, int Cg, int H, int W, int dirs) {
+    return B > 0 && C > 0 && Cg > 0 && H > 0 && W > 0 && C % Cg == 0 && dirs >= 1 && dirs <= 15;
+}
+
+static bool scan_shape_ok(int B, int C, int Cg, int H, int W, int dirs) {
+    if (!scan_args_ok(B, C, Cg, H, W, dirs)) return false;
+    const long long px = (long long)H * W, D = __builtin_popcount(dirs);
+    if (((dirs & 3) && H > SCAN_MAX_LINE) || ((dirs & 12) && W > SCAN_MAX_LINE)) return false;
+    return (long long)B * D * C * px <= 0x7fffffffLL && (long long)B * D * Cg * 3 * px <= 0x7fffffffLL;
+}
+
+static int scan_check_shape(const char* what, int B, int C, int Cg, int H, int W, int dirs) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W); return CSPN_E_BADARG; }
+    if (Cg <= 0 || C % Cg) { set_error("%s: Cg must divide C (got C=%d Cg=%d)", what, C, Cg); return CSPN_E_BADARG; }
+    if (dirs < 1 || dirs > 15) { set_error("%s: dirs must be a non-empty mask of the directions 0 .. 3 (1 .. 15), got %d", what, dirs); return CSPN_E_BADARG; }
+    if (!scan_shape_ok(B, C, Cg, H, W, dirs)) {
+        set_error("%s: a line of more than %d pixels (H for directions 0 / 1, W for 2 / 3), or a tensor too large for 32-bit element indexing", what, SCAN_MAX_LINE);
+        return CSPN_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// the forward needs no memory beyond its tensors; the one block keeps the query's "0 = rejected" readable
+size_t cspn2d_scan_workspace_bytes(int B, int C, int Cg, int H, int W, int dirs, int has_lam) {
+    (void)has_lam;
+    return scan_shape_ok(B, C, Cg, H, W, dirs) ? 256 : 0;
+}
+
+size_t cspn2d_backward_scan_workspace_bytes(int B, int C, int Cg, int H, int W, int dirs, int has_lam) {
+    (void)has_lam;
+    return scan_shape_ok(B, C, Cg, H, W, dirs) ? ScanBackwardWs(B, C, Cg, H, W, __builtin_popcount(dirs)).bytes : 0;
+}
+
+int cspn2d_forward_scan_f32(const float* x, const float* gates, const float* lam, float* out, int B, int C, int Cg, int H, int W, int dirs, void* ws,
+                            size_t ws_bytes, cspn_stream_t stream) {
+    const char* what = "cspn2d_forward_scan_f32";
+    if (!x || !gates || !out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (int e = scan_check_shape(what, B, C, Cg, H, W, dirs)) return e;
+    const int D = __builtin_popcount(dirs);
+    const size_t xb = kxk_values_bytes(B, C, H, W), ob = xb * D, gb = ob / C * Cg * 3;
+    const size_t need = cspn2d_scan_workspace_bytes(B, C, Cg, H, W, dirs, lam != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    if (kxk_overlaps(out, ob, {{x, xb}, {gates, gb}, {lam, ob}, {ws, ws_bytes}}) || kxk_overlaps(ws, ws_bytes, {{x, xb}, {gates, gb}, {lam, ob}})) {
+        set_error("%s: out and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    return scan_forward(x, gates, lam, out, B, C, Cg, H, W, dirs, (hipStream_t)stream);
+}
+
+int cspn2d_backward_scan_f32(const float* x, const float* gates, const float* lam, const float* out, const float* grad_out, float* grad_x,
+                             float* grad_gates, float* grad_lam, int B, int C, int Cg, int H, int W, int dirs, void* ws, size_t ws_bytes,
+                             cspn_stream_t stream) {
+    const char* what = "cspn2d_backward_scan_f32";
+    if (!x || !gates || !out || !grad_out) { set_error("%s: null pointer", what); return CSPN_E_BADARG; }
+    if (grad_lam && !lam) { set_error("%s: grad_lam without lam", what); return CSPN_E_BADARG; }
+    if (int e = scan_check_shape(what, B, C, Cg, H, W, dirs)) return e;
+    const int D = __builtin_popcount(dirs);
+    const size_t xb = kxk_values_bytes(B, C, H, W), ob = xb * D, gb = ob / C * Cg * 3;
+    const size_t need = cspn2d_backward_scan_workspace_bytes(B, C, Cg, H, W, dirs, lam != nullptr);
+    if (int e = kxk_check_ws(what, ws, ws_bytes, need)) return e;
+    if ((grad_x && ((void*)grad_x == (void*)grad_gates || (void*)grad_x == (void*)grad_lam)) || (grad_gates && (void*)grad_gates == (void*)grad_lam)) {
+        set_error("%s: grad_x, grad_gates and grad_lam must not alias", what);
+        return CSPN_E_BADARG;
+    }
+    if (kxk_overlaps(grad_x, xb, {{x, xb}, {gates, gb}, {lam, ob}, {out, ob}, {grad_out, ob}, {grad_gates, gb}, {grad_lam, ob}, {ws, ws_bytes}}) ||
+        kxk_overlaps(grad_gates, gb, {{x, xb}, {gates, gb}, {lam, ob}, {out, ob}, {grad_out, ob}, {grad_lam, ob}, {ws, ws_bytes}}) ||
+        kxk_overlaps(grad_lam, ob, {{x, xb}, {gates, gb}, {lam, ob}, {out, ob}, {grad_out, ob}, {ws, ws_bytes}}) ||
+        kxk_overlaps(ws, ws_bytes, {{x, xb}, {gates, gb}, {lam, ob}, {out, ob}, {grad_out, ob}})) {
+        set_error("%s: grad_x, grad_gates, grad_lam and the workspace must not alias an input or each other", what);
+        return CSPN_E_BADARG;
+    }
+    if (!grad_x && !grad_gates && !grad_lam) return 0;
+    return scan_backward(x, gates, lam, out, grad_out, grad_x, grad_gates, grad_lam, B, C, Cg, H, W, dirs, ws, (hipStream_t)stream);
+}
+
 // ---- the depth-completion contract over a K x K neighbourhood, K = 3, 5 or 7 (cspn2d_kxk.hip) ----
 size_t cspn2d_kxk_norm_workspace_bytes(int B, int C, int sparse_C, int H, int W, int K, int n_iter) {
     if (!kxk_norm_shape_ok(B, C, sparse_C, H, W, K, n_iter) || n_iter < 1) return 0;

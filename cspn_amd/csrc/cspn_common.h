@@ -191,6 +191,27 @@ int kxk_dyn_forward(const float* guid, const float* att, const float* x, const f
 int kxk_dyn_backward(const float* guid, const float* att, const float* x, const float* sparse, const float* hist, const float* gout, float* gg, float* ga,
                      float* gx, int N, int C, int H, int W, int K, int n_iter, void* ws, hipStream_t st);
 
+// ---- line-scan propagation, SPN's three-way recurrence (cspn2d_scan.hip): x [B][C][H][W], gates [B][D Cg 3][H][W] used as
+// given (channel (d Cg + j) 3 + k), lam NULL or [B][D C][H][W], out [B][D C][H][W]; dirs a 4-bit mask of {0 left->right, 1 right->left,
+// 2 top->bottom, 3 bottom->top}, D its size.  float32 throughout ----
+// the longest line (H for directions 0 / 1, W for 2 / 3): 8 pixels for each of a workgroup's 256 threads
+constexpr int SCAN_MAX_LINE = 2048;
+// the backward's workspace, in bytes from its start (every part 256-byte aligned): grad_x of the directions d = 1 .. D-1 ([D-1][B][C][H][W]),
+// grad_gates of a group's channels r = 1 .. C/Cg - 1 ([C/Cg - 1][B][D Cg 3][H][W]); never empty
+struct ScanBackwardWs {
+    size_t xpart, gpart, bytes;
+    ScanBackwardWs(int B, int C, int Cg, int H, int W, int D) {
+        const size_t HW = (size_t)H * W;
+        xpart = 256;
+        gpart = xpart + round256(sizeof(float) * (size_t)(D - 1) * B * C * HW);
+        bytes = gpart + round256(sizeof(float) * (size_t)(C / Cg - 1) * B * D * Cg * 3 * HW);
+    }
+};
+int scan_forward(const float* x, const float* gates, const float* lam, float* out, int B, int C, int Cg, int H, int W, int dirs, hipStream_t st);
+// gx (summed over the directions), gg (summed over a group's channels) and gl may each be NULL
+int scan_backward(const float* x, const float* gates, const float* lam, const float* out, const float* gout, float* gx, float* gg, float* gl, int B, int C,
+                  int Cg, int H, int W, int dirs, void* ws, hipStream_t st);
+
 // ---- non-local propagation with learned offsets, K = 3 (cspn2d_nl.hip): aff [B][KK][H][W] used as given, off [B][2 KK][H][W] (dy_k, dx_k
 // interleaved), values [B][C][H][W] on shared aff / off, sparse NULL or [B][H][W] (pinned where > 0).  Neighbour k's base is (t - R, l - R):
 // the deformable convolution's sign, the opposite of the K x K engine's.  adt / odt: the storage types of aff (and gaff) and of off (and goff),

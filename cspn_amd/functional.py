@@ -721,6 +721,84 @@ def cspn2d_backward_kxk_dyn(guidance, att, x, grad_out, kernel_size, n_iter, spa
     return gg, ga, gx
 
 
+# ---- line-scan propagation, SPN's three-way recurrence (cspn2d_scan.hip) ----
+def _scan_mask(dirs):
+    """dirs: a non-empty collection of distinct direction codes 0 .. 3 -> (the 4-bit mask, D).  The engine numbers the directions in ascending
+    order of their code, whatever the order they are given in"""
+    try:
+        codes = list(dirs)
+    except TypeError:
+        raise ValueError("dirs must be a non-empty tuple of distinct directions out of 0, 1, 2, 3 (got %r)" % (dirs,)) from None
+    if not codes or len(set(codes)) != len(codes) or any(isinstance(d, bool) or not isinstance(d, int) or not 0 <= d <= 3 for d in codes):
+        raise ValueError("dirs must be a non-empty tuple of distinct directions out of 0, 1, 2, 3 (got %r)" % (dirs,))
+    return sum(1 << d for d in codes), len(codes)
+
+
+def _scan_args(x, gates, dirs, lam, extra=()):
+    """shapes and dtypes of the cspn2d_*_scan calls -> (x, gates, lam, mask, B, C, Cg, D, H, W) + the extra tensors ([B,D*C,H,W] each), prepared.
+    float32 only: any other dtype is a TypeError"""
+    mask, D = _scan_mask(dirs)
+    named = [(x, "x"), (gates, "gates")] + ([(lam, "lam")] if lam is not None else []) + list(extra)
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32 (got %s): line-scan propagation has no 16-bit kernels" % (name, t.dtype))
+    if x.dim() != 4 or x.shape[1] < 1:
+        raise ValueError("x must be [B,C,H,W] with C >= 1, got %s" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    if gates.dim() != 4 or gates.shape[0] != B or tuple(gates.shape[2:]) != (H, W) or gates.shape[1] < 1 or gates.shape[1] % (3 * D):
+        raise ValueError("gates must be [B,D*Cg*3,H,W] = (%d, %d*Cg*3, %d, %d), got %s" % (B, D, H, W, tuple(gates.shape)))
+    Cg = gates.shape[1] // (3 * D)
+    if C % Cg:
+        raise ValueError("the %d gate groups (gates has %d = %d*Cg*3 channels) must divide the %d channels of x" % (Cg, gates.shape[1], D, C))
+    for t, name in named[2:]:
+        if tuple(t.shape) != (B, D * C, H, W):
+            raise ValueError("%s must be [B,D*C,H,W] = %s, got %s" % (name, (B, D * C, H, W), tuple(t.shape)))
+    ts = [_prep(t, name) for t, name in named]
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError("all tensors must live on the same device")
+    n = 3 if lam is not None else 2
+    return (ts[0], ts[1], ts[2] if lam is not None else None, mask, B, C, Cg, D, H, W) + tuple(ts[n:])
+
+
+def cspn2d_forward_scan(x, gates, dirs=(0, 1, 2, 3), lam=None):
+    """Line-scan propagation, the linear three-way recurrence of SPN (cspn2d_forward_scan_f32): x [B,C,H,W]; dirs a non-empty subset of
+    {0: left->right, 1: right->left, 2: top->bottom, 3: bottom->top}, D its size, the directions numbered d = 0 .. D-1 in ascending order of their
+    code; gates [B,D*Cg*3,H,W], channel (d*Cg + j)*3 + k, used as given (any sign, no normalisation), Cg divides C and channel c uses group
+    j = c // (C // Cg); lam [B,D*C,H,W] or None -> out [B,D*C,H,W], channel d*C + c.  With t the coordinate along the scan, i along the line
+    (directions 0 / 1: a line is a column, t the column index; 2 / 3: a line is a row), L the line length, t- the line visited just before t:
+        g^_k(i,t) = g_k(i,t) if t is not the first line and 0 <= i + k - 1 < L, else 0
+        b(i,t)    = lam(i,t) if lam is given, else 1 - sum_k g^_k(i,t)
+        h(i,t)    = b(i,t) x(i,t) + sum_k g^_k(i,t) h(i + k - 1, t-)
+    Written from the published description of the method, not from a source: compare it with your model.  One launch for all
+    directions and steps.  A line has at most 2048 pixels.  float32 only: any other dtype is a TypeError.  Bitwise reproducible."""
+    x, g, lm, mask, B, C, Cg, D, H, W = _scan_args(x, gates, dirs, lam)
+    out = torch.empty((B, D * C, H, W), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    _launch("cspn2d_forward_scan_f32", x.device, (_ptr(x), _ptr(g), _ptr(lm), _ptr(out), B, C, Cg, H, W, mask),
+            ("cspn2d_scan_workspace_bytes", B, C, Cg, H, W, mask, int(lm is not None)))
+    return out
+
+
+def cspn2d_backward_scan(x, gates, out, grad_out, dirs=(0, 1, 2, 3), lam=None, need_x=True, need_gates=True, need_lam=True):
+    """Gradient of cspn2d_forward_scan -> (dL/dx [B,C,H,W] summed over the directions, dL/dgates [B,D*Cg*3,H,W] summed over a group's channels,
+    dL/dlam [B,D*C,H,W]), None where not asked for or (dL/dlam) where lam is None; cspn2d_backward_scan_f32.  out: what the forward returned,
+    the only history.  A(i,t) = grad_out(i,t) + sum_k g^_k(i - (k-1), t+) A(i - (k-1), t+); dL/dx = sum_d b A; dL/dlam = A x;
+    dL/dg_k = sum_c A (h(i + k - 1, t-) - x) without lam, sum_c A h(i + k - 1, t-) with it, exactly 0 where the gate is dropped (first line,
+    line ends).  One launch and at most one fixed-order reduction; no atomics: run-to-run bitwise."""
+    x, g, lm, mask, B, C, Cg, D, H, W, o, go = _scan_args(x, gates, dirs, lam, ((out, "out"), (grad_out, "grad_out")))
+    gx = torch.empty_like(x) if need_x else None
+    gg = torch.empty_like(g) if need_gates else None
+    gl = torch.empty_like(lm) if need_lam and lm is not None else None
+    if (gx is None and gg is None and gl is None) or o.numel() == 0:
+        return gx, gg, gl
+    _launch("cspn2d_backward_scan_f32", x.device, (_ptr(x), _ptr(g), _ptr(lm), _ptr(o), _ptr(go), _ptr(gx), _ptr(gg), _ptr(gl), B, C, Cg, H, W, mask),
+            ("cspn2d_backward_scan_workspace_bytes", B, C, Cg, H, W, mask, int(lm is not None)))
+    return gx, gg, gl
+
+
 class _AffinityPropagateKxKFunction(torch.autograd.Function):
     """2D K x K, any C on shared gates: the forward keeps H_1 .. H_{n-1}, the backward is one cspn2d_backward_kxk_f32 call"""
 

@@ -56,7 +56,8 @@ extern "C" {
                               *    Paddle contract (cspn3d_*_g16, cspn_gate_absnorm*_g16), the backward of the 3D normalising / masked modes
                               *    (cspn3d_backward_norm_f32), dilated K x K propagation (cspn2d_*_kxk_{norm,assemble}_dil),
                               *    K x K propagation pinned to the measured depth with a confidence (cspn2d_*_kxk_{norm,assemble}_pin),
-                              *    K x K propagation with per-step attention (cspn2d_*_kxk_dyn_*) */
+                              *    K x K propagation with per-step attention (cspn2d_*_kxk_dyn_*),
+                              *    line-scan propagation, SPN's three-way recurrence (cspn2d_*_scan_*) */
 
 /* hipStream_t, spelled without the HIP headers. NULL = the null stream. */
 typedef void* cspn_stream_t;
@@ -782,6 +783,45 @@ int cspn2d_backward_kxk_dyn_f32(const float* guidance, const float* att, const f
                                 size_t history_bytes, const float* grad_out, float* grad_guidance, float* grad_att, float* grad_x,
                                 int B, int C, int H, int W, int K, int n_iter,
                                 void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+
+/* ---- line-scan propagation: the linear, three-way scan-line recurrence of SPN ("Learning Affinity via Spatial Propagation Networks"), the
+ * contract "line scan, three-way".  IT WAS WRITTEN FROM THE PUBLISHED DESCRIPTION, NOT FROM A SOURCE: compare it with your model before you
+ * port it.  Tensors are float32, contiguous NCHW.
+ *   x     [B,C,H,W]
+ *   dirs  a non-empty subset of {0: left->right, 1: right->left, 2: top->bottom, 3: bottom->top} as a 4-bit mask (bit c = direction c, 1 .. 15);
+ *         D is its size, the directions are numbered d = 0 .. D-1 in ascending order of their code
+ *   gates [B,D Cg 3,H,W]   channel (d Cg + j) 3 + k; Cg divides C and channel c uses group j = c / (C / Cg): Cg = 1 is shared gates, Cg = C is
+ *                          SPN's per-channel gates.  Gates are used AS GIVEN (any sign, no normalisation in the engine)
+ *   lam   [B,D C,H,W] or NULL        out [B,D C,H,W], channel d C + c
+ * For one direction, t is the coordinate along the scan and i the coordinate along the line.  Directions 0 / 1: a line is a column, t is the
+ * column index, ascending for 0 and descending for 1, and i is the row.  Directions 2 / 3: a line is a row, t is the row index, i the column.
+ * L is the line length, t- the line visited just before t, k in {0,1,2} the connection to h(i + k - 1, t-):
+ *     g^_k(i,t) = g_k(i,t)  if t is not the first line and 0 <= i + k - 1 < L,   else 0
+ *     b(i,t)    = lam(i,t)  if lam is given,   else 1 - sum_k g^_k(i,t)
+ *     h(i,t)    = b(i,t) x(i,t) + sum_k g^_k(i,t) h(i + k - 1, t-)                  (first line: h = b x)
+ *
+ *     A(i,t)    = grad_out(i,t) + sum_k g^_k(i - (k-1), t+) A(i - (k-1), t+)        (t+: the line visited after t; last line: A = grad_out)
+ *     grad_x    = sum_d b A            grad_lam = A x (lam given)
+ *     grad_g_k  = sum_{c in group} A (h(i + k - 1, t-) - x(i,t))  without lam,   sum_{c in group} A h(i + k - 1, t-)  with lam;
+ *                 exactly 0 wherever g^_k is the dropped 0
+ * The backward reads x, gates, lam, out (the forward's own result is the only history) and grad_out.  Each of grad_x, grad_gates and grad_lam
+ * may be NULL (grad_lam without lam is CSPN_E_BADARG).  Nothing is guarded: gates with sum |g| > 1 diverge as the formulas do.
+ * One launch runs all directions, images, channels and steps of the forward; the backward is one launch plus at most one fixed-order reduction
+ * launch.  No atomics: forward and backward are run-to-run bitwise.
+ * A line (H for directions 0 / 1, W for 2 / 3) has at most 2048 pixels: beyond that, and for a tensor of more than 2^31 - 1 elements, the calls
+ * return CSPN_E_UNSUPPORTED and the byte queries 0.  The scan itself may be of any length.
+ * Workspaces: pure host arithmetic, multiples of 256, 0 wherever the arguments are rejected (Cg not dividing C, dirs outside 1 .. 15, a size
+ * <= 0, the limits above) and >= 256 otherwise.  The forward's holds no tensor (256 bytes); the backward's holds grad_x of the directions
+ * d >= 1 ((D - 1) B C H W floats) and grad_gates of the channels beyond a group's first ((C / Cg - 1) B D Cg 3 H W floats).
+ * Arguments, ranges, alignment (workspace 256 bytes; any tensor alignment and any H, W >= 1 is taken) and error codes as the kxk_dyn entry
+ * points: out / the gradients must not alias an input, each other or the workspace. */
+size_t cspn2d_scan_workspace_bytes(int B, int C, int Cg, int H, int W, int dirs, int has_lam);
+int cspn2d_forward_scan_f32(const float* x, const float* gates, const float* lam, float* out, int B, int C, int Cg, int H, int W, int dirs,
+                            void* workspace, size_t workspace_bytes, cspn_stream_t stream);
+size_t cspn2d_backward_scan_workspace_bytes(int B, int C, int Cg, int H, int W, int dirs, int has_lam);
+int cspn2d_backward_scan_f32(const float* x, const float* gates, const float* lam, const float* out, const float* grad_out, float* grad_x,
+                             float* grad_gates, float* grad_lam, int B, int C, int Cg, int H, int W, int dirs,
+                             void* workspace, size_t workspace_bytes, cspn_stream_t stream);
 
 /* ---- the steps right next to the path, on the device ----
  * cspn_metrics_f32: reference cspn_pytorch/utils.py:19-47 (evaluate_error) and loss.py:16-23 (Wighted_L1_Loss = MAE
